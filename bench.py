@@ -25,7 +25,10 @@ For N > 1 the frame-summed uint64 histograms are all-reduced over RCCL in every 
 The default line carries the same measurement as the object `msd` (fewer steps), so that one run per N gives both halves
 of BASELINE.json's metric: atom-pairs/s (RDF) and frame-pairs/s (MSD).
 
-Rank 0 prints ONE JSON line. Beside the contract's keys it carries (N = 1 only, all measured in this run):
+Rank 0 prints ONE JSON line: the contract's keys and the flat scalars of `config`, `roofline` and `cpu_baseline`
+(result_line; ~2 KB, so that a record which keeps only the tail of stdout still holds all of it). The full record
+(~25 KB) goes to --detail (default bench_detail.json beside this file). Beside the contract's keys it carries (N = 1 only,
+all measured in this run):
   roofline        the dominant kernel against the VALU-issue roof MEASURED for its instruction mix
                   (profiles/r02_ubench_valu.json), HBM traffic from the committed PMC run
   parity_checked  the timed histograms == the sum of a per-frame run, whose frames are compared bit for bit with
@@ -35,6 +38,10 @@ Rank 0 prints ONE JSON line. Beside the contract's keys it carries (N = 1 only, 
   c3, c4, c5      BASELINE.json configs[2..4] at FULL size on this GPU, each with its roofline and a bounded
                   cpu_baseline sample
   cpu_baseline    oracle/cpu_ref.c on the host cores (bounded sample), the checker — never the thing measured
+
+--dump-outputs DIR writes what the timed path returned in its last timed step as DIR/<name>.npy (float64): the
+histograms (and CN counts) of the RDF line, the three MSD results of --workload c4. The inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 
 import argparse
@@ -1073,6 +1080,50 @@ FLAT_ROOFLINE_KEYS = ROOFLINE_HEAD
 FLAT_CONFIG_KEYS = ("lib_build_match", "lib_build_id", "parity_checked")
 
 
+def result_line(out):
+    """The line bench.py prints: what driver_filter keeps of the full record `out`, with the run's parity and build
+    flags (small, top level) in place of their bare names."""
+    line = driver_filter(out)
+    for k in ("parity_checked", "f64_value", "lib_build_id"):
+        if k in out:
+            line[k] = out[k]
+    return line
+
+
+def emit(out, detail):
+    """Write the full record to `detail` (if given) and print the result line."""
+    if detail:
+        try:
+            with open(detail, "w") as fh:
+                json.dump(out, fh)
+        except OSError as e:
+            print("bench.py: the full record was not written: %s" % e, file=sys.stderr)
+            detail = None
+    line = result_line(out)
+    line["detail"] = detail or None
+    print(json.dumps(line), flush=True)
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one `path`/<name>.npy per array, float32 kept, everything else as float64 (integer counts must
+    stay below 2**53, where float64 still holds them exactly)."""
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype.kind in "ui" and a.size:
+            assert int(a.max()) < 2 ** 53 and int(a.min()) > -2 ** 53, name
+        conv[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_CAP_BYTES:
+        raise ValueError("--dump-outputs: %d bytes of outputs, more than %d" % (total, DUMP_CAP_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def head_first(d, head):
     """`d` with the keys of `head` first (in that order), everything else behind them in its present order."""
     out = {k: d[k] for k in head if k in d}
@@ -1187,7 +1238,7 @@ def c4_shards(torch, device, synth, rank, world, D, E=50_000, F=5000, block=250)
     return r_f, r_e, (lo, hi), (e_lo, e_hi)
 
 
-def msd_sharded(torch, dist, D, B, ctx, device, synth, rank, world, backend, steps, warmup, fence):
+def msd_sharded(torch, dist, D, B, ctx, device, synth, rank, world, backend, steps, warmup, fence, outputs=None):
     """
     BASELINE.json configs[3] on `world` GPUs, strong scaling. One step =
       single origin   (diffusion.py:212-218) frames dealt to the ranks: origin frame broadcast (24 E bytes), every rank
@@ -1197,7 +1248,8 @@ def msd_sharded(torch, dist, D, B, ctx, device, synth, rank, world, backend, ste
       full lag        (superset) ENTITIES dealt to the ranks: every rank all lags of its entities (default path:
                       autocorrelation theorem, msd_power_lds_kernel), [F][G][4] sums all-reduced         F(F-1)/2 frame pairs
     The collectives run on the device buffers the kernels wrote (RCCL; gloo stages through the host) and are inside
-    the timed region; every call returns its result to the host (one small D2H each).
+    the timed region; every call returns its result to the host (one small D2H each). `outputs` (a dict), when given,
+    receives the three results of the last timed step.
     """
     E, F, tao = 50_000, 5000, 4
     # the shards are the one place where a rank can fail alone (memory): the ranks agree before anyone enters a collective
@@ -1251,6 +1303,9 @@ def msd_sharded(torch, dist, D, B, ctx, device, synth, rank, world, backend, ste
     stamps = run(steps, True)
     fence()
     elapsed = time.perf_counter() - t0
+    if outputs is not None:
+        outputs.update(msd_single_origin=np.array(res["single"]), msd_fixed_lag=np.array(res["fixed"]),
+                       msd_full_lag=np.array(res["lag"]))
     step_ms = [(b - a) * 1e3 for a, b in zip(stamps[:-1], stamps[1:])]
     kern = [float(np.mean(k_ms[k])) if k_ms[k] else 0.0 for k in ("single", "fixed", "lag")]
     parts = kern + [elapsed]
@@ -1329,6 +1384,10 @@ def main():
     ap.add_argument("--option", action="append", default=[], help="library option key=value (A/B only)")
     ap.add_argument("--op", choices=["rdf", "cn", "rdf_cn"], default="rdf",
                     help="what the headline loop calls (profiling runs of the CN and the one-sweep kernels; N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy")
+    ap.add_argument("--detail", metavar="FILE", default=os.path.join(HERE, "bench_detail.json"),
+                    help="where the full record goes ('' for nowhere); stdout gets the result line")
     ap.add_argument("--shape", choices=("C1", "C1alt", "C1full"), default=None,
                     help="profiling runs only (implies --no-legs): the headline loop on the reference's own workload shape "
                          "(leg_c1's inputs) instead of C2")
@@ -1337,6 +1396,8 @@ def main():
         args.scaling = "strong" if args.workload == "c4" else "weak"
     if args.workload == "c4" and args.scaling != "strong":
         ap.error("--workload c4 is a strong-scaling workload (BASELINE configs[3]: one C4 trajectory on 1..8 GPUs)")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn(args)
@@ -1387,7 +1448,11 @@ def main():
         torch.cuda.synchronize()
 
     if args.workload == "c4":
-        m = msd_sharded(torch, dist, D, B, ctx, device, synth, rank, world, backend, args.steps, args.warmup, fence)
+        last_out = {}
+        m = msd_sharded(torch, dist, D, B, ctx, device, synth, rank, world, backend, args.steps, args.warmup, fence,
+                        outputs=last_out)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last_out)
         if rank == 0:
             out = {"metric": "frame-pairs/s", "value": m["value"], "unit": m["unit"], "n_gpus": world,
                    "steps": args.steps, "warmup": args.warmup, "ms_per_step": m["ms_per_step"],
@@ -1396,7 +1461,7 @@ def main():
             out["config"]["collectives"] = m.pop("collectives")
             out["roofline"] = m.pop("roofline")
             out["msd"] = m
-            print(json.dumps(out))
+            emit(out, args.detail)
         if dist.is_initialized():
             dist.barrier()
             dist.destroy_process_group()
@@ -1440,7 +1505,8 @@ def main():
 
         def reduce(self):
             if self.pend is not None:
-                self.res = self.pick(self.pend.wait())
+                self.raw = self.pend.wait()  # what the caller of the op receives (--dump-outputs)
+                self.res = self.pick(self.raw)
                 self.stats = self.pend.stats()
                 self.pend = None
             return self
@@ -1465,10 +1531,11 @@ def main():
     # Every step's sums are complete on the host inside the timed region: the loop is drained before the closing fence.
     kernel_ms, aux_ms, launches = 0.0, 0.0, 0
     step_kernel_ms, step_aux_ms = [], []
-    last = [None]
+    last, last_raw = [None], [None]
 
     def finish(h, timed_step):
         last[0] = h.wait()
+        last_raw[0] = getattr(h, "raw", last[0])
         if timed_step and h.stats is not None:
             nonlocal kernel_ms, aux_ms, launches
             kernel_ms += h.stats[0]
@@ -1518,6 +1585,11 @@ def main():
         expect_in = 4.0 / 3.0 * np.pi * cfg["r_cut"] ** 3 / L ** 3
         frac_in = float(full.sum()) / 2.0 / pairs_job
         assert abs(frac_in - expect_in) < 0.01 * expect_in, (frac_in, expect_in)
+    if args.dump_outputs and rank == 0:
+        raw = last_raw[0]
+        names = {"rdf": ("rdf_full", "rdf_part", "rdf_overflow"), "cn": ("cn",),
+                 "rdf_cn": ("rdf_full", "rdf_part", "rdf_overflow", "cn")}[args.op]
+        dump_outputs(args.dump_outputs, dict(zip(names, (raw,) if args.op == "cn" else raw)))
     if args.op != "rdf":
         args.no_legs = True  # a profiling run
     msd_obj = None
@@ -1589,7 +1661,7 @@ def main():
             except Exception as e:
                 out["parity"] = {"error": repr(e)}
                 out["parity_checked"] = False
-                print(json.dumps(out))
+                emit(out, args.detail)
                 sys.exit(4)  # a fast kernel whose results differ from the reference's is not done
         if "f64" in legs:
             run_leg("f64_only", lambda: leg_f64_only(B, ctx, xyz, types, box, rel, cfg, nb, max(5, args.steps // 2),
@@ -1621,7 +1693,7 @@ def main():
         out["config"].update(conf_flat)
         out["roofline"] = head_first(out["roofline"], ROOFLINE_HEAD)
         out["config"] = head_first(out["config"], CONFIG_HEAD)
-        print(json.dumps(out))
+        emit(out, args.detail)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -460,6 +460,54 @@ def golden_cell17():
     print("cell17:", table["reference_here"])
 
 
+def golden_cell17_msd():
+    """Cell 17's MSD without the 139 MB trajectory: Diffusion.get_msd_from_dump (msd_type="com", com_drift=True;
+    diffusion.py:150-224) on all 101 mg_tfsi_dme frames as [frame, molecule type, (dx2, dy2, dz2, msd)] in m^2, and what
+    recomputes some of its rows: the reference's calc_com (common/com_mols.py:5-62, which get_msd_from_dump calls) on
+    every 10th frame (an MSD row depends on frame 0 and its own frame only), and the atoms of the first molecules of
+    each type on the first and the last frame."""
+    import glob
+
+    from pymatgen.io.lammps.outputs import parse_lammps_dumps as shim_parse  # oracle/shims, no product import
+
+    d = Diffusion(timestep=1, units="real", outputs_dir=DATA, diff_dir=tempfile.mkdtemp())
+    with quiet():
+        msd, _, _ = d.get_msd_from_dump(
+            "dump.nvt.*.dump", msd_type="com", num_mols=NUM_MOLS, num_atoms_per_mol=NUM_ATOMS,
+            mass=MASS, com_drift=True, avg_interval=True, tao_coeff=4)
+    table = np.stack([msd[["%s%d" % (c, k + 1) for c in ("dx2", "dy2", "dz2", "msd")]].to_numpy(dtype=np.float64)
+                      for k in range(len(NUM_MOLS))], axis=1)
+    steps = sorted(int(os.path.basename(p).split(".")[2]) for p in glob.glob(os.path.join(DATA, "dump.nvt.*.dump")))
+    com_frames = list(range(0, len(steps), 10))
+    atoms_frames = [0, len(steps) - 1]
+    n_keep = [20, 10, NUM_MOLS[2]]  # molecules of each type whose atoms are kept
+    first = np.concatenate([[0], np.cumsum(np.multiply(NUM_MOLS, NUM_ATOMS))])
+    rows = np.concatenate([np.arange(first[k], first[k] + n_keep[k] * NUM_ATOMS[k]) for k in range(len(NUM_MOLS))])
+    com, seg_mass, atoms_xyz, atoms_type = [], None, [], None
+    for f in sorted(set(com_frames) | set(atoms_frames)):
+        (dump,) = list(shim_parse(os.path.join(DATA, "dump.nvt.%d.dump" % steps[f])))
+        dump.data = dump.data.sort_values(by=["id"])
+        dump.data.reset_index(inplace=True)
+        if f in com_frames:
+            mol = calc_com(dump, NUM_MOLS, NUM_ATOMS, MASS, atom_attributes=["xu", "yu", "zu"])
+            com.append(mol[["xu", "yu", "zu"]].to_numpy(dtype=np.float64))
+            m = mol["mass"].to_numpy(dtype=np.float64)
+            assert seg_mass is None or np.array_equal(m, seg_mass)
+            seg_mass = m
+        if f in atoms_frames:
+            atoms_xyz.append(dump.data[["xu", "yu", "zu"]].to_numpy(dtype=np.float64)[rows])
+            ty = dump.data["type"].to_numpy(dtype=np.int64)[rows]
+            assert atoms_type is None or np.array_equal(ty, atoms_type)
+            atoms_type = ty
+    out = {"steps": np.asarray(steps, dtype=np.int64), "msd_time": msd["Time (s)"].to_numpy(dtype=np.float64),
+           "msd": table, "com_frames": np.asarray(com_frames), "com": np.stack(com), "seg_mass": seg_mass,
+           "num_mols": np.asarray(NUM_MOLS), "num_atoms_per_mol": np.asarray(NUM_ATOMS), "mass": np.asarray(MASS),
+           "atoms_frames": np.asarray(atoms_frames), "atoms_num_mols": np.asarray(n_keep),
+           "atoms_xyz": np.stack(atoms_xyz), "atoms_type": atoms_type}
+    np.savez_compressed(os.path.join(OUT, "cell17_msd.npz"), **out)
+    print("cell17_msd:", table.shape, "com frames", com_frames, "atoms", len(rows))
+
+
 # ----------------------------------------------------------------------------
 def golden_host_logic():
     """Conductivity.detect_time_range / fit_curve / green_kubo and Viscosity.calc_avg_visc /
@@ -522,7 +570,7 @@ def golden_host_logic():
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["synth", "acf", "small", "c1", "cell17", "host", "residence", "inter"]
+    which = sys.argv[1:] or ["synth", "acf", "small", "c1", "cell17", "cell17_msd", "host", "residence", "inter"]
     if "residence" in which:
         golden_residence()
     if "inter" in which:
@@ -539,3 +587,5 @@ if __name__ == "__main__":
         golden_c1_rdf()
     if "cell17" in which:
         golden_cell17()
+    if "cell17_msd" in which:
+        golden_cell17_msd()

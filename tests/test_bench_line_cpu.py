@@ -71,3 +71,53 @@ def test_strings_bench_writes_into_kept_sections_are_short():
     src = inspect.getsource(bench.cpu_baseline)
     m = re.search(r'"sample": "([^"]*)"', src)
     assert m and len(m.group(1) % (10, 200, 99.9, 256)) <= 128
+
+
+def test_result_line_of_a_full_record_is_short():
+    """A full record (round 6's default line, ~25 KB, kept in profiles/) is printed as its result line: the contract's
+    keys, the kept sections and the flags, in well under the 8 KB a record of stdout's tail holds."""
+    import os
+
+    with open(os.path.join(os.path.dirname(bench.__file__), "profiles", "r06_bench_line.json")) as fh:
+        rec = json.load(fh)
+    assert len(json.dumps(rec)) > 20000
+    line = bench.result_line(rec)
+    assert len(json.dumps(line)) <= 4096
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step"):
+        assert line[k] == rec[k], k
+    assert line["roofline"]["frac"] == rec["roofline"]["frac"]
+    assert line["cpu_baseline"]["value"] == rec["cpu_baseline"]["value"]
+    assert line["parity_checked"] is True and line["lib_build_id"] == rec["lib_build_id"]
+
+
+def test_emit_writes_the_record_and_prints_one_line(tmp_path, capsys):
+    rec = _canned()
+    detail = str(tmp_path / "detail.json")
+    bench.emit(rec, detail)
+    out = capsys.readouterr().out.splitlines()
+    assert len(out) == 1
+    line = json.loads(out[0])
+    assert line["detail"] == detail and line == dict(bench.result_line(rec), detail=detail)
+    with open(detail) as fh:
+        assert json.load(fh) == rec
+    bench.emit(rec, "")
+    assert json.loads(capsys.readouterr().out)["detail"] is None
+
+
+def test_dump_outputs_exact_and_capped(tmp_path):
+    import numpy as np
+    import pytest
+
+    counts = np.array([0, 1, 2 ** 53 - 1], dtype=np.uint64)
+    f32 = np.linspace(0, 1, 7, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "d"), {"counts": counts, "f32": f32, "ov": 0})
+    c = np.load(tmp_path / "d" / "counts.npy")
+    assert c.dtype == np.float64 and np.array_equal(c.astype(np.uint64), counts)
+    g = np.load(tmp_path / "d" / "f32.npy")
+    assert g.dtype == np.float32 and np.array_equal(g, f32)
+    assert np.load(tmp_path / "d" / "ov.npy").dtype == np.float64
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "e"), {"big": np.array([2 ** 53], dtype=np.uint64)})
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "f"), {"x": np.zeros(bench.DUMP_CAP_BYTES // 8 + 1)})
+    assert not (tmp_path / "f").exists()

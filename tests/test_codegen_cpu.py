@@ -6,7 +6,8 @@ and the roofline's occupancy assumptions rest on register budgets. hipcc cross-c
 that is checked HERE from the compiler's own assembly (`-S --cuda-device-only`, the flags of mdproptools_amd/build.py):
 a compiler bump that fuses the chain, moves a VALU instruction between an exec-rewriting block and its restore, or
 halves the occupancy fails this test instead of silently changing results or speed.
-The two translation units take ~30 s each to compile; the assembly is cached under /tmp by source hash.
+The two translation units take ~30 s each to compile; the assembly is cached by source hash next to the build's
+objects (mdproptools_amd/csrc/_obj/codegen/, git-ignored), inside this checkout.
 """
 import hashlib
 import os
@@ -27,10 +28,12 @@ def _asm(src):
     for p in [path] + bld.HEADERS:
         with open(p, "rb") as fh:
             h.update(fh.read())
-    out = "/tmp/mdhip_codegen_%s_%s.s" % (os.path.splitext(src)[0], h.hexdigest()[:16])
+    cache = os.path.join(bld.OBJ, "codegen")
+    os.makedirs(cache, exist_ok=True)
+    out = os.path.join(cache, "%s_%s.s" % (os.path.splitext(src)[0], h.hexdigest()[:16]))
     if not os.path.exists(out):
         tmp = out + ".%d.tmp" % os.getpid()
-        subprocess.check_call([bld._hipcc()] + FLAGS + ["-o", tmp, path], cwd="/tmp", stderr=subprocess.DEVNULL)
+        subprocess.check_call([bld._hipcc()] + FLAGS + ["-o", tmp, path], cwd=cache, stderr=subprocess.DEVNULL)
         os.replace(tmp, out)
     with open(out) as fh:
         return fh.read()

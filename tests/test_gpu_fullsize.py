@@ -301,44 +301,80 @@ def test_c5_full_size_acf(B):
     np.testing.assert_allclose(integ[:, -1], 1e-15 * (fft.sum(axis=1) - 0.5 * (fft[:, 0] + fft[:, -1])), rtol=1e-9)
 
 
-def test_bench_launches_its_own_ranks():
+def _run_bench(args, env, tmp_path):
+    """bench.py with `args`: (the line it printed, the full record it wrote to --detail). The line is the record's
+    result_line, short enough for a record of stdout's tail."""
+    detail = str(tmp_path / "bench_detail.json")
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + args + ["--detail", detail], env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and len(lines[0]) <= 4096, [len(l) for l in lines]
+    line = json.loads(lines[0])
+    with open(detail) as fh:
+        rec = json.load(fh)
+    assert line["detail"] == detail
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "scaling"):
+        assert line[k] == rec[k], k
+    return line, rec
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: the last timed step's results as float64 .npy files. The inputs are seeded, so two runs with a
+    different number of steps dump the same histograms; the C4 dump holds the three MSD results, tied together at the
+    longest lag as bench.py's own check ties them."""
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MDHIP_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    dumps = []
+    for steps in ("2", "3"):
+        d = tmp_path / ("rdf_%s" % steps)
+        line, _ = _run_bench(["--steps", steps, "--warmup", "1", "--no-legs", "--no-cpu-baseline",
+                              "--dump-outputs", str(d)], env, tmp_path)
+        assert line["steps"] == int(steps)
+        dumps.append({n: np.load(d / (n + ".npy")) for n in ("rdf_full", "rdf_part", "rdf_overflow")})
+    a, b = dumps
+    assert a["rdf_full"].shape == (400,) and a["rdf_part"].shape == (10, 400)
+    for n in a:
+        assert a[n].dtype == np.float64 and np.array_equal(a[n], b[n]), n
+    assert a["rdf_overflow"].sum() == 0 and a["rdf_full"].sum() > 0
+    d = tmp_path / "c4"
+    _run_bench(["--workload", "c4", "--steps", "1", "--warmup", "1", "--dump-outputs", str(d)], env, tmp_path)
+    single, fixed, lag = (np.load(d / (n + ".npy")) for n in ("msd_single_origin", "msd_fixed_lag", "msd_full_lag"))
+    assert single.shape == (5000, 1, 4) and lag.shape == (5000, 1, 4) and fixed.shape == (50_000, 4)
+    np.testing.assert_allclose(lag[-1, 0], single[-1, 0] / 50_000 / 1e-20, rtol=1e-9)
+
+
+def test_bench_launches_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher: bench.py starts the two ranks itself (here sharing the GPU over
     gloo) — strong scaling, C3's 1000 frames split 500 + 500, all-reduce inside the timed region."""
     env = dict(os.environ, MDHIP_DIST_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--scaling", "strong",
-                        "--steps", "2", "--warmup", "1"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    line, _ = _run_bench(["--gpus", "2", "--scaling", "strong", "--steps", "2", "--warmup", "1"], env, tmp_path)
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["config"]["frames_per_gpu"] == 500
     assert line["config"]["pairs_per_step"] == 1000 * 100_000 * 99_999 // 2
     assert line["value"] > 1e12
 
 
-def test_bench_c4_workload_two_ranks():
+def test_bench_c4_workload_two_ranks(tmp_path):
     """`python bench.py --gpus 2 --workload c4`: the MSD half of BASELINE.json's metric at N > 1 — frames dealt to the
     ranks for single-origin / fixed-lag, entities for the full lag average, collectives inside the timed region (two
     ranks sharing the GPU over gloo here); bench.py's own checks tie the two shardings together."""
     env = dict(os.environ, MDHIP_DIST_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--workload", "c4",
-                        "--steps", "2", "--warmup", "1"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    line, rec = _run_bench(["--gpus", "2", "--workload", "c4", "--steps", "2", "--warmup", "1"], env, tmp_path)
     assert line["metric"] == "frame-pairs/s" and line["unit"].startswith("effective frame-pairs/s") and line["n_gpus"] == 2
     assert line["scaling"] == "strong" and line["config"]["frames_per_gpu"] == 2500
     assert line["config"]["entities_per_gpu"] == 25_000
-    assert line["config"]["collectives"]["world_size"] == 2 and line["config"]["collectives"]["backend"] == "gloo"
-    assert line["value"] > 1e6 and line["msd"]["single_origin"]["value_at_kernel_time"] > 1e4
-    assert line["msd"]["kernel_ms_per_step"] > 0 and len(line["msd"]["step_ms"]["raw"]) == 2
+    assert rec["config"]["collectives"]["world_size"] == 2 and rec["config"]["collectives"]["backend"] == "gloo"
+    assert line["value"] > 1e6 and rec["msd"]["single_origin"]["value_at_kernel_time"] > 1e4
+    assert rec["msd"]["kernel_ms_per_step"] > 0 and len(rec["msd"]["step_ms"]["raw"]) == 2
     assert line["lib_build_id"]["match"] is True
 
 
-def test_bench_through_rccl_with_one_rank():
+def test_bench_through_rccl_with_one_rank(tmp_path):
     """Both bench workloads with a ONE-rank RCCL process group (MDHIP_BENCH_FORCE_DIST=1): every collective of the
     N > 1 path — histogram all-reduce on the device buffer, origin broadcast, row all-gathers, halo all-gather, the
     entity-sharded all-reduce, the max-over-ranks timing — goes through RCCL itself on device tensors (two ranks
@@ -348,13 +384,10 @@ def test_bench_through_rccl_with_one_rank():
         env.pop(k, None)
     for port, extra in ((29541, ["--workload", "c4"]), (29542, ["--legs", "parity", "--no-cpu-baseline", "--msd-steps", "1"])):
         env["MASTER_PORT"] = str(port)
-        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1"] + extra,
-                           env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
-        assert r.returncode == 0, r.stderr[-2000:]
-        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-        coll = line["config"]["collectives"]
+        line, rec = _run_bench(["--steps", "2", "--warmup", "1"] + extra, env, tmp_path)
+        coll = rec["config"]["collectives"]
         assert coll["backend"] == "nccl" and coll["world_size"] == 1 and line["n_gpus"] == 1
-        assert line["msd"]["value"] > 1e8 and line["value"] > 1e8
+        assert rec["msd"]["value"] > 1e8 and line["value"] > 1e8
         if "--workload" not in extra:
             assert line["metric"] == "atom-pairs/s" and line["parity_checked"] is True
 

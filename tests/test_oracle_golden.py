@@ -255,29 +255,39 @@ def test_cell17_published_table():
             assert float("%.6e" % here) == pytest.approx(pub, rel=1e-6) or float("%.6f" % here) == pub
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/data/mg_tfsi_dme"),
-                    reason="full mg_tfsi_dme trajectory only exists in the build container")
 def test_cell17_oracle_chain_full_trajectory():
-    """Oracle restatement of calc_com -> drift -> MSD -> OLS on all 101 frames vs cell 17."""
-    from mdproptools_amd.io import read_dump_arrays
-    steps, bounds, planes = read_dump_arrays(
-        "/root/reference/data/mg_tfsi_dme/dump.nvt.*.dump", ["type", "xu", "yu", "zu"])
-    mass = np.array([16.000, 12.010, 1.008, 14.010, 32.060, 16.000, 12.010, 19.000, 24.305])
-    nm, na = [591, 66, 33], [16, 15, 1]
-    _, _, off, _ = O.molecule_layout(nm, na)
-    amass = mass[planes[0, 0].astype(np.int64) - 1]
-    r, seg_mass = [], None
-    for f in range(len(steps)):
-        com, seg_mass, _ = O.calc_com(planes[f, 1:4].T, amass, off)
-        r.append(com * 1e-10)
+    """Oracle restatement of calc_com -> drift -> MSD -> OLS on the 101 frames of cell 17, stage by stage against the
+    reference, without the 139 MB trajectory (cell17_msd.npz): the oracle's calc_com on the first molecules of each type
+    (first and last frame), its drift removal and MSD on the reference's centres of mass of every 10th frame (an MSD row
+    depends on frame 0 and its own frame only) against the reference's MSD rows, and the fit of all 101 rows against the
+    published table."""
+    g = load_golden("cell17_msd.npz")
+    nm, na = list(g["num_mols"]), list(g["num_atoms_per_mol"])
     goff = np.concatenate([[0], np.cumsum(nm)])
-    r = O.remove_type_drift(np.stack(r), seg_mass * (1e-3 / 6.02214076e23), goff)
+    com_frames = list(g["com_frames"])
+    assert com_frames[0] == 0 and len(com_frames) > 2
+    # calc_com: the kept molecules are the first of each type, so their atoms are the first of each type's block
+    _, _, off, _ = O.molecule_layout(list(g["atoms_num_mols"]), na)
+    mols = np.concatenate([np.arange(goff[k], goff[k] + n) for k, n in enumerate(g["atoms_num_mols"])])
+    amass = g["mass"][g["atoms_type"] - 1]
+    for k, f in enumerate(g["atoms_frames"]):
+        com, seg_mass, _ = O.calc_com(g["atoms_xyz"][k], amass, off)
+        np.testing.assert_allclose(com, g["com"][com_frames.index(f)][mols], rtol=0, atol=1e-12)  # A; summation order
+        np.testing.assert_allclose(seg_mass, g["seg_mass"][mols], rtol=1e-15, atol=0)
+    # drift removal and single-origin MSD, group means: the reference's rows of those frames
+    r = O.remove_type_drift(g["com"] * 1e-10, g["seg_mass"] * (1e-3 / 6.02214076e23), goff)
     mean = O.msd_group_mean(O.msd_single_origin(r), goff)
+    np.testing.assert_allclose(mean, g["msd"][com_frames], rtol=1e-13, atol=0)
+    # the fit on all 101 frames
+    steps = g["steps"]
+    assert len(steps) == 101 and np.all(np.diff(steps) > 0)
     t = steps * 1e-15
+    np.testing.assert_allclose(g["msd_time"], t, rtol=1e-15, atol=0)
     with open(os.path.join(GOLDEN, "cell17.json")) as fh:
         tab = json.load(fh)
+    np.testing.assert_array_equal(g["msd"][-1].reshape(-1), np.asarray(tab["msd_first_last"][1][1:]))
     for k in range(3):
-        slope, bse, r2 = O.ols_origin(t, mean[:, k, 3])
+        slope, bse, r2 = O.ols_origin(t, g["msd"][:, k, 3])
         assert "%.6e" % (slope / 6) == "%.6e" % tab["published"]["diffusion (m2/s)"][k]
         assert "%.6e" % (bse / 6) == "%.6e" % tab["published"]["std"][k]
         assert "%.6f" % r2 == "%.6f" % tab["published"]["R2"][k]
