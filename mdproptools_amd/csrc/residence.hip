@@ -16,9 +16,14 @@
 //     Round 6: rounds 1-5 appended a record per hit and brought a pair's frames together with a 64-bit radix sort of
 //     the records (hipCUB — the one vendor-library call of the product); only the GROUPING was ever needed — the
 //     masks are sets — and the table gives it without a sort, a record list or a run search.
+//     A table that fills up is swept again, sized from the number of distinct pairs there can be: the first sweep's
+//     hits, but never more than n_i * n_j (less the diagonal) — a clustered system's hits are ~F times its pairs.
 //  2. residence_lag_kernel: a wave per occupied slot copies the pair's mask to LDS and adds
 //     popcount(mask & (mask >> k)) to its lag table for every lag k up to the pair's span; tables are merged with
-//     64-bit global atomics (integers: order-independent, so is the table's slot order).
+//     64-bit global atomics (integers: order-independent, so is the table's slot order). The lag table is a WINDOW
+//     [k0, k0 + K) of the lags: one window holds all F lags up to ~20 000 frames (160 KB of LDS); beyond, the host
+//     launches as many windows (grid.y) as LDS requires, each re-reading the masks. Only the mask (<= 1025 words,
+//     8 KB at 65 535 frames) must fit whole.
 
 #include <algorithm>
 #include <cmath>
@@ -53,7 +58,7 @@ __device__ __forceinline__ unsigned long long rt_mix(unsigned long long x)
 }
 
 // the slot of `key` in the table (claimed if new); RT_NONE when `max_probe` slots in a row were other pairs' (the table
-// is too small: the host sweeps again with one sized from the hit count)
+// is too small: the host sweeps again with one sized from the pair count)
 __device__ __forceinline__ unsigned rt_slot(unsigned long long *__restrict__ keys, unsigned slot_mask, unsigned max_probe,
                                             unsigned long long key)
 {
@@ -126,16 +131,18 @@ __global__ __launch_bounds__(RT_TILE) void shell_pairs_kernel(
     if (lost) atomicOr(stat + 1, 1ull);
 }
 
-// One wave per occupied slot (grid-stride over the table). LDS: presence mask [words + 1] + lag table [n_frames] (u64).
+// One wave per occupied slot (grid-stride over the table), grid.y the lag windows [k0, k0 + K) of `win` lags each.
+// LDS: presence mask [words + 1] + lag table [win] (u64).
 __global__ __launch_bounds__(64) void residence_lag_kernel(
     const unsigned long long *__restrict__ keys, const unsigned long long *__restrict__ masks, unsigned long long n_slots,
-    int n_frames, int words, unsigned long long *__restrict__ counts)
+    int n_frames, int words, int win, unsigned long long *__restrict__ counts)
 {
     extern __shared__ unsigned long long s_mem[];
     unsigned long long *mask = s_mem;               // [words + 1] (one zero word behind the end)
-    unsigned long long *table = s_mem + words + 1;  // [n_frames]
+    unsigned long long *table = s_mem + words + 1;  // [win]: lag k0 + k at table[k]
     const int lane = threadIdx.x;
-    for (int k = lane; k < n_frames; k += 64) table[k] = 0ull;
+    const int k0 = (int)blockIdx.y * win, K = n_frames - k0 < win ? n_frames - k0 : win;
+    for (int k = lane; k < K; k += 64) table[k] = 0ull;
     if (lane == 0) mask[words] = 0ull;
     for (unsigned long long r = blockIdx.x; r < n_slots; r += gridDim.x) {
         if (keys[r] == RT_EMPTY) continue;  // (wave-uniform)
@@ -159,7 +166,8 @@ __global__ __launch_bounds__(64) void residence_lag_kernel(
         __syncthreads();
         const int span = t_last - t_first;  // lags beyond the span see no overlap
         const int w0 = t_first >> 6, w1 = t_last >> 6;
-        for (int lag = lane; lag <= span; lag += 64) {
+        const int lag_end = span < k0 + K - 1 ? span : k0 + K - 1;
+        for (int lag = k0 + lane; lag <= lag_end; lag += 64) {
             const int q = lag >> 6, sh = lag & 63;
             unsigned long long c = 0;
             for (int w = w0; w + q <= w1; ++w) {
@@ -167,12 +175,12 @@ __global__ __launch_bounds__(64) void residence_lag_kernel(
                 const unsigned long long shifted = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
                 c += (unsigned long long)__builtin_popcountll(mask[w] & shifted);
             }
-            table[lag] += c;  // a lag belongs to one lane: no conflict
+            table[lag - k0] += c;  // a lag belongs to one lane: no conflict
         }
     }
     __syncthreads();
-    for (int k = lane; k < n_frames; k += 64)
-        if (table[k]) atomicAdd(&counts[k], table[k]);
+    for (int k = lane; k < K; k += 64)
+        if (table[k]) atomicAdd(&counts[k0 + k], table[k]);
 }
 
 }  // namespace
@@ -195,8 +203,16 @@ int mdhip_shell_residence(mdhip_ctx *ctx, int64_t n_frames, int64_t n_i, const d
     MD_REQUIRE((double)n_i * (double)n_j < 9.0e18, "pair key does not fit 63 bits");
     MD_REQUIRE(n_frames <= 65535, "at most 65535 frames per call");
     const int words = (int)((n_frames + 63) / 64);
-    const size_t lds_b = ((size_t)words + 1 + (size_t)n_frames) * 8;
-    MD_REQUIRE(lds_b <= ctx->lds_max - 512, "%lld frames exceed the LDS lag table", (long long)n_frames);
+    // the lag kernel's LDS: the whole mask + a window of `win` lags; ONE window (all F lags) while it fits
+    MD_REQUIRE(((size_t)words + 1 + 64) * 8 <= ctx->lds_max - 512, "%lld frames: the presence mask exceeds LDS",
+               (long long)n_frames);
+    const size_t lds_lags = (ctx->lds_max - 512) / 8 - ((size_t)words + 1);  // (lag slots beside the mask)
+    int win = (int)n_frames, n_win = 1;
+    if ((size_t)n_frames > lds_lags) {
+        n_win = (int)(((size_t)n_frames + lds_lags - 1) / lds_lags);
+        win = (int)std::min<size_t>(lds_lags, ((size_t)(n_frames + n_win - 1) / n_win + 63) / 64 * 64);
+    }
+    const size_t lds_b = ((size_t)words + 1 + (size_t)win) * 8;
     MD_HIP(hipSetDevice(ctx->device));
     int rc;
     const double *d_xi = (const double *)mdhip_stage(ctx, WS_XYZ_I, xi, (size_t)n_frames * 3 * n_i * 8, xi_on_device, &rc);
@@ -222,7 +238,7 @@ int mdhip_shell_residence(mdhip_ctx *ctx, int64_t n_frames, int64_t n_i, const d
     // The table: one slot per PAIR that is ever in the shell (key 8 B + a mask of `words` words), at most half full.
     // ONE sweep in the common case: the slot count comes from the expected number of HITS (the shell's share of the box x
     // pairs x frames x 1.5 + slack: far more than distinct pairs — a pair stays for many frames); only a call whose table
-    // fills up (a clustered system) sweeps again, with slots from the hit count the first sweep returned (>= its pairs).
+    // fills up (a clustered system) sweeps again, with slots from min(hits, n_i * n_j) (>= its pairs).
     const size_t slot_b = 8 + (size_t)words * 8;
     const size_t mem_cap = (size_t)12 << 30;  // (the table's bytes; beyond that the call fails cleanly)
     auto pow2_at_least = [](double v, unsigned long long lo = 1024) {
@@ -266,11 +282,15 @@ int mdhip_shell_residence(mdhip_ctx *ctx, int64_t n_frames, int64_t n_i, const d
         MD_HIP(mdhip_stream_wait(ctx));
         n_hit = h_out[0];
         if (h_out[1] == 0) break;
-        MD_REQUIRE(sweep == 0, "residence: the pair table filled up although it was sized from the hit count");
-        slots = pow2_at_least(2.0 * (double)n_hit);
+        MD_REQUIRE(sweep == 0, "residence: the pair table filled up although it was sized from the pair count");
+        // distinct pairs: at most one per hit, and never more than there are (a clustered system hits each of its pairs
+        // in ~every frame: sizing from the hits alone asks for F times the table it needs)
+        const double max_pairs = (double)n_i * (double)n_j - (exclude_diagonal ? (double)n_i : 0.0);
+        slots = pow2_at_least(2.0 * std::min((double)n_hit, max_pairs));
         if (slots * slot_b > mem_cap)
-            return mdhip_fail(ctx, MDHIP_ELIMIT, "residence: %llu in-shell records over %lld frames need a pair table of %.1f GB",
-                              n_hit, (long long)n_frames, (double)(slots * slot_b) / 1073741824.0);
+            return mdhip_fail(ctx, MDHIP_ELIMIT, "residence: %.0f in-shell pairs over %lld frames need a pair table of %.1f GB",
+                              std::min((double)n_hit, max_pairs), (long long)n_frames,
+                              (double)(slots * slot_b) / 1073741824.0);
     }
     if (n_records) *n_records = n_hit;
     if (n_hit > 0) {
@@ -278,8 +298,8 @@ int mdhip_shell_residence(mdhip_ctx *ctx, int64_t n_frames, int64_t n_i, const d
             MD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(residence_lag_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
         const unsigned lag_grid = (unsigned)std::min<unsigned long long>(slots, (unsigned long long)ctx->cu_count * 16);
-        hipLaunchKernelGGL(residence_lag_kernel, dim3(lag_grid), dim3(64), lds_b, ctx->stream, d_keys, d_masks, slots,
-                           (int)n_frames, words, d_counts);
+        hipLaunchKernelGGL(residence_lag_kernel, dim3(lag_grid, (unsigned)n_win), dim3(64), lds_b, ctx->stream, d_keys,
+                           d_masks, slots, (int)n_frames, words, win, d_counts);
         MD_HIP(hipGetLastError());
     }
     timer.stop();
