@@ -332,6 +332,9 @@ int mdhip_segment_com_async(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, i
  *              (dx2+dy2)+dz2 (the caller divides by the group size: diffusion.py:218)
  *   per_entity host|dev (pe_on_device) [n_pairs][n_ent][4] = msd_all rows, or NULL
  * Tolerance vs the reference: rtol 1e-10 on means (fixed-order tree sums vs pandas' compensated sums).
+ * Any number of pairs (n_pairs * n_groups * 4 < 2^31): a launch covers at most 65535 pairs (grid.y), so longer lists
+ * run as several launches of one call. A pair's sums and rows are the same bits whichever launch computes it.
+ * This holds for every msd_pairs / msd_origin entry point below and their _async twins (one ticket per call).
  */
 int mdhip_msd_pairs(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const double *r,
                     int on_device, double scale, int n_pairs, const int32_t *pairs, int n_groups,
@@ -340,7 +343,7 @@ int mdhip_msd_pairs(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const doubl
 /*
  * M1 for a FRAME SHARD (dynamical/diffusion.py:212-218 when the frames are dealt to one process per GPU): every frame
  * t of r against ONE origin frame that need not be among them — the frame at time 0, broadcast by the rank that owns
- * it — i.e. the frame pairs {(origin, t)}, t = 0..n_frames-1.
+ * it — i.e. the frame pairs {(origin, t)}, t = 0..n_frames-1. Any number of frames, as mdhip_msd_pairs.
  *   origin     host|dev (origin_on_device) [3][n_ent]
  *   sums       host|dev (sums_on_device) [n_frames][n_groups][4]
  *   cols       NULL, or host|dev (cols_on_device) the four per-entity columns as in mdhip_msd_pairs_cols
@@ -479,6 +482,8 @@ int mdhip_xcorr_lags_dev_async(mdhip_ctx *ctx, int64_t n, int n_pairs, const dou
  * dynamical/viscosity.py:151 (cumtrapz) and conductivity.py:231 (cumulative_trapezoid):
  * I[k] = sum_{m<k} dx*(y[m]+y[m+1])/2. y host|dev [n_series][n];
  * out host [n_series][n-1], or [n_series][n] with a leading 0 when leading_zero != 0.
+ * At most 65535 series per call: more fail with MDHIP_EINVAL before anything is written. The same limit holds for
+ * mdhip_green_kubo* (tests/test_gpu_launch_limits.py).
  */
 int mdhip_cumtrapz(mdhip_ctx *ctx, int64_t n, int n_series, const double *y, int on_device,
                    double dx, int leading_zero, double *out);
@@ -502,6 +507,7 @@ int mdhip_cumtrapz_dev_async(mdhip_ctx *ctx, int64_t n, int n_series, const doub
  * Each factor is applied as one multiplication of the finished value — the roundings of `acf * c**2` and
  * `np.multiply(c, integral)` on the host; 1.0 leaves values untouched. a, b host|dev [n_series][n] (b == a:
  * autocorrelation). Destinations in page-locked memory (mdhip_host_alloc) are written by DMA.
+ * At most 65535 series per call, as mdhip_cumtrapz.
  */
 int mdhip_green_kubo(mdhip_ctx *ctx, int64_t n, int n_series, const double *a, const double *b, int on_device,
                      int method, double acf_scale, double dx, double integral_scale, int leading_zero, double *acf,

@@ -589,7 +589,7 @@ int msd_pairs_impl(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const double
     if (rc) return rc;
     if (n_pairs == 0 || chunks.empty()) return cs.end();
     MD_REQUIRE(r != nullptr, "r is NULL");
-    MD_REQUIRE(n_pairs <= 65535, "at most 65535 frame pairs per call");
+    MD_REQUIRE((int64_t)n_pairs * n_groups * 4 <= INT32_MAX, "n_pairs * n_groups * 4 exceeds 2^31 - 1");
     const double *d_r =
         (const double *)mdhip_stage(ctx, WS_XYZ_I, r, (size_t)n_frames * 3 * n_ent * 8, on_device, &rc);
     if (rc) return rc;
@@ -627,20 +627,29 @@ int msd_pairs_impl(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const double
     }
     const long long col_len = (long long)n_pairs * n_ent;
     const long long d_stride = col_stride ? (pe_on_device ? (long long)col_stride : col_len) : 0;
-    KernelTimer timer(ctx);
+    KernelTimer timer(ctx, (n_pairs + 65534) / 65535);
     ctx->last_kernel = "msd_pairs_kernel";
     // 16-byte loads need 16-byte aligned planes and even chunk starts
     bool vec2 = (n_ent % 2 == 0) && ((reinterpret_cast<uintptr_t>(d_r) & 15) == 0) &&
                 ((reinterpret_cast<uintptr_t>(d_origin) & 15) == 0);
     for (const Chunk &c : chunks) vec2 = vec2 && (c.e0 % 2 == 0);
-    if (vec2)
-        hipLaunchKernelGGL(msd_pairs_kernel<true>, dim3((unsigned)n_chunks, (unsigned)n_pairs),
-                           dim3(MSD_THREADS), 0, ctx->stream, d_r, (long long)n_ent, scale, d_pairs,
-                           d_chunks, n_chunks, d_partial, d_pe, d_stride, d_origin);
-    else
-        hipLaunchKernelGGL(msd_pairs_kernel<false>, dim3((unsigned)n_chunks, (unsigned)n_pairs),
-                           dim3(MSD_THREADS), 0, ctx->stream, d_r, (long long)n_ent, scale, d_pairs,
-                           d_chunks, n_chunks, d_partial, d_pe, d_stride, d_origin);
+    // grid.y holds at most 65535 pairs: longer pair lists go in slices, each launch with its pair list, partials and
+    // per-entity rows (or the start of each column) offset to its first pair. Every pair runs the same chunks in the
+    // same order, so its sums do not depend on the slice it lands in; up to 65535 pairs this is one launch.
+    for (int p0 = 0; p0 < n_pairs; p0 += 65535) {
+        const int np = std::min(65535, n_pairs - p0);
+        const int *s_pairs = d_pairs + 2 * (size_t)p0;
+        double *s_partial = d_partial + (size_t)p0 * n_chunks * 4;
+        double *s_pe = d_pe ? d_pe + (size_t)p0 * n_ent * (col_stride ? 1 : 4) : nullptr;
+        if (vec2)
+            hipLaunchKernelGGL(msd_pairs_kernel<true>, dim3((unsigned)n_chunks, (unsigned)np),
+                               dim3(MSD_THREADS), 0, ctx->stream, d_r, (long long)n_ent, scale, s_pairs,
+                               d_chunks, n_chunks, s_partial, s_pe, d_stride, d_origin);
+        else
+            hipLaunchKernelGGL(msd_pairs_kernel<false>, dim3((unsigned)n_chunks, (unsigned)np),
+                               dim3(MSD_THREADS), 0, ctx->stream, d_r, (long long)n_ent, scale, s_pairs,
+                               d_chunks, n_chunks, s_partial, s_pe, d_stride, d_origin);
+    }
     timer.stop();
     MD_HIP(hipGetLastError());
     const int tot = n_pairs * n_groups * 4;
@@ -760,7 +769,7 @@ int mdhip_msd_origin(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const doub
                      int cols_on_device)
 {
     if (!ctx) return MDHIP_EINVAL;
-    MD_REQUIRE(n_frames >= 0 && n_frames <= 65535, "1..65535 frames per call");
+    MD_REQUIRE(n_frames >= 0 && n_frames <= INT32_MAX, "at most 2^31 - 1 frames per call");
     MD_REQUIRE(origin != nullptr || n_ent == 0 || n_frames == 0, "origin is NULL");
     MD_REQUIRE(sums != nullptr || n_frames == 0, "sums is NULL");
     MD_REQUIRE(!cols || col_stride >= n_frames * n_ent, "col_stride is shorter than one column");

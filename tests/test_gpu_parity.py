@@ -336,7 +336,7 @@ def test_segment_kernels_agree_for_any_plane_count(B):
     """The one-(run, frame)-per-block kernel (seg_frame 1, default) and the software-pipelined staged kernel (0) do the
     same products and additions in the same order: bit-identical centres and fluxes, for 1 .. 7 attribute planes (plane
     groups of three, the last one partial), odd and even atom counts (the 16-byte load path needs even ones), many
-    frames (more steps than one grid row holds is not reachable here; the loop is covered by the frame count)."""
+    frames (more steps than one grid row holds: tests/test_gpu_launch_limits.py)."""
     ctx = B.default_context()
     rng = np.random.default_rng(19)
     try:
