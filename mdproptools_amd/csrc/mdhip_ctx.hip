@@ -572,11 +572,6 @@ int mdhip_create(mdhip_ctx **out, int device)
         return mdhip_fail(nullptr, MDHIP_EHIP, "mdhip_create: stream creation failed");
     }
     ctx->stream = ctx->own_stream;
-    if (const char *v = getenv("MDHIP_RDF_VARIANT")) ctx->opt_rdf_variant = atoi(v);  // A/B knobs
-    if (const char *v = getenv("MDHIP_RDF_JSPLIT")) ctx->opt_rdf_jsplit = atoi(v);
-    if (const char *v = getenv("MDHIP_RDF_FPB")) ctx->opt_rdf_fpb = atoi(v);
-    if (const char *v = getenv("MDHIP_RDF_CULL")) ctx->opt_rdf_cull = atoi(v);
-    if (const char *v = getenv("MDHIP_RDF_SJ")) ctx->opt_rdf_sj = atoi(v);
     *out = ctx;
     return MDHIP_OK;
 }

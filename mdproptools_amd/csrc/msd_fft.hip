@@ -359,10 +359,6 @@ constexpr int ST_BUF = 8;    // ring of staged tiles per cluster (3 ST_AHEAD - 4
 constexpr int ST_UNITS = 8;  // 16-byte units a lane moves per tile at most (template parameter UN: 5 for rows per member
                              // Fc <= 320, i.e. F <= 5120; 8 beyond)
 constexpr int ST_FLAG_STRIDE = 32;  // words between two ready counters (a 128-byte line each)
-#ifndef ST_SKIP
-#define ST_SKIP 0  // timing experiments only (wrong results): 1 = no polls, 2 = no staging loads / stores inside the series loop,
-                   // 4 = no wait + signal, 16 = no ring stores, 32 = no staging loads
-#endif
 
 __device__ __forceinline__ int ft_skew(int i) { return i + (i >> 4); }
 
@@ -1020,9 +1016,7 @@ __global__ __launch_bounds__(FT_THREADS) void msd_power_lds2_kernel(
 //    are free again), land during the sub-transforms, and their block sum rides on the second barrier.
 // Plan: 2^m = 8 x [4 x [4]] x 8 ... x 16 (f3_plan); positions/frequencies through f2_pos / f2_freq as above.
 // ---------------------------------------------------------------------------------------------
-#ifndef F3_MIN_M
-#define F3_MIN_M 12  // smallest log2 N the kernel below is used for (it is correct from 9; A/B builds lower this)
-#endif
+constexpr int F3_MIN_M = 12;  // smallest log2 N the kernel below is used for (it is correct from 9)
 __host__ __device__ inline F2Plan f3_plan(int m)  // m >= 8
 {
     F2Plan p{};
@@ -1111,10 +1105,6 @@ __device__ __forceinline__ void f3_head8(const Cx *a, Cx w1, Cx *y)
 // all of the stride-16 pass, the tail and the partner reads. Hand-issued instead: f3_rd<byte offset>(LDS byte address),
 // then ONE f3_wait_*() through which every loaded value passes (the dependency keeps their uses behind the wait; the
 // compiler's own lgkmcnt bookkeeping does not know these reads, which only makes its waits stricter than needed).
-// F3_NO_READ2 = 0 builds the plain C++ reads for A/B.
-#ifndef F3_NO_READ2
-#define F3_NO_READ2 1
-#endif
 __device__ __forceinline__ unsigned f3_lds_addr(const double *p) { return (unsigned)reinterpret_cast<size_t>(p); }
 
 template <int OFF>
@@ -1178,23 +1168,12 @@ __device__ __forceinline__ void f3_bfly(Cx *a, Cx w1)
     }
 }
 
-#ifndef F3_PAIR
-#define F3_PAIR 0  // 1: both butterflies of a lane in flight together where a pass has two. Measured at C4: 8.5 ms
-                   // against 7.1 ms for the call (9.2 against 7.5 while the pair still spilled 50 registers: a scratch
-                   // reload waits for the prefetched samples like any other vector-memory load) - eight waves a CU already
-                   // keep the LDS queue full, a second butterfly per wave only lengthens every wave's wait for its data.
-#endif
-#ifndef F3_PRIO
-#define F3_PRIO 0
-#endif
-#ifndef F3_SKIP
-#define F3_SKIP 0  // timing experiments only (wrong results): 2 = no wave passes, 4 = no tail arithmetic, 8 = no partner reads
-#endif
-#ifndef F3_PREFETCH
-#define F3_PREFETCH 1  // the next series' samples fetched under the sub-transforms (0: at the top of each series)
-#endif
 // `b_lo`, `b_hi`: the lane's butterflies b_lo + lane, b_lo + lane + 64, ... < b_hi of the pass (all of them by default;
 // the SRC == 2 kernel runs a pass in two halves with a staging unit moved in between)
+// (A variant with both butterflies of a lane in flight together where a pass has two measured 8.5 ms against 7.1 ms for
+// the C4 call — 9.2 against 7.5 while it still spilled 50 registers: a scratch reload waits for the prefetched samples
+// like any other vector-memory load. Eight waves a CU already keep the LDS queue full; a second butterfly per wave
+// only lengthens every wave's wait for its data.)
 template <int LR, int LS>
 __device__ __forceinline__ void f3_wave_pass(double *re, double *im, int org, int len, const double2 *tw, int lane,
                                              int b_lo = 0, int b_hi = 1 << 30)
@@ -1209,47 +1188,18 @@ __device__ __forceinline__ void f3_wave_pass(double *re, double *im, int org, in
         return f2_skew(org + (blk << lb) + j);
     };
 #define F3_AT(i0, e) ((i0) + ((e) << LS) + (((e) << LS) >> 5))
-    if (F3_PAIR && nb == 128) {
-        // the second butterfly's reads are in flight under the first one's arithmetic, the first one's writes under
-        // the second one's
-        const int iA = first(lane), iB = first(lane + 64);
-        const double2 wa = tw[lane & (s - 1)], wb = tw[(lane + 64) & (s - 1)];
-        Cx a[R], c[R];
-#pragma unroll
-        for (int e = 0; e < R; ++e) a[e] = {re[F3_AT(iA, e)], im[F3_AT(iA, e)]};
-#pragma unroll
-        for (int e = 0; e < R; ++e) c[e] = {re[F3_AT(iB, e)], im[F3_AT(iB, e)]};
-        f3_bfly<LR>(a, Cx{wa.x, wa.y});
+    for (int b = b_lo + lane; b < nb && b < b_hi; b += 64) {
+        const int i0 = first(b);
+        const double2 wv = tw[b & (s - 1)];
+        Cx a[R];
+        f3_rd_bfly<LS>(a, f3_lds_addr(re + i0), f3_lds_addr(im + i0), std::make_integer_sequence<int, R>{});
+        if constexpr (LR == 3) f3_wait_8(a);
+        else f3_wait_4(a);
+        f3_bfly<LR>(a, Cx{wv.x, wv.y});
 #pragma unroll
         for (int e = 0; e < R; ++e) {
-            re[F3_AT(iA, e)] = a[e].x;
-            im[F3_AT(iA, e)] = a[e].y;
-        }
-        f3_bfly<LR>(c, Cx{wb.x, wb.y});
-#pragma unroll
-        for (int e = 0; e < R; ++e) {
-            re[F3_AT(iB, e)] = c[e].x;
-            im[F3_AT(iB, e)] = c[e].y;
-        }
-    } else {
-        for (int b = b_lo + lane; b < nb && b < b_hi; b += 64) {
-            const int i0 = first(b);
-            const double2 wv = tw[b & (s - 1)];
-            Cx a[R];
-#if F3_NO_READ2
-            f3_rd_bfly<LS>(a, f3_lds_addr(re + i0), f3_lds_addr(im + i0), std::make_integer_sequence<int, R>{});
-            if constexpr (LR == 3) f3_wait_8(a);
-            else f3_wait_4(a);
-#else
-#pragma unroll
-            for (int e = 0; e < R; ++e) a[e] = {re[F3_AT(i0, e)], im[F3_AT(i0, e)]};
-#endif
-            f3_bfly<LR>(a, Cx{wv.x, wv.y});
-#pragma unroll
-            for (int e = 0; e < R; ++e) {
-                re[F3_AT(i0, e)] = a[e].x;
-                im[F3_AT(i0, e)] = a[e].y;
-            }
+            re[F3_AT(i0, e)] = a[e].x;
+            im[F3_AT(i0, e)] = a[e].y;
         }
     }
 #undef F3_AT
@@ -1301,11 +1251,6 @@ __global__ __launch_bounds__(FT_THREADS) void msd_power_lds3_kernel(
     double *red = reinterpret_cast<double *>(tabB + 128);
     double2 *twp = reinterpret_cast<double2 *>(red + 32);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#if F3_PRIO
-    // one of the two waves of every SIMD issues first whenever both can: its LDS reads are served first, it computes
-    // while the other's are served, and the two stay half a phase apart instead of meeting at every LDS queue
-    if (wv < 4) __builtin_amdgcn_s_setprio(F3_PRIO);
-#endif
     if (tid < 256) tabA[tid] = tab[tid];
     const F2Plan pl = f3_plan(m);
     const FftItem it = items[blockIdx.x];
@@ -1387,15 +1332,11 @@ __global__ __launch_bounds__(FT_THREADS) void msd_power_lds3_kernel(
     const __amdgpu_buffer_rsrc_t ring = __builtin_amdgcn_make_buffer_rsrc(
         scratch + (size_t)sg.cluster * ST_BUF * 16 * (size_t)Fs, 0, (int)((size_t)ST_BUF * 16 * (size_t)Fs * 8), 0x00020000);
     constexpr int SC1 = 16, NT_HINT = 2;
-    bool st_on = true;  // (ST_SKIP & 2: off inside the series loop)
-#ifndef ST_LOAD8
-#define ST_LOAD8 0
-#endif
     auto stage_load = [&](long long i, int r, st2_t &sv) {
         const long long T = it.c_lo + i;
-        const bool row_in = st_on && i < nt && 64 * r < st_lim && !(ST_SKIP & 32);
+        const bool row_in = i < nt && 64 * r < st_lim;
         const unsigned soff = (unsigned)(((size_t)(64 * r) * (size_t)cols + (size_t)(16 * T)) * 8);
-        if (ST_LOAD8 || odd_cols) {
+        if (odd_cols) {
             // an odd number of columns: rows start on odd multiples of 8 bytes and the matrix's last column has no
             // partner — two 8-byte loads, each with its own range test (only the matrix's last tile can reach beyond a
             // row's end, where the next row's first columns must not be taken for this tile's)
@@ -1419,7 +1360,7 @@ __global__ __launch_bounds__(FT_THREADS) void msd_power_lds3_kernel(
         const int lo = __builtin_amdgcn_mov_dpp(__double2loint(send), 0xB1, 0xF, 0xF, true);  // quad_perm [1, 0, 3, 2]
         const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(send), 0xB1, 0xF, 0xF, true);
         const double recv = __hiloint2double(hi, lo);
-        const bool in = st_on && i < nt && 64 * r < st_lim2 && !(ST_SKIP & 16);
+        const bool in = i < nt && 64 * r < st_lim2;
         const st2_t out = odd ? st2_t{recv, b} : st2_t{a, recv};
         const unsigned soff = (unsigned)(((size_t)(i & (ST_BUF - 1)) * 16 * (size_t)Fs + (size_t)(64 * r)) * 8);
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(st4_t, out), ring, in ? st_vo : ST_OOB, soff, SC1);
@@ -1438,7 +1379,7 @@ __global__ __launch_bounds__(FT_THREADS) void msd_power_lds3_kernel(
     };
     auto st_wait = [&](long long i, unsigned seen) {
         const unsigned need = 16u * (unsigned)((i >> 3) + 1);
-        if (stalled || seen >= need || (ST_SKIP & 1)) return;
+        if (stalled || seen >= need) return;
         const unsigned *w = st_flag(i);
         unsigned *stall = ready + (size_t)(gridDim.x / 16) * ST_BUF * ST_FLAG_STRIDE;
         for (int spin = 1; __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need; ++spin) {
@@ -1540,7 +1481,6 @@ __global__ __launch_bounds__(FT_THREADS) void msd_power_lds3_kernel(
         mean = ft_block_sum(lane_sum(), red) / (double)F;
     }
     const int cstep = SRC == 2 ? 1 : it.step;
-    if (ST_SKIP & 2) st_on = false;
     for (long long c = it.c_lo; c < it.c_hi; c += cstep) {
         // SRC == 2: tile st_i is staged under this series, five 16-byte units per lane, each stored TWO points of the
         // iteration after it was requested (4100 - 6500 cycles: a load from HBM takes ~2500 here, and with one point
@@ -1599,7 +1539,7 @@ __global__ __launch_bounds__(FT_THREADS) void msd_power_lds3_kernel(
                 }
             }
         }
-        const bool more = (F3_PREFETCH || SRC == 2) && c + cstep < it.c_hi;
+        const bool more = c + cstep < it.c_hi;
         if constexpr (SRC == 2) ST_POINT(P_B);
         else if (more) fetch(c + cstep);
         __syncthreads();
@@ -1615,7 +1555,7 @@ __global__ __launch_bounds__(FT_THREADS) void msd_power_lds3_kernel(
                     // what this wave stored for the tile staged under the PREVIOUS series (its last units at A / A2) has
                     // long been issued: waiting for everything in flight here is free (the youngest request is a phase
                     // old), and lets the second barrier below carry the signal for that tile
-                    if (!(ST_SKIP & 4)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     ST_POINT(P_C);
                 }
             };
@@ -1626,15 +1566,12 @@ __global__ __launch_bounds__(FT_THREADS) void msd_power_lds3_kernel(
                 }
             };
             auto pd = [&]() { ST_POINT(P_D); };
-#if F3_SKIP & 2
-            if (F == 1) {
-#else
             if (JJ == 2 || m == 13) {
-#endif
                 if constexpr (SRC == 2) {
                     // (two butterflies per lane and pass: the halves of a pass touch different points, no barrier between)
                     // (the bound is opaque: with trip counts it can see, the compiler unrolls the halves into one
-                    // schedule with both butterflies' reads in flight — 120 spilled registers, as F3_PAIR found)
+                    // schedule with both butterflies' reads in flight — 120 spilled registers, as the paired variant
+                    // of f3_wave_pass found)
                     int h64 = 64;
                     asm volatile("" : "+s"(h64));
                     f3_wave_pass<3, 7>(re, im, org, s0, tw1, lane, 0, h64);
@@ -1678,17 +1615,10 @@ __global__ __launch_bounds__(FT_THREADS) void msd_power_lds3_kernel(
         }
         Cx z[PR];
         if (owner) {
-#if F3_NO_READ2
             f3_rd_run<0, 1>(z, f3_lds_addr(re + p0), f3_lds_addr(im + p0), std::make_integer_sequence<int, PR>{});
             f3_wait_8(z);
             f3_pass_8(z + 8);
-#else
-#pragma unroll
-            for (int e = 0; e < PR; ++e) z[e] = {re[p0 + e], im[p0 + e]};
-#endif
-#if !(F3_SKIP & 4)
             f2_dft16(z);
-#endif
             // only positions 8 .. 15 go back to LDS: they are what the partner block's lane reads (its 15 - u,
             // u < 8); lane 0 of wave 0 pairs inside its own block and takes its partners from the registers
 #pragma unroll
@@ -1719,23 +1649,14 @@ __global__ __launch_bounds__(FT_THREADS) void msd_power_lds3_kernel(
         }
         __syncthreads();
         if constexpr (SRC == 2) {
-            if (c > it.c_lo && !(ST_SKIP & 4)) st_signal(st_i - 1);  // (the prologue signalled its own tiles)
+            if (c > it.c_lo) st_signal(st_i - 1);  // (the prologue signalled its own tiles)
             ST_POINT(P_G);
         }
-#if F3_SKIP & 8
-        if (owner && F == 1) {
-#else
         if (owner && !kb0) {
-#endif
             // T at 8 of the 16 positions, the partner block's lane has the other 8 (see msd_power_lds2_kernel)
             Cx pz[8];  // pz[u] = the partner block's position 15 - u
-#if F3_NO_READ2
             f3_rd_run<15, -1>(pz, f3_lds_addr(re + pb), f3_lds_addr(im + pb), std::make_integer_sequence<int, 8>{});
             f3_wait_8(pz);
-#else
-#pragma unroll
-            for (int u = 0; u < 8; ++u) pz[u] = {re[pb + 15 - u], im[pb + 15 - u]};
-#endif
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 tacc[u] = __builtin_fma(z[u].x, pz[u].y, tacc[u]);
@@ -1761,10 +1682,6 @@ __global__ __launch_bounds__(FT_THREADS) void msd_power_lds3_kernel(
 #pragma unroll
             for (int w = 0; w < FT_THREADS / 64; ++w) sum += red[8 + w];
             mean = sum / (double)F;
-        }
-        if (!F3_PREFETCH && SRC != 2 && c + cstep < it.c_hi) {
-            fetch(c + cstep);
-            mean = ft_block_sum(lane_sum(), red) / (double)F;
         }
     }
 #undef ST_POINT
@@ -2121,9 +2038,7 @@ int lag_msd_fft_fused(CallScope &cs, long long F, long long E, const double *d_r
     // tiles inside the kernel through a small ring (SRC == 2 of msd_power_lds3_kernel): any 16 blocks, rows per member
     // Fc = F / 16 rounded up to whole 128-byte lines, at most 64 ST_UNITS.
     const int n_clusters = ctx->cu_count / 16;
-#ifndef LAG_DIRECT_DEFAULT
-#define LAG_DIRECT_DEFAULT 2
-#endif
+    constexpr int LAG_DIRECT_DEFAULT = 2;  // where the series come from when the option is -1
     const int src_opt = src_want >= 0 ? src_want : ctx->opt_lag_direct >= 0 ? ctx->opt_lag_direct : LAG_DIRECT_DEFAULT;
     const int Fc = (int)((((F + 15) / 16) + 15) / 16 * 16);
     const bool staged = (v3 || w12) && (src_opt == 2 || src_opt == 3) && ctx->cu_count % 16 == 0 && n_clusters >= 1 &&

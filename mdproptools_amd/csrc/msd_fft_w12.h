@@ -34,11 +34,6 @@ constexpr int W12_SUB = 512;                // points per sub-transform
 constexpr int W12_N = W12_NW * W12_SUB;     // 6144
 constexpr int W12_RS = 520;                 // points between two regions (the second exchange uses 8 x 65)
 constexpr int W12_UN = 4;                   // staging units per lane and tile (96 rows a round: rows per member <= 384)
-#ifndef W12_EXP
-#define W12_EXP 0  // timing experiments only (WRONG results): 1 no first barrier, 2 no second, 4 no third, 8 no partner phase,
-                   // 16 no exchanges (LDS writes + reads of the register passes), 32 no butterfly arithmetic in the passes,
-                   // 64 no first-pass arithmetic, 128 no staging (SRC == 2: loads, stores), 256 no staging loads, 512 no staging stores
-#endif
 // A 16-byte buffer store hands its data registers to the memory pipeline over more than one cycle: a vector instruction
 // that WRITES one of them in the cycle behind the store changes what some lanes store. The compiler knows the hazard
 // (one or two idle cycles behind stores of more than 8 bytes) but not for buffer stores whose scalar offset is a
@@ -49,7 +44,6 @@ constexpr int W12_UN = 4;                   // staging units per lane and tile (
 // 1.013 instead of 1; tools/w12.py ramp). The guard keeps the data registers live across two idle cycles behind the
 // store; tests/test_codegen_cpu.py scans the compiled kernels for the pattern.
 #define W12_STORE_GUARD(v) asm volatile("s_nop 1" ::"v"(v))
-#define W12_BARRIER(bit) do { if (!(W12_EXP & (bit))) __syncthreads(); } while (0)
 
 // LDS: regions | raw plane (QE x 512 points) | two-level twiddle table | b table [12][8] | w_512^lane [64] |
 // w_64^(n0 k1) [8][9] | red
@@ -211,7 +205,7 @@ __global__ __launch_bounds__(W12_THREADS) void msd_power_w12_kernel(
         const st2_t out = st2_t{sv[0] * scale, sv[1] * scale};
         const unsigned soff = (unsigned)(((size_t)(i & (ST_BUF - 1)) * 16 * (size_t)Fs + (size_t)(RPR * r)) * 8);
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(st4_t, out), ring, RPR * r < lim ? st_vo : ST_OOB, soff,
-                                               (W12_EXP & 1024) ? 0 : SC1);  // (timing: a store that ends in this XCD's L2)
+                                               SC1);
         W12_STORE_GUARD(out);
     };
     auto st_flag = [&](long long i) { return ready + ((size_t)sg.cluster * ST_BUF + (size_t)(i & (ST_BUF - 1))) * ST_FLAG_STRIDE; };
@@ -331,33 +325,12 @@ __global__ __launch_bounds__(W12_THREADS) void msd_power_w12_kernel(
     }
     if (it.c_lo < it.c_hi) {  // (a cluster member whose column lies outside the segment transforms zeros)
         fetch(it.c_lo);
-#ifdef W12_VERIFY
-        if constexpr (SRC == 2) {
-            const long long coln = 16 * it.c_lo + sg.k;
-            if (coln >= sg.lo && coln < sg.hi) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int n = tid + W12_THREADS * r;
-                    for (int h = 0; h < 2; ++h) {
-                        const int t = 2 * n + h;
-                        if (t < F && v[r][h] != 16384.0 * (double)coln + (double)t)
-                            printf("BAD0 block %d k %d tile %lld t %d got %.1f want %.1f\n", (int)blockIdx.x, sg.k, it.c_lo, t,
-                                   v[r][h], 16384.0 * (double)coln + (double)t);
-                    }
-                }
-            }
-        }
-#endif
         wave_sum(0);
         __syncthreads();
         centre_store(0);
     }
     __syncthreads();
     const int cstep = SRC == 2 ? 1 : it.step;
-#ifdef W12_VERIFY
-    double vfirst = 0.0;
-    int vfirst_set = 0;
-#endif
     const int c3 = wv % 3, g4 = wv / 3;  // first pass: this wave's residue c = d mod 3 and its quarter of the positions j
     double2 *myR = R + wv * RS;
     const double2 *pR = R + pw * RS;
@@ -365,13 +338,13 @@ __global__ __launch_bounds__(W12_THREADS) void msd_power_w12_kernel(
         const long long st_i = c - it.c_lo + ST_AHEAD;
         // Staging points 0 .. 5 of the iteration: point P stores the unit requested two points ago (P - 2) and requests
         // unit P (< W12_UN), units alternating between the two register pairs (msd_power_lds3_kernel's scheme).
-        // Two other schedules were measured against this one in one process (tools/w12.py exp, C4 call, 4.23-4.28 ms
+        // Two other schedules were measured against this one in one process (C4 call, 4.23-4.28 ms
         // here; 3.52 ms with no staging at all): every unit stored FOUR points after its request (four units, 16
         // registers, live throughout; the signal two series later) 4.33-4.37 ms; all four units requested at the end of
         // the series before and stored together behind the first register pass 4.72 ms. The staging's cost is not the
         // distance between request and use: with it the call moves 18 GB through the fabric port (trajectory in, ring
         // out, ring in: profiles/pmc_secondary.json) in ~4.2 ms.
-        // What it is, from timing builds in one process (W12_EXP 256 / 512 / 128 / 1024; the full kernel 4.11-4.16 ms):
+        // What it is, from timing builds in one process (the full kernel 4.11-4.16 ms):
         // no trajectory loads (zeros stored, ring read back) 3.53 ms; loads but no ring stores 3.75 ms; neither 3.56 ms;
         // ring stores without sc1 4.07-4.17 ms (no change). The stores alone are free, the loads alone cost 0.2 ms, both
         // 0.57 ms: the price follows the BYTES through the fabric port — 6 GB (ring in) 3.56 ms, 12 GB 3.5-3.75 ms,
@@ -390,16 +363,10 @@ __global__ __launch_bounds__(W12_THREADS) void msd_power_w12_kernel(
         if constexpr (SRC == 2) st_lim = st_lim_of(st_i);
         auto point = [&](auto pk) {
             constexpr int P = decltype(pk)::value;
-            if constexpr (SRC == 2 && !(W12_EXP & 128)) {
+            if constexpr (SRC == 2) {
                 st2_t &reg = (P & 1) ? sy : sx;
-                if constexpr (P >= 2 && P - 2 < W12_UN) {
-                    if constexpr (W12_EXP & 512) asm volatile("" ::"v"(reg));  // (timing: the unit is loaded, not stored)
-                    else stage_store(st_i, P - 2, st_lim, reg);
-                }
-                if constexpr (P < W12_UN) {
-                    if constexpr (W12_EXP & 256) reg = st2_t{0.0, 0.0};  // (timing: nothing is loaded, zeros are stored)
-                    else stage_load(st_i, P, st_lim, reg);
-                }
+                if constexpr (P >= 2 && P - 2 < W12_UN) stage_store(st_i, P - 2, st_lim, reg);
+                if constexpr (P < W12_UN) stage_load(st_i, P, st_lim, reg);
             }
         };
 #define W12_POINT(P) point(std::integral_constant<int, (P)>())
@@ -416,29 +383,26 @@ __global__ __launch_bounds__(W12_THREADS) void msd_power_w12_kernel(
             Cx z[QE], o[4];
 #pragma unroll
             for (int e = 0; e < QE; ++e) z[e] = w12_ld(raw + j + W12_SUB * e);
-            if (W12_EXP & 64) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) o[q] = z[q];
-            } else if (c3 == 0) w12_head<QE, 0>(z, o);
+            if (c3 == 0) w12_head<QE, 0>(z, o);
             else if (c3 == 1) w12_head<QE, 1>(z, o);
             else w12_head<QE, 2>(z, o);
 #pragma unroll
             for (int q = 0; q < 4; ++q) w12_st(R + (c3 + 3 * q) * RS + j, o[q]);
         }
         W12_POINT(1);
-        W12_BARRIER(1);
+        __syncthreads();
         // the raw plane is free: the next series' samples are requested into registers and land under the passes
         if (more) fetch(c + cstep, seen);
         // ---- this wave's 512-point sub-transform, in registers ----
         Cx a[8];
 #pragma unroll
         for (int n2 = 0; n2 < 8; ++n2) a[n2] = w12_ld(myR + lane + 64 * n2);
-        if (wv != 0 && !(W12_EXP & 32)) {
+        if (wv != 0) {
 #pragma unroll
             for (int n2 = 1; n2 < 8; ++n2) a[n2] = cx_mul(a[n2], w12_ld(btab + wv * 8 + n2));
         }
-        if (!(W12_EXP & 32)) f2_bfly8(a, Cx{1.0, 0.0}, false);
-        if (!(W12_EXP & 32)) {
+        f2_bfly8(a, Cx{1.0, 0.0}, false);
+        {
             const Cx tw_1 = w12_ld(t1tab + lane);
             Cx t = tw_a;  // w_N^(lane d) w_512^(lane k2), k2 = 0..7
             a[0] = cx_mul(a[0], t);
@@ -451,14 +415,12 @@ __global__ __launch_bounds__(W12_THREADS) void msd_power_w12_kernel(
         // exchange 1: (n0, n1 | k2) -> (n0, k2 | n1): point n0 + 8 k2 + 64 n1
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if (!(W12_EXP & 16)) {
 #pragma unroll
         for (int k2 = 0; k2 < 8; ++k2) w12_st(myR + (lane & 7) + 8 * k2 + 64 * (lane >> 3), a[k2]);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int n1 = 0; n1 < 8; ++n1) a[n1] = w12_ld(myR + lane + 64 * n1);
-        }
         if constexpr (SRC == 2) {
             // what this wave stored for the tile staged under the PREVIOUS series has long been issued, and the youngest
             // request in flight (the next series' samples) is a pass old: waiting for everything here lets the second
@@ -468,8 +430,8 @@ __global__ __launch_bounds__(W12_THREADS) void msd_power_w12_kernel(
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         W12_POINT(2);
-        if (!(W12_EXP & 32)) f2_bfly8(a, Cx{1.0, 0.0}, false);
-        if (!(W12_EXP & 32)) {
+        f2_bfly8(a, Cx{1.0, 0.0}, false);
+        {
             // w_64^(n0 k1) from the table (7 reads of 16 bytes, the 8 lanes of an n0 reading one address) instead of six
             // chained complex products: the kernel is short of vector issue, not of LDS reads
             const double2 *t2 = t2tab + 9 * (lane & 7);
@@ -479,16 +441,14 @@ __global__ __launch_bounds__(W12_THREADS) void msd_power_w12_kernel(
         // exchange 2: (n0, k2 | k1) -> (k1, k2 | n0): point k1 + 8 k2 + 65 n0
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        if (!(W12_EXP & 16)) {
 #pragma unroll
         for (int k1 = 0; k1 < 8; ++k1) w12_st(myR + k1 + 8 * (lane >> 3) + 65 * (lane & 7), a[k1]);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int n0 = 0; n0 < 8; ++n0) a[n0] = w12_ld(myR + lane + 65 * n0);
-        }
         W12_POINT(3);
-        if (!(W12_EXP & 32)) f2_bfly8(a, Cx{1.0, 0.0}, false);
+        f2_bfly8(a, Cx{1.0, 0.0}, false);
         // a[k0] = Z at frequency d + 12 (k2 + 8 k1 + 64 k0), lane = k1 + 8 k2
 #pragma unroll
         for (int k0 = 0; k0 < 8; ++k0) {
@@ -512,11 +472,11 @@ __global__ __launch_bounds__(W12_THREADS) void msd_power_w12_kernel(
         }
         W12_POINT(4);
         if (more) wave_sum(0);
-        W12_BARRIER(2);
+        __syncthreads();
         if constexpr (SRC == 2) {
             if (c > it.c_lo) st_signal(st_i - 1);  // (the prologue signalled its own tiles)
         }
-        if (!self0 && !(W12_EXP & 8)) {
+        if (!self0) {
             Cx pz[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) pz[u] = w12_ld(pR + plane + 64 * (3 - u));  // the partner's register 7 - u
@@ -528,7 +488,7 @@ __global__ __launch_bounds__(W12_THREADS) void msd_power_w12_kernel(
         }
         W12_POINT(5);
         if (more) centre_store(0);
-        W12_BARRIER(4);
+        __syncthreads();
 #undef W12_POINT
     }
     if constexpr (SRC == 2) {

@@ -31,10 +31,6 @@
 //   msd_power_w1_kernel<D2>      F <= 1536: the 512-point sub-transform as the whole transform, one wave per series;
 //   msd_residue_inverse_kernel   the correlations of a non-power-of-two length, directly.
 
-#ifndef W12R_EXP
-#define W12R_EXP 0  // timing experiments only (WRONG results): 1 no input stage, 2 no head, 4 no register passes
-#endif
-
 template <int K, int DD>
 __device__ __forceinline__ Cx w12r_root_mul(double a)  // a * w_DD^K (a real), DD = 4 or 8
 {
@@ -212,7 +208,7 @@ __global__ __launch_bounds__(W12_THREADS) void msd_power_w12r_kernel(const doubl
             constexpr int cls = decltype(ck)::value;
             // ---- the class's inputs y_cls[n] (but for the factor w_L'^(cls j), which rides in the register passes) ----
 #pragma unroll
-            for (int i = 0; i < ((W12R_EXP & 1) ? 1 : 8); ++i) {
+            for (int i = 0; i < 8; ++i) {
                 const int n = tid + W12_THREADS * i, e = n >> 9, j = n & 511;
                 // sum_q x[n + 6144 q] w_D^(cls q)
                 Cx s = {xs[i][0], 0.0};
@@ -227,13 +223,12 @@ __global__ __launch_bounds__(W12_THREADS) void msd_power_w12r_kernel(const doubl
             }
             __syncthreads();
             // ---- head: waves 0 .. 7, the radix-12 butterfly of position j in place ----
-            if (wv < 8 && !(W12R_EXP & 2)) w12r_dft12(R + hj);
+            if (wv < 8) w12r_dft12(R + hj);
             __syncthreads();
             // ---- this wave's 512-point sub-transform, in registers (msd_power_w12_kernel) ----
             Cx a[8];
 #pragma unroll
             for (int n2 = 0; n2 < 8; ++n2) a[n2] = w12_ld(myR + lane + 64 * n2);
-            if (!(W12R_EXP & 4)) {
             if (wv != 0 || cls != 0) {
 #pragma unroll
                 for (int n2 = 1; n2 < 8; ++n2) a[n2] = cx_mul(a[n2], w12_ld(btab_s + (cls * W12_NW + wv) * 8 + n2));
@@ -275,7 +270,6 @@ __global__ __launch_bounds__(W12_THREADS) void msd_power_w12r_kernel(const doubl
 #pragma unroll
             for (int n0 = 0; n0 < 8; ++n0) a[n0] = w12_ld(myR + lane + 65 * n0);
             f2_bfly8(a, Cx{1.0, 0.0}, false);
-            }
             // a[k0] = Y_cls at j = d + 12 (k2 + 8 k1 + 64 k0), lane = k1 + 8 k2
             if constexpr (cls == 0) {
 #pragma unroll

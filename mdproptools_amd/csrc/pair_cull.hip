@@ -2,9 +2,6 @@
 // neighbour-tile lists (SURVEY.md 8f "cell-list variant").
 #include "pair_common.h"
 
-#ifndef SORT_EXP
-#define SORT_EXP 0  // timing experiments of cull_sort_reg_kernel: 1 no division, 2 no Hilbert arithmetic (a plain key)
-#endif
 namespace mdpair {
 namespace {
 
@@ -246,8 +243,8 @@ __global__ __launch_bounds__(SORT_THREADS) void cull_sort_lds_kernel(
 // else to run meanwhile — and took 69 us for the 10k atoms of a C2 frame, a third of it arithmetic. Here a thread's
 // ITEMS atoms (coordinates and type) are requested at the top, all at once, and stay in registers through the three
 // phases; the keys never leave the registers either. 59 us (pre-pass of a C2 step 101 -> 92 us). What is left is not
-// arithmetic (timing builds, -DSORT_EXP: a multiplication for the division of wrapped_frac 0 us, a plain key instead
-// of the Hilbert arithmetic -8 us): the 200 blocks move 56 MB in and 64 MB out in lockstep — all read, all compute,
+// arithmetic (timing builds measured a multiplication for the division of wrapped_frac at 0 us, a plain key instead
+// of the Hilbert arithmetic at -8 us): the 200 blocks move 56 MB in and 64 MB out in lockstep — all read, all compute,
 // all write — so the memory system idles through the middle of every block's life. (Non-temporal stores of the
 // scattered records: 92 -> 204 us, they lose the L2's write combining; of cull_boxes_kernel's f32 records: the
 // pre-pass the same, the sweep that reads them +17 us. Neither kept.)
@@ -313,21 +310,10 @@ __global__ __launch_bounds__(SORT_THREADS) void cull_sort_reg_kernel(
             unsigned c[3];
 #pragma unroll
             for (int ax = 0; ax < 3; ++ax) {
-#if SORT_EXP & 1
-                const double sfr = (p[ax] - org[ax]) * (1.0 / L[ax]);
-                double fr = sfr - __builtin_floor(sfr);
-                fr = fr < 1.0 ? fr : 0.0;
-                int v = (int)(fr * G);
-#else
                 int v = (int)(wrapped_frac(p[ax] - org[ax], L[ax]) * G);
-#endif
                 c[ax] = (unsigned)(v < 0 ? 0 : v > (1 << MORTON_BITS) - 1 ? (1 << MORTON_BITS) - 1 : v);
             }
-#if SORT_EXP & 2
-            key[k] = (c[0] | (c[1] << 5) | (c[2] << 10)) & 0xFFFFu;
-#else
             key[k] = hilbert3(c[0], c[1], c[2]) & 0xFFFFu;  // (the other kernel keeps its keys in 16 bits)
-#endif
             atomicAdd(&s_cells[sort_cell(key[k])], 1u);
         }
     }

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """tools/check_lag_sizes.py LIB.so [key=value ...] — the fused full-lag MSD kernel of one BUILD of libmdhip.so against
 the difference kernel (lag_variant 1, exact) over series lengths that cover every transform size 2^9 .. 2^13, full and
-truncated lag ranges, ragged groups. For variant builds (tools/build_variant.sh ... -DF3_MIN_M=9 puts the wave-private
-kernel on every size). Exit code 1 when a result is outside the bound the library reports."""
+truncated lag ranges, ragged groups. For variant builds (a build with F3_MIN_M in msd_fft.hip lowered to 9 puts the
+wave-private kernel on every size). Exit code 1 when a result is outside the bound the library reports."""
 import os
 import sys
 

@@ -4,8 +4,6 @@
   check [quick]   against the round-3/4 kernel (lag_fft_kernel 2, padded length 16384) and the exact-difference kernel on
                   shapes that take it (F + max_lag in (8192, 12288]), both sources (lag_direct 0: transposed copy, 2: in-kernel
                   staging): times and relative differences                                  -> profiles/rNN_w12_check.txt
-  exp LIB.so ...  C4-shape call time through several BUILDS (-DW12_EXP=bits timing builds give wrong results and only say
-                  where the time goes; tools/build_variant.sh makes them), both sources      -> profiles/rNN_w12_exp.txt
   det LIB.so ...  six staged runs per build: bit-identical? relative difference to the copy source
   ramp [LIB.so]   integer ramp x[t][c] = 16384 c + t: MSD(k) = k^2 exactly (the input that exposed the unguarded store
                   hazard of round 5; the regression test is tests/test_gpu_hardening.py)
@@ -81,24 +79,6 @@ def mode_check():
     print("fallbacks", ctx.fallbacks())
 
 
-def mode_exp():
-    F, E = 5000, 50_000
-    r = walk(F, E, 1)
-    for p in libs:
-        ctx = context_of(p)
-        ctx.set_option("lag_variant", 2)
-        row = []
-        for src in (0, 2):
-            ctx.set_option("lag_direct", src)
-            ms = []
-            for _ in range(4):
-                B.lag_msd(r, F - 1, [0, E], ctx=ctx)
-                ms.append(ctx.last_kernel_ms()[0])
-            row.append(min(ms[1:]))
-        print("%-28s copy %.3f ms   staged %.3f ms   %s" % (os.path.basename(p), row[0], row[1], ctx.last_kernel_name()), flush=True)
-        ctx.close()
-
-
 def mode_det():
     F, E = 5000, 8192
     r = walk(F, E, F + E)
@@ -134,4 +114,4 @@ def mode_ramp():
                 F, E, src, ctx.last_kernel_name(), d.max(), d.max(axis=0), ctx.fallbacks()), flush=True)
 
 
-{"check": mode_check, "exp": mode_exp, "det": mode_det, "ramp": mode_ramp}[mode]()
+{"check": mode_check, "det": mode_det, "ramp": mode_ramp}[mode]()
