@@ -544,6 +544,31 @@ int mdhip_shell_residence(mdhip_ctx *ctx, int64_t n_frames, int64_t n_i, const d
                           int64_t n_j, const double *xj, int xj_on_device, const double *box, double r_lo_sq,
                           double r_hi_sq, int exclude_diagonal, uint64_t *counts, uint64_t *n_records);
 
+/* ---- solvation shells of cluster extraction (cluster_analysis.py get_clusters) ---- */
+/*
+ * Replaces the per-centre pair work of get_clusters            structural/cluster_analysis.py:47-235
+ * for a batch of frames: coordinates xyz [F][3][n_atoms] (atoms in ascending-id order), box [F][3], centre atom
+ * indices centres[n_centres], mol_of[n_atoms] the molecule index of every atom (molecules are contiguous runs of
+ * atoms, as num_mols / num_atoms_per_mol lay them out, cluster_analysis.py:113-120).
+ *   shell(f, c) = { mol_of[a] : rsq(centre c, atom a) < r_cut_sq }  cluster_analysis.py:127-142
+ * with the reference's single-wrap rsq (rdf_cn.py:36-58: d = centre - atom, wrapped once when d > L/2 or
+ * d < -L/2, (dx*dx + dy*dy) + dz*dz unfused); r_cut_sq is the caller's r_cut ** 2.
+ *   mols [F][n_centres][cap]: the shell's molecule indices, ascending, padded with -1;
+ *   count[F][n_centres]: the number of shell molecules, exact even when it exceeds cap (that row of mols is then
+ *   incomplete: call again for its frame with cap >= count). 1 <= cap <= 16384.
+ */
+int mdhip_shell_members(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int xyz_on_device,
+                        const double *box, int32_t n_centres, const int32_t *centres, const int32_t *mol_of,
+                        double r_cut_sq, int32_t cap, int32_t *mols, int32_t *count);
+/*
+ * The per-molecule sums of the cluster force filter            cluster_analysis.py:146-152
+ * (groupby(["mol_type", "mol_id"]).agg({"fx": "sum", ...})): attr [F][n_attr][n_atoms] -> out [F][n_attr][n_mols],
+ * molecule m the atoms [seg_off[m], seg_off[m+1]). Each value is pandas' compensated group sum over the atoms in
+ * ascending order: y = v - c; t = s + y; c = (t - s) - y; s = t (bit-identical to pandas, not to a plain sum).
+ */
+int mdhip_mol_kahan_sums(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, int n_attr, const double *attr,
+                         int attr_on_device, int64_t n_mols, const int64_t *seg_off, double *out);
+
 /*
  * Replaces, for the inputs of the path, the un-vendored pymatgen `parse_lammps_dumps` + pandas
  * `read_csv` the reference uses (call sites structural/rdf_cn.py:176, dynamical/diffusion.py:172,

@@ -124,6 +124,9 @@ PROTOTYPES = {
                                              vp]),
     "mdhip_shell_residence": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, C.c_int64, vp, C.c_int, c_dp,
                                         C.c_double, C.c_double, C.c_int, c_up, c_up]),
+    "mdhip_shell_members": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int32, c_ip, c_ip,
+                                      C.c_double, C.c_int32, c_ip, c_ip]),
+    "mdhip_mol_kahan_sums": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, vp, C.c_int, C.c_int64, c_lp, c_dp]),
     "mdhip_dump_open": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "mdhip_dump_close": (None, [vp]),
     "mdhip_dump_error": (C.c_char_p, [vp]),

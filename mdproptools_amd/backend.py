@@ -560,3 +560,73 @@ def shell_residence(xyz_i, xyz_j, box, r_lo_sq, r_hi_sq, exclude_diagonal=False,
         ctx.h, F, Ni, ip, i_dev, Nj, jp, j_dev, ptr(bx), float(r_lo_sq), float(r_hi_sq),
         int(bool(exclude_diagonal)), ptr(counts, C.c_uint64), C.byref(nrec)))
     return counts, int(nrec.value)
+
+
+SHELL_CAP = 32  # first-try molecules per (frame, centre) row of shell_members; rows that hold more are re-run
+
+
+def shell_members(xyz, box, centres, mol_of, r_cut_sq, cap=SHELL_CAP, ctx=None):
+    """
+    Solvation shells of get_clusters (cluster_analysis.py:127-142): xyz [F,3,N] (atoms in id order), box [F,3],
+    centre atom indices [C], mol_of [N] (contiguous molecules) -> (mols int32 [F,C,K], count int32 [F,C]).
+    Row (f, c) of mols holds the count[f, c] molecules with an atom at rsq < r_cut_sq from centre c, ascending, then
+    -1 up to K = max(cap, largest count). Frames whose shells overflow `cap` are run again with a cap of their
+    largest count (include/mdhip.h: mdhip_shell_members).
+    """
+    ctx = ctx or default_context()
+    F, _, N = _shape3(xyz, "xyz")
+    cen = _i32(centres).ravel()
+    mol = _i32(mol_of).ravel()
+    if len(mol) != N:
+        raise ValueError("mol_of must hold one molecule index per atom")
+    C_ = len(cen)
+    bx = _f64(box).reshape(F, 3)
+    xp, x_dev, keep = as_input(xyz, ctx)
+    cap = max(1, int(cap))
+    mols = np.empty((F, C_, cap), dtype=np.int32)
+    count = np.zeros((F, C_), dtype=np.int32)
+    ctx.check(ctx.lib.mdhip_shell_members(
+        ctx.h, F, N, xp, x_dev, ptr(bx), C_, ptr(cen, C.c_int32), ptr(mol, C.c_int32), float(r_cut_sq), cap,
+        ptr(mols, C.c_int32), ptr(count, C.c_int32)))
+    over = np.flatnonzero((count > cap).any(axis=1)) if C_ else np.zeros(0, dtype=np.int64)
+    if len(over) == 0:
+        return mols, count
+    big = int(count[over].max())
+    out = np.full((F, C_, big), -1, dtype=np.int32)
+    out[:, :, :cap] = mols
+    if not x_dev:
+        sub = np.ascontiguousarray(keep[over])
+    elif hasattr(xyz, "index_select"):  # a torch tensor: the overflowing frames stay on the device
+        import torch
+
+        sub = xyz.index_select(0, torch.as_tensor(over, device=xyz.device)).contiguous()
+    else:
+        raise ValueError("shells overflow cap=%d: pass a larger cap with a DevPtr input" % cap)
+    sp, s_dev, keep2 = as_input(sub, ctx)
+    sbx = np.ascontiguousarray(bx[over])
+    rm = np.empty((len(over), C_, big), dtype=np.int32)
+    rc = np.zeros((len(over), C_), dtype=np.int32)
+    ctx.check(ctx.lib.mdhip_shell_members(
+        ctx.h, len(over), N, sp, s_dev, ptr(sbx), C_, ptr(cen, C.c_int32), ptr(mol, C.c_int32), float(r_cut_sq), big,
+        ptr(rm, C.c_int32), ptr(rc, C.c_int32)))
+    if not np.array_equal(rc, count[over]):
+        raise RuntimeError("shell_members: the re-run found other shell sizes than the first sweep")
+    out[over] = rm
+    return out, count
+
+
+def mol_kahan_sums(attr, seg_off, ctx=None):
+    """
+    Per-molecule sums of get_clusters' force filter (cluster_analysis.py:146-152): attr [F,K,N] -> [F,K,M], molecule m
+    the atoms [seg_off[m], seg_off[m+1]), each value pandas' compensated groupby().sum() in ascending atom order.
+    """
+    ctx = ctx or default_context()
+    if len(attr.shape) != 3:
+        raise ValueError("attr must have shape [n_frames, n_attr, n_atoms]")
+    F, K, N = tuple(attr.shape)
+    off = _i64(seg_off).ravel()
+    M = len(off) - 1
+    ap, a_dev, keep = as_input(attr, ctx)
+    out = np.zeros((F, K, M), dtype=np.float64)
+    ctx.check(ctx.lib.mdhip_mol_kahan_sums(ctx.h, F, N, K, ap, a_dev, M, ptr(off, C.c_int64), ptr(out)))
+    return out
