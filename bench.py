@@ -3,6 +3,7 @@
 bench.py — throughput of the RDF hot path (atom-pairs/s) on N GPUs of one node.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full   # + the MSD object, CPU baselines, parity and the legs
     python bench.py --gpus 4                       # starts 4 fresh ranks itself (torch.distributed.run), see spawn()
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -22,15 +23,18 @@ For N > 1 the frame-summed uint64 histograms are all-reduced over RCCL in every 
                             dynamical/diffusion.py:212-218) and its fixed-lag windows (one-frame halo, [E][4] all-reduced;
                             diffusion.py:225-237), the 50 000 entities for the full lag x origin average (no exchange in,
                             [F][G][4] all-reduced). Every collective runs on device buffers, inside the timed region.
-The default line carries the same measurement as the object `msd` (fewer steps), so that one run per N gives both halves
-of BASELINE.json's metric: atom-pairs/s (RDF) and frame-pairs/s (MSD).
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes --dump-outputs and prints
+the line. Everything else it can measure or check runs only with --full (after the timed steps, which it leaves as they
+are): the object `msd` (the --workload c4 step at the RDF line's N, fewer steps, so that one run per N gives both halves
+of BASELINE.json's metric: atom-pairs/s and frame-pairs/s), the CPU baselines and the legs below.
 
 Rank 0 prints ONE JSON line: the contract's keys and the flat scalars of `config`, `roofline` and `cpu_baseline`
 (result_line; ~2 KB, so that a record which keeps only the tail of stdout still holds all of it). The full record
-(~25 KB) goes to --detail (default bench_detail.json beside this file). Beside the contract's keys it carries (N = 1 only,
-all measured in this run):
+(~25 KB with --full) goes to --detail (default bench_detail.json beside this file). Beside the contract's keys it carries
+(measured in this run):
   roofline        the dominant kernel against the VALU-issue roof MEASURED for its instruction mix
                   (profiles/r02_ubench_valu.json), HBM traffic from the committed PMC run
+and with --full (N = 1 only; --legs picks the legs, --no-legs / --no-cpu-baseline drop them):
   parity_checked  the timed histograms == the sum of a per-frame run, whose frames are compared bit for bit with
                   the C oracle (as many frames as the all-cores CPU leg computes anyway)
   f64_only        the same step with the all-f64 sweep (the reference's arithmetic type end to end)
@@ -1366,7 +1370,11 @@ def msd_sharded(torch, dist, D, B, ctx, device, synth, rank, world, backend, ste
 
 
 # ------------------------------------------------------------------------------------------------------------------
-def main():
+FULL_LEGS = "parity,f64,h2d,c1,residence,c3,c4,lag_long,c5"
+FULL_ONLY = {"legs": FULL_LEGS, "msd_steps": 5, "cpu_frames": 10}  # options that choose what --full runs, and defaults
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -1375,11 +1383,16 @@ def main():
                     help="rdf: weak (default) = C2 on every rank, strong = C3 split; c4 is always strong")
     ap.add_argument("--workload", choices=["rdf", "c4"], default="rdf",
                     help="rdf: the pair histogram (atom-pairs/s); c4: sharded MSD of BASELINE configs[3] (frame-pairs/s)")
-    ap.add_argument("--msd-steps", type=int, default=5, help="timed steps of the `msd` object of the default line")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="headline only (profiling runs)")
-    ap.add_argument("--legs", default="parity,f64,h2d,c1,residence,c3,c4,lag_long,c5")
-    ap.add_argument("--cpu-frames", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the `msd` object, the CPU baselines, the parity check and the "
+                         "legs (rdf workload); without it a run is the headline alone")
+    ap.add_argument("--msd-steps", type=int, default=None,
+                    help="timed steps of the `msd` object of a --full line (default %d)" % FULL_ONLY["msd_steps"])
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-legs", action="store_true", help="--full without the legs and the `msd` object")
+    ap.add_argument("--legs", default=None, help="the legs a --full run takes (default %s)" % FULL_LEGS)
+    ap.add_argument("--cpu-frames", type=int, default=None,
+                    help="frames of the one-core CPU baseline of a --full run (default %d)" % FULL_ONLY["cpu_frames"])
     ap.add_argument("--variant", type=int, default=None, help="kernel variant knob (A/B only)")
     ap.add_argument("--option", action="append", default=[], help="library option key=value (A/B only)")
     ap.add_argument("--op", choices=["rdf", "cn", "rdf_cn"], default="rdf",
@@ -1391,14 +1404,23 @@ def main():
     ap.add_argument("--shape", choices=("C1", "C1alt", "C1full"), default=None,
                     help="profiling runs only (implies --no-legs): the headline loop on the reference's own workload shape "
                          "(leg_c1's inputs) instead of C2")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.scaling is None:
         args.scaling = "strong" if args.workload == "c4" else "weak"
     if args.workload == "c4" and args.scaling != "strong":
         ap.error("--workload c4 is a strong-scaling workload (BASELINE configs[3]: one C4 trajectory on 1..8 GPUs)")
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    for key, default in FULL_ONLY.items():
+        if getattr(args, key) is None:
+            setattr(args, key, default)
+        elif not args.full:
+            ap.error("--%s chooses what --full runs; add --full" % key.replace("_", "-"))
+    return args
 
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn(args)
 
@@ -1493,7 +1515,7 @@ def main():
     for f0 in range(0, F, 50):
         blk = synth.rdf_frames(n, frame_ids[f0:f0 + 50], L, cfg["seed_offset"])
         xyz[f0:f0 + 50] = torch.from_numpy(blk).to(device)
-        if not strong and world == 1:
+        if args.full and not strong and world == 1:  # (the h2d leg's source and the parity leg's oracle frame)
             xyz_host = blk if xyz_host is None else np.concatenate([xyz_host, blk])
     pairs_per_frame = n * (n - 1) // 2
     pairs_local = F * pairs_per_frame
@@ -1593,7 +1615,7 @@ def main():
     if args.op != "rdf":
         args.no_legs = True  # a profiling run
     msd_obj = None
-    if args.op == "rdf" and not args.no_legs and args.msd_steps > 0:
+    if args.full and args.op == "rdf" and not args.no_legs and args.msd_steps > 0:
         # the MSD half of BASELINE.json's metric, same sharding at every N (every rank takes part: before rank 0 goes on alone)
         try:
             msd_obj = msd_sharded(torch, dist, D, B, ctx, device, synth, rank, world, backend, args.msd_steps, 1, fence)
@@ -1633,10 +1655,10 @@ def main():
             out["config"]["collectives"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size()}
         if msd_obj is not None:
             out["msd"] = msd_obj
-        legs = [] if (args.no_legs or world > 1 or strong) else args.legs.split(",")
+        legs = [] if (not args.full or args.no_legs or world > 1 or strong) else args.legs.split(",")
         sync = torch.cuda.synchronize
         oracle_frames = []
-        if world == 1 and not strong and not args.no_cpu_baseline:
+        if args.full and world == 1 and not strong and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, types, rel, nb, args.cpu_frames)
             try:
                 rep, oracle_frames = cpu_baseline_all_cores(cfg, types, rel, nb)

@@ -121,3 +121,19 @@ def test_dump_outputs_exact_and_capped(tmp_path):
     with pytest.raises(ValueError):
         bench.dump_outputs(str(tmp_path / "f"), {"x": np.zeros(bench.DUMP_CAP_BYTES // 8 + 1)})
     assert not (tmp_path / "f").exists()
+
+
+def test_full_is_off_by_default_and_owns_what_it_runs():
+    """A plain run is the headline alone; the options that choose what --full adds are refused without it (a run that
+    silently skipped the legs it was asked for would look like a pass), the headline's own switches are not."""
+    import pytest
+
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert plain.full is False and (plain.steps, plain.warmup) == (3, 1)
+    full = bench.parse_args(["--full"])
+    assert full.full and full.legs == bench.FULL_LEGS and full.msd_steps == 5 and full.cpu_frames == 10
+    assert bench.parse_args(["--full", "--legs", "parity", "--msd-steps", "1"]).legs == "parity"
+    for extra in (["--legs", "parity"], ["--msd-steps", "1"], ["--cpu-frames", "4"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(extra)
+    assert not bench.parse_args(["--no-legs", "--no-cpu-baseline", "--dump-outputs", "d"]).full

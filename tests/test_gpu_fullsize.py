@@ -345,6 +345,22 @@ def test_bench_dump_outputs(tmp_path):
     np.testing.assert_allclose(lag[-1, 0], single[-1, 0] / 50_000 / 1e-20, rtol=1e-9)
 
 
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: the timed steps, their roofline and step record and the build id —
+    no `msd` object, no CPU baseline, no parity check, no leg."""
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MDHIP_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    line, rec = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1"], env, tmp_path)
+    assert line["metric"] == "atom-pairs/s" and line["unit"] == "atom-pairs/s" and line["higher_is_better"] is True
+    assert line["value"] > 1e12 and line["ms_per_step"] > 0 and line["dtype"] in ("f32/f64", "f64")
+    assert line["roofline"]["launch_ms"] > 0 and len(rec["roofline"]["step_ms"]["raw"]) == 3
+    assert line["lib_build_id"]["match"] is True
+    moved = {"msd", "cpu_baseline", "parity", "parity_checked", "f64_only", "f64_value", "h2d_inclusive", "c1", "c1_alt",
+             "c1_full", "residence", "c3", "c4", "lag_long", "c5"}
+    assert not moved & set(rec), sorted(moved & set(rec))
+
+
 def test_bench_launches_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher: bench.py starts the two ranks itself (here sharing the GPU over
     gloo) — strong scaling, C3's 1000 frames split 500 + 500, all-reduce inside the timed region."""
@@ -382,7 +398,8 @@ def test_bench_through_rccl_with_one_rank(tmp_path):
     env = dict(os.environ, MDHIP_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MDHIP_DIST_BACKEND"):
         env.pop(k, None)
-    for port, extra in ((29541, ["--workload", "c4"]), (29542, ["--legs", "parity", "--no-cpu-baseline", "--msd-steps", "1"])):
+    for port, extra in ((29541, ["--workload", "c4"]),
+                        (29542, ["--full", "--legs", "parity", "--no-cpu-baseline", "--msd-steps", "1"])):
         env["MASTER_PORT"] = str(port)
         line, rec = _run_bench(["--steps", "2", "--warmup", "1"] + extra, env, tmp_path)
         coll = rec["config"]["collectives"]

@@ -15,8 +15,8 @@ for s in "$@"; do
   case $s in
     tests) timeout -k 10 1100 python -m pytest tests -m gpu -x -q > $O/gpu_tests.log 2>&1; rc=$?; echo "tests rc=$rc"; tail -5 $O/gpu_tests.log; [ $rc -eq 0 ] || exit 1 ;;
     tests_k=*) K=${s#tests_k=}; timeout -k 10 900 python -m pytest tests -m gpu -x -q -k "$K" > $O/gpu_tests_k.log 2>&1; rc=$?; echo "tests_k rc=$rc"; tail -15 $O/gpu_tests_k.log; [ $rc -eq 0 ] || exit 1 ;;
-    bench) timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_line_${TAG}.json 2> $O/bench_err_${TAG}.log; echo "bench rc=$?"; tail -3 $O/bench_err_${TAG}.log; python3 tools/show_steps.py $O/bench_line_${TAG}.json ;;
-    bench_legs=*) LG=${s#bench_legs=}; timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --legs $LG > $O/bench_${LG//,/_}_${TAG}.json 2> $O/bench_err_${TAG}.log; echo "bench rc=$?"; tail -3 $O/bench_err_${TAG}.log; python3 tools/show_steps.py $O/bench_${LG//,/_}_${TAG}.json ;;
+    bench) timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_line_${TAG}.json 2> $O/bench_err_${TAG}.log; echo "bench rc=$?"; tail -3 $O/bench_err_${TAG}.log; python3 tools/show_steps.py $O/bench_line_${TAG}.json ;;
+    bench_legs=*) LG=${s#bench_legs=}; timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --legs $LG > $O/bench_${LG//,/_}_${TAG}.json 2> $O/bench_err_${TAG}.log; echo "bench rc=$?"; tail -3 $O/bench_err_${TAG}.log; python3 tools/show_steps.py $O/bench_${LG//,/_}_${TAG}.json ;;
     head1) timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-legs --no-cpu-baseline > $O/fresh_${TAG}.json 2> $O/fresh_${TAG}.err; echo "head rc=$?"; python3 tools/show_steps.py $O/fresh_${TAG}.json ;;
     head3) for k in 1 2 3; do timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-legs --no-cpu-baseline > $O/head_${TAG}_$k.json 2> $O/head_${TAG}_$k.err; echo "head $k rc=$?"; python3 tools/show_steps.py $O/head_${TAG}_$k.json; done ;;
     shape=*) SH=${s#shape=}; for o in "" "--option rdf_disp=0"; do timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --shape $SH $o > $O/shape_${SH}_${TAG}.json 2> $O/shape_err.log; echo "shape $SH [$o] rc=$?"; python3 tools/show_steps.py $O/shape_${SH}_${TAG}.json; done ;;
@@ -35,7 +35,7 @@ for s in "$@"; do
     pmc2) timeout -k 10 1150 bash tools/pmc_secondary.sh ${ROUND} > $O/pmc2.log 2>&1; echo "pmc2 rc=$?"; tail -3 $O/pmc2.log ;;
     soaks) ( timeout -k 10 500 python tests/bench/soak_pk.py 2500 5 oracle 2>&1 | tail -2; timeout -k 10 400 python tests/bench/soak_cn.py 1000 2>&1 | tail -2; timeout -k 10 300 python tests/bench/soak_cull.py 1000 2>&1 | tail -2; timeout -k 10 400 python tests/bench/soak_lag.py 300 2>&1 | tail -2; timeout -k 10 600 python tests/bench/soak_lag_long.py 120 2>&1 | tail -3; timeout -k 10 600 python tests/bench/soak_lag_short.py 600 2>&1 | tail -2; timeout -k 10 600 python tests/bench/soak_lag_ends.py 150 2>&1 | tail -2; timeout -k 10 200 python tests/bench/soak_fft.py 2>&1 | tail -2 ) > $O/${ROUND}_soaks.txt 2>&1; cat $O/${ROUND}_soaks.txt ;;
     stats) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o ${ROUND}_bench -- python3 $R/bench.py --no-cpu-baseline --no-legs > $O/bench_line_rocprof.json 2> $O/rocprof_err.log); echo "stats rc=$?" ;;
-    stats_legs) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o ${ROUND}_bench_legs -- python3 $R/bench.py --no-cpu-baseline > $O/bench_line_rocprof_legs.json 2> $O/rocprof_legs_err.log); echo "stats_legs rc=$?"; tail -2 $O/rocprof_legs_err.log ;;
+    stats_legs) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o ${ROUND}_bench_legs -- python3 $R/bench.py --full --no-cpu-baseline > $O/bench_line_rocprof_legs.json 2> $O/rocprof_legs_err.log); echo "stats_legs rc=$?"; tail -2 $O/rocprof_legs_err.log ;;
     ab_lag) timeout -k 10 400 python tools/ab_libs_lag.py $LP $L 2>&1 | grep -v amdgpu > $O/${ROUND}_ab_lag_${TAG}.txt; cat $O/${ROUND}_ab_lag_${TAG}.txt ;;
     ab_pair) timeout -k 10 400 python tools/ab_libs.py $LP $L 2>&1 | grep -v amdgpu > $O/${ROUND}_ab_pair_${TAG}.txt; cat $O/${ROUND}_ab_pair_${TAG}.txt ;;
     w12_check) timeout -k 10 400 python tools/w12.py check 2>&1 | grep -v amdgpu > $O/${ROUND}_w12_check.txt; tail -12 $O/${ROUND}_w12_check.txt ;;
