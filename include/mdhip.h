@@ -569,6 +569,38 @@ int mdhip_shell_members(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const
 int mdhip_mol_kahan_sums(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, int n_attr, const double *attr,
                          int attr_on_device, int64_t n_mols, const int64_t *seg_off, double *out);
 
+/* ---- cation-water orientation of the hydration number (hydration_number.py get_hydration_number) ---- */
+/*
+ * Replaces the per-cation pair work of get_hydration_number      structural/hydration_number.py:13-99
+ * for a batch of frames: coordinates xyz [F][3][n_atoms] (atoms in ascending-id order, host or device memory as
+ * xyz_on_device says), box [F][3], cation atom indices cations[n_cations], and per water the index of its first atom
+ * waters[n_waters] (O; H1 and H2 are the next two atoms). For every (frame f, cation c) the waters w with
+ *   rsq(cation c, O of w) < r_cut_sq                               hydration_number.py:17-20
+ * (the reference's single-wrap rsq, rdf_cn.py:36-58; r_cut_sq is the caller's r_cut ** 2), and their cosine
+ *   d = cation - O wrapped once per axis, v = ((0 + H1) + H2) - 2 O from the raw coordinates,
+ *   cos = (((0 + dx vx) + dy vy) + dz vz) / (sqrt((dx dx + dy dy) + dz dz) * sqrt((vx vx + vy vy) + vz vz))
+ * unfused, correctly rounded sqrt and division (hydration_number.py:28-32, numpy's double); a zero vector gives NaN.
+ *
+ * mdhip_hydration_cosines (list mode):
+ *   idx [F][n_cations][cap]: the water indices (positions in `waters`), ascending, padded with -1;
+ *   cosines [F][n_cations][cap]: their cosines in the same order, padded with NaN;
+ *   count [F][n_cations]: the number of waters, exact even when it exceeds cap (that row is then incomplete: call
+ *   again for its frame with cap >= count). 1 <= cap <= 16384.
+ * mdhip_hydration_counts (counts mode, no capacity limit):
+ *   n_water [F][n_cations], n_away [F][n_cations]: the waters, and those with cos < cos_cut (NaN is not);
+ *   hist [n_bins] (uint64, summed over all frames and cations): bin trunc((cos + 1.0) / bin_width), clamped to
+ *   [0, n_bins - 1]; a NaN cosine is in no bin. 1 <= n_bins <= 4096.
+ * Outputs are host memory.
+ */
+int mdhip_hydration_cosines(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int xyz_on_device,
+                            const double *box, int32_t n_cations, const int32_t *cations, int32_t n_waters,
+                            const int32_t *waters, double r_cut_sq, int32_t cap, int32_t *idx, double *cosines,
+                            int32_t *count);
+int mdhip_hydration_counts(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int xyz_on_device,
+                           const double *box, int32_t n_cations, const int32_t *cations, int32_t n_waters,
+                           const int32_t *waters, double r_cut_sq, double cos_cut, double bin_width, int32_t n_bins,
+                           int32_t *n_water, int32_t *n_away, uint64_t *hist);
+
 /*
  * Replaces, for the inputs of the path, the un-vendored pymatgen `parse_lammps_dumps` + pandas
  * `read_csv` the reference uses (call sites structural/rdf_cn.py:176, dynamical/diffusion.py:172,

@@ -630,3 +630,82 @@ def mol_kahan_sums(attr, seg_off, ctx=None):
     out = np.zeros((F, K, M), dtype=np.float64)
     ctx.check(ctx.lib.mdhip_mol_kahan_sums(ctx.h, F, N, K, ap, a_dev, M, ptr(off, C.c_int64), ptr(out)))
     return out
+
+
+HYDRATION_CAP = 16  # first-try waters per (frame, cation) row of hydration_cosines; rows that hold more are re-run
+
+
+def hydration_cosines(xyz, box, cations, waters, r_cut_sq, cap=HYDRATION_CAP, ctx=None):
+    """
+    Cation-water cosines of get_hydration_number (hydration_number.py:13-99): xyz [F,3,N] (atoms in id order), box
+    [F,3], cation atom indices [C], the first-atom (O) index of every water [W] (H1, H2 follow it) -> (idx int32
+    [F,C,K], cos float64 [F,C,K], count int32 [F,C]). Row (f, c) holds the count[f, c] waters whose O is at
+    rsq < r_cut_sq from cation c, ascending, and their cosines, then -1 / NaN up to K = max(cap, largest count).
+    Frames whose rows overflow `cap` are run again with a cap of their largest count (include/mdhip.h:
+    mdhip_hydration_cosines).
+    """
+    ctx = ctx or default_context()
+    F, _, N = _shape3(xyz, "xyz")
+    cat = _i32(cations).ravel()
+    wat = _i32(waters).ravel()
+    C_, W = len(cat), len(wat)
+    bx = _f64(box).reshape(F, 3)
+    xp, x_dev, keep = as_input(xyz, ctx)
+
+    def run(n_f, p, dev, b, k):
+        idx = np.empty((n_f, C_, k), dtype=np.int32)
+        cos = np.empty((n_f, C_, k), dtype=np.float64)
+        count = np.zeros((n_f, C_), dtype=np.int32)
+        ctx.check(ctx.lib.mdhip_hydration_cosines(
+            ctx.h, n_f, N, p, dev, ptr(b), C_, ptr(cat, C.c_int32), W, ptr(wat, C.c_int32), float(r_cut_sq), k,
+            ptr(idx, C.c_int32), ptr(cos), ptr(count, C.c_int32)))
+        return idx, cos, count
+
+    cap = max(1, int(cap))
+    idx, cos, count = run(F, xp, x_dev, bx, cap)
+    over = np.flatnonzero((count > cap).any(axis=1)) if C_ else np.zeros(0, dtype=np.int64)
+    if len(over) == 0:
+        return idx, cos, count
+    big = int(count[over].max())
+    out_i = np.full((F, C_, big), -1, dtype=np.int32)
+    out_c = np.full((F, C_, big), np.nan)
+    out_i[:, :, :cap] = idx
+    out_c[:, :, :cap] = cos
+    if not x_dev:
+        sub = np.ascontiguousarray(keep[over])
+    elif hasattr(xyz, "index_select"):  # a torch tensor: the overflowing frames stay on the device
+        import torch
+
+        sub = xyz.index_select(0, torch.as_tensor(over, device=xyz.device)).contiguous()
+    else:
+        raise ValueError("rows overflow cap=%d: pass a larger cap with a DevPtr input" % cap)
+    sp, s_dev, keep2 = as_input(sub, ctx)
+    ri, rcos, rcount = run(len(over), sp, s_dev, np.ascontiguousarray(bx[over]), big)
+    if not np.array_equal(rcount, count[over]):
+        raise RuntimeError("hydration_cosines: the re-run found other row sizes than the first sweep")
+    out_i[over] = ri
+    out_c[over] = rcos
+    return out_i, out_c, count
+
+
+def hydration_counts(xyz, box, cations, waters, r_cut_sq, cos_cut, bin_width, n_bins, ctx=None):
+    """
+    The counts mode of the same search: -> (n_water int32 [F,C], n_away int32 [F,C], hist uint64 [n_bins]); n_away
+    counts cos < cos_cut, hist bins trunc((cos + 1) / bin_width) clamped to n_bins - 1 over all rows, NaN in no bin
+    (include/mdhip.h: mdhip_hydration_counts). No capacity limit.
+    """
+    ctx = ctx or default_context()
+    F, _, N = _shape3(xyz, "xyz")
+    cat = _i32(cations).ravel()
+    wat = _i32(waters).ravel()
+    C_, W = len(cat), len(wat)
+    bx = _f64(box).reshape(F, 3)
+    xp, x_dev, keep = as_input(xyz, ctx)
+    n_water = np.zeros((F, C_), dtype=np.int32)
+    n_away = np.zeros((F, C_), dtype=np.int32)
+    hist = np.zeros(int(n_bins), dtype=np.uint64)
+    ctx.check(ctx.lib.mdhip_hydration_counts(
+        ctx.h, F, N, xp, x_dev, ptr(bx), C_, ptr(cat, C.c_int32), W, ptr(wat, C.c_int32), float(r_cut_sq),
+        float(cos_cut), float(bin_width), int(n_bins), ptr(n_water, C.c_int32), ptr(n_away, C.c_int32),
+        ptr(hist, C.c_uint64)))
+    return n_water, n_away, hist
