@@ -308,9 +308,10 @@ int mdhip_cn_sites(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const doub
  *   seg_off    host int64 [n_seg+1] (atoms of segment s are seg_off[s]..seg_off[s+1]-1)
  *   out        host|dev (out_on_device) [n_frames][n_attr][n_seg]:  sum(m*a) / sum(m), each product
  *              and sum a separate rounding, atoms added in index order
- *   seg_mass   host [n_seg] or NULL; seg_q host [n_seg] or NULL (sum of atom_q)
+ *   seg_mass   host [n_seg] or NULL; seg_q host [n_seg] or NULL (sum of atom_q), index order from 0.0
  * Floating point: sums are in a different order from pandas' Kahan group sum / BLAS dot; agreement with
- * the reference is to ~1e-15 relative (tests use rtol 1e-13).
+ * the reference is to ~1e-15 relative (tests use rtol 1e-13). Every kernel variant and option setting gives the bits
+ * of the order stated above (tests/test_gpu_segment_exact.py).
  */
 int mdhip_segment_com(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, int n_attr,
                       const double *attr, int attr_on_device, const double *atom_mass,
@@ -430,6 +431,10 @@ int mdhip_lag_msd_status_dev(mdhip_ctx *ctx, double *dst_dev);
  *   vel        host|dev [n_frames][3][n_atoms]; atom_mass, atom_q host [n_atoms]
  *   seg_off    host int64 [n_seg+1]; seg_type host int32 [n_seg] in 0..n_types-1
  *   flux       host [3][n_types][n_frames] (the layout Conductivity.get_charge_flux returns)
+ * Floating point: per molecule ((sum(m v) / sum(m)) * vel_conv) * (sum(q) * charge_conv), the sums as in
+ * mdhip_segment_com; then per type 256 partial sums, partial i adding molecules i, i + 256, ... of the type in order,
+ * and a fixed tree over them (red[i] += red[i + w], w = 128 .. 1). Every kernel variant and option setting gives these
+ * bits (tests/test_gpu_segment_exact.py).
  */
 int mdhip_charge_flux(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *vel,
                       int on_device, const double *atom_mass, const double *atom_q, int64_t n_seg,

@@ -510,7 +510,7 @@ int mdhip_segment_com(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, int n_a
         int64_t want = ((int64_t)ctx->cu_count * 16 + (int64_t)blocks.size() - 1) / (int64_t)blocks.size();
         want = std::max<int64_t>(want, n_frames / 10);
         unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(n_frames, std::min<int64_t>(want, 65535)));
-        if (ctx->opt_seg_gy > 0) gy = (unsigned)std::min<int64_t>(n_frames, ctx->opt_seg_gy);
+        if (ctx->opt_seg_gy > 0) gy = (unsigned)std::min<int64_t>(std::min<int64_t>(n_frames, 65535), ctx->opt_seg_gy);
         ctx->last_kernel = cap == 512 ? "segment_staged_kernel<false, 512, 256>" : "segment_staged_kernel<false, 1024, 256>";
         if (cap == 256) {
             ctx->last_kernel = "segment_staged_kernel<false, 256, 64>";
@@ -663,7 +663,8 @@ static int charge_flux_impl(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, c
     } else if (staged) {
         int64_t want = ((int64_t)ctx->cu_count * 16 + (int64_t)blocks.size() - 1) / (int64_t)blocks.size();
         want = std::max<int64_t>(want, n_frames / 10);
-        const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(n_frames, std::min<int64_t>(want, 65535)));
+        unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(n_frames, std::min<int64_t>(want, 65535)));
+        if (ctx->opt_seg_gy > 0) gy = (unsigned)std::min<int64_t>(std::min<int64_t>(n_frames, 65535), ctx->opt_seg_gy);  // (as mdhip_segment_com)
         ctx->last_kernel = cap == 512 ? "segment_staged_kernel<true, 512, 256>" : "segment_staged_kernel<true, 1024, 256>";
         if (cap == 256) {
             ctx->last_kernel = "segment_staged_kernel<true, 256, 64>";
