@@ -562,6 +562,43 @@ def shell_residence(xyz_i, xyz_j, box, r_lo_sq, r_hi_sq, exclude_diagonal=False,
     return counts, int(nrec.value)
 
 
+def _with_overflow_rerun(run, xyz, inp, bx, cap, pads, what, ctx):
+    """
+    The capped per-row search behind shell_members and hydration_cosines. run(n_frames, pointer, on_device, box, cap)
+    -> the per-row arrays [n_frames, C, cap], then count [n_frames, C] (exact even past cap); inp = as_input(xyz, ctx).
+    Frames with a row that overflowed `cap` are run again, alone, with a cap of their largest count and spliced in; the
+    other frames' rows are padded with `pads` (one value per per-row array). `what` = (function name, noun of a row)
+    for the error texts.
+    """
+    xp, x_dev, keep = inp
+    cap = max(1, int(cap))
+    *rows, count = run(len(bx), xp, x_dev, bx, cap)
+    over = np.flatnonzero((count > cap).any(axis=1))
+    if len(over) == 0:
+        return (*rows, count)
+    big = int(count[over].max())
+    if not x_dev:
+        sub = np.ascontiguousarray(keep[over])
+    elif hasattr(xyz, "index_select"):  # a torch tensor: the overflowing frames stay on the device
+        import torch
+
+        sub = xyz.index_select(0, torch.as_tensor(over, device=xyz.device)).contiguous()
+    else:
+        raise ValueError("%ss overflow cap=%d: pass a larger cap with a DevPtr input" % (what[1], cap))
+    sp, s_dev, sub_keep = as_input(sub, ctx)  # (sub_keep: what sp points at, alive until the call below has returned)
+    *rerun, rcount = run(len(over), sp, s_dev, np.ascontiguousarray(bx[over]), big)
+    del sub_keep
+    if not np.array_equal(rcount, count[over]):
+        raise RuntimeError("%s: the re-run found other %s sizes than the first sweep" % what)
+    outs = []
+    for first, again, pad in zip(rows, rerun, pads):
+        out = np.full(first.shape[:2] + (big,), pad, dtype=first.dtype)
+        out[:, :, :cap] = first
+        out[over] = again
+        outs.append(out)
+    return (*outs, count)
+
+
 SHELL_CAP = 32  # first-try molecules per (frame, centre) row of shell_members; rows that hold more are re-run
 
 
@@ -581,38 +618,16 @@ def shell_members(xyz, box, centres, mol_of, r_cut_sq, cap=SHELL_CAP, ctx=None):
         raise ValueError("mol_of must hold one molecule index per atom")
     C_ = len(cen)
     bx = _f64(box).reshape(F, 3)
-    xp, x_dev, keep = as_input(xyz, ctx)
-    cap = max(1, int(cap))
-    mols = np.empty((F, C_, cap), dtype=np.int32)
-    count = np.zeros((F, C_), dtype=np.int32)
-    ctx.check(ctx.lib.mdhip_shell_members(
-        ctx.h, F, N, xp, x_dev, ptr(bx), C_, ptr(cen, C.c_int32), ptr(mol, C.c_int32), float(r_cut_sq), cap,
-        ptr(mols, C.c_int32), ptr(count, C.c_int32)))
-    over = np.flatnonzero((count > cap).any(axis=1)) if C_ else np.zeros(0, dtype=np.int64)
-    if len(over) == 0:
-        return mols, count
-    big = int(count[over].max())
-    out = np.full((F, C_, big), -1, dtype=np.int32)
-    out[:, :, :cap] = mols
-    if not x_dev:
-        sub = np.ascontiguousarray(keep[over])
-    elif hasattr(xyz, "index_select"):  # a torch tensor: the overflowing frames stay on the device
-        import torch
 
-        sub = xyz.index_select(0, torch.as_tensor(over, device=xyz.device)).contiguous()
-    else:
-        raise ValueError("shells overflow cap=%d: pass a larger cap with a DevPtr input" % cap)
-    sp, s_dev, keep2 = as_input(sub, ctx)
-    sbx = np.ascontiguousarray(bx[over])
-    rm = np.empty((len(over), C_, big), dtype=np.int32)
-    rc = np.zeros((len(over), C_), dtype=np.int32)
-    ctx.check(ctx.lib.mdhip_shell_members(
-        ctx.h, len(over), N, sp, s_dev, ptr(sbx), C_, ptr(cen, C.c_int32), ptr(mol, C.c_int32), float(r_cut_sq), big,
-        ptr(rm, C.c_int32), ptr(rc, C.c_int32)))
-    if not np.array_equal(rc, count[over]):
-        raise RuntimeError("shell_members: the re-run found other shell sizes than the first sweep")
-    out[over] = rm
-    return out, count
+    def run(n_f, p, dev, b, k):
+        mols = np.empty((n_f, C_, k), dtype=np.int32)
+        count = np.zeros((n_f, C_), dtype=np.int32)
+        ctx.check(ctx.lib.mdhip_shell_members(
+            ctx.h, n_f, N, p, dev, ptr(b), C_, ptr(cen, C.c_int32), ptr(mol, C.c_int32), float(r_cut_sq), k,
+            ptr(mols, C.c_int32), ptr(count, C.c_int32)))
+        return mols, count
+
+    return _with_overflow_rerun(run, xyz, as_input(xyz, ctx), bx, cap, (-1,), ("shell_members", "shell"), ctx)
 
 
 def mol_kahan_sums(attr, seg_off, ctx=None):
@@ -650,7 +665,6 @@ def hydration_cosines(xyz, box, cations, waters, r_cut_sq, cap=HYDRATION_CAP, ct
     wat = _i32(waters).ravel()
     C_, W = len(cat), len(wat)
     bx = _f64(box).reshape(F, 3)
-    xp, x_dev, keep = as_input(xyz, ctx)
 
     def run(n_f, p, dev, b, k):
         idx = np.empty((n_f, C_, k), dtype=np.int32)
@@ -661,31 +675,8 @@ def hydration_cosines(xyz, box, cations, waters, r_cut_sq, cap=HYDRATION_CAP, ct
             ptr(idx, C.c_int32), ptr(cos), ptr(count, C.c_int32)))
         return idx, cos, count
 
-    cap = max(1, int(cap))
-    idx, cos, count = run(F, xp, x_dev, bx, cap)
-    over = np.flatnonzero((count > cap).any(axis=1)) if C_ else np.zeros(0, dtype=np.int64)
-    if len(over) == 0:
-        return idx, cos, count
-    big = int(count[over].max())
-    out_i = np.full((F, C_, big), -1, dtype=np.int32)
-    out_c = np.full((F, C_, big), np.nan)
-    out_i[:, :, :cap] = idx
-    out_c[:, :, :cap] = cos
-    if not x_dev:
-        sub = np.ascontiguousarray(keep[over])
-    elif hasattr(xyz, "index_select"):  # a torch tensor: the overflowing frames stay on the device
-        import torch
-
-        sub = xyz.index_select(0, torch.as_tensor(over, device=xyz.device)).contiguous()
-    else:
-        raise ValueError("rows overflow cap=%d: pass a larger cap with a DevPtr input" % cap)
-    sp, s_dev, keep2 = as_input(sub, ctx)
-    ri, rcos, rcount = run(len(over), sp, s_dev, np.ascontiguousarray(bx[over]), big)
-    if not np.array_equal(rcount, count[over]):
-        raise RuntimeError("hydration_cosines: the re-run found other row sizes than the first sweep")
-    out_i[over] = ri
-    out_c[over] = rcos
-    return out_i, out_c, count
+    return _with_overflow_rerun(run, xyz, as_input(xyz, ctx), bx, cap, (-1, np.nan), ("hydration_cosines", "row"),
+                                ctx)
 
 
 def hydration_counts(xyz, box, cations, waters, r_cut_sq, cos_cut, bin_width, n_bins, ctx=None):

@@ -21,6 +21,12 @@ def molecule_layout(num_mols, num_atoms_per_mol):
     return seg_off, mol_type, mol_id
 
 
+def check_atom_count(n_layout, n_frame):
+    """The reference's error (pandas', on assigning the molecule columns) for a frame of another size than the layout."""
+    if n_layout != n_frame:
+        raise ValueError(f"Length of values ({int(n_layout)}) does not match length of index ({int(n_frame)})")
+
+
 def atom_masses(data, mass):
     """Per-atom masses: from the `mass` list indexed by type, or from the dump's own column."""
     if not mass:
@@ -40,9 +46,7 @@ def calc_com(dump, num_mols, num_atoms_per_mol, mass=None, atom_attributes=["xu"
     """
     data = dump.data
     seg_off, mol_type, mol_id = molecule_layout(num_mols, num_atoms_per_mol)
-    if seg_off[-1] != len(data):
-        raise ValueError(
-            f"Length of values ({int(seg_off[-1])}) does not match length of index ({len(data)})")
+    check_atom_count(seg_off[-1], len(data))
     m = atom_masses(data, mass)
     attr = np.ascontiguousarray(data[list(atom_attributes)].to_numpy(dtype=np.float64).T)[None]
     q = data["q"].to_numpy(dtype=np.float64) if calc_charge else None

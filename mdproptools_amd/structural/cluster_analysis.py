@@ -26,6 +26,7 @@ import pandas as pd
 
 from .. import backend
 from .. import io as mio
+from ..common.com_mols import check_atom_count, molecule_layout
 from .rdf_cn import _calc_atom_type
 
 FORCE_CONSTANT = 0.043363 / 16.0  # cluster_analysis.py:29
@@ -44,10 +45,8 @@ def cluster_file_name(frame_index, n_frames, centre_index, n_centres):
 
 
 def _layout(num_mols, num_atoms_per_mol):
-    sizes = np.repeat(np.asarray(num_atoms_per_mol, dtype=np.int64), np.asarray(num_mols, dtype=np.int64))
-    seg_off = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
-    mol_of = np.repeat(np.arange(len(sizes), dtype=np.int32), sizes)
-    mol_type = np.repeat(np.arange(1, len(num_mols) + 1), np.asarray(num_mols, dtype=np.int64))
+    seg_off, mol_type, _ = molecule_layout(num_mols, num_atoms_per_mol)
+    mol_of = np.repeat(np.arange(len(mol_type), dtype=np.int32), np.diff(seg_off))
     return mol_of, seg_off, mol_type
 
 
@@ -130,8 +129,7 @@ def _iter_clusters(filename, atom_type, r_cut, num_mols, num_atoms_per_mol, full
 
     def prepare(item):
         fname, k, ts, bounds, names, planes = item
-        if planes.shape[1] != n_atoms:
-            raise ValueError("Length of values (%d) does not match length of index (%d)" % (n_atoms, planes.shape[1]))
+        check_atom_count(n_atoms, planes.shape[1])
         if need_elements and "element" not in names and not elements:  # cluster_analysis.py:122-126
             raise ValueError(
                 "The elements of the atoms in the system should be provided if they "

@@ -27,6 +27,7 @@ import pandas as pd
 
 from .. import backend
 from .. import io as mio
+from ..common.com_mols import check_atom_count, molecule_layout
 
 VERBOSE = False
 COS_CUT = -0.72  # hydration_number.py:35
@@ -37,9 +38,8 @@ def _layout(cation_type, water_type, num_mols, num_atoms_per_mol):
     """(number of atoms, cation atom indices, first-atom index of every water) of the id-ordered molecule layout."""
     if num_mols is None or num_atoms_per_mol is None:
         raise ValueError("num_mols and num_atoms_per_mol are required (the molecule layout in id order)")
-    sizes = np.repeat(np.asarray(num_atoms_per_mol, dtype=np.int64), np.asarray(num_mols, dtype=np.int64))
-    seg_off = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
-    mol_type = np.repeat(np.arange(1, len(num_mols) + 1), np.asarray(num_mols, dtype=np.int64))
+    seg_off, mol_type, _ = molecule_layout(num_mols, num_atoms_per_mol)
+    sizes = np.diff(seg_off)
     atom_type = np.repeat(mol_type, sizes)
     cations = np.flatnonzero(atom_type == cation_type).astype(np.int32)
     water_mols = np.flatnonzero(mol_type == water_type)
@@ -55,8 +55,7 @@ def _iter_batches(pattern, n_atoms):
     steps, boxes, planes = [], [], []
     per_frame = 4 * n_atoms * 8
     for ts, bounds, _, _, pl in mio.iter_native_frames(pattern, ["id", "x", "y", "z"], sort_by="id"):
-        if pl.shape[1] != n_atoms:
-            raise ValueError("Length of values (%d) does not match length of index (%d)" % (n_atoms, pl.shape[1]))
+        check_atom_count(n_atoms, pl.shape[1])
         b = np.asarray(bounds, dtype=np.float64)
         steps.append(int(ts))
         boxes.append(b[:, 1] - b[:, 0])

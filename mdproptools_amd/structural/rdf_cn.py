@@ -29,6 +29,7 @@ import numpy as np
 import pandas as pd
 
 from .. import backend
+from ..common.com_mols import check_atom_count, molecule_layout
 from ..io import parse_lammps_dumps
 
 CON_CONSTANT = 1.660538921  # amu/A^3 -> g/cm^3 (rdf_cn.py:30)
@@ -83,9 +84,7 @@ def _calc_atom_type(ids, num_mols, num_atoms):
 
 def _molecule_layout(num_mols, num_atoms_per_mol):
     """Segment offsets and molecule type labels implied by the sorted-id order (rdf_cn.py:222-230)."""
-    counts = np.repeat(np.asarray(num_atoms_per_mol, dtype=np.int64), np.asarray(num_mols, dtype=np.int64))
-    seg_off = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
-    seg_type = np.repeat(np.arange(1, len(num_mols) + 1), np.asarray(num_mols, dtype=np.int64))
+    seg_off, seg_type, _ = molecule_layout(num_mols, num_atoms_per_mol)
     return seg_off, seg_type.astype(np.int32)
 
 
@@ -565,9 +564,7 @@ def _same_types(batch):
 def _molecular_inputs(batch, num_mols, num_atoms_per_mol, mass):
     """Device-side COM of wrapped coordinates for every frame of the batch (rdf_cn.py:218-241)."""
     seg_off, seg_type = _molecule_layout(num_mols, num_atoms_per_mol)
-    n = batch[0].xyz.shape[1]
-    if seg_off[-1] != n:
-        raise ValueError(f"Length of values ({int(seg_off[-1])}) does not match length of index ({n})")
+    check_atom_count(seg_off[-1], batch[0].xyz.shape[1])
     xyz = _xyz_block(batch)
     atom_mass = np.asarray(mass, dtype=np.float64)[batch[0].types.astype(np.int64) - 1]
     if _same_types(batch):
