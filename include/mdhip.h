@@ -606,6 +606,37 @@ int mdhip_hydration_counts(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, co
                            const int32_t *waters, double r_cut_sq, double cos_cut, double bin_width, int32_t n_bins,
                            int32_t *n_water, int32_t *n_away, uint64_t *hist);
 
+/* ---- atom counts along the axis normal to a surface (number_density.py calc_number_density) ---- */
+/*
+ * Replaces the per-type selections and the counting loop of calc_number_density   structural/number_density.py:76-105
+ * for a batch of frames: the axis coordinate x [F][n_atoms] (host or device memory as x_on_device says) and a 16-bit
+ * code per atom, codes [n_atoms] shared by the frames or [F][n_atoms] (codes_per_frame != 0), host memory:
+ *   code & MDHIP_AP_NONE   the row of the result the atom counts in, 0 .. n_rows - 1; MDHIP_AP_NONE (or any value
+ *                          >= n_rows): in none
+ *   code & MDHIP_AP_SURFACE  the atom belongs to the surface (it may count in a row as well)
+ * Per frame, in float64, unfused, with true division (w = bin_size):
+ *   lo, hi = min, max of x over the surface atoms; NaN coordinates are skipped (pandas' min / max), NaN, NaN without
+ *   a surface atom; -0.0 orders below +0.0                                          number_density.py:76-82
+ *   MDHIP_AP_REF_POS: s = x - lo; the atoms with s < dist: b = s - (hi - lo)        number_density.py:87-96
+ *   MDHIP_AP_REF_NEG: s = x - lo; the atoms with s > dist: b = s                    number_density.py:97-105
+ *     k = trunc(b / w); counted in bin k when 0 <= k < n_bins, in bin k + n_bins when -n_bins <= k < 0 (the
+ *     reference indexes a numpy row with k), else in outside[f] and in no bin (the reference raises IndexError)
+ *   MDHIP_AP_PROFILE: s = x - origin_f, origin_f = lo (origin_kind 0), hi (1) or origin[f] (2);
+ *     t = (s - dist) / w (dist = the lower end of the binned range); counted in bin trunc(t) when t >= 0 and
+ *     trunc(t) < n_bins, else (NaN included) in outside[f]; nothing wraps
+ * counts [F][n_rows][n_bins] (uint32), extent [F][2] (lo, hi), outside [F] (uint32): host memory, exact.
+ * 1 <= n_rows < MDHIP_AP_NONE, n_bins >= 1, n_rows * n_bins < 2^31, n_atoms < 2^31.
+ */
+#define MDHIP_AP_REF_POS 0
+#define MDHIP_AP_REF_NEG 1
+#define MDHIP_AP_PROFILE 2
+#define MDHIP_AP_SURFACE 0x4000u
+#define MDHIP_AP_NONE 0x3FFFu
+int mdhip_axis_profile(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *x, int x_on_device,
+                       const uint16_t *codes, int codes_per_frame, int32_t n_rows, int mode, double bin_size,
+                       double dist, int32_t n_bins, int origin_kind, const double *origin, uint32_t *counts,
+                       double *extent, uint32_t *outside);
+
 /*
  * Replaces, for the inputs of the path, the un-vendored pymatgen `parse_lammps_dumps` + pandas
  * `read_csv` the reference uses (call sites structural/rdf_cn.py:176, dynamical/diffusion.py:172,

@@ -700,3 +700,55 @@ def hydration_counts(xyz, box, cations, waters, r_cut_sq, cos_cut, bin_width, n_
         float(cos_cut), float(bin_width), int(n_bins), ptr(n_water, C.c_int32), ptr(n_away, C.c_int32),
         ptr(hist, C.c_uint64)))
     return n_water, n_away, hist
+
+
+AP_REF_POS, AP_REF_NEG, AP_PROFILE = 0, 1, 2  # binning modes of axis_profile (include/mdhip.h: MDHIP_AP_*)
+AP_SURFACE = 0x4000  # code bit: the atom belongs to the surface
+AP_NONE = 0x3FFF     # row field of an atom that counts in no row
+
+
+def axis_profile_codes(row, surface):
+    """The 16-bit atom codes of axis_profile: `row` (integers, -1 = counts in no row) and `surface` (booleans), of one
+    shape ([N] or [F,N])."""
+    row = np.asarray(row, dtype=np.int64)
+    if row.size and (row.min() < -1 or row.max() >= AP_NONE):
+        raise ValueError("rows must be in [-1, %d)" % AP_NONE)
+    code = np.where(row < 0, AP_NONE, row) | np.where(np.asarray(surface, dtype=bool), AP_SURFACE, 0)
+    return np.ascontiguousarray(code, dtype=np.uint16)
+
+
+def axis_profile(x, rows, mode, bin_size, dist, n_bins, n_rows, origin="lo", ctx=None):
+    """
+    Per-frame atom counts along one axis, measured from a surface (number_density.py:76-105; include/mdhip.h:
+    mdhip_axis_profile): x [F,N] the axis coordinate (host array or contiguous float64 device tensor), rows the uint16 codes of
+    axis_profile_codes, [N] shared by the frames or [F,N] -> (counts uint32 [F,n_rows,n_bins], extent float64 [F,2]
+    (lo, hi of the surface atoms; NaN without any), outside uint32 [F]).
+    mode AP_REF_POS / AP_REF_NEG: the reference's selection on `dist` (dist_from_interface) and its binning, negative
+    bin indices wrapped; AP_PROFILE: s = x - origin ("lo", "hi" or a value per frame [F]), bins of bin_size from
+    s = dist, nothing wraps. `outside` counts the selected atoms that have no bin.
+    """
+    ctx = ctx or default_context()
+    shp = tuple(x.shape)
+    if len(shp) != 2:
+        raise ValueError("x must have shape [n_frames, n_atoms]")
+    F, N = shp
+    codes = np.ascontiguousarray(rows, dtype=np.uint16)
+    if codes.shape not in ((N,), (F, N)):
+        raise ValueError("rows must have shape [n_atoms] or [n_frames, n_atoms]")
+    per_frame = codes.ndim == 2
+    org, kind = None, 0
+    if isinstance(origin, str):
+        if origin not in ("lo", "hi"):
+            raise ValueError('origin must be "lo", "hi" or a value per frame')
+        kind = 1 if origin == "hi" else 0
+    else:
+        org, kind = _f64(np.broadcast_to(np.asarray(origin, dtype=np.float64), (F,))), 2
+    xp, x_dev, keep = as_input(x, ctx)
+    counts = result_array((F, int(n_rows), int(n_bins)), dtype=np.uint32, device=ctx.device)
+    extent = np.empty((F, 2), dtype=np.float64)
+    outside = np.empty(F, dtype=np.uint32)
+    ctx.check(ctx.lib.mdhip_axis_profile(
+        ctx.h, F, N, xp, x_dev, ptr(codes, C.c_uint16), int(per_frame), int(n_rows), int(mode), float(bin_size),
+        float(dist), int(n_bins), kind, None if org is None else ptr(org), ptr(counts, C.c_uint32), ptr(extent),
+        ptr(outside, C.c_uint32)))
+    return counts, extent, outside
