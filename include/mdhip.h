@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MDHIP_VERSION 600 /* 0.6.0: + mdhip_row_displacement, MDHIP_EUNKNOWN (mdhip_ticket_status of a forgotten ticket), mdhip_lag_msd* finishes on the device at every length; 0.5.0: + mdhip_ticket_status / mdhip_fallbacks / MDHIP_EPENDING (a call's own completion status), mdhip_lag_msd_status_dev; 0.4.0: the *_async entry points with mdhip_sync / mdhip_wait / mdhip_call_stats, mdhip_green_kubo, mdhip_cumtrapz_dev */
+#define MDHIP_VERSION 600 /* 0.6.0: + mdhip_pair_plan (which pair kernel a call would run, without a device), mdhip_row_displacement, MDHIP_EUNKNOWN (mdhip_ticket_status of a forgotten ticket), mdhip_lag_msd* finishes on the device at every length; 0.5.0: + mdhip_ticket_status / mdhip_fallbacks / MDHIP_EPENDING (a call's own completion status), mdhip_lag_msd_status_dev; 0.4.0: the *_async entry points with mdhip_sync / mdhip_wait / mdhip_call_stats, mdhip_green_kubo, mdhip_cumtrapz_dev */
 
 #define MDHIP_OK 0
 #define MDHIP_EINVAL (-1)  /* bad argument (shape, NULL, unsupported size) */
@@ -191,6 +191,36 @@ double mdhip_pk_error_bound(double r_cut, double bin_size, int nbins, int n_rows
  */
 int mdhip_row_displacement(int n_ti, int n_tj, const int32_t *cls, int32_t *a, int32_t *b, int32_t *row_cls,
                            int *n_rows);
+
+/*
+ * What a pair call would launch, decided from its shape alone: the library's own plan function (the one every
+ * mdhip_rdf_* / mdhip_cn_* call runs before it stages anything) behind the same label -> class -> row-displacement
+ * steps, with no device. ctx: NULL (the defaults of a fresh context), or a context whose options and device limits
+ * are read (never changed). op: MDHIP_PLAN_RDF (mdhip_rdf_atomic[_dev] / mdhip_rdf_sites), MDHIP_PLAN_CN
+ * (mdhip_cn_atomic / mdhip_cn_sites), MDHIP_PLAN_RDF_CN (mdhip_rdf_cn_atomic); a synchronous call.
+ *   type [n_type], site_type [n_site_type]   labels: the type column, or just every label that occurs in it;
+ *                      site_type NULL: atom-atom, else atoms x sites with n_sites sites
+ *   box                host [n_frames][3]
+ *   cn_r_cut_sq        [n_rel] for the two CN ops (r_cut_sq, bin_size, nbins are ignored by MDHIP_PLAN_CN), else NULL
+ *   result_on_device   1: the frame-summed RDF stays on the device (mdhip_rdf_atomic_dev)
+ *   xyz_on_device      0: host-resident frames, staged batch by batch (counts in the launches)
+ *   cu_count, lds_bytes   the two device limits the decision reads (<= 0: the context's; 256 / 65536 without one)
+ *   opt_key, opt_value [n_opt] overrides as for mdhip_set_option
+ * Out: info[8] = { status, scalar-j mode (-1: an LDS-tile kernel; see sj_kernel in csrc/pair_common.h), class passes
+ * per batch, pair-kernel launches of the whole call, ordered rows (0: class rows), rows displaced, BIG block,
+ * packed-f32 sweep }; status MDHIP_OK, MDHIP_PLAN_TWO_SWEEPS (an RDF + CN call that takes two sweeps: the RDF sweep is
+ * the one described) or a negative MDHIP_E* code. text: the kernel's name as mdhip_last_kernel_name reports it (first
+ * batch), or the error text. Returns MDHIP_EINVAL for unusable arguments, else MDHIP_OK. A pure function, deterministic.
+ */
+#define MDHIP_PLAN_RDF 0
+#define MDHIP_PLAN_CN 1
+#define MDHIP_PLAN_RDF_CN 2
+#define MDHIP_PLAN_TWO_SWEEPS 1
+int mdhip_pair_plan(const mdhip_ctx *ctx, int op, int64_t n_frames, int64_t n_atoms, const int32_t *type, int64_t n_type,
+                    int64_t n_sites, const int32_t *site_type, int64_t n_site_type, const double *box, int n_rel,
+                    const int32_t *rel, double r_cut_sq, double bin_size, int nbins, const double *cn_r_cut_sq, int per_frame,
+                    int result_on_device, int xyz_on_device, int cu_count, int64_t lds_bytes, int n_opt,
+                    const char *const *opt_key, const int *opt_value, char *text, int text_cap, int32_t *info);
 
 /* ---- R3: _rdf_loop (+ _calc_rsq, _remove_outliers) ------------------------ */
 /*

@@ -25,12 +25,14 @@
 //   pair_cull.hip   the spatial pre-pass: Hilbert sort, bounding boxes, neighbour-tile lists
 //   pair_dense.hip  LDS-tile kernels: dense half-shell sweep for small frames, the edge-table kernel of the
 //                   first commit (A/B baseline, fallback for > 64 CN cutoffs)
-// This file: relations -> classes, edge tables, batching, launch geometry, rows -> outputs, the C-ABI.
-#include <chrono>
+// This file: relations -> classes (classify), batching (batch_parts, run_parts), one batch as plan -> stage_tables ->
+// cull_prepass -> launch_pass -> collect_* (pair_hist_run_batch; the plan itself — kernel variant, row layout, error
+// bands, launch geometry, table offsets — is pair_plan.h: pure arithmetic, no device), rows -> outputs, the C-ABI.
 #include <map>
 #include <mutex>
+#include <optional>
 
-#include "pair_common.h"
+#include "pair_plan.h"
 
 using namespace mdpair;
 
@@ -39,49 +41,6 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-
-struct PairProblem {
-    int64_t n_frames;
-    int64_t ni, nj;
-    const double *d_xi, *d_xj;  // device
-    const int *d_ti, *d_tj;     // device compact type index
-    int64_t ti_fs, tj_fs;
-    const double *d_box;        // device [F][3]
-    const double *h_box;        // host   [F][3]
-    bool tri;
-    int n_ti, n_tj;
-    std::vector<int> cls;  // [n_ti][n_tj] -> class id (< n_cls; any number of classes: the device sees pass-local bytes)
-    int n_cls;
-    // displaced ordered rows (displace_rows below): row of (ti, tj) = disp_a[ti] + disp_b[tj]; disp_rows == 0: none found
-    std::vector<int> disp_a, disp_b, disp_cls;  // disp_cls[row] -> class id (-1: no type pair lands there)
-    int disp_rows = 0;
-    int nbins;
-    const double *edges;  // host [nbins+1]
-    double rc2;
-    float gscale;
-    double bin_size;  // RDF: the reference's bin_size (0 for CN edge tables)
-    int per_frame;
-    // frame-summed RDF outputs kept on the device (mdhip_rdf_atomic_dev): full | part | overflow, accumulated by
-    // derive_rdf_kernel straight from the row sums when the batch runs as one scalar-j pass; otherwise the batch
-    // comes back as host class histograms like every other call and the caller adds them in
-    unsigned long long *dev_out = nullptr;
-    int n_rel = 0;
-    const int *rel_cls = nullptr;   // host [n_rel]
-    const int *rel_mult = nullptr;  // host [n_rel]
-    // coordination numbers from the same sweep (mdhip_rdf_cn_atomic): one cutoff^2 per class (0: none). The bins of
-    // the histogram are exact, so only the pairs of the bin that holds a class's cutoff (its split bin) need the exact
-    // comparison: Hsplit counts those that are inside. Only the packed-f32 sweep does this — a batch that cannot run
-    // it returns CN_UNFUSED and the caller runs a separate CN job
-    int n_cn = 0;                             // != 0: on
-    const double *cn_c2_cls = nullptr;        // host [n_cls]
-    std::vector<uint64_t> *Hsplit = nullptr;  // out: [F|1][n_cls] pairs of the split bin with rsq < cutoff^2
-    // Host-resident coordinates staged batch by batch (pair_hist_run): h_xi / h_xj are the caller's arrays, d_xi / d_xj
-    // the (still empty) device buffers for all frames; the copy of batch k+1 runs on ctx->copy_stream while batch k is
-    // swept. nullptr: the coordinates are on the device already.
-    const double *h_xi = nullptr, *h_xj = nullptr;
-};
-constexpr int CN_UNFUSED = 1;  // (positive: not an error code of the ABI)
-constexpr int SPLIT_BATCH = 2;  // a block may have wrapped a 32-bit LDS word: run the batch again in halves
 
 // Row displacement for the ordered-pair rows. The table-free sweep adds to word A[ti] + B[tj] + bin — the lane holds
 // A[ti] rows as its base, the j atom's record carries B[tj] rows in the addend of the bin guess — and the plain layout
@@ -93,7 +52,8 @@ constexpr int SPLIT_BATCH = 2;  // a block may have wrapped a 32-bit LDS word: r
 // integers A, B with  A[i] + B[j] == A[k] + B[l]  =>  cls(i, j) == cls(k, l),  minimising max A + max B + 1. Greedy,
 // type by type (A[k] and B[k] together, smallest resulting row count first), over a few orders; 15 rows instead of 36
 // for the example above. The kernels are unchanged: they see A and B through the records (pack_w) and row_mul.
-// Cached per class table (the search costs ~1 ms; a drop-in run repeats the same relations for every batch).
+// Cached per class table (the search costs ~1 ms, at most DISPLACE_BUDGET candidates plus one attempt; a drop-in run
+// repeats the same relations for every batch).
 struct DispKey {
     int n_ti, n_tj;
     std::vector<int> cls;
@@ -110,7 +70,7 @@ struct DispVal {
 };
 
 static int displace_greedy(int n_ti, int n_tj, const std::vector<int> &cls, const std::vector<int> &order, int give_up,
-                           std::vector<int> &A, std::vector<int> &B, std::vector<int> &row_cls)
+                           std::vector<int> &A, std::vector<int> &B, std::vector<int> &row_cls, uint64_t &trials)
 {
     const int n = std::max(n_ti, n_tj);
     A.assign(n_ti, -1);
@@ -128,6 +88,7 @@ static int displace_greedy(int n_ti, int n_tj, const std::vector<int> &cls, cons
             for (int bi = 0; bi < (has_b ? lim : 1); ++bi) {
                 const int ma = has_a ? std::max(max_a, ai) : max_a, mb = has_b ? std::max(max_b, bi) : max_b;
                 const int r = ma + mb + 1, sc = ai + bi;
+                ++trials;
                 if (r >= give_up) break;  // (bi only grows)
                 if (r > best_r || (r == best_r && sc >= best_s)) continue;
                 // consistent with every row written so far, and with itself?
@@ -176,6 +137,7 @@ static int displace_greedy(int n_ti, int n_tj, const std::vector<int> &cls, cons
     return rows;
 }
 
+constexpr uint64_t DISPLACE_BUDGET = 2500000;  // (ai, bi) candidates per table, checked between attempts
 // -> rows of the best displaced layout found (0: none with fewer rows than the plain layout, or too many types to try)
 static int displace_rows(int n_ti, int n_tj, const std::vector<int> &cls, std::vector<int> &A, std::vector<int> &B,
                          std::vector<int> &row_cls)
@@ -200,7 +162,7 @@ static int displace_rows(int n_ti, int n_tj, const std::vector<int> &cls, std::v
     std::vector<int> order(n), a, b, rc;
     for (int k = 0; k < n; ++k) order[k] = k;
     uint64_t lcg = 0x9E3779B97F4A7C15ull;
-    const auto t_start = std::chrono::steady_clock::now();
+    uint64_t trials = 0;  // (ai, bi) candidates looked at so far, over all attempts
     for (int attempt = 0; attempt < 400; ++attempt) {
         if (attempt == 1) std::reverse(order.begin(), order.end());
         if (attempt >= 2)
@@ -209,14 +171,14 @@ static int displace_rows(int n_ti, int n_tj, const std::vector<int> &cls, std::v
                 std::swap(order[k], order[(size_t)((lcg >> 33) % (uint64_t)(k + 1))]);
             }
         const int give_up = best.rows ? best.rows : plain;  // only strictly better layouts
-        const int rows = displace_greedy(n_ti, n_tj, cls, order, give_up, a, b, rc);
+        const int rows = displace_greedy(n_ti, n_tj, cls, order, give_up, a, b, rc, trials);
         if (rows > 0 && (best.rows == 0 || rows < best.rows)) {
             best.rows = rows;
             best.a = a;
             best.b = b;
             best.row_cls = rc;
         }
-        if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() > 0.02) break;
+        if (trials > DISPLACE_BUDGET) break;  // a fixed amount of work, not of time: the layout never depends on the machine's load
     }
     {
         std::lock_guard<std::mutex> lk(mu);
@@ -229,8 +191,402 @@ static int displace_rows(int n_ti, int n_tj, const std::vector<int> &cls, std::v
     return best.rows;
 }
 
+// what the host half of a batch's passes accumulates (shared with the completion step of a deferred batch)
+struct BatchAcc {
+    double total_ms = 0.0, prep_ms = 0.0;
+    int launches = 0;
+    unsigned long long ov = 0;
+    bool prep_timed = false;
+    KernelTimer prep;
+    explicit BatchAcc(const KernelTimer &t) : prep(t) {}
+};
+
+// One batch between plan and results: the staged tables, the flag words, and where the results go.
+struct Batch {
+    const PairProblem &p;
+    const PairPlan &pl;
+    std::vector<uint64_t> &H;
+    size_t out_frames;
+    unsigned char *d_tab = nullptr, *h_tab = nullptr;  // the packed table buffer (PairPlan's offsets), device | pinned
+    unsigned long long *d_misc = nullptr;              // flag words [8] | row sums (one_sum)
+    std::shared_ptr<BatchAcc> acc;
+};
+
+// One launched pass: its classes [c0, c0 + nc), its rows on the device, its timer.
+struct Pass {
+    int pass, c0, nc;
+    int sj_rows, cn_len, sj_words;       // scalar-j: rows of the block histograms, split counters per row, words
+    size_t words;                        // dense: words of the pass's class histograms
+    unsigned long long *d_rows = nullptr, *d_hist = nullptr;
+    std::optional<KernelTimer> timer;
+};
+
+// Writes the plan's packed table buffer — edges | class table of every pass | CN tables | displaced A, B | row map —
+// into pinned memory and sends it to the device in ONE small copy. -> the displaced-row tables as the sort pre-pass
+// wants them, and the reach of the split bins.
+static int stage_tables(mdhip_ctx *ctx, Batch &b, RowDisp &disp_i, RowDisp &disp_j, float &cn_reach)
+{
+    const PairProblem &p = b.p;
+    const PairPlan &pl = b.pl;
+    const std::vector<int> &row_cls = *pl.row_cls;
+    MD_WS(d_tab, unsigned char, WS_TABLES, pl.tab_al + pl.map_b);
+    MD_PIN(h_tab, unsigned char, pl.tab_al + pl.map_b + 32);
+    double *e = reinterpret_cast<double *>(h_tab);
+    std::copy(p.edges, p.edges + p.nbins + 1, e);
+    e[p.nbins + 1] = std::numeric_limits<double>::infinity();
+    if (p.n_cn) {
+        int *fl = reinterpret_cast<int *>(h_tab + pl.cn_off);
+        double *c2r = reinterpret_cast<double *>(fl + pl.cn_fw);
+        std::fill(fl, fl + pl.cn_fw, -1);
+        double reach = 0.0;
+        for (int r = 0; r < pl.cn_rows; ++r) {
+            const int cl = pl.ordered ? row_cls[r] : (r < p.n_cls ? r : -1);
+            const double c2 = cl >= 0 ? p.cn_c2_cls[cl] : 0.0;
+            c2r[r] = c2;
+            if (!(c2 > 0.0)) continue;
+            // split bin kc: edges[kc] <= c2 < edges[kc + 1]; none when the cutoff sits exactly on an edge
+            const int kc = (int)(std::upper_bound(p.edges, p.edges + p.nbins + 1, c2) - p.edges) - 1;
+            if (p.edges[kc] == c2) continue;
+            fl[r] = r * (p.nbins + 1) + kc;
+            const double top = kc + 1 <= p.nbins ? std::sqrt(p.edges[kc + 1]) : std::sqrt(p.rc2);
+            reach = std::max(reach, std::min(top, std::sqrt(p.rc2)));
+        }
+        cn_reach = (float)((reach + 1e-3) * 1.00001);
+    }
+    for (int pass = 0; pass < pl.n_pass; ++pass) {
+        const int c0 = pl.pass_c0(pass), nc = pl.pass_nc(pass, p.n_cls);
+        unsigned char *t = h_tab + pl.edges_b + (size_t)pass * pl.cls_b;
+        for (size_t k = 0; k < (size_t)p.n_ti * p.n_tj; ++k) {
+            const int c = p.cls[k];  // (pass-local ids are < 250: they fit the byte, 0xFF = other pass)
+            t[k] = (c >= c0 && c < c0 + nc) ? (unsigned char)(c - c0) : 0xFF;
+        }
+    }
+    if (pl.disp_b) {
+        int *h_d = reinterpret_cast<int *>(h_tab + pl.disp_off);
+        std::copy(p.disp_a.begin(), p.disp_a.end(), h_d);
+        std::copy(p.disp_b.begin(), p.disp_b.end(), h_d + p.n_ti);
+        const int *d_d = reinterpret_cast<const int *>(d_tab + pl.disp_off);
+        // atom-atom: one sorted set plays both roles (low word A, addend B); atoms x sites: the i set's addend and the j
+        // set's low word are never read
+        disp_i.lo = d_d;
+        disp_i.hi = p.tri ? d_d + p.n_ti : d_d;
+        disp_j.lo = disp_j.hi = d_d + p.n_ti;
+    }
+    if (pl.map_rides) {
+        int *h_map = reinterpret_cast<int *>(h_tab + pl.tab_al);
+        for (int r = 0; r < pl.sj_rows1; ++r) h_map[r] = pl.ordered ? row_cls[r] : (r < p.n_cls ? r : -1);
+        for (int kl = 0; kl < p.n_rel; ++kl) {
+            h_map[pl.sj_rows1 + kl] = p.rel_cls[kl];
+            h_map[pl.sj_rows1 + p.n_rel + kl] = p.rel_mult[kl];
+        }
+    }
+    b.d_tab = d_tab;
+    b.h_tab = h_tab;
+    return mdhip_copy_small(ctx, d_tab, h_tab, pl.tab_al + pl.map_b, hipMemcpyHostToDevice);
+}
+
+// The culled path's pre-pass — Hilbert sort, tile boxes, neighbour-tile lists; once, shared by all class passes —
+// under a timer of its own. Points `a` at the sorted copies.
+static int cull_prepass(mdhip_ctx *ctx, Batch &b, const RowDisp &disp_i, const RowDisp &disp_j, PairArgs &a)
+{
+    const PairProblem &p = b.p;
+    const PairPlan &pl = b.pl;
+    const int64_t F = p.n_frames;
+    const int nTi = pl.nTi, nTj = pl.nTj;
+    const long long N = p.ni;
+    const bool want_soa = !pl.sj;  // only the LDS-tile kernel (atom-atom) reads the SoA copy
+    MD_WS(d_l, unsigned short, WS_LIST, (size_t)F * nTi * (p.tri ? nTi : nTj) * 2);
+    MD_WS(d_lc, int, WS_LISTCNT, (size_t)F * nTi * 4);
+    KernelTimer ptimer(ctx, 1, true);  // second event pair: collected with the pair kernel's
+    SortedSet si, sj_set;
+    const int slot_i[5] = {WS_SORT_AOS, WS_BBOX, WS_GSPH, WS_WSPH, WS_GSPH4};
+    // (the bin-guess addend near + type * row_len and the tile-relative f32 records belong to the j set)
+    const float near = pl.ordered ? pl.near_ord : 0.f;
+    const int row_len = pl.ordered ? p.nbins + 1 : 0;
+    int rc = cull_prepare_set(ctx, F, p.d_xi, p.d_ti, (long long)p.ti_fs, p.d_box, N, nTi, p.n_ti, near, row_len, disp_i,
+                              want_soa, pl.pk && p.tri ? pl.rel_block : 0, pl.pk_rows ? 1 : 0, pl.pk ? 1 : 0, slot_i, si);
+    if (rc) return rc;
+    if (p.tri) {
+        sj_set = si;
+    } else {
+        const int slot_j[5] = {WS_SORT_AOS_J, WS_BBOX_J, WS_GSPH_J, WS_WSPH_J, WS_GSPH4_J};
+        rc = cull_prepare_set(ctx, F, p.d_xj, p.d_tj, (long long)p.tj_fs, p.d_box, p.nj, nTj, p.n_ti, near, row_len, disp_j,
+                              false, pl.pk ? pl.rel_block : 0, pl.pk_rows ? 1 : 0, pl.pk ? 1 : 0, slot_j, sj_set);
+        if (rc) return rc;
+    }
+    launch_cull_lists(ctx->stream, p.tri, F, si.bbox, sj_set.bbox, nTi, nTj, p.d_box, p.rc2 * (1.0 + 1e-9) + 1e-9, d_l,
+                      d_lc);
+    ptimer.stop();
+    MD_HIP(hipGetLastError());
+    b.acc = std::make_shared<BatchAcc>(ptimer);
+    b.acc->prep_timed = true;
+    a.gsph = sj_set.gs;    // 8-atom boxes of the j set (LDS-tile kernel)
+    a.gsph4 = sj_set.gs4;  // 4-atom boxes of the j set (scalar-j kernel)
+    a.wsph = si.ws;        // 64-atom boxes of the i set
+    if (want_soa) {
+        a.xi = a.xj = si.sx;
+        a.ti = a.tj = si.st;
+        a.ti_fs = a.tj_fs = N;
+    }
+    a.list = d_l;
+    a.list_cnt = d_lc;
+    a.aos = si.aos;
+    a.aos_j = sj_set.aos;
+    a.rel = sj_set.rel;
+    a.cen = sj_set.cen;
+    return MDHIP_OK;
+}
+
+// Everything of the kernel's arguments that is the same for every pass (the inputs as the caller gave them:
+// cull_prepass redirects them to the sorted copies).
+static PairArgs batch_args(const Batch &b, float cn_reach)
+{
+    const PairProblem &p = b.p;
+    const PairPlan &pl = b.pl;
+    PairArgs a{};
+    a.xi = p.d_xi;
+    a.xj = p.d_xj;
+    a.ti = p.d_ti;
+    a.tj = p.d_tj;
+    a.ti_fs = p.ti_fs;
+    a.tj_fs = p.tj_fs;
+    a.reach = (float)((std::sqrt(p.rc2) + 1e-3) * 1.00001);
+    a.tri = p.tri ? 1 : 0;
+    a.box = p.d_box;
+    a.edges = reinterpret_cast<const double *>(b.d_tab);
+    a.overflow = b.d_misc;
+    a.ni = p.ni;
+    a.nj = p.nj;
+    a.rc2 = p.rc2;
+    a.gscale = p.gscale;
+    a.n_ti = p.n_ti;
+    a.n_tj = p.n_tj;
+    a.row_mul = pl.ordered && pl.displaced ? 1 : p.n_tj;
+    a.n_rows_ord = pl.ord_rows;
+    a.nbins = p.nbins;
+    a.n_frames = (int)p.n_frames;
+    a.nTi = pl.nTi;
+    a.nTj = pl.nTj;
+    a.jsplit = pl.jsplit;
+    a.blocks_per_frame = pl.blocks_per_frame;
+    a.per_frame = p.per_frame;
+    a.slots = pl.slots;
+    a.fpb = pl.fpb;
+    a.near = pl.pk_rows ? pl.near_pk_f : pl.near_ord;
+    a.s_cap = pl.s_cap;
+    a.rc2hi = pl.rc2hi;
+    a.cut_lo = pl.cut_lo;
+    a.n_cn = p.n_cn;
+    a.cn_tab = reinterpret_cast<const unsigned *>(b.d_tab + pl.cn_off);
+    a.cn_reach = cn_reach;
+    a.work = reinterpret_cast<unsigned *>(b.d_misc + 4);
+    return a;
+}
+
+// Launches one class pass (and, for the scalar-j kernels, the merge of the blocks' histogram slices) under ps.timer.
+// The scalar-j grid is sized here: it needs the kernel's occupancy on this device.
+static int launch_pass(mdhip_ctx *ctx, const Batch &b, PairArgs a, Pass &ps)
+{
+    const PairProblem &p = b.p;
+    const PairPlan &pl = b.pl;
+    const int64_t F = p.n_frames;
+    const bool sj = pl.sj;
+    const size_t acc_frames = p.per_frame ? (size_t)F : (size_t)pl.slots;
+    MD_WS(d_hist, unsigned long long, WS_HIST, (acc_frames + 1) * ps.words * 8);
+    // (the scalar-j kernels keep their histograms in LDS and store them to their own slices: nothing of theirs is
+    // added to d_hist, so it need not be emptied for them — one fill less per call)
+    if (!sj) MD_HIP(hipMemsetAsync(d_hist, 0, acc_frames * ps.words * 8, ctx->stream));
+    ps.d_hist = d_hist;
+    a.cls = b.d_tab + pl.edges_b + (size_t)ps.pass * pl.cls_b;
+    a.hist = d_hist;
+    a.n_cls = ps.nc;
+    const size_t lds = pl.lds[ps.pass];
+    if (sj) {
+        a.guard_off = (unsigned)((lds + 15) & ~size_t(15));
+        a.guard_tiles = pl.guard_tiles;
+    }
+    const size_t lds_launch = sj ? ((lds + 15) & ~size_t(15)) + 16 : lds;
+    const int bs = pl.bs, wpb = bs / 64;  // independent waves per block (scalar-j kernels)
+    ctx->last_kernel = pl.kname;
+    if (lds_launch > 65536)
+        MD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pl.kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds_launch));
+    long long launch_grid = pl.grid;
+    if (sj) {
+        int per_cu = 0;
+        MD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(pl.kern), bs,
+                                                            lds_launch));
+        if (per_cu < 1) per_cu = 1;
+        const long long capacity = (long long)per_cu * ctx->cu_count;
+        // blocks' worth of wave items per frame (a frame has nTi * 4 * jsplit wave items)
+        const long long block_items = ((long long)pl.nTi * 4 * pl.jsplit + wpb - 1) / wpb;
+        a.fpb = 1;
+        if (pl.persist) {
+            launch_grid = std::min(capacity, F * block_items + 8);
+            launch_grid = (launch_grid + 7) / 8 * 8;
+            // (the work counters: the first pass finds them empty, d_misc was zeroed whole at the top of the batch)
+            if (ps.pass > 0) MD_HIP(hipMemsetAsync(b.d_misc + 4, 0, 32, ctx->stream));
+        } else {
+            // per-frame output: as many blocks per frame as keeps one resident set busy, each flushing once
+            // blocks per frame: few frames in flight per XCD (their records should stay in its 4 MB L2: 32 B per
+            // atom per frame), every wave still left with a few items to draw
+            const long long cap_xcd = std::max<long long>(1, capacity / 8);
+            const long long frames_xcd = (F + 7) / 8;
+            const long long in_flight = std::max<long long>(1, std::min<long long>(frames_xcd, ctx->opt_rdf_inflight));
+            long long bpf = std::max<long long>(1, cap_xcd / in_flight);
+            bpf = std::min(bpf, std::max<long long>(1, block_items / 2));
+            // every block stores one copy of its LDS histogram: keep that workspace within ~2 GiB
+            while (bpf > 8 && (double)(((F + 7) / 8) * 8 * bpf) * (double)lds > 2147483648.0) bpf /= 2;
+            a.blocks_per_frame = (int)bpf;
+            launch_grid = ((F + 7) / 8) * 8 * bpf;
+            MD_WS(d_work, unsigned, WS_WORK, (size_t)F * 4);
+            MD_HIP(hipMemsetAsync(d_work, 0, (size_t)F * 4, ctx->stream));
+            a.work = d_work;
+        }
+        // every block stores its LDS histogram into its own slice; a merge kernel adds them up
+        MD_WS(d_sl, unsigned, WS_SLICES, (size_t)launch_grid * ps.sj_words * 4);
+        if (pl.one_sum && pl.rows1_b == (size_t)ps.sj_words * 8) {
+            ps.d_rows = b.d_misc + 8;  // (emptied with the flag words at the top of the batch)
+        } else {
+            ps.d_rows = (unsigned long long *)mdhip_ws(ctx, WS_ROWS, b.out_frames * (size_t)ps.sj_words * 8);
+            if (!ps.d_rows) return MDHIP_ENOMEM;
+            if (!p.per_frame) MD_HIP(hipMemsetAsync(ps.d_rows, 0, (size_t)ps.sj_words * 8, ctx->stream));
+        }
+        a.slices = d_sl;
+    }
+    ps.timer.emplace(ctx);
+    hipLaunchKernelGGL(pl.kern, dim3((unsigned)launch_grid), dim3(bs), lds_launch, ctx->stream, a);
+    if (sj) {
+        const unsigned gy = p.per_frame ? (unsigned)F : (unsigned)std::min<long long>(64, launch_grid);
+        launch_merge_slices(ctx->stream, a.slices, ps.sj_words, launch_grid, p.per_frame, a.blocks_per_frame, gy, ps.d_rows);
+    }
+    ps.timer->stop();
+    MD_HIP(hipGetLastError());
+    return MDHIP_OK;
+}
+
+// the launch's flags (pinned): [0] deferred pairs lost, [1] work-loop assertion, [2] overflow guard
+static int check_flags(mdhip_ctx *ctx, const uint64_t *hlost)
+{
+    if (hlost[2]) return SPLIT_BATCH;
+    if (hlost[0] || hlost[1])
+        return mdhip_fail(ctx, MDHIP_EHIP, "pair_hist: internal check failed (%llu deferred pairs lost, work loop %llu)",
+                          (unsigned long long)hlost[0], (unsigned long long)hlost[1]);
+    return MDHIP_OK;
+}
+
+static void collect_times(BatchAcc &acc, const KernelTimer &timer)
+{
+    acc.total_ms += timer.collect();
+    ++acc.launches;
+    if (acc.prep_timed) {  // the pre-pass ran ahead of the first pass on the same stream: its events are complete
+        acc.prep_ms = acc.prep.collect();
+        acc.prep_timed = false;
+    }
+}
+
+// Collector 1 — results stay on the device: rows -> full | part | overflow by derive_rdf_kernel (added to dev_out; the
+// row map came with the tables: map_rides); only the flag words come back. -> the pass's host half in `fin`.
+static int collect_device(mdhip_ctx *ctx, const Batch &b, const Pass &ps, std::function<int()> &fin)
+{
+    const PairProblem &p = b.p;
+    const PairPlan &pl = b.pl;
+    if (!pl.map_rides || ps.sj_rows != pl.sj_rows1)
+        return mdhip_fail(ctx, MDHIP_EHIP, "pair_hist: internal: the row map of the device-resident path is missing");
+    const int *d_map = reinterpret_cast<const int *>(b.d_tab + pl.tab_al);
+    launch_derive_rdf(ctx->stream, ps.d_rows, ps.sj_rows, p.nbins, d_map, p.n_rel, d_map + ps.sj_rows,
+                      d_map + ps.sj_rows + p.n_rel, b.d_misc + 3, p.dev_out);
+    MD_HIP(hipGetLastError());
+    uint64_t *hlost = reinterpret_cast<uint64_t *>(b.h_tab + pl.tab_al + ((pl.map_b + 7) & ~size_t(7)));
+    const int rcc = mdhip_copy_small(ctx, hlost, b.d_misc + 1, 24, hipMemcpyDeviceToHost);
+    if (rcc) return rcc;
+    fin = [ctx, acc = b.acc, timer = *ps.timer, hlost]() {
+        const int rcf = check_flags(ctx, hlost);
+        if (rcf) return rcf;
+        collect_times(*acc, timer);
+        return (int)MDHIP_OK;
+    };
+    return MDHIP_OK;
+}
+
+// Collector 2 — scalar-j rows: D2H of the row sums (pinned staging), then rows -> classes, the split counters and the
+// overflow words on the host. -> the pass's host half in `fin`.
+static int collect_sj_rows(mdhip_ctx *ctx, const Batch &b, const Pass &ps, std::function<int()> &fin)
+{
+    const PairProblem &p = b.p;
+    const PairPlan &pl = b.pl;
+    const size_t out_frames = b.out_frames, sj_words = (size_t)ps.sj_words;
+    MD_PIN(hall, uint64_t, (out_frames * sj_words + 16) * 8);
+    uint64_t *hrows = hall + 8;
+    uint64_t *hlost = hrows + out_frames * sj_words;  // [0] queue overflow, [1] work-loop assertion
+    if (ps.d_rows == b.d_misc + 8 && out_frames == 1) {
+        // the row sums sit behind the flag words (one_sum): flags and rows leave in ONE copy
+        hlost = hall + 1;
+        const int rcc = mdhip_copy_small(ctx, hall, b.d_misc, (8 + sj_words) * 8, hipMemcpyDeviceToHost);
+        if (rcc) return rcc;
+    } else {
+        int rcc = mdhip_copy_small(ctx, hrows, ps.d_rows, out_frames * sj_words * 8, hipMemcpyDeviceToHost);
+        if (!rcc) rcc = mdhip_copy_small(ctx, hlost, b.d_misc + 1, 24, hipMemcpyDeviceToHost);
+        if (rcc) return rcc;
+    }
+    std::vector<uint64_t> *Hp = &b.H, *Hsplit = p.Hsplit;
+    fin = [ctx, acc = b.acc, timer = *ps.timer, hrows, hlost, Hp, Hsplit, out_frames, sj_words, sj_rows = ps.sj_rows,
+           cn_len = ps.cn_len, ordered = pl.ordered, nc = ps.nc, c0 = ps.c0, n_cls_all = p.n_cls, nbins_all = p.nbins,
+           cls = pl.ordered ? *pl.row_cls : std::vector<int>()]() {
+        const int rcf = check_flags(ctx, hlost);
+        if (rcf) return rcf;
+        collect_times(*acc, timer);
+        const int row_len = nbins_all + 1;
+        for (size_t fr = 0; fr < out_frames && cn_len; ++fr)
+            for (int r = 0; r < sj_rows; ++r) {
+                const uint64_t *src = hrows + fr * sj_words + (size_t)sj_rows * row_len + (size_t)r;
+                const int cl = ordered ? cls[r] : (r < nc ? c0 + r : -1);
+                if (cl >= 0) (*Hsplit)[fr * n_cls_all + cl] += src[0];
+            }
+        for (size_t fr = 0; fr < out_frames; ++fr)
+            for (int r = 0; r < sj_rows; ++r) {
+                const uint64_t *src = hrows + fr * sj_words + (size_t)r * row_len;
+                acc->ov += src[nbins_all];
+                // ordered rows (ti, tj) -> class of the unordered pair; class rows of this pass -> c0 + r, the
+                // extra row holds the pairs whose class belongs to another pass
+                const int cl = ordered ? (int)cls[r] : (r < nc ? c0 + r : -1);
+                if (cl < 0) continue;
+                uint64_t *dst = &(*Hp)[(fr * n_cls_all + cl) * nbins_all];
+                for (int k = 0; k < nbins_all; ++k) dst[k] += src[k];
+            }
+        return (int)MDHIP_OK;
+    };
+    return MDHIP_OK;
+}
+
+// Collector 3 — dense slots (LDS-tile and edge-table kernels): reduce the replicas, D2H (pinned staging) into the right
+// class rows behind a stream sync; the overflow word rides along with the last pass.
+static int collect_dense(mdhip_ctx *ctx, Batch &b, const Pass &ps)
+{
+    const PairProblem &p = b.p;
+    const PairPlan &pl = b.pl;
+    const size_t out_frames = b.out_frames, words = ps.words;
+    const bool last = ps.pass == pl.n_pass - 1;
+    unsigned long long *d_final = ps.d_hist;
+    if (!p.per_frame && pl.slots > 1) {
+        d_final = ps.d_hist + (size_t)pl.slots * words;
+        launch_reduce_slots(ctx->stream, ps.d_hist, d_final, (int)words, pl.slots);
+        MD_HIP(hipGetLastError());
+    }
+    MD_PIN(tmp, uint64_t, (out_frames * words + 1) * 8);
+    MD_HIP(hipMemcpyAsync(tmp, d_final, out_frames * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (last) MD_HIP(hipMemcpyAsync(tmp + out_frames * words, b.d_misc, 8, hipMemcpyDeviceToHost, ctx->stream));
+    MD_HIP(mdhip_stream_wait(ctx));
+    if (last) b.acc->ov = tmp[out_frames * words];  // (d_misc[0] accumulates over the passes)
+    collect_times(*b.acc, *ps.timer);
+    for (size_t fr = 0; fr < out_frames; ++fr)
+        memcpy(&b.H[(fr * p.n_cls + ps.c0) * p.nbins], &tmp[fr * words], words * 8);
+    return MDHIP_OK;
+}
+
 // Runs the kernel over one batch of frames (in several passes when the class rows do not fit LDS) and
-// returns the class histograms on the host: H [F|1][n_cls][nbins], overflow count.
+// returns the class histograms on the host: H [F|1][n_cls][nbins], overflow count. The sequence: pair_plan ->
+// stage_tables -> cull_prepass -> per pass: launch_pass, one of the three collectors.
 // `defer` (an asynchronous call's scope, or nullptr): when the batch runs as ONE scalar-j pass, its host half — flag
 // check, timer read-out, folding the row sums into H — is left as a completion step of that call instead of being done
 // behind a stream sync here; H, *overflow, p.Hsplit and *redo must then outlive the call (they are parts of the entry
@@ -239,364 +595,32 @@ static int displace_rows(int n_ti, int n_tj, const std::vector<int> &cls, std::v
 int pair_hist_run_batch(mdhip_ctx *ctx, const PairProblem &p, std::vector<uint64_t> &H, uint64_t *overflow,
                         CallScope *defer = nullptr, bool *redo = nullptr)
 {
-    const int64_t F = p.n_frames;
-    const int nTi = (int)((p.ni + TILE - 1) / TILE);
-    const int nTj = (int)((p.nj + TILE - 1) / TILE);
-    const size_t out_frames = p.per_frame ? (size_t)F : 1;
+    const size_t out_frames = p.per_frame ? (size_t)p.n_frames : 1;
     H.assign(out_frames * p.n_cls * p.nbins, 0);
     if (p.Hsplit) p.Hsplit->assign(out_frames * p.n_cls, 0);
     *overflow = 0;
-    if (F == 0 || p.ni == 0 || p.nj == 0) return MDHIP_OK;
+    if (p.n_frames == 0 || p.ni == 0 || p.nj == 0) return MDHIP_OK;
 
-    // kernel variant: 0 = reference-shaped loops with an edge-table lookup per pair (always used for CN
-    // edge tables, gscale == 0); 1 = fast kernel (table-free binning with an exact guard band)
-    const bool mode_cn = !(p.gscale > 0.f);  // CN edge table: a few sorted cutoffs^2, bins found by counting
-    // The table-free bin guess of the fast kernels indexes a row of nbins + 1 words: that is enough exactly when
-    // nbins = int(r_cut / bin_size) as the reference computes it (rdf_cn.py:169); a caller that passes fewer bins
-    // gets the edge-table kernel, which clamps.
-    const bool bins_ok = mode_cn || !(p.bin_size > 0.0) || std::sqrt(p.rc2) / p.bin_size < (double)p.nbins + 1.0 - 1e-9;
-    const bool fast = ctx->opt_rdf_variant == 1 && bins_ok && (mode_cn ? p.nbins <= 64 : p.nbins <= 100000);
-
-    // spatial culling: worth it when the cutoff sphere is a small part of the box (atoms x sites: scalar-j
-    // kernel only)
-    bool cull = false;
-    if (fast && nTi >= 8 && nTi <= 65535 && nTj <= 65535 && ctx->opt_rdf_cull != 0 &&
-        (p.tri || (ctx->opt_rdf_sj != 0 && nTj >= 2))) {
-        const double V = p.h_box[0] * p.h_box[1] * p.h_box[2];
-        const double edge = 0.5 * (std::cbrt((double)TILE * V / (double)p.ni) +
-                                   std::cbrt((double)TILE * V / (double)p.nj));
-        const double reach = std::sqrt(p.rc2) + 0.8 * edge;
-        const double est = 4.18879 * reach * reach * reach / V;  // share of tile pairs that survive
-        cull = ctx->opt_rdf_cull == 1 || est < 1.5;  // measured: still +5 % at est = 1.08 (BASELINE C2)
-    }
-
-    // classes per pass limited by LDS (keep >= 2 blocks per CU when possible)
-    const size_t lds_cap = ctx->lds_max > 0 ? ctx->lds_max : 65536;
-    const size_t fixed = fast ? lds_bytes_fast(p.nbins, 0, p.n_ti, p.n_tj) : lds_bytes(p.nbins, 0, p.n_ti, p.n_tj);
-    const size_t row_b = fast ? (size_t)(p.nbins + 1) * 4 : (size_t)p.nbins * 4;
-    if (fixed + row_b > lds_cap)
-        return mdhip_fail(ctx, MDHIP_ELIMIT, "pair_hist: %d bins do not fit LDS (%zu B)", p.nbins,
-                          lds_cap);
-    const size_t budget = lds_cap / 2 > fixed + row_b ? lds_cap / 2 : lds_cap;
-    int cls_per_pass = (int)((budget - fixed) / row_b);
-    if (cls_per_pass > p.n_cls) cls_per_pass = p.n_cls;
-    if (cls_per_pass > 250) cls_per_pass = 250;
-
-    // Ordered-pair rows (MODE 2 / 3 of the scalar-j kernel): one LDS row per (ti, tj) addressed without a table —
-    // the row offset rides in the addend of the bin guess. Needs all n_ti^2 rows in LDS and all classes in one pass:
-    // at >= 4 blocks of 4 waves per CU for the all-f64 sweep, at 3 blocks of 8 waves (6 waves per SIMD) for the
-    // packed-f32 sweep, whose blocks share one histogram among 8 waves.
-    // Row layout of the ordered modes: plain (row = ti * n_tj + tj) unless that does not fit the packed sweep's third of
-    // LDS and the displaced layout of displace_rows (row = A[ti] + B[tj], classes never mixed in a row) does.
-    // (class rows of the packed sweep: as many classes per pass as fit a third of LDS)
-    int pk_cls_fit = 0;
-    for (int nc = std::min(p.n_cls, 250); nc >= 1; --nc)
-        if (lds_bytes_sj_pk_rows(p.nbins, nc, p.n_ti, p.n_tj, p.n_cn) <= lds_cap / 3 - 512) {
-            pk_cls_fit = nc;
-            break;
-        }
-    int ord_rows = p.n_ti * p.n_tj, ord_maxb = p.n_tj - 1;
-    bool displaced = false, big = false;
-    {
-        const size_t third = lds_cap / 3 - 512, whole = lds_cap - 1024;
-        const bool have_disp = p.disp_rows > 0 && p.disp_rows < ord_rows && ctx->opt_rdf_disp != 0;
-        auto use_disp = [&]() {
-            displaced = true;
-            ord_rows = p.disp_rows;
-            ord_maxb = *std::max_element(p.disp_b.begin(), p.disp_b.end());
-        };
-        if (lds_bytes_sj_pk(p.nbins, ord_rows, p.n_cn) <= third) {
-            if (have_disp && ctx->opt_rdf_disp == 2) use_disp();  // (A/B: whenever it has fewer rows)
-        } else if (have_disp && lds_bytes_sj_pk(p.nbins, p.disp_rows, p.n_cn) <= third) {
-            use_disp();
-        } else if (p.n_cn == 0 && ctx->opt_rdf_big != 0 && lds_cap >= 160 * 1024 && pk_cls_fit < p.n_cls) {
-            // neither fits a third of LDS, and the class rows would need several passes (all classes in ONE pass of class rows
-            // measured faster than this: 3.12 against 3.37 ms at C1's shape): ONE 16-wave block per CU with the whole LDS for
-            // its histogram (BIG, pair_sj.hip) — every pair of nine types named is 81 rows, 130 KB — on whichever layout has
-            // fewer rows
-            const int rows_small = have_disp ? p.disp_rows : ord_rows;
-            if (lds_bytes_sj_pk(p.nbins, rows_small, 0, true) <= whole) {
-                big = true;
-                if (have_disp) use_disp();
-            }
-        }
-    }
-    const std::vector<int> &row_cls = displaced ? p.disp_cls : p.cls;  // ordered row -> class
-    const size_t ord_b = lds_bytes_sj_ordered(p.nbins, ord_rows);
-    const bool ord_base = cull && ctx->opt_rdf_sj != 0 && !mode_cn && ctx->opt_rdf_rows != 0 &&
-                          p.n_cls <= 250 && (double)(ord_maxb + 1) * (p.nbins + 1) < 65536.0;
-    bool ordered = ord_base && ord_b <= lds_cap / 4;
-    // Packed-f32 classification (MODE 3-6 of the scalar-j kernel, header in pair_sj.hip) when the error band is
-    // narrow: with the ordered rows when they fit a third of LDS (3 blocks of 8 waves per CU), else with class rows
-    // and their row table (any number of types). The cutoff on a bin edge lets the band of that edge decide in/out
-    // of the cutoff; a cutoff inside the last bin has its own band tested per pair (cut_guard).
-    bool pk = false, pk_rows = false;
-    float s_cap = 0.f, rc2hi = 0.f, near_pk_f = 0.f, cut_lo = 0.f;
-    bool cut_guard = false;
-    double pk_err = 0.0;  // error bound of the f32 distance, in bins
-    int rel_block = 0;  // != 0: the packed sweep's f32 records are wanted (relative to their tile's centre)
-    if (cull && ctx->opt_rdf_sj != 0 && !mode_cn && p.n_cls <= 250 && ctx->opt_rdf_pk != 0 && p.bin_size > 0.0) {
-        const bool fits_ordered = ord_base && (big || lds_bytes_sj_pk(p.nbins, ord_rows, p.n_cn) <= lds_cap / 3 - 512);
-        // class rows: as many classes per pass as fit a third of LDS. Round 6: when they do not all fit (every pair of nine
-        // types named: 45 classes x 401 words = 72 KB) the packed sweep runs in SEVERAL passes over the pairs instead of
-        // leaving the call to the all-f64 class-row kernel — C1's atoms with all 45 relations: 14.5 -> 6.3 ms per 200 frames
-        // (`bench.py --shape C1full`); coordination numbers from the same sweep need one pass (else: two sweeps, as before)
-        // (at least 8 classes per pass: with rows so long that fewer fit, the f64 kernel's half-of-LDS passes are as few)
-        const bool fits_rows = pk_cls_fit >= p.n_cls || (pk_cls_fit >= 8 && p.n_cn == 0 && ctx->opt_rdf_pk_passes != 0);
-        const double r_cut = std::sqrt(p.rc2);
-        const double cpos = r_cut / p.bin_size, K = std::floor(cpos + 0.5);
-        double l_max = 0.0, v_max = 0.0;
-        for (int64_t f = 0; f < F; ++f) {
-            const double *b = p.h_box + 3 * f;
-            l_max = std::max(l_max, std::max(b[0], std::max(b[1], b[2])));
-            v_max = std::max(v_max, b[0] * b[1] * b[2]);
-        }
-        // tile edge of the sparser of the two sets (atoms x sites: the sites)
-        const double edge = std::cbrt((double)TILE * v_max / (double)std::min(p.ni, p.nj));
-        const double cap = r_cut + 3.5 * edge;
-        // (the guess carries tj * row_len with ordered rows, nothing with class rows)
-        const double err = pk_error_bound(r_cut, p.bin_size, p.nbins, fits_ordered ? ord_maxb + 1 : 1, cap, l_max);
-        const double u = std::ldexp(1.0, -24);
-        const double near_pk = 2.0 * err + 4.5 * u * (p.nbins + 1) + 2.0e-5;
-        const bool on_edge = std::fabs(cpos - K) <= 1e-6 && (K == (double)p.nbins || K == (double)p.nbins + 1.0);
-        if ((fits_ordered || fits_rows) && (on_edge || std::floor(cpos) == (double)p.nbins) && near_pk <= 0.02 &&
-            std::isfinite(l_max)) {
-            pk = true;
-            pk_err = err;
-            pk_rows = !fits_ordered;
-            ordered = fits_ordered;
-            cut_guard = !on_edge;
-            // sqrt(rsq32) < cut_lo  =>  sqrt(rsq) < cut_lo + err * bin_size < r_cut: inside the cutoff for certain
-            cut_lo = std::nextafterf((float)(r_cut - 1.1 * err * p.bin_size), 0.f);
-            // the f32 records are relative to the centre of their whole tile (64-atom blocks bought a little f32
-            // precision for 4x the per-block work: measured slower in round 2, retired in round 4)
-            rel_block = TILE;
-            near_pk_f = (float)near_pk;
-            s_cap = (float)cap;
-            // every pair with rsq < r_cut^2 has sqrt(rsq32) <= r_cut + err * bin_size
-            const double r_hi = r_cut + err * p.bin_size;
-            rc2hi = std::nextafterf((float)(r_hi * r_hi * (1.0 + 2.0 * u)), std::numeric_limits<float>::infinity());
-            if (pk_rows) {  // all classes in one pass when they fit, else balanced passes of at most pk_cls_fit classes
-                const int np = (p.n_cls + pk_cls_fit - 1) / pk_cls_fit;
-                cls_per_pass = (p.n_cls + np - 1) / np;
-            }
-        }
-    }
-    big = big && pk && ordered && ctx->opt_rdf_pk != 2;  // (only the packed ordered sweep has the 16-wave instance)
-    if (p.n_cn > 0 && (!pk || ctx->opt_rdf_pk == 2)) return CN_UNFUSED;
-    float near_ord = 0.f;
-    if (ordered) {
-        cls_per_pass = p.n_cls;
-        // |error| of the f32 guess g = fma(sqrt((float)rsq), 1/ddr, near + tj*row_len): relative 2^-25 (conversion,
-        // halved by the root) + 2^-23 (v_sqrt_f32, 1 ulp) + 2^-24 (rounded 1/ddr) = 2.1e-7 of the bin number, plus
-        // half an ulp of the largest value each for the rounding of the addend and of the fma. near = 2 x that.
-        const double maxg = (double)(ord_maxb + 1) * (p.nbins + 1) + 1.0;  // the addend carries B[tj] * row_len only
-        const double ulp = std::ldexp(1.0, (int)std::floor(std::log2(maxg)) - 23);
-        near_ord = (float)(2.0 * ((double)p.nbins * 2.1e-7 + ulp) + 1.0e-5);
-        near_ord = std::max(near_ord, near_pk_f);  // one band for the f32 guess of either sweep
-    }
-    const int n_pass = (p.n_cls + cls_per_pass - 1) / cls_per_pass;
-
-    // geometry
-    int max_list = p.tri ? tri_shifts(nTi, 0) : nTj;
-    int jsplit = ctx->opt_rdf_jsplit;
-    if (jsplit <= 0) {
-        const int64_t want = (int64_t)ctx->cu_count * 48;  // ~12 blocks per CU slot: short tail
-        const int64_t base = (int64_t)nTi * F;
-        jsplit = (int)((want + base - 1) / base);
-    }
-    if (jsplit > max_list) jsplit = max_list;
-    if (cull && jsplit > 4) jsplit = 4;
-    // scalar-j kernels: items are (frame, tile, wave, slice); 4 slices measured best at C2 and C3, for the persistent
-    // grid and for per-frame output alike (with one slice a 100k-atom frame has only two items per resident wave)
-    if (cull && ctx->opt_rdf_sj != 0 && ctx->opt_rdf_jsplit <= 0) {
-        // ... when the lists are long. A short reach (coordination cutoffs: a handful of neighbour tiles per tile) leaves
-        // a slice one tile or none, and every item pays its set-up (counter, boxes, context) for it: round 4 measured
-        // 4.72 -> 2.93 ms per 64 C3 frames for CN alone with ONE slice (tools/ab_pair.py rdf_jsplit=4,2,1 C3 cn).
-        // Expected list length: the share of tile pairs within reach (as for the culling decision above) x tiles / 2.
-        const double V = p.h_box[0] * p.h_box[1] * p.h_box[2];
-        const double edge = 0.5 * (std::cbrt((double)TILE * V / (double)p.ni) + std::cbrt((double)TILE * V / (double)p.nj));
-        const double reach = std::sqrt(p.rc2) + 0.8 * edge;
-        const double share = std::min(1.0, 4.18879 * reach * reach * reach / V);
-        const double list_est = share * (double)nTj * (p.tri ? 0.5 : 1.0);
-        jsplit = std::min(list_est >= 12.0 ? 4 : list_est >= 6.0 ? 2 : 1, max_list);
-    }
-    if (jsplit < 1) jsplit = 1;
-    const int blocks_per_frame = nTi * jsplit;
-    // frames per block (fast kernel, frame-summed output): as many as keeps >= `want` blocks in flight
-    int fpb = 1;
-    if (fast && !p.per_frame) {
-        fpb = ctx->opt_rdf_fpb;
-        if (fpb <= 0) {
-            const int64_t want = (int64_t)ctx->cu_count * 24;
-            fpb = (int)(((int64_t)blocks_per_frame * F) / want);
-        }
-        if (fpb < 1) fpb = 1;
-        if (fpb > 64) fpb = 64;
-    }
-    const int64_t fgroups = (F + 8LL * fpb - 1) / (8LL * fpb);
-    const int64_t grid = fgroups * 8 * blocks_per_frame;
-    if (grid > 0x7fffffffLL)
-        return mdhip_fail(ctx, MDHIP_ELIMIT, "pair_hist: grid of %lld blocks is too large",
-                          (long long)grid);
-    int slots = p.per_frame ? 1 : ctx->opt_rdf_slots;
-
-    // device tables
-    const size_t edges_b = (size_t)(p.nbins + 2) * 8;  // + a +inf sentinel after the last edge
-    // CN tables of the scalar-j rows (one pass, all rows): word index of every row's split bin | cutoff^2 per row
-    const int cn_rows = p.n_cn ? (ordered ? ord_rows : p.n_cls + 1) : 0;
-    const size_t cn_fw = ((size_t)cn_rows + 1) & ~size_t(1);
-    const size_t cn_b = p.n_cn ? (cn_fw + 2 * (size_t)cn_rows) * 4 : 0;
-    float cn_reach = 0.f;
-    const size_t cls_b = ((size_t)p.n_ti * p.n_tj + 63) & ~size_t(63);
-    // edges and the class table of every pass: one pinned staging buffer, one H2D copy
-    // (displaced rows: A | B as ints behind the CN tables, for pack_w of the sort pre-pass)
-    const size_t disp_off = (edges_b + (size_t)n_pass * cls_b + cn_b + 7) & ~size_t(7);
-    const size_t disp_b = ordered && displaced ? ((size_t)p.n_ti + p.n_tj) * 4 : 0;
-    const size_t tab_b = disp_off + disp_b + 8;
-    // The common case of the scalar-j sweep — one class pass, frame-summed rows — needs two more small things that a
-    // C2 step paid a copy / a fill of their own for (round 5: ~12 us each with the gaps around them): the row map of
-    // derive_rdf_kernel (results left on the device) rides behind the tables in the same copy, and the row sums sit
-    // behind the flag words so that ONE fill empties both.
-    const bool sj_path = cull && ctx->opt_rdf_sj != 0;
-    const bool one_sum = sj_path && n_pass == 1 && !p.per_frame;
-    const int sj_rows1 = ordered ? ord_rows : p.n_cls + 1;
-    const size_t rows1_b = one_sum ? (size_t)sj_rows1 * (size_t)(p.nbins + 1 + (p.n_cn ? 1 : 0)) * 8 : 0;
-    const bool map_rides = one_sum && p.dev_out != nullptr;
-    const size_t tab_al = (tab_b + 15) & ~size_t(15);
-    const size_t map_b = map_rides ? ((size_t)sj_rows1 + 2 * (size_t)p.n_rel) * 4 : 0;
-    MD_WS(d_tab, unsigned char, WS_TABLES, tab_al + map_b);
-    MD_PIN(h_tab, unsigned char, tab_al + map_b + 32);
-    {
-        double *e = reinterpret_cast<double *>(h_tab);
-        std::copy(p.edges, p.edges + p.nbins + 1, e);
-        e[p.nbins + 1] = std::numeric_limits<double>::infinity();
-        if (p.n_cn) {
-            int *fl = reinterpret_cast<int *>(h_tab + edges_b + (size_t)n_pass * cls_b);
-            double *c2r = reinterpret_cast<double *>(fl + cn_fw);
-            std::fill(fl, fl + cn_fw, -1);
-            double reach = 0.0;
-            for (int r = 0; r < cn_rows; ++r) {
-                const int cl = ordered ? row_cls[r] : (r < p.n_cls ? r : -1);
-                const double c2 = cl >= 0 ? p.cn_c2_cls[cl] : 0.0;
-                c2r[r] = c2;
-                if (!(c2 > 0.0)) continue;
-                // split bin kc: edges[kc] <= c2 < edges[kc + 1]; none when the cutoff sits exactly on an edge
-                const int kc = (int)(std::upper_bound(p.edges, p.edges + p.nbins + 1, c2) - p.edges) - 1;
-                if (p.edges[kc] == c2) continue;
-                fl[r] = r * (p.nbins + 1) + kc;
-                const double top = kc + 1 <= p.nbins ? std::sqrt(p.edges[kc + 1]) : std::sqrt(p.rc2);
-                reach = std::max(reach, std::min(top, std::sqrt(p.rc2)));
-            }
-            cn_reach = (float)((reach + 1e-3) * 1.00001);
-        }
-        for (int pass = 0; pass < n_pass; ++pass) {
-            const int c0 = pass * cls_per_pass;
-            const int nc = (p.n_cls - c0) < cls_per_pass ? (p.n_cls - c0) : cls_per_pass;
-            unsigned char *t = h_tab + edges_b + (size_t)pass * cls_b;
-            for (size_t k = 0; k < (size_t)p.n_ti * p.n_tj; ++k) {
-                const int c = p.cls[k];  // (pass-local ids are < 250: they fit the byte, 0xFF = other pass)
-                t[k] = (c >= c0 && c < c0 + nc) ? (unsigned char)(c - c0) : 0xFF;
-            }
-        }
-    }
+    PairPlan pl;
+    int rc = pair_plan(ctx, p, pl);
+    if (rc) return rc;
+    Batch b{p, pl, H, out_frames};
     RowDisp disp_i, disp_j;
-    if (disp_b) {
-        int *h_d = reinterpret_cast<int *>(h_tab + disp_off);
-        std::copy(p.disp_a.begin(), p.disp_a.end(), h_d);
-        std::copy(p.disp_b.begin(), p.disp_b.end(), h_d + p.n_ti);
-        const int *d_d = reinterpret_cast<const int *>(d_tab + disp_off);
-        // atom-atom: one sorted set plays both roles (low word A, addend B); atoms x sites: the i set's addend and the j
-        // set's low word are never read
-        disp_i.lo = d_d;
-        disp_i.hi = p.tri ? d_d + p.n_ti : d_d;
-        disp_j.lo = disp_j.hi = d_d + p.n_ti;
-    }
-    if (map_rides) {
-        int *h_map = reinterpret_cast<int *>(h_tab + tab_al);
-        for (int r = 0; r < sj_rows1; ++r) h_map[r] = ordered ? row_cls[r] : (r < p.n_cls ? r : -1);
-        for (int kl = 0; kl < p.n_rel; ++kl) {
-            h_map[sj_rows1 + kl] = p.rel_cls[kl];
-            h_map[sj_rows1 + p.n_rel + kl] = p.rel_mult[kl];
-        }
-    }
-    {
-        const int rcc = mdhip_copy_small(ctx, d_tab, h_tab, tab_al + map_b, hipMemcpyHostToDevice);
-        if (rcc) return rcc;
-    }
-    MD_WS(d_misc, unsigned long long, WS_MISC, 64 + rows1_b);
-    MD_HIP(hipMemsetAsync(d_misc, 0, 64 + rows1_b, ctx->stream));
-
-    // ---- culled path: Morton sort, tile boxes, neighbour-tile lists (once, shared by all class passes) ----
-    const double *k_xi = p.d_xi, *k_xj = p.d_xj;
-    const int *k_ti = p.d_ti, *k_tj = p.d_tj;
-    long long k_ti_fs = p.ti_fs, k_tj_fs = p.tj_fs;
-    const unsigned short *d_list = nullptr;
-    const int *d_list_cnt = nullptr;
-    const float4 *d_gsph = nullptr, *d_wsph = nullptr, *d_gsph4 = nullptr;
-    const double4 *d_aos = nullptr;
-    // what the host half of the passes accumulates (shared with the completion step of a deferred batch)
-    struct BatchAcc {
-        double total_ms = 0.0, prep_ms = 0.0;
-        int launches = 0;
-        unsigned long long ov = 0;
-        bool prep_timed = false;
-        KernelTimer prep;
-        explicit BatchAcc(const KernelTimer &t) : prep(t) {}
-    };
-    std::shared_ptr<BatchAcc> acc;
-    const double4 *d_aos_j = nullptr;
-    const float *d_rel = nullptr;
-    const double *d_cen = nullptr;
-    if (cull) {
-        const long long N = p.ni;
-        const bool want_soa = ctx->opt_rdf_sj == 0;  // only the LDS-tile kernel (atom-atom) reads the SoA copy
-        MD_WS(d_l, unsigned short, WS_LIST, (size_t)F * nTi * (p.tri ? nTi : nTj) * 2);
-        MD_WS(d_lc, int, WS_LISTCNT, (size_t)F * nTi * 4);
-        KernelTimer ptimer(ctx, 1, true);  // second event pair: collected with the pair kernel's
-        SortedSet si, sj_set;
-        const int slot_i[5] = {WS_SORT_AOS, WS_BBOX, WS_GSPH, WS_WSPH, WS_GSPH4};
-        // (the bin-guess addend near + type * row_len and the tile-relative f32 records belong to the j set)
-        int rc = cull_prepare_set(ctx, F, p.d_xi, p.d_ti, (long long)p.ti_fs, p.d_box, N, nTi, p.n_ti,
-                                  ordered ? near_ord : 0.f, ordered ? p.nbins + 1 : 0, disp_i, want_soa,
-                                  pk && p.tri ? rel_block : 0, pk_rows ? 1 : 0, pk ? 1 : 0, slot_i, si);
+    float cn_reach = 0.f;
+    rc = stage_tables(ctx, b, disp_i, disp_j, cn_reach);
+    if (rc) return rc;
+    MD_WS(d_misc, unsigned long long, WS_MISC, 64 + pl.rows1_b);
+    MD_HIP(hipMemsetAsync(d_misc, 0, 64 + pl.rows1_b, ctx->stream));
+    b.d_misc = d_misc;
+    PairArgs args = batch_args(b, cn_reach);
+    if (pl.cull) {
+        rc = cull_prepass(ctx, b, disp_i, disp_j, args);
         if (rc) return rc;
-        if (p.tri) {
-            sj_set = si;
-        } else {
-            const int slot_j[5] = {WS_SORT_AOS_J, WS_BBOX_J, WS_GSPH_J, WS_WSPH_J, WS_GSPH4_J};
-            rc = cull_prepare_set(ctx, F, p.d_xj, p.d_tj, (long long)p.tj_fs, p.d_box, p.nj, nTj, p.n_ti,
-                                  ordered ? near_ord : 0.f, ordered ? p.nbins + 1 : 0, disp_j, false, pk ? rel_block : 0,
-                                  pk_rows ? 1 : 0, pk ? 1 : 0, slot_j, sj_set);
-            if (rc) return rc;
-        }
-        launch_cull_lists(ctx->stream, p.tri, F, si.bbox, sj_set.bbox, nTi, nTj, p.d_box,
-                          p.rc2 * (1.0 + 1e-9) + 1e-9, d_l, d_lc);
-        ptimer.stop();
-        MD_HIP(hipGetLastError());
-        acc = std::make_shared<BatchAcc>(ptimer);
-        acc->prep_timed = true;
-        d_gsph = sj_set.gs;    // 8-atom boxes of the j set (LDS-tile kernel)
-        d_gsph4 = sj_set.gs4;  // 4-atom boxes of the j set (scalar-j kernel)
-        d_wsph = si.ws;      // 64-atom boxes of the i set
-        if (want_soa) {
-            k_xi = k_xj = si.sx;
-            k_ti = k_tj = si.st;
-            k_ti_fs = k_tj_fs = N;
-        }
-        d_list = d_l;
-        d_list_cnt = d_lc;
-        d_aos = si.aos;
-        d_aos_j = sj_set.aos;
-        d_rel = sj_set.rel;
-        d_cen = sj_set.cen;
     }
-
     // (total_ms: the pair kernel alone; the culling pre-pass is reported separately)
-    if (!acc) acc = std::make_shared<BatchAcc>(KernelTimer(ctx, 1, true));
-    const int n_cls_all = p.n_cls, nbins_all = p.nbins;
+    if (!b.acc) b.acc = std::make_shared<BatchAcc>(KernelTimer(ctx, 1, true));
     // the end of the batch: what the passes found goes to the caller and to the context's registers
-    auto finalize = [ctx, acc, overflow, n_pass]() {
+    auto finalize = [ctx, acc = b.acc, overflow, n_pass = pl.n_pass]() {
         // with several passes every in-cutoff overflow pair is seen once per pass
         *overflow = acc->ov / (uint64_t)n_pass;
         ctx->last_ms = acc->total_ms;
@@ -604,282 +628,37 @@ int pair_hist_run_batch(mdhip_ctx *ctx, const PairProblem &p, std::vector<uint64
         ctx->last_aux_ms = acc->prep_ms;
         return MDHIP_OK;
     };
-    bool deferred = false;
-    for (int pass = 0; pass < n_pass; ++pass) {
-        const int c0 = pass * cls_per_pass;
-        const int nc = (p.n_cls - c0) < cls_per_pass ? (p.n_cls - c0) : cls_per_pass;
-        const size_t words = (size_t)nc * p.nbins;
-        const size_t acc_frames = p.per_frame ? (size_t)F : (size_t)slots;
-        MD_WS(d_hist, unsigned long long, WS_HIST, (acc_frames + 1) * words * 8);
-        // (the scalar-j kernels keep their histograms in LDS and store them to their own slices: nothing of theirs is
-        // added to d_hist, so it need not be emptied for them — one fill less per call)
-        if (!(cull && ctx->opt_rdf_sj != 0)) MD_HIP(hipMemsetAsync(d_hist, 0, acc_frames * words * 8, ctx->stream));
-
-        PairArgs a;
-        a.xi = k_xi;
-        a.xj = k_xj;
-        a.ti = k_ti;
-        a.tj = k_tj;
-        a.list = d_list;
-        a.list_cnt = d_list_cnt;
-        a.gsph = d_gsph;
-        a.gsph4 = d_gsph4;
-        a.wsph = d_wsph;
-        a.reach = (float)((std::sqrt(p.rc2) + 1e-3) * 1.00001);
-        a.aos = d_aos;
-        a.aos_j = d_aos_j;
-        a.tri = p.tri ? 1 : 0;
-        a.box = p.d_box;
-        a.cls = d_tab + edges_b + (size_t)pass * cls_b;
-        a.edges = reinterpret_cast<const double *>(d_tab);
-        a.hist = d_hist;
-        a.overflow = d_misc;
-        a.ni = p.ni;
-        a.nj = p.nj;
-        a.ti_fs = k_ti_fs;
-        a.tj_fs = k_tj_fs;
-        a.rc2 = p.rc2;
-        a.gscale = p.gscale;
-        a.n_ti = p.n_ti;
-        a.n_tj = p.n_tj;
-        a.row_mul = ordered && displaced ? 1 : p.n_tj;
-        a.n_rows_ord = ord_rows;
-        a.n_cls = nc;
-        a.nbins = p.nbins;
-        a.n_frames = (int)F;
-        a.nTi = nTi;
-        a.nTj = nTj;
-        a.jsplit = jsplit;
-        a.blocks_per_frame = blocks_per_frame;
-        a.per_frame = p.per_frame;
-        a.slots = slots;
-        a.fpb = fpb;
-
-        a.near = pk_rows ? near_pk_f : near_ord;
-        a.rel = d_rel;
-        a.cen = d_cen;
-        a.s_cap = s_cap;
-        a.rc2hi = rc2hi;
-        a.cut_lo = cut_lo;
-        a.n_cn = p.n_cn;
-        a.cn_tab = reinterpret_cast<const unsigned *>(d_tab + edges_b + (size_t)n_pass * cls_b);
-        a.cn_reach = cn_reach;
-        const bool sj = cull && ctx->opt_rdf_sj != 0;  // wave-independent sweep with scalar loads of the j atoms
-        const bool persist = sj && !p.per_frame && ctx->opt_rdf_sj != 2;  // resident grid + per-XCD work counters
-        a.work = reinterpret_cast<unsigned *>(d_misc + 4);
-        const size_t lds = pk_rows ? lds_bytes_sj_pk_rows(p.nbins, nc, p.n_ti, p.n_tj, p.n_cn)
-                           : pk    ? lds_bytes_sj_pk(p.nbins, ord_rows, p.n_cn, big)
-                           : ordered ? ord_b
-                           : sj    ? lds_bytes_sj(p.nbins, nc, p.n_ti, p.n_tj, mode_cn)
-                           : fast ? lds_bytes_fast(p.nbins, nc, p.n_ti, p.n_tj)
-                                  : lds_bytes(p.nbins, nc, p.n_ti, p.n_tj);
-        if (sj) {
-            a.guard_off = (unsigned)((lds + 15) & ~size_t(15));
-            // one neighbour tile adds at most 64 x 256 to any one word of a block: 2^32 / 2^14 tiles, with margin
-            a.guard_tiles = ctx->opt_rdf_guard > 0 ? (unsigned)ctx->opt_rdf_guard : 250000u;
-        }
-        const size_t lds_launch = sj ? ((lds + 15) & ~size_t(15)) + 16 : lds;
-        const char *kname = "";
-        const int sj_mode = pk && ctx->opt_rdf_pk != 2 ? (pk_rows ? 5 : 3) + (cut_guard ? 1 : 0) : ordered ? 2 : mode_cn ? 1 : 0;
-        const bool big_launch = big && sj_mode >= 3 && sj_mode <= 4;
-        const int bs = sj ? sj_block_threads(sj_mode, big_launch) : TILE;  // threads per block
-        const int wpb = bs / 64;                                // independent waves per block (scalar-j kernels)
-        PairKernel kern = sj ? sj_kernel(sj_mode, persist, p.n_cn > 0, big_launch, &kname)
-                             : dense_kernel(fast, p.tri, mode_cn, fast && cull, &kname);
-        ctx->last_kernel = kname;
-        if (lds_launch > 65536)
-            MD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_launch));
-        long long launch_grid = grid;
-        if (sj) {
-            int per_cu = 0;
-            MD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kern), bs,
-                                                                lds_launch));
-            if (per_cu < 1) per_cu = 1;
-            const long long capacity = (long long)per_cu * ctx->cu_count;
-            // blocks' worth of wave items per frame (a frame has nTi * 4 * jsplit wave items)
-            const long long block_items = ((long long)nTi * 4 * jsplit + wpb - 1) / wpb;
-            a.fpb = 1;
-            if (persist) {
-                launch_grid = std::min(capacity, F * block_items + 8);
-                launch_grid = (launch_grid + 7) / 8 * 8;
-                // (the work counters: the first pass finds them empty, d_misc was zeroed whole at the top of the batch)
-                if (pass > 0) MD_HIP(hipMemsetAsync(d_misc + 4, 0, 32, ctx->stream));
-            } else {
-                // per-frame output: as many blocks per frame as keeps one resident set busy, each flushing once
-                // blocks per frame: few frames in flight per XCD (their records should stay in its 4 MB L2: 32 B per
-                // atom per frame), every wave still left with a few items to draw
-                const long long cap_xcd = std::max<long long>(1, capacity / 8);
-                const long long frames_xcd = (F + 7) / 8;
-                const long long in_flight = std::max<long long>(1, std::min<long long>(frames_xcd, ctx->opt_rdf_inflight));
-                long long bpf = std::max<long long>(1, cap_xcd / in_flight);
-                bpf = std::min(bpf, std::max<long long>(1, block_items / 2));
-                // every block stores one copy of its LDS histogram: keep that workspace within ~2 GiB
-                while (bpf > 8 && (double)(((F + 7) / 8) * 8 * bpf) * (double)lds > 2147483648.0) bpf /= 2;
-                a.blocks_per_frame = (int)bpf;
-                launch_grid = ((F + 7) / 8) * 8 * bpf;
-                MD_WS(d_work, unsigned, WS_WORK, (size_t)F * 4);
-                MD_HIP(hipMemsetAsync(d_work, 0, (size_t)F * 4, ctx->stream));
-                a.work = d_work;
-            }
-        }
-        // scalar-j kernels: every block stores its LDS histogram into its own slice; a merge kernel adds them up
-        const int sj_rows = ordered ? ord_rows : nc + 1;
+    for (int pass = 0; pass < pl.n_pass; ++pass) {
+        const int nc = pl.pass_nc(pass, p.n_cls);
+        const int sj_rows = pl.ordered ? pl.ord_rows : nc + 1;
         const int cn_len = p.n_cn ? 1 : 0;  // one split counter per row, behind all histogram rows
-        const int sj_words = sj_rows * (p.nbins + 1 + cn_len);
-        unsigned long long *d_rows = nullptr;
-        if (sj) {
-            MD_WS(d_sl, unsigned, WS_SLICES, (size_t)launch_grid * sj_words * 4);
-            if (one_sum && rows1_b == (size_t)sj_words * 8) {
-                d_rows = d_misc + 8;  // (emptied with the flag words at the top of the batch)
-            } else {
-                d_rows = (unsigned long long *)mdhip_ws(ctx, WS_ROWS, out_frames * (size_t)sj_words * 8);
-                if (!d_rows) return MDHIP_ENOMEM;
-                if (!p.per_frame) MD_HIP(hipMemsetAsync(d_rows, 0, (size_t)sj_words * 8, ctx->stream));
-            }
-            a.slices = d_sl;
+        Pass ps{pass, pl.pass_c0(pass), nc, sj_rows, cn_len, sj_rows * (p.nbins + 1 + cn_len), (size_t)nc * p.nbins};
+        rc = launch_pass(ctx, b, args, ps);
+        if (rc) return rc;
+        if (!pl.sj) {
+            rc = collect_dense(ctx, b, ps);
+            if (rc) return rc;
+            continue;
         }
-        KernelTimer timer(ctx);
-        hipLaunchKernelGGL(kern, dim3((unsigned)launch_grid), dim3(bs), lds_launch, ctx->stream, a);
-        if (sj) {
-            const unsigned gy = p.per_frame ? (unsigned)F : (unsigned)std::min<long long>(64, launch_grid);
-            launch_merge_slices(ctx->stream, a.slices, sj_words, launch_grid, p.per_frame, a.blocks_per_frame, gy,
-                                d_rows);
-        }
-        timer.stop();
-        MD_HIP(hipGetLastError());
-
-        const bool can_defer = defer != nullptr && sj && n_pass == 1;
-        // the launch's flags (pinned): [0] deferred pairs lost, [1] work-loop assertion, [2] overflow guard
-        auto check_flags = [ctx](const uint64_t *hlost) {
-            if (hlost[2]) return SPLIT_BATCH;
-            if (hlost[0] || hlost[1])
-                return mdhip_fail(ctx, MDHIP_EHIP, "pair_hist: internal check failed (%llu deferred pairs lost, work loop %llu)",
-                                  (unsigned long long)hlost[0], (unsigned long long)hlost[1]);
+        std::function<int()> fin;
+        rc = p.dev_out && pl.one_sum ? collect_device(ctx, b, ps, fin) : collect_sj_rows(ctx, b, ps, fin);
+        if (rc) return rc;
+        // the pass's host half: a completion step of an asynchronous call's one pass, else behind a stream sync now
+        if (defer != nullptr && pl.n_pass == 1) {
+            defer->defer([fin, finalize, redo]() {
+                const int rcf = fin();
+                if (rcf == SPLIT_BATCH) {
+                    *redo = true;
+                    return (int)MDHIP_OK;
+                }
+                return rcf ? rcf : finalize();
+            });
             return MDHIP_OK;
-        };
-        auto collect_times = [acc, timer]() {
-            acc->total_ms += timer.collect();
-            ++acc->launches;
-            if (acc->prep_timed) {  // the pre-pass ran ahead of the first pass on the same stream: its events are complete
-                acc->prep_ms = acc->prep.collect();
-                acc->prep_timed = false;
-            }
-        };
-        if (sj && p.dev_out && n_pass == 1 && !p.per_frame) {
-            // outputs stay on the device: rows -> full | part | overflow by derive_rdf_kernel (added to dev_out)
-            // (the row map came with the tables, in the copy at the top of the batch: map_rides)
-            if (!map_rides || sj_rows != sj_rows1)
-                return mdhip_fail(ctx, MDHIP_EHIP, "pair_hist: internal: the row map of the device-resident path is missing");
-            const int *d_map = reinterpret_cast<const int *>(d_tab + tab_al);
-            launch_derive_rdf(ctx->stream, d_rows, sj_rows, p.nbins, d_map, p.n_rel, d_map + sj_rows,
-                              d_map + sj_rows + p.n_rel, d_misc + 3, p.dev_out);
-            MD_HIP(hipGetLastError());
-            uint64_t *hlost = reinterpret_cast<uint64_t *>(h_tab + tab_al + ((map_b + 7) & ~size_t(7)));
-            {
-                const int rcc = mdhip_copy_small(ctx, hlost, d_misc + 1, 24, hipMemcpyDeviceToHost);
-                if (rcc) return rcc;
-            }
-            auto fin = [check_flags, collect_times, hlost]() {
-                const int rcf = check_flags(hlost);
-                if (rcf) return rcf;
-                collect_times();
-                return (int)MDHIP_OK;
-            };
-            if (can_defer) {
-                defer->defer([fin, finalize, redo]() {
-                    const int rcf = fin();
-                    if (rcf == SPLIT_BATCH) {
-                        *redo = true;
-                        return (int)MDHIP_OK;
-                    }
-                    return rcf ? rcf : finalize();
-                });
-                deferred = true;
-                continue;
-            }
-            MD_HIP(mdhip_stream_wait(ctx));
-            const int rcf = fin();
-            if (rcf) return rcf;
-            continue;
         }
-        if (sj) {
-            // D2H of the row sums (pinned staging), then rows -> classes and the overflow words on the host
-            MD_PIN(hall, uint64_t, (out_frames * (size_t)sj_words + 16) * 8);
-            uint64_t *hrows = hall + 8;
-            uint64_t *hlost = hrows + out_frames * (size_t)sj_words;  // [0] queue overflow, [1] work-loop assertion
-            if (d_rows == d_misc + 8 && out_frames == 1) {
-                // the row sums sit behind the flag words (one_sum): flags and rows leave in ONE copy
-                hlost = hall + 1;
-                const int rcc = mdhip_copy_small(ctx, hall, d_misc, (8 + (size_t)sj_words) * 8, hipMemcpyDeviceToHost);
-                if (rcc) return rcc;
-            } else {
-                int rcc = mdhip_copy_small(ctx, hrows, d_rows, out_frames * (size_t)sj_words * 8, hipMemcpyDeviceToHost);
-                if (!rcc) rcc = mdhip_copy_small(ctx, hlost, d_misc + 1, 24, hipMemcpyDeviceToHost);
-                if (rcc) return rcc;
-            }
-            std::vector<uint64_t> *Hp = &H, *Hsplit = p.Hsplit;
-            auto fin = [check_flags, collect_times, acc, hrows, hlost, Hp, Hsplit, out_frames, sj_words, sj_rows, cn_len,
-                        ordered, nc, c0, n_cls_all, nbins_all, cls = ordered ? row_cls : std::vector<int>()]() {
-                const int rcf = check_flags(hlost);
-                if (rcf) return rcf;
-                collect_times();
-                const int row_len = nbins_all + 1;
-                for (size_t fr = 0; fr < out_frames && cn_len; ++fr)
-                    for (int r = 0; r < sj_rows; ++r) {
-                        const uint64_t *src = hrows + fr * (size_t)sj_words + (size_t)sj_rows * row_len + (size_t)r;
-                        const int cl = ordered ? cls[r] : (r < nc ? c0 + r : -1);
-                        if (cl >= 0) (*Hsplit)[fr * n_cls_all + cl] += src[0];
-                    }
-                for (size_t fr = 0; fr < out_frames; ++fr)
-                    for (int r = 0; r < sj_rows; ++r) {
-                        const uint64_t *src = hrows + fr * (size_t)sj_words + (size_t)r * row_len;
-                        acc->ov += src[nbins_all];
-                        // ordered rows (ti, tj) -> class of the unordered pair; class rows of this pass -> c0 + r, the
-                        // extra row holds the pairs whose class belongs to another pass
-                        const int cl = ordered ? (int)cls[r] : (r < nc ? c0 + r : -1);
-                        if (cl < 0) continue;
-                        uint64_t *dst = &(*Hp)[(fr * n_cls_all + cl) * nbins_all];
-                        for (int k = 0; k < nbins_all; ++k) dst[k] += src[k];
-                    }
-                return (int)MDHIP_OK;
-            };
-            if (can_defer) {
-                defer->defer([fin, finalize, redo]() {
-                    const int rcf = fin();
-                    if (rcf == SPLIT_BATCH) {
-                        *redo = true;
-                        return (int)MDHIP_OK;
-                    }
-                    return rcf ? rcf : finalize();
-                });
-                deferred = true;
-                continue;
-            }
-            MD_HIP(mdhip_stream_wait(ctx));
-            const int rcf = fin();
-            if (rcf) return rcf;
-            continue;
-        }
-
-        unsigned long long *d_final = d_hist;
-        if (!p.per_frame && slots > 1) {
-            d_final = d_hist + (size_t)slots * words;
-            launch_reduce_slots(ctx->stream, d_hist, d_final, (int)words, slots);
-            MD_HIP(hipGetLastError());
-        }
-        // D2H (pinned staging) into the right class rows; the overflow word rides along with the last pass
-        MD_PIN(tmp, uint64_t, (out_frames * words + 1) * 8);
-        MD_HIP(hipMemcpyAsync(tmp, d_final, out_frames * words * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (pass == n_pass - 1)
-            MD_HIP(hipMemcpyAsync(tmp + out_frames * words, d_misc, 8, hipMemcpyDeviceToHost, ctx->stream));
         MD_HIP(mdhip_stream_wait(ctx));
-        if (pass == n_pass - 1) acc->ov = tmp[out_frames * words];  // (d_misc[0] accumulates over the passes)
-        collect_times();
-        for (size_t fr = 0; fr < out_frames; ++fr)
-            memcpy(&H[(fr * p.n_cls + c0) * p.nbins], &tmp[fr * words], words * 8);
+        rc = fin();
+        if (rc) return rc;
     }
-    if (deferred) return MDHIP_OK;
     return finalize();
 }
 
@@ -903,23 +682,13 @@ static int stage_batch_async(mdhip_ctx *ctx, const PairProblem &p, int64_t f0, i
     return MDHIP_OK;
 }
 
-static int pair_hist_run_range(mdhip_ctx *ctx, const PairProblem &p, int64_t f0, int64_t n, std::vector<uint64_t> &H,
-                               uint64_t *overflow, std::vector<uint64_t> *Hsplit, CallScope *defer = nullptr,
-                               bool *redo = nullptr);
-
-// Splits the frames into batches so that the culled path's workspace (sorted copy, keys, cell counts, boxes,
-// neighbour-tile lists) stays within ~2 GiB and a launch's grid.y within 65535, and merges the batches.
-// Host-resident coordinates (p.h_xi): the batches are also the unit of the host-to-device staging — the copy of batch
-// k + 1 is issued on the copy stream before batch k is swept, so that it runs under that sweep (page-locked sources:
-// a DMA the host does not wait for; pageable sources: the runtime stages them synchronously, so the copy simply comes
-// first, as without this scheme). A shorter first batch lets the sweep start early.
-// `defer` / `redo`: see pair_hist_run_batch — used when the frames are ONE batch whose coordinates are on the device.
-int pair_hist_run(mdhip_ctx *ctx, const PairProblem &p, std::vector<uint64_t> &H, uint64_t *overflow,
-                  CallScope *defer = nullptr, bool *redo = nullptr)
+// The batches [f0, f0 + n) of F frames: the culled path's workspace (sorted copy, keys, cell counts, boxes,
+// neighbour-tile lists) stays within ~2 GiB and a launch's grid.y within 65535. `staged` (host-resident coordinates):
+// a shorter first batch lets the sweep start early. Pure arithmetic (mdhip_pair_plan counts launches with it).
+static std::vector<std::pair<int64_t, int64_t>> batch_parts(const mdhip_ctx *ctx, int64_t F, int64_t ni, bool staged)
 {
-    const int64_t F = p.n_frames;
-    const int64_t nT = (p.ni + TILE - 1) / TILE;
-    const double per_frame_b = 54.0 * (double)p.ni + 4.0 * MORTON_CELLS + 2.0 * (double)nT * (double)nT + 1024.0;
+    const int64_t nT = (ni + TILE - 1) / TILE;
+    const double per_frame_b = 54.0 * (double)ni + 4.0 * MORTON_CELLS + 2.0 * (double)nT * (double)nT + 1024.0;
     int64_t batch = (int64_t)(2147483648.0 / per_frame_b);
     if (batch < 1) batch = 1;
     if (batch > 32768) batch = 32768;
@@ -927,63 +696,60 @@ int pair_hist_run(mdhip_ctx *ctx, const PairProblem &p, std::vector<uint64_t> &H
     // frames a batch sorted in two rounds of 1.1 ms where 256 take one
     if (batch > ctx->cu_count && ctx->cu_count > 0) batch = batch / ctx->cu_count * ctx->cu_count;
     if (ctx->opt_rdf_batch > 0) batch = ctx->opt_rdf_batch;
-    const bool staged = p.h_xi || p.h_xj;
-    // the batches: [f0, f0 + n)
     std::vector<std::pair<int64_t, int64_t>> parts;
-    {
-        int64_t f0 = 0;
-        if (staged && F >= 32) {
-            // first batch: a quarter of the frames (whole multiples of 8: frames are dealt to the 8 XCDs). Its sweep has
-            // to last as long as the copy of the rest — the sweep consumes frames ~3.7x slower than PCIe delivers them
-            // at C2 and at C3 size (61 against 230 frames per ms at 10k atoms) — or the second sweep waits for data
-            // (a sixth measured 3.94 ms per C2 step with a 0.18 ms stall)
-            int64_t b0 = std::max<int64_t>(8, (F / 4) / 8 * 8);
-            b0 = std::min(b0, batch);
-            parts.emplace_back(0, b0);
-            f0 = b0;
-        }
-        for (; f0 < F; f0 += batch) parts.emplace_back(f0, std::min<int64_t>(batch, F - f0));
+    int64_t f0 = 0;
+    if (staged && F >= 32) {
+        // first batch: a quarter of the frames (whole multiples of 8: frames are dealt to the 8 XCDs). Its sweep has
+        // to last as long as the copy of the rest — the sweep consumes frames ~3.7x slower than PCIe delivers them
+        // at C2 and at C3 size (61 against 230 frames per ms at 10k atoms) — or the second sweep waits for data
+        // (a sixth measured 3.94 ms per C2 step with a 0.18 ms stall)
+        int64_t b0 = std::max<int64_t>(8, (F / 4) / 8 * 8);
+        b0 = std::min(b0, batch);
+        parts.emplace_back(0, b0);
+        f0 = b0;
     }
-    const size_t row = (size_t)p.n_cls * p.nbins;
-    const size_t row_cn = (size_t)p.n_cls;
-    if (staged) {
-        const int rc = stage_batch_async(ctx, p, parts[0].first, parts[0].second, ctx->copy_ev[0]);
-        if (rc) return rc;
-    }
-    if (parts.size() == 1 && !staged) return pair_hist_run_range(ctx, p, 0, F, H, overflow, p.Hsplit, defer, redo);
-    H.assign((p.per_frame ? (size_t)F : 1) * row, 0);
-    if (p.Hsplit) p.Hsplit->assign((p.per_frame ? (size_t)F : 1) * row_cn, 0);
+    for (; f0 < F; f0 += batch) parts.emplace_back(f0, std::min<int64_t>(batch, F - f0));
+    return parts;
+}
+
+static int pair_hist_run_range(mdhip_ctx *ctx, const PairProblem &p, int64_t f0, int64_t n, std::vector<uint64_t> &H,
+                               uint64_t *overflow, std::vector<uint64_t> *Hsplit, CallScope *defer = nullptr,
+                               bool *redo = nullptr);
+
+// Runs the parts [first, first + second) of the frames [f0, f0 + n) one after the other and merges them — the batches of
+// a call, or the halves of a batch that raised the overflow guard: the parts' class histograms and split counts go into
+// the whole's, per frame or added up, and the timing registers of the context add up. `before(k)` runs ahead of part k.
+template <class Before>
+static int run_parts(mdhip_ctx *ctx, const PairProblem &p, const std::vector<std::pair<int64_t, int64_t>> &parts, int64_t f0,
+                     int64_t n, std::vector<uint64_t> &H, uint64_t *overflow, std::vector<uint64_t> *Hsplit, Before before)
+{
+    const size_t row = (size_t)p.n_cls * p.nbins, row_cn = (size_t)p.n_cls;
+    H.assign((p.per_frame ? (size_t)n : 1) * row, 0);
+    if (Hsplit) Hsplit->assign((p.per_frame ? (size_t)n : 1) * row_cn, 0);
     *overflow = 0;
     double ms = 0.0, aux = 0.0;
     int launches = 0;
     std::vector<uint64_t> part, part_cn;
     for (size_t k = 0; k < parts.size(); ++k) {
-        const int64_t f0 = parts[k].first, n = parts[k].second;
-        if (staged) {
-            // this batch's frames must have landed before the launch stream touches them; the next batch's copy goes
-            // out now, ahead of this batch's kernels
-            MD_HIP(hipStreamWaitEvent(ctx->stream, ctx->copy_ev[k & 1], 0));
-            if (k + 1 < parts.size()) {
-                const int rc = stage_batch_async(ctx, p, parts[k + 1].first, parts[k + 1].second, ctx->copy_ev[(k + 1) & 1]);
-                if (rc) return rc;
-            }
-        }
+        int rc = before(k);
+        if (rc) return rc;
         uint64_t ov = 0;
-        const int rc = pair_hist_run_range(ctx, p, f0, n, part, &ov, p.Hsplit ? &part_cn : nullptr);
+        rc = pair_hist_run_range(ctx, p, parts[k].first, parts[k].second, part, &ov, Hsplit ? &part_cn : nullptr);
         if (rc) return rc;
         *overflow += ov;
         ms += ctx->last_ms;
         aux += ctx->last_aux_ms;
         launches += ctx->last_launches;
+        const size_t at = (size_t)(parts[k].first - f0);
         if (p.per_frame)
-            std::copy(part.begin(), part.end(), H.begin() + (size_t)f0 * row);
+            std::copy(part.begin(), part.end(), H.begin() + at * row);
         else
             for (size_t q = 0; q < row; ++q) H[q] += part[q];
-        if (p.Hsplit) {
+        if (Hsplit) {
             if (p.per_frame)
-                std::copy(part_cn.begin(), part_cn.end(), p.Hsplit->begin() + (size_t)f0 * row_cn);
+                std::copy(part_cn.begin(), part_cn.end(), Hsplit->begin() + at * row_cn);
             else
-                for (size_t q = 0; q < row_cn; ++q) (*p.Hsplit)[q] += part_cn[q];
+                for (size_t q = 0; q < row_cn; ++q) (*Hsplit)[q] += part_cn[q];
         }
     }
     ctx->last_ms = ms;
@@ -1013,38 +779,36 @@ static int pair_hist_run_range(mdhip_ctx *ctx, const PairProblem &p, int64_t f0,
         return mdhip_fail(ctx, MDHIP_ELIMIT, "pair_hist: one frame can overflow the 32-bit block histograms "
                                               "(%lld x %lld atoms)", (long long)p.ni, (long long)p.nj);
     // (device-resident sums, dev_out, are left untouched by a flagged launch)
-    const size_t row = (size_t)p.n_cls * p.nbins, row_cn = (size_t)p.n_cls;
-    H.assign((p.per_frame ? (size_t)n : 1) * row, 0);
-    if (Hsplit) Hsplit->assign((p.per_frame ? (size_t)n : 1) * row_cn, 0);
-    *overflow = 0;
-    double ms = 0.0, aux = 0.0;
-    int launches = 0;
-    std::vector<uint64_t> part, part_cn;
     const int64_t half = (n + 1) / 2;
-    for (int64_t h0 = 0; h0 < n; h0 += half) {
-        uint64_t ov = 0;
-        const int rc = pair_hist_run_range(ctx, p, f0 + h0, std::min<int64_t>(half, n - h0), part, &ov,
-                                           Hsplit ? &part_cn : nullptr);
+    return run_parts(ctx, p, {{f0, half}, {f0 + half, n - half}}, f0, n, H, overflow, Hsplit, [](size_t) { return 0; });
+}
+
+// Runs the batches of batch_parts and merges them.
+// Host-resident coordinates (p.h_xi): the batches are also the unit of the host-to-device staging — the copy of batch
+// k + 1 is issued on the copy stream before batch k is swept, so that it runs under that sweep (page-locked sources:
+// a DMA the host does not wait for; pageable sources: the runtime stages them synchronously, so the copy simply comes
+// first, as without this scheme).
+// `defer` / `redo`: see pair_hist_run_batch — used when the frames are ONE batch whose coordinates are on the device.
+int pair_hist_run(mdhip_ctx *ctx, const PairProblem &p, std::vector<uint64_t> &H, uint64_t *overflow,
+                  CallScope *defer = nullptr, bool *redo = nullptr)
+{
+    const int64_t F = p.n_frames;
+    const bool staged = p.h_xi || p.h_xj;
+    const std::vector<std::pair<int64_t, int64_t>> parts = batch_parts(ctx, F, p.ni, staged);
+    if (staged) {
+        const int rc = stage_batch_async(ctx, p, parts[0].first, parts[0].second, ctx->copy_ev[0]);
         if (rc) return rc;
-        *overflow += ov;
-        ms += ctx->last_ms;
-        aux += ctx->last_aux_ms;
-        launches += ctx->last_launches;
-        if (p.per_frame)
-            std::copy(part.begin(), part.end(), H.begin() + (size_t)h0 * row);
-        else
-            for (size_t k = 0; k < row; ++k) H[k] += part[k];
-        if (Hsplit) {
-            if (p.per_frame)
-                std::copy(part_cn.begin(), part_cn.end(), Hsplit->begin() + (size_t)h0 * row_cn);
-            else
-                for (size_t k = 0; k < row_cn; ++k) (*Hsplit)[k] += part_cn[k];
-        }
     }
-    ctx->last_ms = ms;
-    ctx->last_aux_ms = aux;
-    ctx->last_launches = launches;
-    return MDHIP_OK;
+    if (parts.size() == 1 && !staged) return pair_hist_run_range(ctx, p, 0, F, H, overflow, p.Hsplit, defer, redo);
+    return run_parts(ctx, p, parts, 0, F, H, overflow, p.Hsplit, [&](size_t k) {
+        if (!staged) return (int)MDHIP_OK;
+        // this batch's frames must have landed before the launch stream touches them; the next batch's copy goes
+        // out now, ahead of this batch's kernels
+        MD_HIP(hipStreamWaitEvent(ctx->stream, ctx->copy_ev[k & 1], 0));
+        if (k + 1 < parts.size())
+            return stage_batch_async(ctx, p, parts[k + 1].first, parts[k + 1].second, ctx->copy_ev[(k + 1) & 1]);
+        return (int)MDHIP_OK;
+    });
 }
 
 // labels -> compact indices 0..T-1 (sorted unique labels)
@@ -1160,26 +924,57 @@ struct RelJob {
     std::vector<double> *cn_c2_cls = nullptr; // out: the cutoff^2 of every class
 };
 
+// Labels -> compact type indices -> classes -> displaced rows: the part of a job that needs no device, shared by
+// run_job and mdhip_pair_plan. Fills p.tri, n_ti, n_tj, cls, n_cls and the displaced layout; idx_i / idx_j are the
+// compact type columns (lab_j: rectangular only).
+static int classify(mdhip_ctx *ctx, bool tri, const int32_t *lab_i, size_t n_lab_i, const int32_t *lab_j, size_t n_lab_j,
+                    int n_rel, const int32_t *rel, PairProblem &p, std::vector<int> &rel_cls, std::vector<int32_t> &idx_i,
+                    std::vector<int32_t> &idx_j)
+{
+    std::vector<int32_t> ui, uj;
+    compact_labels(lab_i, n_lab_i, ui, idx_i);
+    if (!tri) compact_labels(lab_j, n_lab_j, uj, idx_j);
+    const int n_ti = merge_unnamed_labels(ui, idx_i, n_rel, rel, tri ? -1 : 0);
+    const int n_tj = tri ? n_ti : merge_unnamed_labels(uj, idx_j, n_rel, rel, 1);
+    if ((size_t)n_ti * (size_t)n_tj > 16384)
+        return mdhip_fail(ctx, MDHIP_ELIMIT, "too many distinct types named by relations (%d x %d)", n_ti, n_tj);
+    p.tri = tri;
+    build_classes(tri, ui, tri ? ui : uj, n_ti, n_tj, n_rel, rel, p.cls, rel_cls, p.n_cls);
+    p.n_ti = n_ti;
+    p.n_tj = n_tj;
+    if (ctx->opt_rdf_disp != 0) p.disp_rows = displace_rows(n_ti, n_tj, p.cls, p.disp_a, p.disp_b, p.disp_cls);
+    return MDHIP_OK;
+}
+
+// One coordination cutoff^2 per class (0: none) from one per relation; false: relations that name the same pair of
+// types with different cutoffs (such a call takes two sweeps).
+static bool class_cutoffs(int n_rel, const std::vector<int> &rel_cls, const double *cn_rc2, int n_cls, std::vector<double> &c2)
+{
+    c2.assign(n_cls, 0.0);
+    std::vector<char> seen(n_cls, 0);
+    for (int kl = 0; kl < n_rel; ++kl) {
+        const int cl = rel_cls[kl];
+        if (cl < 0) continue;
+        const double v = cn_rc2[kl] > 0.0 ? cn_rc2[kl] : 0.0;
+        if (seen[cl] && c2[cl] != v) return false;
+        seen[cl] = 1;
+        c2[cl] = v;
+    }
+    return true;
+}
+
 // Stages everything, runs the kernel and returns class histograms + the relation->class map.
 // `defer` / `redo`: see pair_hist_run_batch (H, rel_cls, *overflow, j.Hsplit and *redo then live in the entry point's
 // heap state; what a deferred step needs from this function's locals is copied into it).
 int run_job(mdhip_ctx *ctx, const RelJob &j, std::vector<uint64_t> &H, std::vector<int> &rel_cls,
             int &n_cls, uint64_t *overflow, CallScope *defer = nullptr, bool *redo = nullptr)
 {
-    std::vector<int32_t> ui, idx_i, uj, idx_j;
-    const size_t n_lab_i = j.lab_i_fs ? (size_t)j.F * j.ni : (size_t)j.ni;
-    compact_labels(j.lab_i, n_lab_i, ui, idx_i);
-    if (!j.tri) compact_labels(j.lab_j, (size_t)j.nj, uj, idx_j);
-    const int n_ti = merge_unnamed_labels(ui, idx_i, j.n_rel, j.rel, j.tri ? -1 : 0);
-    const int n_tj = j.tri ? n_ti : merge_unnamed_labels(uj, idx_j, j.n_rel, j.rel, 1);
-    const std::vector<int32_t> &ujr = j.tri ? ui : uj;
-    if ((size_t)n_ti * (size_t)n_tj > 16384)
-        return mdhip_fail(ctx, MDHIP_ELIMIT, "too many distinct types named by relations (%d x %d)", n_ti, n_tj);
-
+    std::vector<int32_t> idx_i, idx_j;
     PairProblem p;
-    p.tri = j.tri;
-    build_classes(j.tri, ui, ujr, n_ti, n_tj, j.n_rel, j.rel, p.cls, rel_cls, n_cls);
-    p.n_cls = n_cls;
+    int rc = classify(ctx, j.tri, j.lab_i, j.lab_i_fs ? (size_t)j.F * j.ni : (size_t)j.ni, j.lab_j, (size_t)j.nj, j.n_rel,
+                      j.rel, p, rel_cls, idx_i, idx_j);
+    if (rc) return rc;
+    n_cls = p.n_cls;
     std::vector<int> rel_mult(j.n_rel, 1);
     if (j.dev_out) {
         for (int kl = 0; kl < j.n_rel; ++kl) rel_mult[kl] = (j.tri && j.rel[2 * kl] == j.rel[2 * kl + 1]) ? 2 : 1;
@@ -1188,11 +983,7 @@ int run_job(mdhip_ctx *ctx, const RelJob &j, std::vector<uint64_t> &H, std::vect
         p.rel_cls = rel_cls.data();
         p.rel_mult = rel_mult.data();
     }
-    p.n_ti = n_ti;
-    p.n_tj = n_tj;
-    if (ctx->opt_rdf_disp != 0) p.disp_rows = displace_rows(n_ti, n_tj, p.cls, p.disp_a, p.disp_b, p.disp_cls);
 
-    int rc;
     // Host-resident coordinates are staged batch by batch under the sweeps (pair_hist_run); the guard drains the copy
     // stream on every way out, so that no copy still reads the caller's arrays after this call has returned.
     struct CopyGuard {
@@ -1289,20 +1080,9 @@ int run_job(mdhip_ctx *ctx, const RelJob &j, std::vector<uint64_t> &H, std::vect
     p.bin_size = j.bin_size;
     p.per_frame = j.per_frame;
     if (j.cn_rc2) {
-        // one cutoff per class: relations that name the same pair of types with different cutoffs take two sweeps
-        std::vector<double> &c2 = *j.cn_c2_cls;
-        c2.assign(n_cls, 0.0);
-        std::vector<char> seen(n_cls, 0);
-        for (int kl = 0; kl < j.n_rel; ++kl) {
-            const int cl = rel_cls[kl];
-            if (cl < 0) continue;
-            const double v = j.cn_rc2[kl] > 0.0 ? j.cn_rc2[kl] : 0.0;
-            if (seen[cl] && c2[cl] != v) return CN_UNFUSED;
-            seen[cl] = 1;
-            c2[cl] = v;
-        }
+        if (!class_cutoffs(j.n_rel, rel_cls, j.cn_rc2, n_cls, *j.cn_c2_cls)) return CN_UNFUSED;
         p.n_cn = 1;
-        p.cn_c2_cls = c2.data();
+        p.cn_c2_cls = j.cn_c2_cls->data();
         p.Hsplit = j.Hsplit;
     }
     rc = pair_hist_run(ctx, p, H, overflow, defer, redo);
@@ -1378,15 +1158,16 @@ struct PairState {
     bool redo = false;  // the launch raised the overflow guard of the 32-bit block histograms: run again, synchronously
 };
 
-static const double *state_edges(PairState &st, const double *edges, double bin_size, int nbins)
+// The call's own copy of the bin edges: the caller's, or (NULL) the exact edges of trunc(sqrt(rsq) / bin_size).
+static const double *own_edges(std::vector<double> &store, const double *edges, double bin_size, int nbins)
 {
     if (edges) {
-        st.edges.assign(edges, edges + nbins + 1);
+        store.assign(edges, edges + nbins + 1);
     } else {
-        st.edges.resize((size_t)nbins + 1);
-        mdhip_bin_edges(bin_size, nbins, st.edges.data());
+        store.resize((size_t)nbins + 1);
+        mdhip_bin_edges(bin_size, nbins, store.data());
     }
-    return st.edges.data();
+    return store.data();
 }
 
 static void atomic_job(RelJob &j, int64_t n_frames, int64_t n_atoms, const double *xyz, int on_device, const int32_t *type,
@@ -1409,6 +1190,40 @@ static void atomic_job(RelJob &j, int64_t n_frames, int64_t n_atoms, const doubl
     j.gscale = bin_size > 0.0 ? (float)(1.0 / bin_size) : 0.f;
     j.bin_size = bin_size;
     j.per_frame = per_frame;
+}
+
+// ... and of atoms x sites (rectangular: ordered (atom type, site type) classes, one type column for all frames)
+static void sites_job(RelJob &j, int64_t n_frames, int64_t n_atoms, const double *xyz, int xyz_on_device, const int32_t *type,
+                      int64_t n_sites, const double *sites, int sites_on_device, const int32_t *site_type, const double *box,
+                      int n_rel, const int32_t *rel, double r_cut_sq, double bin_size, int nbins, const double *edges,
+                      int per_frame)
+{
+    atomic_job(j, n_frames, n_atoms, xyz, xyz_on_device, type, 0, box, n_rel, rel, r_cut_sq, bin_size, nbins, edges, per_frame);
+    j.tri = false;
+    j.nj = n_sites;
+    j.xj = sites;
+    j.xj_dev = sites_on_device;
+    j.lab_j = site_type;
+}
+
+// Class rows Hf [n_cls][nbins] of one output frame -> the reference's atom-atom outputs (either may be NULL):
+// full[bin] += 2 per pair (rdf_cn.py:85-86); part [n_rel][nbins]: the relation's class row, +1 per unordered {a,b}
+// pair, +2 when a == b — ASSIGNED (a relation whose labels do not occur: zeros), or with `add` added to what is there.
+static void rows_to_outputs(const uint64_t *Hf, int n_cls, int nbins, int n_rel, const int32_t *rel,
+                            const std::vector<int> &rel_cls, uint64_t *full, uint64_t *part, bool add)
+{
+    for (int c = 0; c < n_cls && full; ++c)
+        for (int b = 0; b < nbins; ++b) full[b] += 2 * Hf[(size_t)c * nbins + b];
+    for (int kl = 0; kl < n_rel && part; ++kl) {
+        uint64_t *dst = part + (size_t)kl * nbins;
+        if (rel_cls[kl] < 0) {
+            if (!add) std::fill(dst, dst + nbins, (uint64_t)0);
+            continue;
+        }
+        const uint64_t mult = rel[2 * kl] == rel[2 * kl + 1] ? 2 : 1;
+        const uint64_t *row = Hf + (size_t)rel_cls[kl] * nbins;
+        for (int b = 0; b < nbins; ++b) dst[b] = (add ? dst[b] : 0) + mult * row[b];
+    }
 }
 
 int mdhip_rdf_atomic(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz,
@@ -1435,7 +1250,7 @@ int mdhip_rdf_atomic(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const do
     auto st = std::make_shared<PairState>();
     RelJob j{};
     atomic_job(j, n_frames, n_atoms, xyz, on_device, type, type_frame_stride, box, n_rel, rel, r_cut_sq, bin_size, nbins,
-               state_edges(*st, edges, bin_size, nbins), per_frame);
+               own_edges(st->edges, edges, bin_size, nbins), per_frame);
     st->rel.assign(rel, rel + 2 * (size_t)n_rel);
     rc = run_job(ctx, j, st->H, st->rel_cls, st->n_cls, &st->ov, cs.async() ? &cs : nullptr, &st->redo);
     if (rc) return rc;
@@ -1445,22 +1260,9 @@ int mdhip_rdf_atomic(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const do
                                     st->rel.data(), r_cut_sq, bin_size, nbins, st->edges.data(), per_frame, hist_full,
                                     hist_part, overflow);
         if (overflow) *overflow = st->ov;
-        const int n_cls = st->n_cls;
-        const int32_t *rl = st->rel.data();
-        // rdf_full[bin] += 2 per pair (rdf_cn.py:85-86); rdf_part: +1 per unordered {a,b} pair, +2 when a == b
-        for (size_t f = 0; f < out_frames; ++f) {
-            const uint64_t *Hf = &st->H[f * n_cls * nbins];
-            uint64_t *full = hist_full + f * nbins;
-            for (int c = 0; c < n_cls; ++c)
-                for (int b = 0; b < nbins; ++b) full[b] += 2 * Hf[(size_t)c * nbins + b];
-            for (int kl = 0; kl < n_rel; ++kl) {
-                if (st->rel_cls[kl] < 0) continue;
-                const uint64_t mult = rl[2 * kl] == rl[2 * kl + 1] ? 2 : 1;
-                uint64_t *part = hist_part + (f * n_rel + kl) * nbins;
-                const uint64_t *row = Hf + (size_t)st->rel_cls[kl] * nbins;
-                for (int b = 0; b < nbins; ++b) part[b] = mult * row[b];
-            }
-        }
+        for (size_t f = 0; f < out_frames; ++f)
+            rows_to_outputs(&st->H[f * st->n_cls * nbins], st->n_cls, nbins, n_rel, st->rel.data(), st->rel_cls,
+                            hist_full + f * nbins, n_rel ? hist_part + f * n_rel * nbins : nullptr, false);
         return (int)MDHIP_OK;
     });
     return cs.end();
@@ -1485,7 +1287,7 @@ int mdhip_rdf_atomic_dev(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, cons
     auto st = std::make_shared<PairState>();
     RelJob j{};
     atomic_job(j, n_frames, n_atoms, xyz, on_device, type, type_frame_stride, box, n_rel, rel, r_cut_sq, bin_size, nbins,
-               state_edges(*st, edges, bin_size, nbins), 0);
+               own_edges(st->edges, edges, bin_size, nbins), 0);
     j.dev_out = reinterpret_cast<unsigned long long *>(out_dev);
     st->rel.assign(rel, rel + 2 * (size_t)n_rel);
     rc = run_job(ctx, j, st->H, st->rel_cls, st->n_cls, &st->ov, cs.async() ? &cs : nullptr, &st->redo);
@@ -1501,19 +1303,10 @@ int mdhip_rdf_atomic_dev(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, cons
         for (size_t k = 0; k < H.size() && !any; ++k) any = H[k] != 0;
         if (!any) return (int)MDHIP_OK;
         CallScope fix(ctx);
-        const int n_cls = st->n_cls;
-        const int32_t *rl = st->rel.data();
         MD_PIN(out, uint64_t, words * 8);
         MD_HIP(hipMemcpyAsync(out, out_dev, words * 8, hipMemcpyDeviceToHost, ctx->stream));
         MD_HIP(mdhip_stream_wait(ctx));
-        for (int c = 0; c < n_cls; ++c)
-            for (int b = 0; b < nbins; ++b) out[b] += 2 * H[(size_t)c * nbins + b];
-        for (int kl = 0; kl < n_rel; ++kl) {
-            if (st->rel_cls[kl] < 0) continue;
-            const uint64_t mult = rl[2 * kl] == rl[2 * kl + 1] ? 2 : 1;
-            for (int b = 0; b < nbins; ++b)
-                out[(size_t)(1 + kl) * nbins + b] += mult * H[(size_t)st->rel_cls[kl] * nbins + b];
-        }
+        rows_to_outputs(H.data(), st->n_cls, nbins, n_rel, st->rel.data(), st->rel_cls, out, out + nbins, true);  // ADDED
         out[words - 1] += st->ov;
         MD_HIP(hipMemcpyAsync(out_dev, out, words * 8, hipMemcpyHostToDevice, ctx->stream));
         return fix.end();
@@ -1531,6 +1324,15 @@ static int deliver_counts(mdhip_ctx *ctx, const uint64_t *src, size_t n, uint64_
     return mdhip_deliver_to_device(ctx, dst, src, n * 8);
 }
 
+// The first condition of the one-sweep route: something to do, and no coordination cutoff beyond r_cut.
+static bool cn_within_r_cut(int64_t n_frames, int64_t n_atoms, int n_rel, const double *cn_r_cut_sq, double r_cut_sq)
+{
+    bool fused = n_rel > 0 && n_frames > 0 && n_atoms >= 2;
+    for (int kl = 0; kl < n_rel && fused; ++kl) fused = !(cn_r_cut_sq[kl] > r_cut_sq);
+    return fused;
+}
+constexpr int CN_PK_BINS = 64;  // bins of the coarse histogram mdhip_cn_atomic's cutoffs ride on (option cn_pk)
+
 // One sweep for the histograms AND the coordination counts. hist_full / hist_part / overflow may be
 // NULL (coordination counts only: mdhip_cn_atomic runs its cutoffs through here with a coarse 64-bin histogram whose
 // cutoff is the largest coordination cutoff). Returns MDHIP_OK, an error, or CN_UNFUSED when this call has to take the
@@ -1544,15 +1346,13 @@ static int fused_rdf_cn(CallScope &cs, int64_t n_frames, int64_t n_atoms, const 
                         uint64_t *overflow, uint64_t *cn, int cn_on_device)
 {
     mdhip_ctx *ctx = cs.ctx;
-    bool fused = n_rel > 0 && n_frames > 0 && n_atoms >= 2;
-    for (int kl = 0; kl < n_rel && fused; ++kl) fused = !(cn_r_cut_sq[kl] > r_cut_sq);
-    if (!fused) return CN_UNFUSED;
+    if (!cn_within_r_cut(n_frames, n_atoms, n_rel, cn_r_cut_sq, r_cut_sq)) return CN_UNFUSED;
     MD_HIP(hipSetDevice(ctx->device));
     const size_t out_frames = per_frame ? (size_t)n_frames : 1;
     auto st = std::make_shared<PairState>();
     RelJob j{};
     atomic_job(j, n_frames, n_atoms, xyz, on_device, type, type_frame_stride, box, n_rel, rel, r_cut_sq, bin_size, nbins,
-               state_edges(*st, edges, bin_size, nbins), per_frame);
+               own_edges(st->edges, edges, bin_size, nbins), per_frame);
     st->rel.assign(rel, rel + 2 * (size_t)n_rel);
     auto cuts = std::make_shared<std::vector<double>>(cn_r_cut_sq, cn_r_cut_sq + n_rel);
     j.cn_rc2 = cuts->data();
@@ -1581,22 +1381,14 @@ static int fused_rdf_cn(CallScope &cs, int64_t n_frames, int64_t n_atoms, const 
         uint64_t *cn_out = cn_on_device ? cn_host.data() : cn;
         for (size_t f = 0; f < out_frames; ++f) {
             const uint64_t *Hf = &H[f * n_cls * nbins];
-            if (hist_full) {
-                uint64_t *full = hist_full + f * nbins;
-                for (int c = 0; c < n_cls; ++c)
-                    for (int b = 0; b < nbins; ++b) full[b] += 2 * Hf[(size_t)c * nbins + b];
-            }
+            rows_to_outputs(Hf, n_cls, nbins, n_rel, rl, st->rel_cls, hist_full ? hist_full + f * nbins : nullptr,
+                            hist_part ? hist_part + f * n_rel * nbins : nullptr, false);
             for (int kl = 0; kl < n_rel; ++kl) {
-                uint64_t *part = hist_part ? hist_part + (f * n_rel + kl) * nbins : nullptr;
                 uint64_t s = 0;
                 const uint64_t mult = rl[2 * kl] == rl[2 * kl + 1] ? 2 : 1;
-                if (st->rel_cls[kl] < 0) {
-                    if (part) std::fill(part, part + nbins, (uint64_t)0);
-                } else {
+                if (st->rel_cls[kl] >= 0) {
                     const int cl = st->rel_cls[kl];
                     const uint64_t *row = Hf + (size_t)cl * nbins;
-                    if (part)
-                        for (int b = 0; b < nbins; ++b) part[b] = mult * row[b];
                     const double c2 = st->c2_cls[cl];
                     if (c2 > 0.0) {
                         // bins below the split bin are inside the cutoff (exact edges); the split bin's share was
@@ -1613,37 +1405,6 @@ static int fused_rdf_cn(CallScope &cs, int64_t n_frames, int64_t n_atoms, const 
         return deliver_counts(ctx, cn_out, out_frames * (size_t)n_rel, cn, cn_on_device);
     });
     return MDHIP_OK;
-}
-
-static int cn_atomic_impl(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int on_device,
-                          const int32_t *type, int64_t type_frame_stride, const double *box, int n_rel,
-                          const int32_t *rel, const double *r_cut_sq, int per_frame, uint64_t *cn, int cn_on_device);
-
-int mdhip_rdf_cn_atomic(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int on_device,
-                        const int32_t *type, int64_t type_frame_stride, const double *box, int n_rel,
-                        const int32_t *rel, double r_cut_sq, double bin_size, int nbins, const double *edges,
-                        const double *cn_r_cut_sq, int per_frame, uint64_t *hist_full, uint64_t *hist_part,
-                        uint64_t *overflow, uint64_t *cn)
-{
-    if (!ctx) return MDHIP_EINVAL;
-    CallScope cs(ctx);
-    int rc = check_common(ctx, n_frames, n_atoms, xyz, type, box, n_rel, rel);
-    if (rc) return rc;
-    MD_REQUIRE(nbins >= 1 && bin_size > 0.0, "nbins and bin_size must be positive");
-    MD_REQUIRE(type_frame_stride == 0 || type_frame_stride == n_atoms, "type_frame_stride must be 0 or n_atoms");
-    MD_REQUIRE(hist_full && (n_rel == 0 || (hist_part && cn_r_cut_sq && cn)), "NULL output or cutoff array");
-    rc = fused_rdf_cn(cs, n_frames, n_atoms, xyz, on_device, type, type_frame_stride, box, n_rel, rel, r_cut_sq,
-                      bin_size, nbins, edges, cn_r_cut_sq, per_frame, hist_full, hist_part, overflow, cn, 0);
-    if (rc == MDHIP_OK) return cs.end();
-    if (rc != CN_UNFUSED) return rc;
-    // this call does not run as one packed sweep — two sweeps (calls of their own, complete on return), same integers
-    rc = mdhip_rdf_atomic(ctx, n_frames, n_atoms, xyz, on_device, type, type_frame_stride, box, n_rel, rel, r_cut_sq,
-                          bin_size, nbins, edges, per_frame, hist_full, hist_part, overflow);
-    if (rc) return rc;
-    rc = cn_atomic_impl(ctx, n_frames, n_atoms, xyz, on_device, type, type_frame_stride, box, n_rel, rel,
-                        cn_r_cut_sq, per_frame, cn, 0);
-    if (rc) return rc;
-    return cs.end();
 }
 
 static int cn_atomic_impl(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int on_device,
@@ -1674,7 +1435,7 @@ static int cn_atomic_impl(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, con
         // finds inside — the same integers as the f64 edge-table kernel below, which is the route for
         // everything the packed sweep does not take (small frames, two cutoffs for one class, ...) and for cn_pk = 0.
         const double c_max = std::sqrt(edges.back());
-        const int nb = 64;
+        const int nb = CN_PK_BINS;
         rc = fused_rdf_cn(cs, n_frames, n_atoms, xyz, on_device, type, type_frame_stride, box, n_rel, rel,
                           edges.back(), c_max / nb, nb, nullptr, r_cut_sq, per_frame, nullptr, nullptr, nullptr, cn,
                           cn_on_device);
@@ -1706,6 +1467,33 @@ static int cn_atomic_impl(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, con
     } else {
         memcpy(cn, cn_host.data(), cn_host.size() * 8);
     }
+    return cs.end();
+}
+
+int mdhip_rdf_cn_atomic(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int on_device,
+                        const int32_t *type, int64_t type_frame_stride, const double *box, int n_rel,
+                        const int32_t *rel, double r_cut_sq, double bin_size, int nbins, const double *edges,
+                        const double *cn_r_cut_sq, int per_frame, uint64_t *hist_full, uint64_t *hist_part,
+                        uint64_t *overflow, uint64_t *cn)
+{
+    if (!ctx) return MDHIP_EINVAL;
+    CallScope cs(ctx);
+    int rc = check_common(ctx, n_frames, n_atoms, xyz, type, box, n_rel, rel);
+    if (rc) return rc;
+    MD_REQUIRE(nbins >= 1 && bin_size > 0.0, "nbins and bin_size must be positive");
+    MD_REQUIRE(type_frame_stride == 0 || type_frame_stride == n_atoms, "type_frame_stride must be 0 or n_atoms");
+    MD_REQUIRE(hist_full && (n_rel == 0 || (hist_part && cn_r_cut_sq && cn)), "NULL output or cutoff array");
+    rc = fused_rdf_cn(cs, n_frames, n_atoms, xyz, on_device, type, type_frame_stride, box, n_rel, rel, r_cut_sq,
+                      bin_size, nbins, edges, cn_r_cut_sq, per_frame, hist_full, hist_part, overflow, cn, 0);
+    if (rc == MDHIP_OK) return cs.end();
+    if (rc != CN_UNFUSED) return rc;
+    // this call does not run as one packed sweep — two sweeps (calls of their own, complete on return), same integers
+    rc = mdhip_rdf_atomic(ctx, n_frames, n_atoms, xyz, on_device, type, type_frame_stride, box, n_rel, rel, r_cut_sq,
+                          bin_size, nbins, edges, per_frame, hist_full, hist_part, overflow);
+    if (rc) return rc;
+    rc = cn_atomic_impl(ctx, n_frames, n_atoms, xyz, on_device, type, type_frame_stride, box, n_rel, rel,
+                        cn_r_cut_sq, per_frame, cn, 0);
+    if (rc) return rc;
     return cs.end();
 }
 
@@ -1792,33 +1580,10 @@ int mdhip_rdf_sites(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const dou
     if (n_rel) std::fill(hist_part, hist_part + out_frames * n_rel * nbins, (uint64_t)0);
     if (overflow) *overflow = 0;
     if (n_frames == 0 || n_atoms == 0 || n_sites == 0 || n_rel == 0) return cs.end();
-    std::vector<double> own_edges;
-    if (!edges) {
-        own_edges.resize(nbins + 1);
-        mdhip_bin_edges(bin_size, nbins, own_edges.data());
-        edges = own_edges.data();
-    }
+    std::vector<double> edge_store;
     RelJob j{};
-    j.tri = false;
-    j.F = n_frames;
-    j.ni = n_atoms;
-    j.nj = n_sites;
-    j.xi = xyz;
-    j.xi_dev = xyz_on_device;
-    j.xj = sites;
-    j.xj_dev = sites_on_device;
-    j.lab_i = type;
-    j.lab_i_fs = 0;
-    j.lab_j = site_type;
-    j.box = box;
-    j.n_rel = n_rel;
-    j.rel = rel;
-    j.nbins = nbins;
-    j.edges = edges;
-    j.rc2 = r_cut_sq;
-    j.gscale = (float)(1.0 / bin_size);
-    j.bin_size = bin_size;
-    j.per_frame = per_frame;
+    sites_job(j, n_frames, n_atoms, xyz, xyz_on_device, type, n_sites, sites, sites_on_device, site_type, box, n_rel, rel,
+              r_cut_sq, bin_size, nbins, own_edges(edge_store, edges, bin_size, nbins), per_frame);
     std::vector<uint64_t> H;
     std::vector<int> rel_cls;
     int n_cls = 0;
@@ -1857,25 +1622,8 @@ int mdhip_cn_sites(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const doub
     const int nbins = (int)edges.size() - 1;
     if (nbins == 0) return cs.end();
     RelJob j{};
-    j.tri = false;
-    j.F = n_frames;
-    j.ni = n_atoms;
-    j.nj = n_sites;
-    j.xi = xyz;
-    j.xi_dev = xyz_on_device;
-    j.xj = sites;
-    j.xj_dev = sites_on_device;
-    j.lab_i = type;
-    j.lab_i_fs = 0;
-    j.lab_j = site_type;
-    j.box = box;
-    j.n_rel = n_rel;
-    j.rel = rel;
-    j.nbins = nbins;
-    j.edges = edges.data();
-    j.rc2 = edges.back();
-    j.gscale = 0.f;
-    j.per_frame = per_frame;
+    sites_job(j, n_frames, n_atoms, xyz, xyz_on_device, type, n_sites, sites, sites_on_device, site_type, box, n_rel, rel,
+              edges.back(), 0.0, nbins, edges.data(), per_frame);
     std::vector<uint64_t> H;
     std::vector<int> rel_cls;
     int n_cls = 0;
@@ -1891,6 +1639,107 @@ int mdhip_cn_sites(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const doub
             cn[f * n_rel + kl] = s;
         }
     return cs.end();
+}
+
+int mdhip_pair_plan(const mdhip_ctx *ctx, int op, int64_t n_frames, int64_t n_atoms, const int32_t *type, int64_t n_type,
+                    int64_t n_sites, const int32_t *site_type, int64_t n_site_type, const double *box, int n_rel,
+                    const int32_t *rel, double r_cut_sq, double bin_size, int nbins, const double *cn_r_cut_sq, int per_frame,
+                    int result_on_device, int xyz_on_device, int cu_count, int64_t lds_bytes, int n_opt,
+                    const char *const *opt_key, const int *opt_value, char *text, int text_cap, int32_t *info)
+{
+    if (!text || text_cap < 1 || !info || op < MDHIP_PLAN_RDF || op > MDHIP_PLAN_RDF_CN) return MDHIP_EINVAL;
+    if (n_frames < 0 || n_atoms < 0 || n_sites < 0 || n_type < 0 || n_rel < 0 || (n_rel && !rel)) return MDHIP_EINVAL;
+    if (n_frames && n_atoms && (!type || !box)) return MDHIP_EINVAL;
+    if (op != MDHIP_PLAN_RDF && (n_rel && !cn_r_cut_sq)) return MDHIP_EINVAL;
+    if (op != MDHIP_PLAN_CN && !(nbins >= 1 && bin_size > 0.0)) return MDHIP_EINVAL;
+    if (op == MDHIP_PLAN_RDF_CN && site_type) return MDHIP_EINVAL;
+    mdhip_ctx c = ctx ? *ctx : mdhip_ctx();  // (a copy: options and limits only — nothing below touches a device)
+    if (cu_count > 0) c.cu_count = cu_count;
+    if (lds_bytes > 0) c.lds_max = (size_t)lds_bytes;
+    text[0] = 0;
+    for (int k = 0; k < 8; ++k) info[k] = 0;
+    info[1] = -1;
+    auto fail = [&](int code) {
+        info[0] = code;
+        snprintf(text, (size_t)text_cap, "%s", c.err.c_str());
+        return (int)MDHIP_OK;
+    };
+    for (int k = 0; k < n_opt; ++k)
+        if (const int rc = mdhip_set_option(&c, opt_key[k], opt_value[k])) return fail(rc);
+    const bool tri = site_type == nullptr;
+    if (n_frames == 0 || (tri ? n_atoms < 2 : n_atoms == 0 || n_sites == 0 || n_rel == 0)) return MDHIP_OK;  // nothing runs
+    if (op == MDHIP_PLAN_CN && n_rel == 0) return MDHIP_OK;
+
+    PairProblem p{};
+    std::vector<int> rel_cls;
+    std::vector<int32_t> idx_i, idx_j;
+    if (const int rc = classify(&c, tri, type, (size_t)n_type, site_type, (size_t)n_site_type, n_rel, rel, p, rel_cls, idx_i, idx_j))
+        return fail(rc);
+    p.ni = n_atoms;
+    p.nj = tri ? n_atoms : n_sites;
+    p.per_frame = per_frame;
+    if (result_on_device && op == MDHIP_PLAN_RDF && tri) {  // (mdhip_rdf_atomic_dev; the plan asks only whether it is set)
+        static unsigned long long somewhere;
+        p.dev_out = &somewhere;
+        p.n_rel = n_rel;
+    }
+    const bool staged = c.opt_h2d_overlap != 0 && !xyz_on_device;  // (as a synchronous call stages host-resident frames)
+    const auto parts = batch_parts(&c, n_frames, n_atoms, staged);
+    std::vector<double> c2;
+    // one sweep of all batches -> MDHIP_OK (info and text describe it), CN_UNFUSED, or an error
+    auto sweep = [&](double rc2, double bsz, int nb, const double *cuts) {
+        p.rc2 = rc2;
+        p.bin_size = bsz;
+        p.gscale = bsz > 0.0 ? (float)(1.0 / bsz) : 0.f;
+        p.nbins = nb;
+        p.n_cn = 0;
+        if (cuts) {
+            if (!class_cutoffs(n_rel, rel_cls, cuts, p.n_cls, c2)) return (int)CN_UNFUSED;
+            p.n_cn = 1;
+            p.cn_c2_cls = c2.data();
+        }
+        info[3] = 0;
+        for (size_t k = 0; k < parts.size(); ++k) {
+            PairPlan pl;
+            p.n_frames = parts[k].second;
+            p.h_box = box + 3 * parts[k].first;
+            if (const int rc = pair_plan(&c, p, pl)) return rc;
+            info[3] += pl.n_pass;
+            if (k) continue;  // (the first batch is the one described)
+            info[1] = pl.sj_mode;
+            info[2] = pl.n_pass;
+            info[4] = pl.ordered ? pl.ord_rows : 0;
+            info[5] = pl.ordered && pl.displaced;
+            info[6] = pl.big;
+            info[7] = pl.pk && pl.sj_mode >= 3;
+            snprintf(text, (size_t)text_cap, "%s", pl.kname);
+        }
+        return (int)MDHIP_OK;
+    };
+    int rc;
+    if (op == MDHIP_PLAN_RDF) {
+        rc = sweep(r_cut_sq, bin_size, nbins, nullptr);
+    } else if (op == MDHIP_PLAN_RDF_CN) {
+        rc = cn_within_r_cut(n_frames, n_atoms, n_rel, cn_r_cut_sq, r_cut_sq) ? sweep(r_cut_sq, bin_size, nbins, cn_r_cut_sq)
+                                                                             : (int)CN_UNFUSED;
+        if (rc == CN_UNFUSED) {  // two sweeps: the RDF's is the one described
+            rc = sweep(r_cut_sq, bin_size, nbins, nullptr);
+            if (rc == MDHIP_OK) rc = CN_UNFUSED;
+        }
+    } else {
+        std::vector<double> edges;
+        std::vector<int> rank;
+        cn_edges(n_rel, cn_r_cut_sq, edges, rank);
+        const int nb = (int)edges.size() - 1;
+        if (nb == 0) return MDHIP_OK;
+        rc = CN_UNFUSED;
+        if (tri && c.opt_cn_pk != 0 && cn_within_r_cut(n_frames, n_atoms, n_rel, cn_r_cut_sq, edges.back()))
+            rc = sweep(edges.back(), std::sqrt(edges.back()) / CN_PK_BINS, CN_PK_BINS, cn_r_cut_sq);
+        if (rc == CN_UNFUSED) rc = sweep(edges.back(), 0.0, nb, nullptr);
+    }
+    if (rc < 0) return fail(rc);
+    info[0] = rc;
+    return MDHIP_OK;
 }
 
 }  // extern "C"

@@ -256,3 +256,118 @@ def test_row_displacement_never_mixes_classes():
     assert 0 < rows_c1 <= 18, rows_c1  # 36 plain rows; <= 33 needed to fit a third of LDS at 400 bins
     assert _displace(cases[3])[0] == 0
     assert gained >= 20
+
+
+# What the MI355X ran for every case of tests/pair_plan_cases.py at the commit BEFORE the plan was split from the batch
+# runner (f070edf, "Add number_density.calc_number_density with a HIP axis-profile kernel"): last_kernel_name() and the
+# launch count of last_kernel_ms() after the real call. A call that takes two sweeps leaves the second sweep's (CN) kernel.
+RECORDED_AT_F070EDF = {
+    "C2":                          ('pair_hist_sj_kernel<3, true, false>', 1),
+    "C1":                          ('pair_hist_sj_kernel<3, true, false>', 1),
+    "C1alt":                       ('pair_hist_sj_kernel<3, true, false>', 1),
+    "C1full":                      ('pair_hist_sj_kernel<3, true, false, true>', 1),
+    "C3_rdf":                      ('pair_hist_sj_kernel<3, true, false>', 1),
+    "C3_cn":                       ('pair_hist_sj_kernel<3, true, true>', 1),
+    "C3_rdf_cn":                   ('pair_hist_sj_kernel<3, true, true>', 1),
+    "sites_rdf":                   ('pair_hist_sj_kernel<3, true, false>', 1),
+    "sites_cn":                    ('pair_hist_sj_kernel<1, true, false>', 1),
+    "base":                        ('pair_hist_sj_kernel<3, true, false>', 1),
+    "base_cn":                     ('pair_hist_sj_kernel<3, true, true>', 1),
+    "base_rdf_cn":                 ('pair_hist_sj_kernel<3, true, true>', 1),
+    "dense_small_frame":           ('pair_hist_fast_kernel<true, 8, 0, false>', 1),
+    "few_bins_edge_table":         ('pair_hist_kernel<true>', 1),
+    "cn_70_cutoffs":               ('pair_hist_kernel<true>', 1),
+    "cutoff_inside_bin":           ('pair_hist_sj_kernel<4, true, false>', 1),
+    "cutoff_inside_bin_rows":      ('pair_hist_sj_kernel<6, true, false>', 1),
+    "per_frame":                   ('pair_hist_sj_kernel<3, false, false>', 1),
+    "device_result":               ('pair_hist_sj_kernel<3, true, false>', 1),
+    "device_result_small_frame":   ('pair_hist_fast_kernel<true, 8, 0, false>', 1),
+    "twelve_types_all_pairs":      ('pair_hist_sj_kernel<5, true, false>', 4),
+    "box_4000":                    ('pair_hist_sj_kernel<2, true, false>', 1),
+    "cn_beyond_r_cut":             ('pair_hist_sj_kernel<3, true, true>', 1),
+    "cn_two_cutoffs_one_class":    ('pair_hist_sj_kernel<1, true, false>', 1),
+    "host_batches":                ('pair_hist_sj_kernel<3, true, false>', 2),
+    "rdf_pk_0":                    ('pair_hist_sj_kernel<2, true, false>', 1),
+    "rdf_pk_2":                    ('pair_hist_sj_kernel<2, true, false>', 1),
+    "rdf_sj_0":                    ('pair_hist_fast_kernel<true, 8, 0, true>', 1),
+    "rdf_sj_2":                    ('pair_hist_sj_kernel<3, false, false>', 1),
+    "rdf_cull_0":                  ('pair_hist_fast_kernel<true, 8, 0, false>', 1),
+    "dense_box":                   ('pair_hist_fast_kernel<true, 8, 0, false>', 1),
+    "rdf_cull_1":                  ('pair_hist_sj_kernel<3, true, false>', 1),
+    "rdf_rows_0":                  ('pair_hist_sj_kernel<5, true, false>', 1),
+    "c1_small":                    ('pair_hist_sj_kernel<3, true, false>', 1),
+    "rdf_disp_0":                  ('pair_hist_sj_kernel<5, true, false>', 1),
+    "star5":                       ('pair_hist_sj_kernel<3, true, false>', 1),
+    "rdf_disp_2":                  ('pair_hist_sj_kernel<3, true, false>', 1),
+    "c1full_small":                ('pair_hist_sj_kernel<3, true, false, true>', 1),
+    "rdf_big_0":                   ('pair_hist_sj_kernel<5, true, false>', 2),
+    "rdf_pk_passes_0":             ('pair_hist_sj_kernel<0, true, false>', 3),
+    "rdf_variant_0":               ('pair_hist_kernel<true>', 1),
+    "cn_pk_0":                     ('pair_hist_sj_kernel<1, true, false>', 1),
+}
+
+
+def test_pair_plan_picks_what_the_device_ran():
+    """mdhip_pair_plan with the MI355X's two limits (256 CUs, 160 KB of LDS) names, for every branch of the decision,
+    the kernel instance and the number of launches recorded from real calls on that device at the parent commit."""
+    import pair_plan_cases as P
+
+    assert set(RECORDED_AT_F070EDF) == set(P.CASES)
+    got = {name: P.plan(case) for name, case in P.CASES.items()}
+    two_sweeps = {"cn_beyond_r_cut", "cn_two_cutoffs_one_class"}
+    for name, (kernel, launches) in RECORDED_AT_F070EDF.items():
+        g = got[name]
+        if name in two_sweeps:
+            # the RDF sweep (described by the plan) and then the CN call of the same shape, whose kernel was recorded
+            assert g["status"] == P.TWO_SWEEPS, (name, g)
+            assert g["kernel"] == got["base"]["kernel"], (name, g)
+            g = P.plan(dict(P.CASES[name], op="cn"))
+        assert g["status"] == 0 and (g["kernel"], g["launches"]) == (kernel, launches), (name, g, kernel, launches)
+    # what the name alone does not show
+    flags = lambda name: tuple(got[name][k] for k in ("sj_mode", "n_pass", "ord_rows", "displaced", "big", "packed"))  # noqa: E731
+    assert flags("C2") == (3, 1, 16, 0, 0, 1)
+    assert flags("C1")[2:] == (15, 1, 0, 1) and flags("c1_small") == flags("C1")   # 36 plain rows do not fit, 15 displaced do
+    assert flags("rdf_disp_0") == (5, 1, 0, 0, 0, 1)                                # ... without them: class rows
+    assert flags("C1full") == (3, 1, 81, 0, 1, 1)                                   # one 16-wave block per CU
+    assert flags("rdf_big_0") == (5, 2, 0, 0, 0, 1)                                 # ... without it: two passes
+    assert flags("star5")[2:4] == (36, 0) and flags("rdf_disp_2")[3] == 1 and flags("rdf_disp_2")[2] < 36
+    assert flags("twelve_types_all_pairs")[:2] == (5, 4) and flags("rdf_pk_passes_0")[0] == 0
+    assert flags("cutoff_inside_bin")[0] == 4 and flags("cutoff_inside_bin_rows")[0] == 6
+    assert flags("box_4000") == (2, 1, 9, 0, 0, 0) and flags("rdf_pk_0") == flags("box_4000")
+    assert flags("rdf_rows_0")[0] == 5 and flags("rdf_pk_2")[0] == 2
+    assert got["host_batches"]["launches"] == 2 and got["base"]["launches"] == 1
+    for name in ("dense_small_frame", "few_bins_edge_table", "cn_70_cutoffs", "rdf_sj_0", "rdf_cull_0", "dense_box",
+                 "rdf_variant_0"):
+        assert got[name]["sj_mode"] == -1, name
+    # the two limit errors come back as the plan's status, with the library's message
+    too_many_bins = P.plan(dict(P.CASES["base"], bin=0.0002, nbins=50000))
+    assert too_many_bins["status"] == -5 and "50000 bins do not fit LDS" in too_many_bins["kernel"]
+    # ... and the limits are read: a device with 64 KB of LDS cannot hold C1full's 81 rows in one block
+    assert P.plan(P.CASES["C1full"], lds_bytes=65536)["big"] == 0
+
+
+def test_row_displacement_is_the_same_in_every_process():
+    """Two fresh interpreters return the same layout (no in-process cache between them, and no clock in the search):
+    the nine-type reference shape and a 20-type random table (budget-limited: DESIGN 4.1f)."""
+    import subprocess
+    import sys
+
+    code = ("import sys, json, numpy as np\n"
+            "sys.path.insert(0, %r)\n"
+            "import test_abi_cpu as T\n"
+            "rng = np.random.default_rng(20)\n"
+            "arms = [(19, int(j)) for j in rng.permutation(19)[:12]]  # twelve random partners of one type, two random pairs\n"
+            "t20 = T._tri_classes(20, arms + [(int(a), int(b)) for a, b in rng.integers(0, 19, (2, 2))])\n"
+            "c1 = T._tri_classes(6, [(4, 0), (4, 2), (4, 3), (4, 4), (0, 1)])\n"
+            "print(json.dumps([[r[0]] + [v.tolist() for v in r[1:]] for r in (T._displace(c1), T._displace(t20))]))\n"
+            % os.path.join(REPO, "tests"))
+    outs = []
+    for _ in range(2):
+        r = subprocess.run([sys.executable, "-c", code], cwd=REPO, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        outs.append(r.stdout.strip().splitlines()[-1])
+    assert outs[0] == outs[1]
+    import json
+
+    c1, t20 = json.loads(outs[0])
+    assert 0 < c1[0] <= 18 and t20[0] > 0

@@ -439,3 +439,28 @@ def test_read_once_sort_every_instance_and_small_copy_paths(B):
     finally:
         ref_ctx.close()
         new_ctx.close()
+
+
+def test_pair_plan_names_the_kernel_a_real_call_runs(B):
+    """mdhip_pair_plan, given a context's own options and device limits, names the kernel instance that the real call
+    of the same shape leaves in last_kernel_name() — bench.py's C2 and C1full, the displaced reference shape, atoms x
+    sites, class rows in passes and RDF + CN from one sweep (tests/pair_plan_cases.py). Every result against the C
+    oracle: all frames of the small calls; for the 200-frame shapes the same call on their first two frames (whose
+    kernel the plan must name as well)."""
+    import pair_plan_cases as P
+    from mdproptools_amd._lib import Context
+
+    for name in ("C2", "c1_small", "C1full", "sites_rdf", "twelve_types_all_pairs", "base_rdf_cn"):
+        case = P.CASES[name]
+        ctx = Context(0)
+        inp, out = P.run(case, B, ctx)
+        want = P.plan(case, 0, 0, ctx=ctx)
+        assert want["status"] == 0 and want["kernel"], (name, want)
+        assert ctx.last_kernel_name() == want["kernel"], (name, ctx.last_kernel_name(), want)
+        assert ctx.last_kernel_ms()[1] == want["launches"], (name, ctx.last_kernel_ms(), want)
+        if case["F"] > 8:
+            case = dict(case, F=2)
+            inp, out = P.run(case, B, ctx)
+            assert ctx.last_kernel_name() == P.plan(case, 0, 0, ctx=ctx)["kernel"], name
+        P.check_against_oracle(case, inp, out, C)
+        ctx.close()
