@@ -603,6 +603,28 @@ int mdhip_shell_members(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const
  */
 int mdhip_mol_kahan_sums(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, int n_attr, const double *attr,
                          int attr_on_device, int64_t n_mols, const int64_t *seg_off, double *out);
+/*
+ * The configuration census of get_unique_configurations          structural/cluster_analysis.py:238-457
+ * taken from the trajectory instead of from cluster files: inputs as mdhip_shell_members, and the molecule layout in
+ * full: seg_off[n_mols + 1] (molecule m is the atoms [seg_off[m], seg_off[m+1]), at most 255 of them, and mol_of
+ * agrees), mol_type[n_mols] (>= 0), cls[n_atoms] the coordination class of every atom (0..7, or 255 for an atom that
+ * never counts), passes [F][n_mols] (NULL: all ones) the force filter's verdict (cluster_analysis.py:146-152).
+ *   members(f, c) = { m : passes[f][m], m is not the centre's own molecule, rsq(centre c, atom a) < r_shell_sq for
+ *                         an atom a of m }                          cluster_analysis.py:127-216
+ *   word(f, c, m) = sum over the atoms b of m with cls[b] != 255 and rsq(centre c, b) < r_coord_sq of
+ *                   1 << (8 * cls[b])                               cluster_analysis.py:347-372
+ * (eight 8-bit counters, one per class; the same single-wrap rsq; the two radii are independent).
+ *   mols [F][n_centres][cap], words [F][n_centres][cap]: the members and their words in ascending
+ *   (mol_type[m], word, m) order, padded with -1 and ~0: two rows are the same configuration exactly when their
+ *   (type, word) sequences are equal;
+ *   count[F][n_centres]: the number of members, exact even when it exceeds cap (that row is then incomplete: call
+ *   again for its frame with cap >= count). 1 <= cap <= 4096.
+ */
+int mdhip_shell_coordination(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int xyz_on_device,
+                             const double *box, int32_t n_centres, const int32_t *centres, int64_t n_mols,
+                             const int32_t *mol_of, const int64_t *seg_off, const int32_t *mol_type,
+                             const uint8_t *cls, const uint8_t *passes, double r_shell_sq, double r_coord_sq,
+                             int32_t cap, int32_t *mols, uint64_t *words, int32_t *count);
 
 /* ---- cation-water orientation of the hydration number (hydration_number.py get_hydration_number) ---- */
 /*

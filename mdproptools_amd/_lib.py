@@ -131,6 +131,9 @@ PROTOTYPES = {
     "mdhip_shell_members": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int32, c_ip, c_ip,
                                       C.c_double, C.c_int32, c_ip, c_ip]),
     "mdhip_mol_kahan_sums": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, vp, C.c_int, C.c_int64, c_lp, c_dp]),
+    "mdhip_shell_coordination": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int32, c_ip, C.c_int64,
+                                           c_ip, c_lp, c_ip, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_double,
+                                           C.c_double, C.c_int32, c_ip, c_up, c_ip]),
     "mdhip_hydration_cosines": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int32, c_ip, C.c_int32,
                                           c_ip, C.c_double, C.c_int32, c_ip, c_dp, c_ip]),
     "mdhip_hydration_counts": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int32, c_ip, C.c_int32,

@@ -562,17 +562,19 @@ def shell_residence(xyz_i, xyz_j, box, r_lo_sq, r_hi_sq, exclude_diagonal=False,
     return counts, int(nrec.value)
 
 
-def _with_overflow_rerun(run, xyz, inp, bx, cap, pads, what, ctx):
+def _with_overflow_rerun(run, xyz, inp, bx, cap, pads, what, ctx, per_frame=None):
     """
     The capped per-row search behind shell_members and hydration_cosines. run(n_frames, pointer, on_device, box, cap)
     -> the per-row arrays [n_frames, C, cap], then count [n_frames, C] (exact even past cap); inp = as_input(xyz, ctx).
     Frames with a row that overflowed `cap` are run again, alone, with a cap of their largest count and spliced in; the
     other frames' rows are padded with `pads` (one value per per-row array). `what` = (function name, noun of a row)
-    for the error texts.
+    for the error texts. `per_frame` (optional, [n_frames, ...]): another per-frame input; run then takes it, or its
+    re-run frames, as a sixth argument.
     """
     xp, x_dev, keep = inp
     cap = max(1, int(cap))
-    *rows, count = run(len(bx), xp, x_dev, bx, cap)
+    more = () if per_frame is None else (per_frame,)
+    *rows, count = run(len(bx), xp, x_dev, bx, cap, *more)
     over = np.flatnonzero((count > cap).any(axis=1))
     if len(over) == 0:
         return (*rows, count)
@@ -586,7 +588,8 @@ def _with_overflow_rerun(run, xyz, inp, bx, cap, pads, what, ctx):
     else:
         raise ValueError("%ss overflow cap=%d: pass a larger cap with a DevPtr input" % (what[1], cap))
     sp, s_dev, sub_keep = as_input(sub, ctx)  # (sub_keep: what sp points at, alive until the call below has returned)
-    *rerun, rcount = run(len(over), sp, s_dev, np.ascontiguousarray(bx[over]), big)
+    more = () if per_frame is None else (np.ascontiguousarray(per_frame[over]),)
+    *rerun, rcount = run(len(over), sp, s_dev, np.ascontiguousarray(bx[over]), big, *more)
     del sub_keep
     if not np.array_equal(rcount, count[over]):
         raise RuntimeError("%s: the re-run found other %s sizes than the first sweep" % what)
@@ -628,6 +631,62 @@ def shell_members(xyz, box, centres, mol_of, r_cut_sq, cap=SHELL_CAP, ctx=None):
         return mols, count
 
     return _with_overflow_rerun(run, xyz, as_input(xyz, ctx), bx, cap, (-1,), ("shell_members", "shell"), ctx)
+
+
+COORD_CLASSES = 8  # 8-bit counters in the 64-bit word of shell_coordination
+COORD_NO_CLASS = 0xFF  # class of an atom that never counts
+COORD_MOL_ATOMS = 255  # what one counter holds
+
+
+def shell_coordination(xyz, box, centres, mol_of, seg_off, mol_type, cls, r_shell_sq, r_coord_sq, passes=None,
+                       cap=SHELL_CAP, ctx=None):
+    """
+    The configuration census of get_unique_configurations (cluster_analysis.py:238-457) from the trajectory: xyz, box,
+    centres, mol_of as shell_members, molecule m the atoms [seg_off[m], seg_off[m+1]) of type mol_type[m], cls uint8
+    [N] the coordination class of every atom (0..7, or 255: never counted), passes [F,M] (None: all pass) the force
+    filter's verdict -> (mols int32 [F,C,K], words uint64 [F,C,K], count int32 [F,C]).
+    Row (f, c) holds the count[f, c] passing molecules other than the centre's own with an atom at rsq < r_shell_sq,
+    each with a word of eight 8-bit counters: per class, its atoms at rsq < r_coord_sq. The entries are in ascending
+    (type, word, molecule) order, then -1 / ~0 up to K = max(cap, largest count): equal configurations are equal
+    (type, word) sequences. Frames whose rows overflow `cap` are run again with a cap of their largest count
+    (include/mdhip.h: mdhip_shell_coordination).
+    """
+    ctx = ctx or default_context()
+    F, _, N = _shape3(xyz, "xyz")
+    cen = _i32(centres).ravel()
+    mol = _i32(mol_of).ravel()
+    off = _i64(seg_off).ravel()
+    mty = _i32(mol_type).ravel()
+    kls = np.ascontiguousarray(cls, dtype=np.uint8).ravel()
+    M = len(off) - 1
+    if len(mol) != N or len(kls) != N:
+        raise ValueError("mol_of and cls must hold one value per atom")
+    if len(mty) != M:
+        raise ValueError("mol_type must hold one type per molecule of seg_off")
+    used = kls[kls != COORD_NO_CLASS]
+    if len(used) and int(used.max()) >= COORD_CLASSES:
+        raise ValueError("at most %d coordination classes (class %d given)" % (COORD_CLASSES, int(used.max())))
+    if M and int(np.diff(off).max()) > COORD_MOL_ATOMS:
+        raise ValueError("a molecule of more than %d atoms: a coordination counter could wrap" % COORD_MOL_ATOMS)
+    C_ = len(cen)
+    bx = _f64(box).reshape(F, 3)
+    mask = None
+    if passes is not None:
+        mask = np.ascontiguousarray(np.asarray(passes).reshape(F, M) != 0, dtype=np.uint8)
+
+    def run(n_f, p, dev, b, k, sub=None):  # sub: the pass mask of the frames of this run
+        mols = np.empty((n_f, C_, k), dtype=np.int32)
+        words = np.empty((n_f, C_, k), dtype=np.uint64)
+        count = np.zeros((n_f, C_), dtype=np.int32)
+        ctx.check(ctx.lib.mdhip_shell_coordination(
+            ctx.h, n_f, N, p, dev, ptr(b), C_, ptr(cen, C.c_int32), M, ptr(mol, C.c_int32), ptr(off, C.c_int64),
+            ptr(mty, C.c_int32), ptr(kls, C.c_uint8), None if sub is None else ptr(sub, C.c_uint8),
+            float(r_shell_sq), float(r_coord_sq), k, ptr(mols, C.c_int32), ptr(words, C.c_uint64),
+            ptr(count, C.c_int32)))
+        return mols, words, count
+
+    return _with_overflow_rerun(run, xyz, as_input(xyz, ctx), bx, cap, (-1, np.uint64(0xFFFFFFFFFFFFFFFF)),
+                                ("shell_coordination", "shell"), ctx, per_frame=mask)
 
 
 def mol_kahan_sums(attr, seg_off, ctx=None):

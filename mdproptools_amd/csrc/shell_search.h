@@ -107,6 +107,39 @@ __device__ __forceinline__ void rank_row(const int *r, int count, int cap, Emit 
     for (int i = n + lane; i < cap; i += 64) pad(i);
 }
 
+// The keyed sibling of rank_row, for rows of (molecule, 64-bit word) records ranked by (type, word, molecule): the
+// n = min(count, cap) records load(i) -> (type, molecule, word) are staged in LDS (the launch's dynamic LDS: cap
+// records of 16 bytes, {word, type << 32 | molecule}) and each is ranked; the molecules are distinct and not negative,
+// so the keys are distinct. emit(rank, molecule, word) for every record, then pad(i) for i in [n, cap).
+constexpr int MAX_KEYED_CAP = 4096;  // 64 KB of LDS
+
+template <class Load, class Emit, class Pad>
+__device__ __forceinline__ void rank_row_keyed(int count, int cap, Load load, Emit emit, Pad pad)
+{
+    extern __shared__ unsigned long long s_keyed[];
+    const int lane = threadIdx.x, n = count < cap ? count : cap;
+    __syncthreads();  // (the previous row's ranks have read s_keyed)
+    for (int i = lane; i < n; i += 64) {
+        int type, mol;
+        unsigned long long word;
+        load(i, type, mol, word);
+        s_keyed[2 * i] = word;
+        s_keyed[2 * i + 1] = ((unsigned long long)(unsigned)type << 32) | (unsigned)mol;
+    }
+    __syncthreads();
+    for (int i = lane; i < n; i += 64) {
+        const unsigned long long w = s_keyed[2 * i], tm = s_keyed[2 * i + 1];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) {
+            const unsigned long long wj = s_keyed[2 * j], tmj = s_keyed[2 * j + 1];
+            const unsigned tj = (unsigned)(tmj >> 32), t = (unsigned)(tm >> 32);
+            rank += tj != t ? tj < t : (wj != w ? wj < w : tmj < tm);
+        }
+        emit(rank, (int)(unsigned)tm, w);
+    }
+    for (int i = n + lane; i < cap; i += 64) pad(i);
+}
+
 struct Inputs {  // on the device
     const double *xyz = nullptr, *box = nullptr;
     const int *centres = nullptr;
