@@ -689,6 +689,42 @@ int mdhip_axis_profile(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const 
                        double dist, int32_t n_bins, int origin_kind, const double *origin, uint32_t *counts,
                        double *extent, uint32_t *outside);
 
+/* ---- displacement over a fixed lag (Displacement.calc_dist; self part of the van Hove function) ---- */
+/*
+ * Finishes what the reference's Displacement.calc_dist sketches      dynamical/residence_time.py:211-254
+ * (the wrapped x y z of the chosen atoms per frame, to be grouped into windows of one residence time): the histogram
+ * of the distance travelled over a fixed lag, over all time origins, i.e. G_s(r, t) before normalisation.
+ *   r          host|dev (r_on_device) [n_frames][3][n_ent]
+ *   box        host [n_frames][3] edge lengths: r is WRAPPED and the image counts are rebuilt; NULL: r is unwrapped
+ *   group_off  host int64 [n_groups+1] contiguous entity groups (as mdhip_msd_pairs); empty groups are allowed
+ *   jobs       host int32 [n_jobs][3] = (group, lag, stride), 1 <= lag <= n_frames-1, stride >= 1; several jobs may
+ *              name one group (a van Hove call asks for many lags that way)
+ *   edges      host [nbins+1] from mdhip_bin_edges, or NULL to have it computed from bin_size; 1 <= nbins <= 2^20
+ * Anything else is MDHIP_EINVAL before anything is written.
+ * Image counts (box != NULL), per entity and axis: n(0) = 0; for f >= 1, d = x(f) - x(f-1), L = box[f][axis]:
+ * n(f) = n(f-1) - 1 when d > L/2, n(f-1) + 1 when d < -L/2, else n(f-1) — strict, the reference's single-wrap
+ * convention (rdf_cn.py:44-57); a NaN compares false and shifts nothing. xu(f) = x(f) + (double)n(f) * L(f), one
+ * multiplication and one addition, unfused; xu = x when box == NULL. Only meaningful when no entity moves more than
+ * half a box edge between consecutive frames.
+ * Per job (g, k, s): origins t0 = 0, s, 2s, ... with t0 + k <= n_frames-1, entities of group g; for every (origin,
+ * entity) d = xu(t0+k) - xu(t0), rsq = (dx*dx + dy*dy) + dz*dz unfused, bin = (int64)(sqrt(rsq) / bin_size) decided by
+ * comparing rsq with the edge table (never by device sqrt).
+ *   hist       host uint64 [n_jobs][nbins]: +1 in hist[job][bin] when bin < nbins
+ *   overflow   host uint64 [n_jobs]: the windows with bin >= nbins or a NaN rsq
+ *   windows    host uint64 [n_jobs] = origins * group size
+ *   moments    host double [n_jobs][3] = sum sqrt(rsq), sum rsq, sum rsq*rsq over ALL windows of the job (overflowing
+ *              ones included; sqrt correctly rounded); fixed order per launch geometry, no float atomics: within
+ *              windows * 2^-52 relative of any other summation order, bit-identical from call to call
+ *   crossings  host uint64 [1] or NULL: the (frame step, entity, axis) triples that shifted; 0 when box == NULL
+ * The integer outputs are exact and independent of the launch geometry. Any number of frames, entities and jobs:
+ * launch dimensions over 65535 are split inside the call.
+ */
+int mdhip_displacement_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const double *r, int r_on_device,
+                            const double *box, int n_groups, const int64_t *group_off, int n_jobs,
+                            const int32_t *jobs, double bin_size, int32_t nbins, const double *edges,
+                            uint64_t *hist, uint64_t *overflow, uint64_t *windows, double *moments,
+                            uint64_t *crossings);
+
 /*
  * Replaces, for the inputs of the path, the un-vendored pymatgen `parse_lammps_dumps` + pandas
  * `read_csv` the reference uses (call sites structural/rdf_cn.py:176, dynamical/diffusion.py:172,

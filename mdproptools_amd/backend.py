@@ -811,3 +811,53 @@ def axis_profile(x, rows, mode, bin_size, dist, n_bins, n_rows, origin="lo", ctx
         float(dist), int(n_bins), kind, None if org is None else ptr(org), ptr(counts, C.c_uint32), ptr(extent),
         ptr(outside, C.c_uint32)))
     return counts, extent, outside
+
+
+def displacement_hist(r, box, group_off, jobs, bin_size, n_bins, ctx=None):
+    """
+    Histogram of the distance travelled over a fixed lag, over all time origins (include/mdhip.h:
+    mdhip_displacement_hist; the finished form of the reference's Displacement.calc_dist sketch, residence_time.py:
+    211-254): r [F,3,E] (host array or contiguous float64 device tensor), box [F,3] edge lengths when r is wrapped (the
+    kernel rebuilds the image counts) or None when it is unwrapped, group_off int64 [G+1] contiguous entity groups,
+    jobs int32 [J,3] rows (group, lag, stride) -> (hist uint64 [J,n_bins], overflow uint64 [J], windows uint64 [J],
+    moments float64 [J,3] = sums of r, r^2, r^4 over the job's windows, crossings int: the image shifts found).
+    """
+    F, _, E = _shape3(r, "r")
+    bx = None
+    if box is not None:
+        bx = _f64(box)
+        if bx.shape != (F, 3):
+            raise ValueError("box must have shape [n_frames, 3]")
+    off = _i64(group_off)
+    if off.ndim != 1 or off.size < 1 or off[0] < 0 or off[-1] > E or np.any(np.diff(off) < 0):
+        raise ValueError("group_off must be ascending offsets [n_groups + 1] within [0, n_ent]")
+    G = off.size - 1
+    jb = np.asarray(jobs)
+    if jb.size and (jb.ndim != 2 or jb.shape[1] != 3):
+        raise ValueError("jobs must have shape [n_jobs, 3]: (group, lag, stride)")
+    jb = _i32(jb).reshape(-1, 3)
+    if len(jb):
+        if jb[:, 0].min() < 0 or jb[:, 0].max() >= G:
+            raise ValueError("a job names a group outside [0, %d)" % G)
+        if jb[:, 1].min() < 1 or jb[:, 1].max() > F - 1:
+            raise ValueError("every lag must be in [1, n_frames - 1 = %d]" % (F - 1))
+        if jb[:, 2].min() < 1:
+            raise ValueError("every stride must be at least 1")
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= 1 << 20:
+        raise ValueError("n_bins must be in [1, 2^20]")
+    if not (float(bin_size) > 0.0 and np.isfinite(bin_size)):
+        raise ValueError("bin_size must be positive and finite")
+    ctx = ctx or default_context()
+    rp, r_dev, keep = as_input(r, ctx)
+    J = len(jb)
+    hist = result_array((J, n_bins), dtype=np.uint64, device=ctx.device)
+    overflow = np.empty(J, dtype=np.uint64)
+    windows = np.empty(J, dtype=np.uint64)
+    moments = np.empty((J, 3), dtype=np.float64)
+    crossings = C.c_uint64(0)
+    ctx.check(ctx.lib.mdhip_displacement_hist(
+        ctx.h, F, E, rp, r_dev, None if bx is None else ptr(bx), G, ptr(off, C.c_int64), J, ptr(jb, C.c_int32),
+        float(bin_size), n_bins, None, ptr(hist, C.c_uint64), ptr(overflow, C.c_uint64), ptr(windows, C.c_uint64),
+        ptr(moments), C.byref(crossings)))
+    return hist, overflow, windows, moments, int(crossings.value)

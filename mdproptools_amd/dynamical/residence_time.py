@@ -14,9 +14,19 @@ What runs where
 Deliberate difference: with default ids (no num_mols / num_atoms_per_mol) the reference stops with a
 broadcast ValueError (it hands `_calc_rsq(..., num_of_ids=0)` rows of [id, x, y, z]:
 residence_time.py:96-101, rdf_cn.py:43); here that mode works and selects atoms by their LAMMPS type.
-`Displacement` (residence_time.py:203-254, unfinished upstream) is not provided.
+
+`Displacement` (residence_time.py:211-254): same constructor arguments and defaults, but the reference's `calc_dist`
+is unfinished — it collects the wrapped x y z of the chosen atom types per frame, prints them and returns nothing; a
+commented-out sketch groups the frames into windows of one residence time. Deliberate difference: here `calc_dist`
+finishes that sketch — the distance every atom of a type travels over one residence time of its shell, over
+consecutive (or all) time origins — and `calc_van_hove` gives the same distribution at any lags, G_s(r, t), with the
+non-Gaussian parameter.
+  GPU (`mdhip_displacement_hist`): image counts of the wrapped coordinates, the displacement of every (origin, atom)
+      window, its histogram and the sums of r, r^2, r^4.
+  Host: parsing, selection of the atoms by type, lag rounding, normalisation and the CSV files.
 """
 
+import math
 import os
 
 import numpy as np
@@ -25,6 +35,7 @@ from scipy.optimize import curve_fit
 from scipy.special import gamma
 
 from .. import backend
+from .. import io as mio
 from ..structural.rdf_cn import _calc_atom_type, _load_frames
 
 VERBOSE = False
@@ -149,3 +160,156 @@ class ResidenceTime:
         if _is_writer():
             fig.savefig(self.working_dir + f"/{col}_fit.png", bbox_inches="tight", pad_inches=0.1)
         plt.close()
+
+
+class Displacement:
+    def __init__(self, atom_types, residence_time, filename, dt=1, save_mode=True, working_dir=None, bin_size=0.1,
+                 r_max=None, overlap=False, coords="wrapped"):
+        """
+        atom_types: LAMMPS types to follow; residence_time: {type: time in ps} (the "r (ps)" row of
+        ResidenceTime.fit_auto_correlation's table); filename: dump file or '*' pattern; dt: timestep in fs.
+        bin_size, r_max: bins of the distance histograms, in the dump's length unit (r_max=None: half the smallest box
+        edge of the trajectory); overlap: False = consecutive windows (origins one lag apart, the reference's
+        pd.Grouper sketch), True = every frame is an origin.
+        coords="wrapped" reads `id type x y z` as the reference does and rebuilds the periodic image counts on the
+        GPU: only meaningful when no atom moves more than half a box edge between consecutive frames.
+        coords="unwrapped" reads `xu yu zu`. Triclinic boxes are not supported. The dumps are read on first use.
+        """
+        if coords not in ("wrapped", "unwrapped"):
+            raise ValueError('coords must be "wrapped" or "unwrapped"')
+        self.atom_types = atom_types
+        self.residence_time = residence_time
+        self.filename = filename
+        self.dt = dt * 10 ** -3  # input dt in fs (residence_time.py:224)
+        self.save_mode = save_mode
+        self.working_dir = working_dir or os.getcwd()
+        self.bin_size = bin_size
+        self.r_max = r_max
+        self.overlap = overlap
+        self.coords = coords
+        self.dist_df = None
+        self.hist_df = None
+        self._traj = None
+
+    def _load(self):
+        """(r [F,3,E] the atoms of the requested types, grouped by type in the order of atom_types, ids ascending
+        inside a type; box [F,3]; group_off [T+1]; frame spacing in ps)."""
+        if self._traj is not None:
+            return self._traj
+        xyz_cols = ["x", "y", "z"] if self.coords == "wrapped" else ["xu", "yu", "zu"]
+        steps, boxes, planes = [], [], []
+        ids = types = sel = None
+        for ts, bounds, lengths, _, pl in mio.iter_native_frames(self.filename, ["id", "type"] + xyz_cols,
+                                                                 sort_by="id"):
+            b = np.asarray(bounds, dtype=np.float64)
+            ext = b[:, 1] - b[:, 0]
+            if np.any(np.abs(np.asarray(lengths, dtype=np.float64) - ext) > 1e-12 * np.abs(ext)):
+                raise ValueError("triclinic boxes are not supported")
+            if ids is None:
+                ids, types = pl[0].copy(), pl[1].copy()
+                groups = [np.flatnonzero(types == t) for t in self.atom_types]
+                group_off = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int64)
+                sel = np.concatenate(groups).astype(np.int64) if groups else np.zeros(0, dtype=np.int64)
+            elif pl.shape[1] != len(ids) or not np.array_equal(pl[0], ids) or not np.array_equal(pl[1], types):
+                raise ValueError("every frame must hold the same atom ids with the same types")
+            steps.append(int(ts))
+            boxes.append(ext)
+            planes.append(pl[2:5][:, sel])
+        if len(steps) < 2:
+            raise ValueError("a displacement needs at least two frames")
+        d_step = np.diff(np.asarray(steps, dtype=np.int64))
+        if d_step[0] <= 0 or np.any(d_step != d_step[0]):
+            raise ValueError("the frames must be uniformly spaced in time")
+        r = np.ascontiguousarray(np.stack(planes), dtype=np.float64)
+        self._traj = (r, np.ascontiguousarray(np.stack(boxes)), group_off, float(d_step[0]) * self.dt)
+        return self._traj
+
+    @staticmethod
+    def _lag_frames(tau, delta):
+        return max(1, int(math.floor(tau / delta + 0.5)))
+
+    def _bins(self, box):
+        r_max = 0.5 * float(box.min()) if self.r_max is None else float(self.r_max)
+        return max(1, int(math.ceil(r_max / self.bin_size)))
+
+    def _run(self, r, box, group_off, jobs, n_bins):
+        return backend.displacement_hist(r, box if self.coords == "wrapped" else None, group_off, jobs,
+                                         self.bin_size, n_bins)
+
+    @staticmethod
+    def _alpha2(moments, windows):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m2, m4 = moments[:, 1] / windows, moments[:, 2] / windows
+            return 3.0 * m4 / (5.0 * (m2 * m2)) - 1.0
+
+    def calc_dist(self):
+        """Distance travelled by the atoms of every type during one residence time of that type: a row per type in
+        `dist_df` (returned), the distance distributions (probability densities over r) in `hist_df`."""
+        r, box, group_off, delta = self._load()
+        n_frames = r.shape[0]
+        lags = []
+        for t in self.atom_types:
+            k = self._lag_frames(self.residence_time[t], delta)
+            if k > n_frames - 1:
+                raise ValueError("the residence time of type %s (%g ps = %d frames) is longer than the trajectory "
+                                 "(%d frames)" % (t, self.residence_time[t], k, n_frames))
+            lags.append(k)
+        jobs = [(g, k, 1 if self.overlap else k) for g, k in enumerate(lags)]
+        n_bins = self._bins(box)
+        hist, overflow, windows, moments, _ = self._run(r, box, group_off, jobs, n_bins)
+        w = windows.astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.dist_df = pd.DataFrame({
+                "type": list(self.atom_types),
+                "residence time (ps)": [self.residence_time[t] for t in self.atom_types],
+                "lag (frames)": lags,
+                "windows": windows.astype(np.int64),
+                "mean distance": moments[:, 0] / w,
+                "rms distance": np.sqrt(moments[:, 1] / w),
+                "alpha2": self._alpha2(moments, w),
+                "beyond r_max": overflow.astype(np.int64),
+            })
+            dist = {"r": (np.arange(n_bins) + 0.5) * self.bin_size}
+            for g, t in enumerate(self.atom_types):
+                dist[t] = hist[g] / (w[g] * self.bin_size)
+        self.hist_df = pd.DataFrame(dist)
+        if self.save_mode and _is_writer():
+            self.dist_df.to_csv(self.working_dir + "/displacement.csv")
+            self.hist_df.to_csv(self.working_dir + "/displacement_distribution.csv")
+        return self.dist_df
+
+    def calc_van_hove(self, times):
+        """Self part of the van Hove function at the lags `times` (ps; rounded to frames, duplicates dropped), every
+        frame an origin: ({type: DataFrame of r and G_s(r, t) per lag time as a probability density over r},
+        DataFrame of the non-Gaussian parameter alpha2 = 3 <r^4> / (5 <r^2>^2) - 1 per lag time and type)."""
+        r, box, group_off, delta = self._load()
+        n_frames = r.shape[0]
+        lags = []
+        for t in times:
+            k = self._lag_frames(t, delta)
+            if k > n_frames - 1:
+                raise ValueError("the time %g ps (%d frames) is longer than the trajectory (%d frames)"
+                                 % (t, k, n_frames))
+            if k not in lags:
+                lags.append(k)
+        lag_ps = [k * delta for k in lags]
+        jobs = [(g, k, 1) for g in range(len(self.atom_types)) for k in lags]
+        n_bins = self._bins(box)
+        hist, _, windows, moments, _ = self._run(r, box, group_off, jobs, n_bins)
+        w = windows.astype(np.float64)
+        a2 = self._alpha2(moments, w)
+        gs, alpha2 = {}, {"Time (ps)": lag_ps}
+        n = len(lags)
+        for g, t in enumerate(self.atom_types):
+            cols = {"r": (np.arange(n_bins) + 0.5) * self.bin_size}
+            with np.errstate(invalid="ignore", divide="ignore"):
+                for i, tp in enumerate(lag_ps):
+                    cols[tp] = hist[g * n + i] / (w[g * n + i] * self.bin_size)
+            gs[t] = pd.DataFrame(cols)
+            alpha2[t] = a2[g * n:(g + 1) * n]
+        alpha2 = pd.DataFrame(alpha2)
+        if self.save_mode and _is_writer():
+            for t, df in gs.items():
+                df.to_csv(self.working_dir + "/van_hove_%s.csv" % t)
+            alpha2.to_csv(self.working_dir + "/alpha2.csv")
+        return gs, alpha2
