@@ -75,6 +75,20 @@ int mdhip_set_stream(mdhip_ctx *ctx, void *hip_stream);
  * asynchronous path does not take (frames in pageable host memory, class passes, the edge-table kernels) are
  * handled by completing that part of the work before the call returns: correct, just not overlapped.
  * A synchronous call completes everything issued before it first. mdhip_destroy completes what is still in flight.
+ *
+ * Two pair calls on the device at once. The context owns a second compute stream with a second set of every buffer a
+ * pair call writes (sorted records, boxes, lists, slices, row sums, flag words, results, host-frame staging).
+ * Consecutive asynchronous atom-atom pair calls (mdhip_rdf_atomic*_async, mdhip_cn_atomic_async,
+ * mdhip_rdf_cn_atomic_async) alternate between the two streams, each call's whole chain in order on its own: the
+ * pre-pass of call k + 1 runs while the sweep of call k empties out, and the blocks of sweep k + 1 move in as those of
+ * sweep k retire. Results do not change (integer sums). The rule for memory: a call overlaps only when its frames are
+ * ONE batch of the pair path (the batches are bounded by ~2 GiB of workspace each, so the second set costs at most
+ * that much again) AND two sets of what that batch needs fit the free device memory (asked for whenever a call is
+ * larger than any before it). Otherwise — a call of several batches keeps its full-size batches — it runs
+ * un-overlapped: alone, behind everything issued before it, as every other kind of call does (ordered by events,
+ * without a host wait). So do all calls while the context launches on a caller's stream (mdhip_set_stream): their
+ * order against the other work of that stream is the caller's. Growing a buffer waits for the calls of that buffer's
+ * own stream only.
  */
 /* Completes every call in flight, then waits for the stream. Returns the first error among them, 0 if none. */
 int mdhip_sync(mdhip_ctx *ctx);
@@ -103,8 +117,10 @@ int mdhip_ticket_stats(mdhip_ctx *ctx, long long ticket, double *kernel_ms, doub
 int mdhip_ticket_status(mdhip_ctx *ctx, long long ticket, int *n_fallbacks);
 /* Slow-path repeats (see mdhip_ticket_status) since the context was created. */
 long long mdhip_fallbacks(mdhip_ctx *ctx);
-/* Device time (ms, hipEvent pair on the launch stream) of the dominant kernel of the last call,
- * and the number of times that kernel was launched by that call. */
+/* Device time (ms, hipEvent pair on the call's launch stream) of the dominant kernel of the last call,
+ * and the number of times that kernel was launched by that call. Each call's time is taken from its own events:
+ * launches of two pair calls that overlap share the machine, so the per-call times of a pipeline may add up to more
+ * than the wall time it took. */
 double mdhip_last_kernel_ms(mdhip_ctx *ctx, int *n_launches);
 /* Device time (ms) of the preparation kernels of the last call that are not part of the dominant kernel
  * (the spatial sort / tile lists of the culled pair path); 0 when there were none. */

@@ -58,7 +58,8 @@ enum WsSlot {
     WS_OUT2,       // second / third device result of a chained call (mdhip_green_kubo: running integrals, their mean)
     WS_OUT3,
     WS_SCAN,       // one-pass scan (scan.hip): block totals | flags | ticket counter, kept from call to call
-    WS_XYZ_I2,     // second staging buffer of host-resident coordinates (asynchronous pair calls alternate between the two)
+    WS_XYZ_I2,     // second staging buffer of host-resident coordinates (asynchronous pair calls that stay on one
+                   // lane alternate between the two; calls that alternate between the lanes use each lane's first)
     WS_COUNT
 };
 
@@ -87,7 +88,8 @@ struct CallStats {
     int fallbacks = 0;     // slow-path repeats the call took (the staged full-lag kernel's stalled ring, a guard re-run)
 };
 
-// One invocation of an entry point. Everything it enqueues goes to the context's stream; what is left to do on the
+// One invocation of an entry point. Everything it enqueues goes to the stream of ITS LANE (mdhip_ctx::lane_stream: the
+// context's stream, or — every other asynchronous pair-histogram call — the second compute stream); what is left to do on the
 // host once that work has run (timer read-out, folding row sums, copying out of pinned staging, a rare re-run) is a list
 // of completion steps. A synchronous call completes before it returns; an asynchronous one (the *_async entry points)
 // returns with its work queued and completes inside mdhip_sync / mdhip_wait — in issue order.
@@ -101,13 +103,34 @@ struct mdhip_call {
     hipEvent_t done = nullptr;
     CallStats stats;                           // kernel name / launches as set while the call was issued
     bool inner = false;                        // made from inside another call or from a completion step
+    int lane = 0;                              // the lane the call was issued on (its stream, its workspace set)
+    bool top = false;                          // a top-level call: it chose the lane, and gives it back when it has been issued
+    bool exclusive = true;                     // nothing of another call may run beside it (every call but an overlapped pair call)
     CallStats outer;                           // ... the registers of the call around it, as they were
 };
 
 struct mdhip_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;  // the stream of the call being issued: lane_stream[lane]
+    // Lanes: two compute streams, each with a workspace set of its own (ws / ws2), so that two pair-histogram calls can be
+    // on the device at once — the pre-pass of call k + 1 runs while the sweep of call k drains, and the blocks of sweep
+    // k + 1 move into the CUs as those of sweep k retire. Lane 0 is the context's stream (its own, or the caller's:
+    // mdhip_set_stream); lane 1 is created on first use. Consecutive OVERLAPPED calls alternate between the lanes: the
+    // asynchronous atom-atom pair calls whose frames are one workspace-bounded batch (pair_overlap_ok, pair_hist.hip),
+    // while the context launches on its own stream. Every other call is EXCLUSIVE: it runs on lane 0, ordered behind
+    // everything issued before it on either lane, and everything issued after it is ordered behind it (events, no host
+    // wait). A call's whole chain stays in order on its lane's stream; a lane's buffers belong to the calls of that lane,
+    // in stream order — mdhip_ws grows a buffer behind a wait for that lane's stream alone.
+    hipStream_t lane_stream[2] = {nullptr, nullptr};
+    int lane = 0;                 // lane of the call being issued / completed
+    int pair_flip = 0;            // lane of the next overlapped call
+    bool want_overlap = false;    // set with want_async by an entry point whose call may overlap (AsyncCall)
+    hipEvent_t lane1_ev = nullptr;  // behind the last call issued on lane 1
+    hipEvent_t excl_ev = nullptr;   // behind the last exclusive asynchronous call (lane 0)
+    bool lane1_busy = false;      // lane 1 has been given work since everything in flight was last completed
+    bool excl_busy = false;       // ... an exclusive asynchronous call has been issued since then
+    double lane_fit_bytes = 0.0;  // largest workspace need of a call for which two sets were found to fit (pair_overlap_ok)
     // calls (see mdhip_call): the one being issued, those issued asynchronously and not yet completed, and the pools
     mdhip_call *cur = nullptr;
     std::deque<mdhip_call *> inflight;
@@ -137,11 +160,12 @@ struct mdhip_ctx {
     hipStream_t copy_stream = nullptr;
     hipEvent_t copy_ev[2] = {nullptr, nullptr};
     // asynchronous pair calls on host-resident frames: the whole trajectory of call k + 1 is copied (copy stream) into
-    // the staging buffer call k does NOT use, while call k's kernels run; stage_ev[b]: recorded on the launch stream
-    // behind the last kernels that read buffer b
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};
-    bool stage_used[2] = {false, false};
-    int stage_flip = 0;
+    // the staging buffer call k does NOT use, while call k's kernels run — the other lane's buffer when the calls
+    // alternate between the lanes, else the other one of the lane's two; stage_ev[lane][b]: recorded on the lane's
+    // stream behind the last kernels that read buffer b of that lane
+    hipEvent_t stage_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    bool stage_used[2][2] = {{false, false}, {false, false}};
+    int stage_flip[2] = {0, 0};
     int opt_rdf_relblock = 0;  // (retired: the f32 records are relative to their whole tile's centre; accepted, ignored)
     int opt_h2d_overlap = 1;  // 1 (default): overlapped staging of host-resident pair inputs, 0: one copy up front (A/B)
     int opt_small_copy = 1;   // 1 (default): copies of up to MD_SMALL_COPY_MAX bytes between page-locked host memory and the
@@ -160,7 +184,8 @@ struct mdhip_ctx {
     int h2d_chunk_next[2] = {0, 0};
     struct CopyPool *copy_pool = nullptr;  // helper threads of mdhip_h2d_any (created on first use)
     std::string err;
-    DevBuf ws[WS_COUNT];
+    DevBuf ws[WS_COUNT];   // lane 0's workspace set
+    DevBuf ws2[WS_COUNT];  // lane 1's (only what an overlapped pair call asks for is ever allocated)
     double last_ms = 0.0;
     double last_aux_ms = 0.0;  // device time of the preparation kernels of the last call (e.g. spatial sort)
     int last_launches = 0;
@@ -291,7 +316,29 @@ int mdhip_fft_xcorr(mdhip_ctx *ctx, const double *d_a, const double *d_b, long l
 int mdhip_cumtrapz_enqueue(mdhip_ctx *ctx, int64_t n, int n_series, const double *d_y, double dx, int lead, double *d_out,
                            double post_scale);
 
-void *mdhip_ws(mdhip_ctx *ctx, int slot, size_t bytes);  // nullptr on failure (error set)
+void *mdhip_ws(mdhip_ctx *ctx, int slot, size_t bytes);  // of the current lane's set; nullptr on failure (error set)
+// bytes that slot holds now, in the same set
+static inline size_t mdhip_ws_cap(const mdhip_ctx *ctx, int slot) { return (ctx->lane ? ctx->ws2 : ctx->ws)[slot].cap; }
+// Room for the other lane. A CU that holds its full share of the persistent sweep's blocks takes no
+// workgroup of another queue, however small, and the one-block-per-frame sort needs a CU's whole LDS — so beside a full
+// resident grid the next call's pre-pass starts only when whole CUs have emptied. A call issued beside another one
+// therefore (a) leaves LANE_FREE_BLOCKS slots of the resident grid unused and (b) sorts with the multi-block kernels,
+// whose small blocks fit into such slots: its pre-pass runs under the sweep before it, and its own sweep leaves room
+// for the pre-pass after it. Measured at C2 (profiles/ab_pair_overlap.txt): 4 or 8 slots per XCD, little between them.
+constexpr int LANE_FREE_BLOCKS = 64;
+// the top-level call around the one being issued (itself, when it is one)
+static inline const mdhip_call *mdhip_top_call(const mdhip_ctx *ctx)
+{
+    const mdhip_call *c = ctx->cur;
+    while (c && c->parent) c = c->parent;
+    return c;
+}
+// the call being issued runs beside another pair call that is still in flight
+static inline bool mdhip_beside_another(const mdhip_ctx *ctx)
+{
+    const mdhip_call *c = mdhip_top_call(ctx);
+    return c && !c->exclusive && !ctx->inflight.empty();
+}
 // pinned host memory that belongs to the call being issued (ctx->cur) until it completes; nullptr on failure (error set)
 void *mdhip_pin(mdhip_ctx *ctx, size_t bytes);
 hipEvent_t mdhip_timer_event(mdhip_ctx *ctx);  // a timing event that belongs to the call being issued; nullptr on failure
@@ -356,10 +403,15 @@ struct CallScope {
 
 // What an *_async entry point does before it runs the body it shares with its synchronous twin: the next top-level
 // call of this context is issued asynchronously. Cleared on the way out whatever happened.
+// `overlap`: the call may run beside the asynchronous pair call before it (see mdhip_ctx::lane_stream).
 struct AsyncCall {
     mdhip_ctx *ctx;
-    explicit AsyncCall(mdhip_ctx *c) : ctx(c) { c->want_async = true; }
-    ~AsyncCall() { ctx->want_async = false; }
+    explicit AsyncCall(mdhip_ctx *c, bool overlap = false) : ctx(c)
+    {
+        c->want_async = true;
+        c->want_overlap = overlap;
+    }
+    ~AsyncCall() { ctx->want_async = ctx->want_overlap = false; }
 };
 
 // msd_fft.hip: full-lag MSD through the autocorrelation theorem. d_r device [F][3][E]. Enqueues the transforms and

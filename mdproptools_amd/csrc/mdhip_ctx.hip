@@ -29,11 +29,11 @@ int mdhip_fail(mdhip_ctx *ctx, int code, const char *fmt, ...)
 
 void *mdhip_ws(mdhip_ctx *ctx, int slot, size_t bytes)
 {
-    DevBuf &b = ctx->ws[slot];
+    DevBuf &b = (ctx->lane ? ctx->ws2 : ctx->ws)[slot];
     if (bytes == 0) bytes = 16;
     if (b.cap >= bytes) return b.p;
     if (b.p) {
-        // the buffer may still be in use by queued work
+        // the buffer may still be in use by queued work — of this lane: the other lane's calls have buffers of their own
         (void)hipStreamSynchronize(ctx->stream);
         (void)hipFree(b.p);
         b.p = nullptr;
@@ -155,11 +155,54 @@ hipError_t mdhip_stream_wait(mdhip_ctx *ctx)
     return rc;
 }
 
+static inline void set_lane(mdhip_ctx *ctx, int lane)
+{
+    ctx->lane = lane;
+    ctx->stream = ctx->lane_stream[lane];
+}
+
+// The second compute stream and the two ordering events exist (created on first use).
+static bool lane1_ready(mdhip_ctx *ctx)
+{
+    if (ctx->lane_stream[1]) return true;
+    hipStream_t st = nullptr;
+    hipEvent_t e1 = nullptr, e2 = nullptr;
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&e1, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&e2, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        if (e1) (void)hipEventDestroy(e1);
+        if (st) (void)hipStreamDestroy(st);
+        return false;
+    }
+    ctx->lane_stream[1] = st;
+    ctx->lane1_ev = e1;
+    ctx->excl_ev = e2;
+    return true;
+}
+
+// `stream` runs nothing more before `ev` has fired (a host wait if the runtime refuses the dependency)
+static void order_behind(hipStream_t stream, hipEvent_t ev)
+{
+    if (hipStreamWaitEvent(stream, ev, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipEventSynchronize(ev);
+    }
+}
+
 mdhip_call *mdhip_call_begin(mdhip_ctx *ctx)
 {
     const bool top = ctx->cur == nullptr && ctx->completing == 0;
     const bool async = ctx->want_async && top;
+    // beside the call before it: an asynchronous pair call that asked for it, while the context launches on its own stream
+    // (work on a caller's stream is ordered against that stream's other work: it all stays there)
+    const bool fresh = ctx->lane_stream[1] == nullptr;
+    const bool overlap = async && ctx->want_overlap && ctx->lane_stream[0] == ctx->own_stream && lane1_ready(ctx);
+    // (a second stream that has just come into being: behind whatever exclusive call is still in flight)
+    if (overlap && fresh && !ctx->inflight.empty() && hipEventRecord(ctx->excl_ev, ctx->lane_stream[0]) == hipSuccess)
+        ctx->excl_busy = true;
     ctx->want_async = false;
+    ctx->want_overlap = false;
     if (top && !async && !ctx->inflight.empty()) {
         // a synchronous call drains what is in flight BEFORE it issues anything: its own staging (copy stream, the
         // batch-by-batch path of host-resident frames) is not ordered behind the kernels of the calls before it
@@ -169,6 +212,21 @@ mdhip_call *mdhip_call_begin(mdhip_ctx *ctx)
     mdhip_call *c = new mdhip_call();
     c->parent = ctx->cur;
     c->async = async;
+    c->top = top;
+    if (top) {
+        c->exclusive = !overlap;
+        int lane = 0;
+        if (overlap) {
+            lane = ctx->pair_flip;
+            ctx->pair_flip ^= 1;
+        }
+        set_lane(ctx, lane);
+        // ordering between the lanes, only where something is shared: an exclusive call behind what lane 1 still runs,
+        // lane 1 behind the last exclusive call (lane 0 is behind it in stream order)
+        if (c->exclusive && ctx->lane1_busy) order_behind(ctx->stream, ctx->lane1_ev);
+        if (!c->exclusive && lane == 1 && ctx->excl_busy) order_behind(ctx->stream, ctx->excl_ev);
+    }
+    c->lane = ctx->lane;
     if (!c->parent && ctx->completing == 0) {
         c->stats.ticket = ++ctx->tickets;
     } else {
@@ -199,6 +257,9 @@ static void release_call(mdhip_ctx *ctx, mdhip_call *c)
 static int complete_call(mdhip_ctx *ctx, mdhip_call *c)
 {
     int rc = MDHIP_OK;
+    // the steps (a re-run among them) work on the call's own lane: its stream, its buffers
+    const int lane_was = ctx->lane;
+    set_lane(ctx, c->lane);
     hipError_t e = c->done ? wait_event(ctx, c->done) : mdhip_stream_wait(ctx);
     if (e != hipSuccess) rc = mdhip_fail(ctx, MDHIP_EHIP, "waiting for a call's device work failed: %s", hipGetErrorString(e));
     // the registers the steps work on start from what the call set while it was issued (a part of the work that
@@ -238,6 +299,7 @@ static int complete_call(mdhip_ctx *ctx, mdhip_call *c)
         if (ctx->history.size() > 64) ctx->history.pop_back();
     }
     release_call(ctx, c);
+    set_lane(ctx, lane_was);
     return rc;
 }
 
@@ -256,6 +318,8 @@ int mdhip_complete_inflight(mdhip_ctx *ctx, size_t keep)
             }
         }
     }
+    // nothing in flight: both lanes have run dry (a lane's work belongs to calls, and a call's `done` is behind all of it)
+    if (ctx->inflight.empty()) ctx->lane1_busy = ctx->excl_busy = false;
     return first;
 }
 
@@ -273,6 +337,12 @@ int mdhip_call_end(mdhip_ctx *ctx, mdhip_call *c)
         (void)hipGetLastError();
         ctx->done_free.push_back(c->done);
         c->done = nullptr;  // complete_call then drains the stream instead
+    }
+    if (c->top) {
+        if (c->lane == 1 && hipEventRecord(ctx->lane1_ev, ctx->stream) == hipSuccess) ctx->lane1_busy = true;
+        if (c->async && c->exclusive && ctx->lane_stream[1] && hipEventRecord(ctx->excl_ev, ctx->stream) == hipSuccess)
+            ctx->excl_busy = true;
+        set_lane(ctx, 0);  // (the call has been issued: the context is back on its own stream)
     }
     if (c->async) {
         ctx->inflight.push_back(c);
@@ -294,6 +364,7 @@ void mdhip_call_abandon(mdhip_ctx *ctx, mdhip_call *c)
     if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
     (void)hipGetLastError();
     ctx->cur = c->parent;
+    if (c->top) set_lane(ctx, 0);
     release_call(ctx, c);
 }
 
@@ -369,8 +440,8 @@ int mdhip_deliver_to_device(mdhip_ctx *ctx, void *dst_dev, const void *src_host,
         MD_HIP(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
         MD_HIP(hipEventCreateWithFlags(&ctx->copy_ev[0], hipEventDisableTiming));
         MD_HIP(hipEventCreateWithFlags(&ctx->copy_ev[1], hipEventDisableTiming));
-        MD_HIP(hipEventCreateWithFlags(&ctx->stage_ev[0], hipEventDisableTiming));
-        MD_HIP(hipEventCreateWithFlags(&ctx->stage_ev[1], hipEventDisableTiming));
+        for (auto &lane_ev : ctx->stage_ev)
+            for (auto &e : lane_ev) MD_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     // a staging block of its own for the length of the copy (this runs outside any call's issue phase)
     int best = -1;
@@ -571,7 +642,7 @@ int mdhip_create(mdhip_ctx **out, int device)
         delete ctx;
         return mdhip_fail(nullptr, MDHIP_EHIP, "mdhip_create: stream creation failed");
     }
-    ctx->stream = ctx->own_stream;
+    ctx->stream = ctx->lane_stream[0] = ctx->own_stream;
     *out = ctx;
     return MDHIP_OK;
 }
@@ -582,7 +653,15 @@ void mdhip_destroy(mdhip_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)mdhip_complete_inflight(ctx, 0);  // (results of calls nobody waited for still reach their destinations)
     (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->lane_stream[1]) {
+        (void)hipStreamSynchronize(ctx->lane_stream[1]);
+        (void)hipStreamDestroy(ctx->lane_stream[1]);
+        (void)hipEventDestroy(ctx->lane1_ev);
+        (void)hipEventDestroy(ctx->excl_ev);
+    }
     for (auto &b : ctx->ws)
+        if (b.p) (void)hipFree(b.p);
+    for (auto &b : ctx->ws2)
         if (b.p) (void)hipFree(b.p);
     for (auto &b : ctx->pin_free)
         if (b.p) (void)hipHostFree(b.p);
@@ -602,8 +681,9 @@ void mdhip_destroy(mdhip_ctx *ctx)
     copy_pool_destroy(ctx);
     for (auto &e : ctx->copy_ev)
         if (e) (void)hipEventDestroy(e);
-    for (auto &e : ctx->stage_ev)
-        if (e) (void)hipEventDestroy(e);
+    for (auto &lane_ev : ctx->stage_ev)
+        for (auto &e : lane_ev)
+            if (e) (void)hipEventDestroy(e);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
 }
@@ -635,7 +715,8 @@ int mdhip_set_stream(mdhip_ctx *ctx, void *hip_stream)
     MD_HIP(hipSetDevice(ctx->device));
     const int rc = mdhip_complete_inflight(ctx, 0);
     MD_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
+    // (on a caller's stream the pair calls do not alternate between the lanes: see mdhip_call_begin)
+    ctx->stream = ctx->lane_stream[0] = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
     return take_deferred(ctx, rc);
 }
 

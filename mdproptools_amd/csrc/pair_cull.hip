@@ -588,8 +588,9 @@ int cull_prepare_set(mdhip_ctx *ctx, int64_t F, const double *d_x, const int *d_
     // one block per frame with the cell counters in LDS when there are frames enough to fill the chip (or the
     // frames are small); the multi-block path with global counters otherwise
     const size_t sort_lds = SORT_CELL_WORDS * 4 + 3 * 16 * 8;
-    const bool lds_sort = ctx->opt_rdf_sort != 0 && sort_lds + 8192 <= ctx->lds_max && N <= 262144 &&
-                          (ctx->opt_rdf_sort == 1 || F >= ctx->cu_count / 4 || N <= 16384);
+    // (beside another call's sweep the one-block sort would wait for whole CUs to empty: ctx.h, LANE_FREE_BLOCKS)
+    const bool lds_sort = ctx->opt_rdf_sort != 0 && !mdhip_beside_another(ctx) && sort_lds + 8192 <= ctx->lds_max &&
+                          N <= 262144 && (ctx->opt_rdf_sort == 1 || F >= ctx->cu_count / 4 || N <= 16384);
     const int sort_items = (int)((N + SORT_THREADS - 1) / SORT_THREADS);
     if (lds_sort && sort_items <= 12 && ctx->opt_rdf_sort != 3) {
         // (frames of up to 12288 atoms: every atom read once, kept in registers — cull_sort_reg_kernel)

@@ -422,7 +422,9 @@ static int launch_pass(mdhip_ctx *ctx, const Batch &b, PairArgs a, Pass &ps)
         const long long block_items = ((long long)pl.nTi * 4 * pl.jsplit + wpb - 1) / wpb;
         a.fpb = 1;
         if (pl.persist) {
-            launch_grid = std::min(capacity, F * block_items + 8);
+            // (beside another call: room for the pre-pass of the call after this one, see LANE_FREE_BLOCKS)
+            const long long room = mdhip_beside_another(ctx) && capacity >= 8LL * LANE_FREE_BLOCKS ? LANE_FREE_BLOCKS : 0;
+            launch_grid = std::min(capacity - room, F * block_items + 8);
             launch_grid = (launch_grid + 7) / 8 * 8;
             // (the work counters: the first pass finds them empty, d_misc was zeroed whole at the top of the batch)
             if (ps.pass > 0) MD_HIP(hipMemsetAsync(b.d_misc + 4, 0, 32, ctx->stream));
@@ -712,6 +714,32 @@ static std::vector<std::pair<int64_t, int64_t>> batch_parts(const mdhip_ctx *ctx
     return parts;
 }
 
+// Whether an asynchronous atom-atom call may be on the device BESIDE the pair call issued before it — on the other lane,
+// with that lane's own set of everything the pre-pass writes, the sweep reads and the call returns (ctx.h). The rule
+// (include/mdhip.h): its frames are ONE batch of batch_parts (staged = false: the deferred path of an asynchronous call
+// stages host-resident frames whole), and two sets of what such a batch asks for fit the device. A call of several
+// batches fills the ~2 GiB its batches are bounded by, completes batch by batch inside the entry point anyway, and a
+// second set must not make its batches smaller: it runs alone on the context's stream, as every other call does — and
+// so does a call beside whose set a second one finds no room. The need is batch_parts' own estimate plus the staging
+// buffer of host-resident frames; the free memory is asked for only when a call is larger than any checked before.
+static bool pair_overlap_ok(mdhip_ctx *ctx, int64_t F, int64_t n, int on_device)
+{
+    if (F < 1 || n < 2 || F >= (1LL << 31) || n >= (1LL << 31)) return false;
+    if (batch_parts(ctx, F, n, false).size() != 1) return false;
+    const int64_t nT = (n + TILE - 1) / TILE;
+    const double need = (54.0 * (double)n + 4.0 * MORTON_CELLS + 2.0 * (double)nT * (double)nT + 1024.0) * (double)F +
+                        (on_device ? 0.0 : 24.0 * (double)n * (double)F);
+    if (need <= ctx->lane_fit_bytes) return true;
+    size_t free_b = 0, total_b = 0;
+    if (hipSetDevice(ctx->device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    if ((double)free_b < 2.5 * need) return false;  // (both sets may still have to grow to this size, with their slack)
+    ctx->lane_fit_bytes = need;
+    return true;
+}
+
 static int pair_hist_run_range(mdhip_ctx *ctx, const PairProblem &p, int64_t f0, int64_t n, std::vector<uint64_t> &H,
                                uint64_t *overflow, std::vector<uint64_t> *Hsplit, CallScope *defer = nullptr,
                                bool *redo = nullptr);
@@ -999,25 +1027,33 @@ int run_job(mdhip_ctx *ctx, const RelJob &j, std::vector<uint64_t> &H, std::vect
         MD_HIP(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
         MD_HIP(hipEventCreateWithFlags(&ctx->copy_ev[0], hipEventDisableTiming));
         MD_HIP(hipEventCreateWithFlags(&ctx->copy_ev[1], hipEventDisableTiming));
-        MD_HIP(hipEventCreateWithFlags(&ctx->stage_ev[0], hipEventDisableTiming));
-        MD_HIP(hipEventCreateWithFlags(&ctx->stage_ev[1], hipEventDisableTiming));
+        for (auto &lane_ev : ctx->stage_ev)
+            for (auto &e : lane_ev) MD_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     // An ASYNCHRONOUS atom-atom call on host-resident frames: the whole trajectory is copied on the copy stream into the
     // staging buffer the call before this one does not use — i.e. under that call's kernels — and the sweep then runs as
-    // on resident frames (one batch, its host half deferred). The caller's array is read until the call completes (the
-    // contract of the *_async entry points; a pageable source is staged by the runtime before hipMemcpyAsync returns).
+    // on resident frames (one batch, its host half deferred). Calls that alternate between the lanes are double-buffered
+    // by that alone (each lane's set has a WS_XYZ_I); calls that stay on one lane alternate between its two buffers. A
+    // buffer is written again behind the event of the last kernels that read it, on whichever lane they ran. The caller's
+    // array is read until the call completes (the contract of the *_async entry points; a pageable source is staged by the
+    // runtime before hipMemcpyAsync returns).
     int stage_buf = -1;
     if (ctx->completing > 0 && (!j.xi_dev || (!j.tri && !j.xj_dev)))
         MD_HIP(mdhip_stream_wait(ctx));  // a re-run from a completion step: the staging buffers may feed queued kernels
     if (overlap && !j.xi_dev && j.tri && defer != nullptr) {
-        stage_buf = ctx->stage_flip;
-        ctx->stage_flip ^= 1;
+        const int lane = ctx->lane;
+        if (mdhip_top_call(ctx)->exclusive) {  // (a call made from a completion step is its own top: exclusive)
+            stage_buf = ctx->stage_flip[lane];
+            ctx->stage_flip[lane] ^= 1;
+        } else {
+            stage_buf = 0;
+        }
         const size_t xb = (size_t)j.F * 3 * j.ni * 8;
         double *d_x = (double *)mdhip_ws(ctx, stage_buf ? WS_XYZ_I2 : WS_XYZ_I, xb);
         if (!d_x) return MDHIP_ENOMEM;
-        if (ctx->stage_used[stage_buf]) MD_HIP(hipStreamWaitEvent(ctx->copy_stream, ctx->stage_ev[stage_buf], 0));
+        if (ctx->stage_used[lane][stage_buf]) MD_HIP(hipStreamWaitEvent(ctx->copy_stream, ctx->stage_ev[lane][stage_buf], 0));
         {
-            const int rch = mdhip_h2d_any(ctx, d_x, j.xi, xb, ctx->copy_stream, stage_buf);
+            const int rch = mdhip_h2d_any(ctx, d_x, j.xi, xb, ctx->copy_stream, lane ^ stage_buf);
             if (rch) return rch;
         }
         MD_HIP(hipEventRecord(ctx->copy_ev[0], ctx->copy_stream));
@@ -1087,8 +1123,8 @@ int run_job(mdhip_ctx *ctx, const RelJob &j, std::vector<uint64_t> &H, std::vect
     }
     rc = pair_hist_run(ctx, p, H, overflow, defer, redo);
     if (stage_buf >= 0 && (rc == MDHIP_OK || rc == CN_UNFUSED)) {
-        MD_HIP(hipEventRecord(ctx->stage_ev[stage_buf], ctx->stream));  // behind the last kernels that read the buffer
-        ctx->stage_used[stage_buf] = true;
+        MD_HIP(hipEventRecord(ctx->stage_ev[ctx->lane][stage_buf], ctx->stream));  // behind the last kernels that read the buffer
+        ctx->stage_used[ctx->lane][stage_buf] = true;
     }
     return rc;
 }
@@ -1523,7 +1559,7 @@ int mdhip_rdf_atomic_async(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, co
                            int per_frame, uint64_t *hist_full, uint64_t *hist_part, uint64_t *overflow)
 {
     if (!ctx) return MDHIP_EINVAL;
-    AsyncCall mark(ctx);
+    AsyncCall mark(ctx, pair_overlap_ok(ctx, n_frames, n_atoms, on_device));
     return mdhip_rdf_atomic(ctx, n_frames, n_atoms, xyz, on_device, type, type_frame_stride, box, n_rel, rel, r_cut_sq,
                             bin_size, nbins, edges, per_frame, hist_full, hist_part, overflow);
 }
@@ -1534,7 +1570,7 @@ int mdhip_rdf_atomic_dev_async(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms
                                uint64_t *out_dev)
 {
     if (!ctx) return MDHIP_EINVAL;
-    AsyncCall mark(ctx);
+    AsyncCall mark(ctx, pair_overlap_ok(ctx, n_frames, n_atoms, on_device));
     return mdhip_rdf_atomic_dev(ctx, n_frames, n_atoms, xyz, on_device, type, type_frame_stride, box, n_rel, rel, r_cut_sq,
                                 bin_size, nbins, edges, out_dev);
 }
@@ -1546,7 +1582,7 @@ int mdhip_rdf_cn_atomic_async(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms,
                               uint64_t *overflow, uint64_t *cn)
 {
     if (!ctx) return MDHIP_EINVAL;
-    AsyncCall mark(ctx);
+    AsyncCall mark(ctx, pair_overlap_ok(ctx, n_frames, n_atoms, on_device));
     return mdhip_rdf_cn_atomic(ctx, n_frames, n_atoms, xyz, on_device, type, type_frame_stride, box, n_rel, rel, r_cut_sq,
                                bin_size, nbins, edges, cn_r_cut_sq, per_frame, hist_full, hist_part, overflow, cn);
 }
@@ -1556,7 +1592,7 @@ int mdhip_cn_atomic_async(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, con
                           const int32_t *rel, const double *r_cut_sq, int per_frame, uint64_t *cn, int cn_on_device)
 {
     if (!ctx) return MDHIP_EINVAL;
-    AsyncCall mark(ctx);
+    AsyncCall mark(ctx, pair_overlap_ok(ctx, n_frames, n_atoms, on_device));
     return cn_atomic_impl(ctx, n_frames, n_atoms, xyz, on_device, type, type_frame_stride, box, n_rel, rel, r_cut_sq,
                           per_frame, cn, cn_on_device ? 1 : 0);
 }

@@ -962,6 +962,25 @@ __device__ __forceinline__ bool work_loop_sane(const PairArgs &a, long long iter
     return false;
 }
 
+#ifdef PAIR_DRAIN_TRACE
+// The tool build of tools/drain_trace.py (never the library's): when a launch's blocks start, when each of their waves
+// runs dry and when the block flushes — per block [start | flush | dry time of wave 0 .. 15], in ticks of the 100 MHz
+// wall clock. How long the CUs empty out at the end of a sweep is read from these.
+constexpr int DRAIN_TRACE_BLOCKS = 4096, DRAIN_TRACE_WORDS = 18;
+__device__ unsigned long long g_drain_trace[DRAIN_TRACE_BLOCKS * DRAIN_TRACE_WORDS];
+extern "C" int mdhip_drain_trace(unsigned long long *out, int n_blocks)
+{
+    if (!out || n_blocks < 1 || n_blocks > DRAIN_TRACE_BLOCKS) return MDHIP_EINVAL;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_drain_trace), (size_t)n_blocks * DRAIN_TRACE_WORDS * 8) == hipSuccess
+               ? MDHIP_OK
+               : MDHIP_EHIP;
+}
+#define DRAIN_TRACE(word)                                                                                      \
+    if (bid < DRAIN_TRACE_BLOCKS && (threadIdx.x & 63) == 0) g_drain_trace[bid * DRAIN_TRACE_WORDS + (word)] = wall_clock64()
+#else
+#define DRAIN_TRACE(word)
+#endif
+
 // PERSIST = true (frame-summed output): the grid is one resident set of blocks; every WAVE draws items
 // (frame, tile, wave, list slice) from its XCD's counter — frames stay dealt to XCDs (f % 8) so a frame's
 // records live in one L2 — and the block flushes its LDS histograms once, when its four waves have run
@@ -1050,6 +1069,7 @@ pair_hist_sj_kernel(const PairArgs a)
             }
     }
     __syncthreads();  // tables ready; from here on the waves do not synchronise until the flush
+    if (tid == 0) DRAIN_TRACE(0);
 
     const int lane = tid & 63;
     int f_out = 0;
@@ -1103,8 +1123,10 @@ pair_hist_sj_kernel(const PairArgs a)
     // atomics on rows spread over HBM cost ~40 ps each: 10^7 of them per launch were 6 % of the kernel);
     // merge_slices_kernel adds the slices up afterwards ----
     (void)f_out;
+    DRAIN_TRACE(2 + (tid >> 6));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();
+    if (tid == 0) DRAIN_TRACE(1);
     if (tid == 0 && *s_guard > a.guard_tiles) atomicOr(a.overflow + 3, 1ull);
     unsigned *slice = a.slices + (size_t)bid * (size_t)hist_words;
     for (int w = tid; w < hist_words; w += BS) slice[w] = s_hist[w];

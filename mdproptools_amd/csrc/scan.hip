@@ -191,7 +191,7 @@ int mdhip_cumtrapz_enqueue(mdhip_ctx *ctx, int64_t n, int n_series, const double
     // double per series, alternating with the totals (a buffer that has to grow for more series is emptied again)
     const size_t n_carry = (size_t)std::max(n_series, 64);
     const size_t words = 2 * cap + 16 + 2 * n_carry;
-    const bool fresh = ctx->ws[WS_SCAN].cap < words * 8 || ctx->scan_capacity <= 0;
+    const bool fresh = mdhip_ws_cap(ctx, WS_SCAN) < words * 8 || ctx->scan_capacity <= 0;
     MD_WS(d_ws, double, WS_SCAN, words * 8);
     double *d_set[2] = {d_ws, d_ws + cap};
     unsigned *d_stall = reinterpret_cast<unsigned *>(d_ws + 2 * cap);
