@@ -741,6 +741,54 @@ int mdhip_displacement_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, con
                             uint64_t *hist, uint64_t *overflow, uint64_t *windows, double *moments,
                             uint64_t *crossings);
 
+/* ---- Einstein-Helfand conductivity (Conductivity.einstein / nernst; `pass` in the reference,
+ *      dynamical/conductivity.py:399-403) ---- */
+/*
+ * The charge-weighted collective displacement of every group, per frame:
+ *   P[g][x][t] = sum over the entities e of group g of c_e * (r[t][x][e] - r[0][x][e]),   c_e = weight[e] * scale
+ *   r          host|dev (r_on_device) [n_frames][3][n_ent] UNWRAPPED entity coordinates (molecule centres of mass)
+ *   weight     host [n_ent] (the charge, already in output units); scale: the coordinates' unit factor. c_e is formed
+ *              once on the host, one multiplication.
+ *   group_off  host int64 [n_groups+1] contiguous entity groups, 1 <= n_groups <= 16; empty groups give zeros
+ *   P          host|dev (P_on_device) [n_groups][3][n_frames], time-major: the input layout of mdhip_cross_msd
+ *   weighted_dev  NULL, or DEVICE [n_frames][3][n_ent] that receives c_e * (r[t] - r[0]) per entity (0 for an entity
+ *              of no group): fed to mdhip_lag_msd with scale 1 it yields the self part sum_e c_e^2 <|dr_e|^2> (total
+ *              column times the group size), so the Nernst-Einstein sum needs no weighting pass of its own
+ * Frame 0 is subtracted BEFORE the weighted sum: unwrapped coordinates of tens of angstrom summed over thousands of
+ * ions of both signs would otherwise cancel the digits the displacement lives in.
+ * Floating point: per entity one subtraction and one multiplication, unfused; per (frame, axis, group) 256 partial
+ * sums, partial i adding the entities i, i + 256, ... of the group in order, and a fixed tree over them
+ * (red[i] += red[i + w], w = 128 .. 1). The order depends on the group size alone; no floating-point atomics: every
+ * call gives the same bits. A NaN stays in its own group and axis. One read of the trajectory: HBM-bound.
+ * n_groups outside 1..16, n_frames < 1 or a group_off that does not ascend within [0, n_ent]: MDHIP_EINVAL before
+ * anything is written.
+ */
+int mdhip_collective_displacement(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const double *r, int r_on_device,
+                                  const double *weight, double scale, int n_groups, const int64_t *group_off,
+                                  double *P, int P_on_device, double *weighted_dev);
+
+/*
+ * The cross-displacement correlation of the collective series at every lag (the Einstein-Helfand sum):
+ *   out[k][a][b] = ( sum_{t=0}^{n-1-k} sum_x (P[a][x][t+k] - P[a][x][t]) * (P[b][x][t+k] - P[b][x][t]) ) / (n - k)
+ *   P          host|dev (P_on_device) [n_groups][3][n], 1 <= n_groups <= 16, 1 <= n < 2^29
+ *   max_lag    0 .. n-1
+ *   out        host|dev (out_on_device) [max_lag+1][n_groups][n_groups]; symmetric bit for bit (a <= b is computed and
+ *              mirrored)
+ *   abs_out    NULL, or the same shape and place as out: the same sum over |term|, term = one axis' product. It is the
+ *              scale of the rounding error: out is within (3 (n - k) + 2) * 2^-53 * abs_out of the exact sum over
+ *              the given P (plus one rounding of the division), whatever the order.
+ * Difference form throughout: subtract, then one fused multiply-add per term. A product of values is never formed,
+ * so a collective dipole that has wandered far from its start costs no digits (composing the sum from
+ * mdhip_xcorr results would). No floating-point atomics: the terms of a lag are added in an order fixed by n, max_lag,
+ * n_groups and the device's compute-unit count; results are bit-identical from call to call. A NaN in a series of
+ * group g reaches rows and columns g only. n * max_lag / 2 window positions of 3 G subtractions and 3 G (G + 1) / 2
+ * multiply-adds (twice the latter with abs_out): FP64-bound. Any n; launch dimensions never grow with n beyond the
+ * number of lag tiles.
+ * n_groups outside 1..16, n < 1, max_lag outside 0..n-1: MDHIP_EINVAL before anything is written.
+ */
+int mdhip_cross_msd(mdhip_ctx *ctx, int64_t n, int n_groups, const double *P, int P_on_device, int64_t max_lag,
+                    double *out, double *abs_out, int out_on_device);
+
 /*
  * Replaces, for the inputs of the path, the un-vendored pymatgen `parse_lammps_dumps` + pandas
  * `read_csv` the reference uses (call sites structural/rdf_cn.py:176, dynamical/diffusion.py:172,

@@ -861,3 +861,64 @@ def displacement_hist(r, box, group_off, jobs, bin_size, n_bins, ctx=None):
         float(bin_size), n_bins, None, ptr(hist, C.c_uint64), ptr(overflow, C.c_uint64), ptr(windows, C.c_uint64),
         ptr(moments), C.byref(crossings)))
     return hist, overflow, windows, moments, int(crossings.value)
+
+
+def collective_displacement(r, weight, group_off, scale=1.0, out=None, weighted=None, ctx=None):
+    """
+    Charge-weighted collective displacement of every group per frame (include/mdhip.h: mdhip_collective_displacement):
+    r [F,3,E] unwrapped coordinates (host array or contiguous float64 device tensor), weight [E], group_off int64 [G+1]
+    contiguous groups -> P [G,3,F] with P[g,x,t] = sum_{e in g} weight[e] * scale * (r[t,x,e] - r[0,x,e]): a host array,
+    or `out` (float64 CUDA tensor [G,3,F]) when given. `weighted`: a float64 CUDA tensor [F,3,E] that receives the
+    per-entity terms, the input from which `lag_msd` yields the self part.
+    """
+    ctx = ctx or default_context()
+    F, _, E = _shape3(r, "r")
+    rp, r_dev, keep = as_input(r, ctx)
+    w = _f64(weight)
+    if w.shape != (E,):
+        raise ValueError("weight must have shape [n_ent]")
+    off = _i64(group_off)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("group_off must be offsets [n_groups + 1]")
+    G = off.size - 1
+    if out is None:
+        res = np.empty((G, 3, F))
+        op, o_dev = C.c_void_p(res.ctypes.data), 0
+    else:
+        res, op, o_dev = out, _dev_out(out, (G, 3, F), ctx=ctx), 1
+    wp = None if weighted is None else _dev_out(weighted, (F, 3, E), ctx=ctx)
+    ctx.check(ctx.lib.mdhip_collective_displacement(ctx.h, F, E, rp, r_dev, ptr(w), float(scale), G,
+                                                    ptr(off, C.c_int64), op, o_dev, wp))
+    return res
+
+
+def cross_msd(P, max_lag, with_abs=False, out=None, abs_out=None, ctx=None):
+    """
+    Cross-displacement correlation of collective series at every lag (include/mdhip.h: mdhip_cross_msd): P [G,3,n]
+    (host array or contiguous float64 device tensor) -> out [max_lag+1,G,G],
+    out[k,a,b] = sum_t sum_x (P[a,x,t+k] - P[a,x,t]) (P[b,x,t+k] - P[b,x,t]) / (n - k). `with_abs`: also the same sum
+    over the absolute terms (the scale of the rounding error); returns (out, abs) then. `out` / `abs_out`: float64 CUDA
+    tensors of the result's shape that receive them on the device.
+    """
+    ctx = ctx or default_context()
+    shp = tuple(P.shape)
+    if len(shp) != 3 or shp[1] != 3:
+        raise ValueError("P must have shape [n_groups, 3, n]")
+    G, _, n = shp
+    pp, p_dev, keep = as_input(P, ctx)
+    L = int(max_lag) + 1
+    if out is None and abs_out is not None:
+        raise ValueError("abs_out on the device needs out on the device")
+    if out is not None:
+        op, ap = _dev_out(out, (L, G, G), ctx=ctx), None
+        if abs_out is not None:
+            ap = _dev_out(abs_out, (L, G, G), ctx=ctx)
+        elif with_abs:
+            raise ValueError("with_abs needs abs_out when out is a device tensor")
+        ctx.check(ctx.lib.mdhip_cross_msd(ctx.h, n, G, pp, p_dev, int(max_lag), op, ap, 1))
+        return (out, abs_out) if abs_out is not None else out
+    res = np.empty((max(L, 0), G, G))
+    ab = np.empty((max(L, 0), G, G)) if with_abs else None
+    ctx.check(ctx.lib.mdhip_cross_msd(ctx.h, n, G, pp, p_dev, int(max_lag), C.c_void_p(res.ctypes.data),
+                                      None if ab is None else C.c_void_p(ab.ctypes.data), 0))
+    return (res, ab) if with_abs else res

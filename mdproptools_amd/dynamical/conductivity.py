@@ -9,6 +9,12 @@ What runs where
       spreads over a process pool), every flux cross-correlation (conductivity.py:97-114, batched)
       and the running integrals (conductivity.py:216-232).
   Host: parsing, plateau detection (pandas, conductivity.py:116-165), the final Green-Kubo factor.
+
+`einstein` and `nernst` (`pass` in the reference, conductivity.py:399-403) are the Einstein-Helfand route to the same
+numbers, from positions instead of velocities: molecule centres of mass (mdhip_segment_com), their charge-weighted
+collective displacement per molecule type (mdhip_collective_displacement), its cross-displacement correlation at every
+lag (mdhip_cross_msd; the self part through mdhip_lag_msd) on the GPU; the straight-line fit and the 1 / (6 kB T V)
+factor on the host. `ionicity` is their ratio.
 """
 
 import glob
@@ -282,8 +288,262 @@ class Conductivity:
         fig.savefig(f"{self.working_dir}/conductivity.png", bbox_inches="tight", pad_inches=0.1)
         plt.close(fig)
 
-    def einstein(self):
-        pass
+    # ---- Einstein-Helfand / Nernst-Einstein ------------------------------------------------------------------------
 
-    def nernst(self):
-        pass
+    def _com_frames_streamed(self, seg_off):
+        """([device tensor [B,3,M]], timesteps, molecule charges) through the frame stream, or None when the dumps need
+        the general route (compressed text, no xu yu zu, a column missing: the general route names it)."""
+        import torch
+
+        from .. import io as mio
+        from .. import stream as S
+
+        pattern = f"{self.working_dir}/{self.filename}"
+        mine = mio._sorted_matches(pattern)
+        if not mine or any(str(f).endswith(".gz") for f in mine):
+            return None
+        nd = mio.NativeDumpFile(mine[0])
+        try:
+            names = nd.header(0)[4] if nd.n_frames else []
+        finally:
+            nd.close()
+        second = "type" if self.mass else "mass"
+        if not {"id", "q", second, "xu", "yu", "zu"} <= set(names):
+            return None
+        ctx = backend.default_context()
+        dev = torch.device("cuda", ctx.device)
+        m = q = q_mol = None
+        parts, steps = [], []
+        M = len(seg_off) - 1
+        for batch in S.FrameStream(pattern, files=mine, columns=("q", second, "xu", "yu", "zu")):
+            n = batch.xyz.shape[2]
+            if seg_off[-1] != n:
+                raise ValueError(f"Length of values ({int(seg_off[-1])}) does not match length of index ({n})")
+            if m is None:  # masses and charges of the first frame
+                tm = batch.types[0]
+                m = np.asarray(self.mass, dtype=np.float64)[tm.astype(np.int64) - 1] if self.mass else tm.copy()
+                q = batch.ids[0].copy()
+            out = torch.empty((len(batch), 3, M), dtype=torch.float64, device=dev)
+            _, _, seg_q = backend.segment_com(batch.xyz, m, seg_off, atom_q=q, out=out, ctx=ctx)
+            if q_mol is None:
+                q_mol = seg_q
+            parts.append(out)
+            steps.extend(int(ts) for ts in batch.timesteps)
+        if not parts:
+            return None
+        return parts, steps, q_mol
+
+    def _com_frames_general(self, seg_off):
+        """The same from whole frames: either reader, xu yu zu as dumped or made from x y z and the image flags."""
+        import torch
+
+        from .. import io as mio
+
+        second = "type" if self.mass else "mass"
+
+        def wanted(names):
+            for c in ("id", "q", second):
+                if c not in names:
+                    raise ValueError(f"Missing column '{c}' in dump file.")
+            if "xu" in names and "yu" in names and "zu" in names:
+                return ["q", second, "xu", "yu", "zu"]
+            for c in ("x", "y", "z", "ix", "iy", "iz"):
+                if c not in names:
+                    raise ValueError(f"Missing column '{c}' in dump file (no xu yu zu to use instead).")
+            return ["q", second, "x", "y", "z", "ix", "iy", "iz"]
+
+        def frames():
+            if mio.USE_NATIVE_READER:
+                for ts, bounds, _l, names, planes in mio.iter_native_frames(
+                        f"{self.working_dir}/{self.filename}", wanted, sort_by="id"):
+                    yield ts, bounds, dict(zip(wanted(names), planes))
+            else:
+                for dump in self.dumps:
+                    data = dump.data.sort_values(by=["id"])
+                    sel = wanted(list(data.columns))
+                    yield (dump.timestep, np.asarray(dump.box.bounds, dtype=np.float64),
+                           {c: data[c].to_numpy(dtype=np.float64) for c in sel})
+
+        m = q = None
+        xu, steps = [], []
+        for ts, bounds, cols in frames():
+            if "zu" not in cols:
+                for k, axis in enumerate("xyz"):
+                    cols[axis + "u"] = cols[axis] + cols["i" + axis] * (bounds[k][1] - bounds[k][0])
+            n = len(cols["q"])
+            if seg_off[-1] != n:
+                raise ValueError(f"Length of values ({int(seg_off[-1])}) does not match length of index ({n})")
+            if m is None:
+                tm = cols[second]
+                m = np.asarray(self.mass, dtype=np.float64)[tm.astype(np.int64) - 1] if self.mass else tm
+                q = cols["q"]
+            xu.append(np.stack([cols["xu"], cols["yu"], cols["zu"]]))
+            steps.append(int(ts))
+        if not xu:
+            raise ValueError(f"no frames match {self.working_dir}/{self.filename}")
+        ctx = backend.default_context()
+        out = torch.empty((len(xu), 3, len(seg_off) - 1), dtype=torch.float64, device=torch.device("cuda", ctx.device))
+        _, _, q_mol = backend.segment_com(np.stack(xu), m, seg_off, atom_q=q, out=out, ctx=ctx)
+        return [out], steps, q_mol
+
+    @staticmethod
+    def frame_times(steps, time_unit):
+        """(order, times [s]) of frames with integer timesteps `steps`: sorted by time; ValueError unless they are equally
+        spaced (a lag must be a time)."""
+        steps = np.asarray(steps, dtype=np.int64)
+        order = np.argsort(steps, kind="stable")
+        gaps = np.diff(steps[order])
+        if len(gaps) and (gaps[0] <= 0 or np.any(gaps != gaps[0])):
+            raise ValueError("the frames are not equally spaced in time (timestep gaps from %d to %d): a lag must be "
+                             "a time" % (int(gaps.min()), int(gaps.max())))
+        return order, steps[order].astype(np.float64) * time_unit
+
+    def _collective(self):
+        """Parses the dumps once per instance: frame times (a separate array: `self.time` belongs to get_charge_flux),
+        the collective displacement P [G,3,F] of every molecule type and the per-molecule weighted displacements
+        [F,3,M], both on the device."""
+        got = getattr(self, "_collective_cache", None)
+        if got is not None:
+            return got
+        import torch
+
+        from .. import io as mio
+
+        seg_off, mol_type, _ = molecule_layout(self.num_mols, self.num_atoms_per_mol)
+        loaded = self._com_frames_streamed(seg_off) if (mio.USE_NATIVE_READER and STREAM) else None
+        if loaded is None:
+            loaded = self._com_frames_general(seg_off)
+        parts, steps, q_mol = loaded
+        order, times = self.frame_times(steps, constants.TIME_CONVERSION[self.units] * self.timestep)
+        com = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+        if np.any(order != np.arange(len(order))):
+            com = com.index_select(0, torch.as_tensor(order, device=com.device)).contiguous()
+        group_off = np.concatenate(([0], np.cumsum(self.num_mols))).astype(np.int64)
+        F, _, M = com.shape
+        P = torch.empty((len(self.num_mols), 3, F), dtype=torch.float64, device=com.device)
+        weighted = torch.empty((F, 3, M), dtype=torch.float64, device=com.device)
+        backend.collective_displacement(com, np.asarray(q_mol) * constants.CHARGE_CONVERSION[self.units], group_off,
+                                        scale=constants.DISTANCE_CONVERSION[self.units], out=P, weighted=weighted)
+        self._collective_cache = {"times": times, "P": P, "weighted": weighted, "group_off": group_off}
+        return self._collective_cache
+
+    @staticmethod
+    def fit_window(lag_times, initial_time=None, final_time=None):
+        """(first, last) lag index of the fit, both included: the lags with initial_time <= t <= final_time [s]; a
+        missing end defaults to 20 % (rounded up) / 80 % (rounded down) of max_lag = len(lag_times) - 1."""
+        lag_times = np.asarray(lag_times, dtype=np.float64)
+        max_lag = len(lag_times) - 1
+        lo = -(-max_lag // 5) if initial_time is None else int(np.searchsorted(lag_times, initial_time, side="left"))
+        hi = (4 * max_lag) // 5 if final_time is None else int(np.searchsorted(lag_times, final_time, side="right")) - 1
+        if hi - lo < 1:
+            raise ValueError("the fit window [%r, %r] holds fewer than two of the %d lags" % (initial_time, final_time,
+                                                                                          max_lag + 1))
+        return lo, hi
+
+    @staticmethod
+    def fit_weights(t):
+        """w with slope = w @ y: the ordinary least-squares line with intercept through (t, y)."""
+        t = np.asarray(t, dtype=np.float64)
+        c = t - t.mean()
+        return c / np.sum(c * c)
+
+    def helfand(self, slope):
+        """sigma = slope / (6 kB T V)."""
+        return np.asarray(slope) / 6 / constants.BOLTZMANN / self.temp / self.volume
+
+    def _lag_range(self, n_frames, max_lag):
+        max_lag = (n_frames - 1) // 2 if max_lag is None else int(max_lag)
+        if not 1 <= max_lag <= n_frames - 1:
+            raise ValueError("max_lag must be in [1, n_frames - 1 = %d]" % (n_frames - 1))
+        return max_lag
+
+    def _finish_helfand(self, name, t, cols, lo, hi, cond, save, plot):
+        """The table `t, 1, ..., tot` of a method and what save / plot write for it."""
+        n_types = len(self.num_mols)
+        table = pd.DataFrame(dict([("t", t)] + [(str(i + 1), cols[i]) for i in range(n_types)] + [("tot", cols[-1])]))
+        if save:
+            header = "t," + ",".join(str(i + 1) for i in range(n_types)) + ",tot"
+            np.savetxt(f"{self.working_dir}/{name}_msd.csv", table.to_numpy(), delimiter=",", header=header, comments="")
+            rows = np.asarray([[t[lo]] * len(cond), [t[hi]] * len(cond), cond])
+            np.savetxt(f"{self.working_dir}/{name}_conductivity.csv", rows.T, delimiter=",",
+                       header="start_t,end_t,cond", comments="")
+        if plot:
+            self._plot_helfand(name, t, cols, (t[lo], t[hi]))
+        return table
+
+    def einstein(self, max_lag=None, initial_time=None, final_time=None, save=False, plot=False):
+        """
+        Einstein-Helfand conductivity [S/m] per molecule type followed by the total: sigma_ab = slope of
+        <dP_a(t) . dP_b(t)> / (6 kB T V), P_a the charge-weighted collective displacement of type a; element i is
+        sum_b sigma_ib (the convention of calc_cond). Lags 0 .. max_lag frames (default (F - 1) // 2); the line is fitted
+        over [initial_time, final_time] seconds (default: lags from 20 % to 80 % of max_lag). Keeps `self.onsager`
+        (sigma_ab) and `self.einstein_msd` (t, one column per type: the row sum, tot). save writes einstein_msd.csv and
+        einstein_conductivity.csv, plot writes einstein.png, into working_dir.
+        """
+        col = self._collective()
+        times = col["times"]
+        max_lag = self._lag_range(len(times), max_lag)
+        out = backend.cross_msd(col["P"], max_lag)
+        t = times[: max_lag + 1] - times[0]
+        lo, hi = self.fit_window(t, initial_time, final_time)
+        w = self.fit_weights(t[lo:hi + 1])
+        self.onsager = self.helfand(np.tensordot(w, out[lo:hi + 1], axes=(0, 0)))
+        cond = np.append(self.onsager.sum(axis=1), self.onsager.sum())
+        cols = [out[:, a, :].sum(axis=1) for a in range(out.shape[1])] + [out.sum(axis=(1, 2))]
+        self.einstein_msd = self._finish_helfand("einstein", t, cols, lo, hi, cond, save, plot)
+        self._einstein_cond = cond
+        return cond
+
+    def nernst(self, max_lag=None, initial_time=None, final_time=None, save=False, plot=False):
+        """
+        Nernst-Einstein conductivity [S/m] per molecule type followed by the total: the self part of `einstein`,
+        S_a(t) = sum over the molecules e of type a of c_e^2 <|dr_e(t)|^2>, same lags, fit and factor. Keeps
+        `self.nernst_msd`; save writes nernst_msd.csv and nernst_conductivity.csv, plot writes nernst.png.
+        """
+        col = self._collective()
+        times = col["times"]
+        max_lag = self._lag_range(len(times), max_lag)
+        msd = backend.lag_msd(col["weighted"], max_lag, col["group_off"], scale=1.0)
+        size = np.diff(col["group_off"]).astype(np.float64)
+        self_part = np.where(size > 0, msd[:, :, 3] * size, 0.0)  # [lag, type]: mean over molecules -> sum
+        t = times[: max_lag + 1] - times[0]
+        lo, hi = self.fit_window(t, initial_time, final_time)
+        w = self.fit_weights(t[lo:hi + 1])
+        sigma = self.helfand(w @ self_part[lo:hi + 1])
+        cond = np.append(sigma, sigma.sum())
+        cols = [self_part[:, a] for a in range(self_part.shape[1])] + [self_part.sum(axis=1)]
+        self.nernst_msd = self._finish_helfand("nernst", t, cols, lo, hi, cond, save, plot)
+        self._nernst_cond = cond
+        return cond
+
+    def ionicity(self):
+        """sigma_Einstein / sigma_Nernst-Einstein of the whole system; computes whichever is missing with its defaults."""
+        if getattr(self, "_einstein_cond", None) is None:
+            self.einstein()
+        if getattr(self, "_nernst_cond", None) is None:
+            self.nernst()
+        return self._einstein_cond[-1] / self._nernst_cond[-1]
+
+    def _plot_helfand(self, name, t, cols, window):
+        import matplotlib
+
+        matplotlib.use("Agg", force=False)
+        import matplotlib.pyplot as plt
+
+        from ..utilities.plots import set_axis
+
+        t_ns = np.asarray(t) * 10 ** 9
+        cmap = plt.get_cmap("Paired")
+        fig, ax = plt.subplots(1, 1, figsize=(10, 5))
+        for i in range(len(cols) - 1):
+            ax.plot(t_ns, cols[i], linewidth=2, color=cmap(i / 10), label=i + 1)
+        ax.plot(t_ns, cols[-1], linewidth=2, color="black", label="total")
+        for edge in window:
+            ax.axvline(edge * 10 ** 9, linewidth=2, color="black", linestyle="--")
+        set_axis(ax, axis="both")
+        ax.set_xlabel(r"$\mathrm{Time, 10^9 (s)}$", fontsize=18)
+        ax.set_ylabel(r"$\mathrm{\langle \Delta P(t)\cdot \Delta P(t)\rangle, C^2 m^2}$", fontsize=18)
+        ax.legend(fontsize=16, loc="center left", bbox_to_anchor=(1, 0.5), frameon=False)
+        fig.tight_layout(pad=3)
+        fig.savefig(f"{self.working_dir}/{name}.png", bbox_inches="tight", pad_inches=0.1)
+        plt.close(fig)
