@@ -65,6 +65,36 @@ def _shape3(x, name):
     return shp
 
 
+def _pair_inputs(xyz, types, box, relation_matrix, ctx, check_types=True):
+    """What every atom-atom pair call marshals: (F, N, coordinate pointer, on_device, keepalive, types int32, their
+    frame stride (0: one [N] row shared by the frames), box [F,3], relations int32 [R,2])."""
+    F, _, N = _shape3(xyz, "xyz")
+    xp, on_dev, keep = as_input(xyz, ctx)
+    ty = _i32(types)
+    stride = 0 if ty.ndim == 1 else N
+    if check_types and ty.size != (N if stride == 0 else F * N):
+        raise ValueError("types must have shape [N] or [F, N]")
+    return F, N, xp, on_dev, keep, ty, stride, _f64(box).reshape(F, 3), _i32(relation_matrix).reshape(-1, 2)
+
+
+def _dest(out, shape, ctx, dtype=np.float64, dev_dtype="torch.float64", pinned=False):
+    """Where a call writes its result: (result, pointer, on_device flag) — a fresh host array of `shape` (zeroed, or
+    from `result_array`: page-locked when large) without `out`, else `out`, a device tensor validated by _dev_out."""
+    if out is not None:
+        return out, _dev_out(out, shape, dev_dtype, ctx), 1
+    res = result_array(shape, dtype, device=ctx.device) if pinned else np.zeros(shape, dtype=dtype)
+    return res, ptr(res, np.ctypeslib.as_ctypes_type(dtype)), 0
+
+
+def _check_cols(cols, n, what):
+    """A host destination of per-entity columns: float64 [4, n] whose rows are contiguous (they may be rows of a larger
+    C-ordered block). Returns (its address, the row stride in doubles)."""
+    if not (isinstance(cols, np.ndarray) and cols.dtype == np.float64 and cols.shape == (4, n)
+            and (n == 0 or (cols.strides[1] == 8 and cols.strides[0] % 8 == 0 and cols.strides[0] >= 8 * n))):
+        raise ValueError("cols must be a float64 array [4, %s] with contiguous rows" % what)
+    return C.c_void_p(cols.ctypes.data), cols.strides[0] // 8
+
+
 def cutoff_sq(r_cut):
     """r_cut**2 as the jitted reference evaluates it: one multiply (numba lowers `x ** 2` with a
     literal exponent to x*x; rdf_cn.py:66). CPython's float pow differs in ~0.1% of inputs."""
@@ -80,14 +110,7 @@ def rdf_loop(xyz, types, box, relation_matrix, r_cut, ddr, nbins, per_frame=True
     [nbins] / [R,nbins] when per_frame is False.
     """
     ctx = ctx or default_context()
-    F, _, N = _shape3(xyz, "xyz")
-    xp, on_dev, keep = as_input(xyz, ctx)
-    ty = _i32(types)
-    stride = 0 if ty.ndim == 1 else N
-    if ty.size != (N if stride == 0 else F * N):
-        raise ValueError("types must have shape [N] or [F, N]")
-    bx = _f64(box).reshape(F, 3)
-    rel = _i32(relation_matrix).reshape(-1, 2)
+    F, N, xp, on_dev, keep, ty, stride, bx, rel = _pair_inputs(xyz, types, box, relation_matrix, ctx)
     R = len(rel)
     lead = (F,) if per_frame else ()
     full = np.zeros(lead + (nbins,), dtype=np.uint64)
@@ -111,14 +134,7 @@ def rdf_loop_dev(xyz, types, box, relation_matrix, r_cut, ddr, nbins, out, ctx=N
     Used by the multi-GPU layer so that the all-reduce reads the buffer the kernels wrote.
     """
     ctx = ctx or default_context()
-    F, _, N = _shape3(xyz, "xyz")
-    xp, on_dev, keep = as_input(xyz, ctx)
-    ty = _i32(types)
-    stride = 0 if ty.ndim == 1 else N
-    if ty.size != (N if stride == 0 else F * N):
-        raise ValueError("types must have shape [N] or [F, N]")
-    bx = _f64(box).reshape(F, 3)
-    rel = _i32(relation_matrix).reshape(-1, 2)
+    F, N, xp, on_dev, keep, ty, stride, bx, rel = _pair_inputs(xyz, types, box, relation_matrix, ctx)
     words = (1 + len(rel)) * int(nbins) + 1
     if not (getattr(out, "is_cuda", False) and out.is_contiguous() and str(out.dtype) == "torch.int64"
             and out.numel() == words):
@@ -140,14 +156,7 @@ def rdf_cn_loop(xyz, types, box, relation_matrix, r_cut, ddr, nbins, cn_cut_list
     (rdf_full, rdf_part, overflow, cn) — the integers of rdf_loop(...) and cn_loop(..., cn_cut_list).
     """
     ctx = ctx or default_context()
-    F, _, N = _shape3(xyz, "xyz")
-    xp, on_dev, keep = as_input(xyz, ctx)
-    ty = _i32(types)
-    stride = 0 if ty.ndim == 1 else N
-    if ty.size != (N if stride == 0 else F * N):
-        raise ValueError("types must have shape [N] or [F, N]")
-    bx = _f64(box).reshape(F, 3)
-    rel = _i32(relation_matrix).reshape(-1, 2)
+    F, N, xp, on_dev, keep, ty, stride, bx, rel = _pair_inputs(xyz, types, box, relation_matrix, ctx)
     R = len(rel)
     rc2 = _f64([cutoff_sq(r) for r in cn_cut_list])
     if len(rc2) != R:
@@ -172,37 +181,23 @@ def cn_loop(xyz, types, box, relation_matrix, r_cut_list, per_frame=True, ctx=No
     """`_cn_loop` (rdf_cn.py:100-119): raw counts uint64 [F,R] (or [R]). `out` (frame-summed only): an int64 CUDA
     tensor [R] that receives the counts on the device (their bit patterns; the multi-GPU layer all-reduces it)."""
     ctx = ctx or default_context()
-    F, _, N = _shape3(xyz, "xyz")
-    xp, on_dev, keep = as_input(xyz, ctx)
-    ty = _i32(types)
-    stride = 0 if ty.ndim == 1 else N
-    bx = _f64(box).reshape(F, 3)
-    rel = _i32(relation_matrix).reshape(-1, 2)
+    # (the shape of `types` is not checked here, and the library cannot: it sees a pointer and a stride)
+    F, N, xp, on_dev, keep, ty, stride, bx, rel = _pair_inputs(xyz, types, box, relation_matrix, ctx, check_types=False)
     rc2 = _f64([cutoff_sq(r) for r in r_cut_list])
     if len(rc2) != len(rel):
         raise ValueError("one cutoff per relation is required")
-    if out is not None:
-        if per_frame:
-            raise ValueError("a device result buffer holds the frame-summed counts: pass per_frame=False")
-        op = _dev_out(out, (len(rel),), "torch.int64", ctx)
-        if async_:
-            ctx.check(ctx.lib.mdhip_cn_atomic_async(
-                ctx.h, F, N, xp, on_dev, ptr(ty, C.c_int32), stride, ptr(bx), len(rel), ptr(rel, C.c_int32),
-                ptr(rc2), 0, op, 1))
-            return Pending(ctx, out, keep=(keep, ty, bx, rel, rc2))
-        ctx.check(ctx.lib.mdhip_cn_atomic_dev(
-            ctx.h, F, N, xp, on_dev, ptr(ty, C.c_int32), stride, ptr(bx), len(rel), ptr(rel, C.c_int32),
-            ptr(rc2), op))
-        return out
-    cn = np.zeros(((F,) if per_frame else ()) + (len(rel),), dtype=np.uint64)
+    if out is not None and per_frame:
+        raise ValueError("a device result buffer holds the frame-summed counts: pass per_frame=False")
+    per_frame = int(bool(per_frame))
+    cn, op, dev = _dest(out, ((F,) if per_frame else ()) + (len(rel),), ctx, np.uint64, "torch.int64")
+    args = (ctx.h, F, N, xp, on_dev, ptr(ty, C.c_int32), stride, ptr(bx), len(rel), ptr(rel, C.c_int32), ptr(rc2))
     if async_:
-        ctx.check(ctx.lib.mdhip_cn_atomic_async(
-            ctx.h, F, N, xp, on_dev, ptr(ty, C.c_int32), stride, ptr(bx), len(rel), ptr(rel, C.c_int32),
-            ptr(rc2), int(bool(per_frame)), C.c_void_p(cn.ctypes.data), 0))
+        ctx.check(ctx.lib.mdhip_cn_atomic_async(*args, per_frame, op, dev))
         return Pending(ctx, cn, keep=(keep, ty, bx, rel, rc2))
-    ctx.check(ctx.lib.mdhip_cn_atomic(
-        ctx.h, F, N, xp, on_dev, ptr(ty, C.c_int32), stride, ptr(bx), len(rel), ptr(rel, C.c_int32),
-        ptr(rc2), int(bool(per_frame)), ptr(cn, C.c_uint64)))
+    if dev:
+        ctx.check(ctx.lib.mdhip_cn_atomic_dev(*args, op))
+    else:
+        ctx.check(ctx.lib.mdhip_cn_atomic(*args, per_frame, op))
     return cn
 
 
@@ -331,11 +326,8 @@ def msd_origin(r, origin, group_off, scale=1.0, cols=None, out=None, ctx=None, a
         if getattr(cols, "is_cuda", False):
             cp, c_dev, stride = _dev_out(cols, (4, F * E), ctx=ctx), 1, F * E
         else:
-            if not (isinstance(cols, np.ndarray) and cols.dtype == np.float64 and cols.shape == (4, F * E)
-                    and (F * E == 0 or (cols.strides[1] == 8 and cols.strides[0] % 8 == 0
-                                        and cols.strides[0] >= 8 * F * E))):
-                raise ValueError("cols must be a float64 array [4, n_frames * n_ent] with contiguous rows")
-            cp, stride = C.c_void_p(cols.ctypes.data), (cols.strides[0] // 8 if F * E else 0)
+            cp, stride = _check_cols(cols, F * E, "n_frames * n_ent")
+            stride = stride if F * E else 0
     fn = ctx.lib.mdhip_msd_origin_async if async_ else ctx.lib.mdhip_msd_origin
     ctx.check(fn(ctx.h, F, E, rp, on_dev, op, o_dev, float(scale), G, ptr(go, C.c_int64), sp, s_dev, cp, stride, c_dev))
     if async_:
@@ -355,13 +347,11 @@ def msd_pairs_cols(r, pairs, group_off, cols, scale=1.0, ctx=None):
     pr = _i32(pairs).reshape(-1, 2)
     go = _i64(group_off)
     G = len(go) - 1
-    if not (isinstance(cols, np.ndarray) and cols.dtype == np.float64 and cols.shape == (4, len(pr) * E)
-            and cols.strides[1] == 8 and cols.strides[0] % 8 == 0 and cols.strides[0] >= 8 * len(pr) * E):
-        raise ValueError("cols must be a float64 array [4, n_pairs * n_ent] with contiguous rows")
+    cp, stride = _check_cols(cols, len(pr) * E, "n_pairs * n_ent")
     sums = np.zeros((len(pr), G, 4))
     ctx.check(ctx.lib.mdhip_msd_pairs_cols(
         ctx.h, F, E, rp, on_dev, float(scale), len(pr), ptr(pr, C.c_int32), G, ptr(go, C.c_int64),
-        ptr(sums), C.c_void_p(cols.ctypes.data), cols.strides[0] // 8, 0))
+        ptr(sums), cp, stride, 0))
     return sums
 
 
@@ -370,20 +360,13 @@ def msd_windows(r, tao, scale=1.0, ctx=None, out=None, async_=False):
     ctx = ctx or default_context()
     F, _, E = _shape3(r, "r")
     rp, on_dev, keep = as_input(r, ctx)
-    if out is not None:
-        op = _dev_out(out, (E, 4), ctx=ctx)
-        if async_:
-            ctx.check(ctx.lib.mdhip_msd_windows_async(ctx.h, F, E, rp, on_dev, float(scale), int(tao), op, 1))
-            return Pending(ctx, out, keep=keep)
-        ctx.check(ctx.lib.mdhip_msd_windows_dev(ctx.h, F, E, rp, on_dev, float(scale), int(tao), op))
-        return out
-    out = np.zeros((E, 4))
+    res, op, dev = _dest(out, (E, 4), ctx)
+    args = (ctx.h, F, E, rp, on_dev, float(scale), int(tao), op)
     if async_:
-        ctx.check(ctx.lib.mdhip_msd_windows_async(ctx.h, F, E, rp, on_dev, float(scale), int(tao),
-                                                  C.c_void_p(out.ctypes.data), 0))
-        return Pending(ctx, out, keep=keep)
-    ctx.check(ctx.lib.mdhip_msd_windows(ctx.h, F, E, rp, on_dev, float(scale), int(tao), ptr(out)))
-    return out
+        ctx.check(ctx.lib.mdhip_msd_windows_async(*args, dev))
+        return Pending(ctx, res, keep=keep)
+    ctx.check((ctx.lib.mdhip_msd_windows_dev if dev else ctx.lib.mdhip_msd_windows)(*args))
+    return res
 
 
 def lag_msd(r, max_lag, group_off, scale=1.0, ctx=None, out=None, async_=False, status_out=None):
@@ -396,28 +379,17 @@ def lag_msd(r, max_lag, group_off, scale=1.0, ctx=None, out=None, async_=False, 
     rp, on_dev, keep = as_input(r, ctx)
     go = _i64(group_off)
     G = len(go) - 1
-    if out is not None:
-        op = _dev_out(out, (int(max_lag) + 1, G, 4), ctx=ctx)
-        if async_:
-            ctx.check(ctx.lib.mdhip_lag_msd_async(ctx.h, F, E, rp, on_dev, float(scale), int(max_lag), G,
-                                                  ptr(go, C.c_int64), op, 1))
-            pend = Pending(ctx, out, keep=(keep, go, status_out))
-            if status_out is not None:
-                ctx.check(ctx.lib.mdhip_lag_msd_status_dev(ctx.h, _dev_out(status_out, tuple(status_out.shape), ctx=ctx)))
-            return pend
-        ctx.check(ctx.lib.mdhip_lag_msd_dev(ctx.h, F, E, rp, on_dev, float(scale), int(max_lag), G,
-                                            ptr(go, C.c_int64), op))
-        ctx.note_fallbacks()
-        return out
-    out = np.zeros((int(max_lag) + 1, G, 4))
+    res, op, dev = _dest(out, (int(max_lag) + 1, G, 4), ctx)
+    args = (ctx.h, F, E, rp, on_dev, float(scale), int(max_lag), G, ptr(go, C.c_int64), op)
     if async_:
-        ctx.check(ctx.lib.mdhip_lag_msd_async(ctx.h, F, E, rp, on_dev, float(scale), int(max_lag), G,
-                                              ptr(go, C.c_int64), C.c_void_p(out.ctypes.data), 0))
-        return Pending(ctx, out, keep=(keep, go))
-    ctx.check(ctx.lib.mdhip_lag_msd(ctx.h, F, E, rp, on_dev, float(scale), int(max_lag), G,
-                                    ptr(go, C.c_int64), ptr(out)))
+        ctx.check(ctx.lib.mdhip_lag_msd_async(*args, dev))
+        pend = Pending(ctx, res, keep=(keep, go, status_out))
+        if dev and status_out is not None:
+            ctx.check(ctx.lib.mdhip_lag_msd_status_dev(ctx.h, _dev_out(status_out, tuple(status_out.shape), ctx=ctx)))
+        return pend
+    ctx.check((ctx.lib.mdhip_lag_msd_dev if dev else ctx.lib.mdhip_lag_msd)(*args))
     ctx.note_fallbacks()
-    return out
+    return res
 
 
 def charge_flux(vel, atom_mass, atom_q, seg_off, seg_type, n_types, vel_conv, charge_conv, ctx=None, out=None,
@@ -430,26 +402,14 @@ def charge_flux(vel, atom_mass, atom_q, seg_off, seg_type, n_types, vel_conv, ch
     m, q = _f64(atom_mass), _f64(atom_q)
     off = _i64(seg_off)
     st = _i32(seg_type)
-    dev = out is not None
-    if dev:
-        op = _dev_out(out, (3, int(n_types), F), ctx=ctx)
-    else:
-        out = np.zeros((3, int(n_types), F))
-        op = C.c_void_p(out.ctypes.data)
+    res, op, dev = _dest(out, (3, int(n_types), F), ctx)
+    args = (ctx.h, F, N, vp_, on_dev, ptr(m), ptr(q), len(off) - 1, ptr(off, C.c_int64), ptr(st, C.c_int32),
+            int(n_types), float(vel_conv), float(charge_conv), op)
     if async_:
-        ctx.check(ctx.lib.mdhip_charge_flux_async(
-            ctx.h, F, N, vp_, on_dev, ptr(m), ptr(q), len(off) - 1, ptr(off, C.c_int64), ptr(st, C.c_int32),
-            int(n_types), float(vel_conv), float(charge_conv), op, int(dev)))
-        return Pending(ctx, out, keep=(keep, m, q, off, st))
-    if dev:
-        ctx.check(ctx.lib.mdhip_charge_flux_dev(
-            ctx.h, F, N, vp_, on_dev, ptr(m), ptr(q), len(off) - 1, ptr(off, C.c_int64), ptr(st, C.c_int32),
-            int(n_types), float(vel_conv), float(charge_conv), op))
-        return out
-    ctx.check(ctx.lib.mdhip_charge_flux(
-        ctx.h, F, N, vp_, on_dev, ptr(m), ptr(q), len(off) - 1, ptr(off, C.c_int64), ptr(st, C.c_int32),
-        int(n_types), float(vel_conv), float(charge_conv), ptr(out)))
-    return out
+        ctx.check(ctx.lib.mdhip_charge_flux_async(*args, dev))
+        return Pending(ctx, res, keep=(keep, m, q, off, st))
+    ctx.check((ctx.lib.mdhip_charge_flux_dev if dev else ctx.lib.mdhip_charge_flux)(*args))
+    return res
 
 
 def xcorr(a, b=None, method=XCORR_FFT, n_lags=None, ctx=None, lag_begin=0, out=None, async_=False):
@@ -472,18 +432,20 @@ def xcorr(a, b=None, method=XCORR_FFT, n_lags=None, ctx=None, lag_begin=0, out=N
         if b_dev != a_dev:
             raise ValueError("a and b must both be host arrays or both device tensors")
     n_lags = n - int(lag_begin) if n_lags is None else int(n_lags)
-    if out is not None:
+    res, op, dev = _dest(out, (P, n_lags), ctx, pinned=True)
+    args = (ctx.h, n, P, ap, bp, a_dev, int(method), int(lag_begin), n_lags, op)
+    if dev:
         fn = ctx.lib.mdhip_xcorr_lags_dev_async if async_ else ctx.lib.mdhip_xcorr_lags_dev
-        ctx.check(fn(ctx.h, n, P, ap, bp, a_dev, int(method), int(lag_begin), n_lags, _dev_out(out, (P, n_lags), ctx=ctx)))
-        return Pending(ctx, out, keep=(a, b, k1, k2)) if async_ else out
-    out = result_array((P, n_lags), device=ctx.device)
-    if async_:
+    elif async_:
         if lag_begin:
             raise ValueError("a lag range is asynchronous only with a device result buffer")
-        ctx.check(ctx.lib.mdhip_xcorr_async(ctx.h, n, P, ap, bp, a_dev, int(method), n_lags, ptr(out)))
-        return Pending(ctx, out[0] if single else out, keep=(a, b, k1, k2))
-    ctx.check(ctx.lib.mdhip_xcorr_lags(ctx.h, n, P, ap, bp, a_dev, int(method), int(lag_begin), n_lags, ptr(out)))
-    return out[0] if single else out
+        fn, args = ctx.lib.mdhip_xcorr_async, args[:7] + args[8:]  # (this entry point takes no lag_begin)
+    else:
+        fn = ctx.lib.mdhip_xcorr_lags
+    ctx.check(fn(*args))
+    if single and not dev:
+        res = res[0]
+    return Pending(ctx, res, keep=(a, b, k1, k2)) if async_ else res
 
 
 def cumtrapz(y, dx, leading_zero=False, ctx=None, out=None, async_=False):
@@ -495,14 +457,14 @@ def cumtrapz(y, dx, leading_zero=False, ctx=None, out=None, async_=False):
     shp = tuple(y.shape)
     S, n = (1, shp[0]) if single else shp
     m = n - 1 + (1 if leading_zero else 0)
-    if out is not None:
+    res, op, dev = _dest(out, (S, max(m, 0)), ctx, pinned=True)
+    if dev:
         fn = ctx.lib.mdhip_cumtrapz_dev_async if async_ else ctx.lib.mdhip_cumtrapz_dev
-        ctx.check(fn(ctx.h, n, S, yp, on_dev, float(dx), int(bool(leading_zero)), _dev_out(out, (S, max(m, 0)), ctx=ctx)))
-        return Pending(ctx, out, keep=keep) if async_ else out
-    out = result_array((S, max(m, 0)), device=ctx.device)
-    fn = ctx.lib.mdhip_cumtrapz_async if async_ else ctx.lib.mdhip_cumtrapz
-    ctx.check(fn(ctx.h, n, S, yp, on_dev, float(dx), int(bool(leading_zero)), ptr(out)))
-    res = out[0] if single else out
+    else:
+        fn = ctx.lib.mdhip_cumtrapz_async if async_ else ctx.lib.mdhip_cumtrapz
+    ctx.check(fn(ctx.h, n, S, yp, on_dev, float(dx), int(bool(leading_zero)), op))
+    if single and not dev:
+        res = res[0]
     return Pending(ctx, res, keep=keep) if async_ else res
 
 

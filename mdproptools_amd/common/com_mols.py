@@ -9,6 +9,7 @@ import numpy as np
 import pandas as pd
 
 from .. import backend
+from .trajectory import masses
 
 
 def molecule_layout(num_mols, num_atoms_per_mol):
@@ -31,8 +32,8 @@ def atom_masses(data, mass):
     """Per-atom masses: from the `mass` list indexed by type, or from the dump's own column."""
     if not mass:
         assert "mass" in data.columns, "Missing atom masses in dump file."
-        return data["mass"].to_numpy(dtype=np.float64)
-    return np.asarray(mass, dtype=np.float64)[data["type"].to_numpy().astype(np.int64) - 1]
+        return masses(data["mass"].to_numpy(dtype=np.float64), mass)
+    return masses(data["type"].to_numpy(), mass)
 
 
 def calc_com(dump, num_mols, num_atoms_per_mol, mass=None, atom_attributes=["xu", "yu", "zu"],

@@ -25,7 +25,8 @@ import pandas as pd
 
 from .. import backend
 from ..common import constants
-from ..common.com_mols import molecule_layout
+from ..common import trajectory as T
+from ..common.com_mols import check_atom_count, molecule_layout
 from ..io import parse_lammps_dumps
 
 # True: get_charge_flux parses into page-locked staging batches and runs the fused flux kernel on each while the next
@@ -134,12 +135,9 @@ class Conductivity:
 
             frames = from_pandas()
         for ts, v, qcol, tm in frames:
-            if seg_off[-1] != v.shape[1]:
-                raise ValueError(f"Length of values ({int(seg_off[-1])}) does not match length of index "
-                                 f"({v.shape[1]})")
+            check_atom_count(seg_off[-1], v.shape[1])
             if m is None:
-                m = np.asarray(self.mass, dtype=np.float64)[tm.astype(np.int64) - 1] if self.mass else tm
-                q = qcol
+                m, q = T.masses(tm, self.mass), qcol
             vel.append(np.ascontiguousarray(v))
             steps.append(ts * constants.TIME_CONVERSION[self.units])
         flux = None
@@ -152,32 +150,17 @@ class Conductivity:
     def _flux_streamed(self, files, seg_off, mol_type):
         """(flux [3, n_types, F_local] or None, steps) through the frame stream; None when the dumps need the general
         route (compressed text, a column missing: the general route raises the reference's message)."""
-        from .. import io as mio
-        from .. import stream as S
-
         pattern = f"{self.working_dir}/{self.filename}"
-        mine = files if files is not None else mio._sorted_matches(pattern)
-        if not mine or any(str(f).endswith(".gz") for f in mine):
-            return None
-        nd = mio.NativeDumpFile(mine[0])
-        try:
-            names = nd.header(0)[4] if nd.n_frames else []
-        finally:
-            nd.close()
-        second = "type" if self.mass else "mass"
-        if not {"id", "q", second, "vx", "vy", "vz"} <= set(names):
+        # the staging batch carries the charge, ONE more per-atom attribute and the three velocity planes
+        columns = ("q", "type" if self.mass else "mass", "vx", "vy", "vz")
+        mine = T.streamable_files(pattern, ("id",) + columns, files)
+        if mine is None:
             return None
         m = q = None
         parts, steps = [], []
-        # the staging batch carries the charge, ONE more per-atom attribute and the three velocity planes
-        for batch in S.FrameStream(pattern, files=mine, columns=("q", second, "vx", "vy", "vz")):
-            n = batch.xyz.shape[2]
-            if seg_off[-1] != n:
-                raise ValueError(f"Length of values ({int(seg_off[-1])}) does not match length of index ({n})")
+        for batch in T.stream_reduced(pattern, mine, columns, seg_off[-1]):
             if m is None:  # masses and charges of the first frame, as the general route takes them
-                tm = batch.types[0]
-                m = np.asarray(self.mass, dtype=np.float64)[tm.astype(np.int64) - 1] if self.mass else tm.copy()
-                q = batch.ids[0].copy()
+                m, q = T.masses(batch.types[0].copy(), self.mass), batch.ids[0].copy()
             parts.append(backend.charge_flux(batch.xyz, m, q, seg_off, (mol_type - 1).astype(np.int32),
                                              len(self.num_mols), constants.VELOCITY_CONVERSION[self.units],
                                              constants.CHARGE_CONVERSION[self.units]))
@@ -295,34 +278,19 @@ class Conductivity:
         the general route (compressed text, no xu yu zu, a column missing: the general route names it)."""
         import torch
 
-        from .. import io as mio
-        from .. import stream as S
-
         pattern = f"{self.working_dir}/{self.filename}"
-        mine = mio._sorted_matches(pattern)
-        if not mine or any(str(f).endswith(".gz") for f in mine):
-            return None
-        nd = mio.NativeDumpFile(mine[0])
-        try:
-            names = nd.header(0)[4] if nd.n_frames else []
-        finally:
-            nd.close()
-        second = "type" if self.mass else "mass"
-        if not {"id", "q", second, "xu", "yu", "zu"} <= set(names):
+        columns = ("q", "type" if self.mass else "mass") + T.UNWRAPPED
+        mine = T.streamable_files(pattern, ("id",) + columns)
+        if mine is None:
             return None
         ctx = backend.default_context()
         dev = torch.device("cuda", ctx.device)
         m = q = q_mol = None
         parts, steps = [], []
         M = len(seg_off) - 1
-        for batch in S.FrameStream(pattern, files=mine, columns=("q", second, "xu", "yu", "zu")):
-            n = batch.xyz.shape[2]
-            if seg_off[-1] != n:
-                raise ValueError(f"Length of values ({int(seg_off[-1])}) does not match length of index ({n})")
+        for batch in T.stream_reduced(pattern, mine, columns, seg_off[-1]):
             if m is None:  # masses and charges of the first frame
-                tm = batch.types[0]
-                m = np.asarray(self.mass, dtype=np.float64)[tm.astype(np.int64) - 1] if self.mass else tm.copy()
-                q = batch.ids[0].copy()
+                m, q = T.masses(batch.types[0].copy(), self.mass), batch.ids[0].copy()
             out = torch.empty((len(batch), 3, M), dtype=torch.float64, device=dev)
             _, _, seg_q = backend.segment_com(batch.xyz, m, seg_off, atom_q=q, out=out, ctx=ctx)
             if q_mol is None:
@@ -341,16 +309,14 @@ class Conductivity:
 
         second = "type" if self.mass else "mass"
 
+        def missing(c, _have_unwrapped):
+            raise ValueError(f"Missing column '{c}' in dump file (no xu yu zu to use instead).")
+
         def wanted(names):
             for c in ("id", "q", second):
                 if c not in names:
                     raise ValueError(f"Missing column '{c}' in dump file.")
-            if "xu" in names and "yu" in names and "zu" in names:
-                return ["q", second, "xu", "yu", "zu"]
-            for c in ("x", "y", "z", "ix", "iy", "iz"):
-                if c not in names:
-                    raise ValueError(f"Missing column '{c}' in dump file (no xu yu zu to use instead).")
-            return ["q", second, "x", "y", "z", "ix", "iy", "iz"]
+            return T.unwrapped_columns(names, ["q", second], missing)
 
         def frames():
             if mio.USE_NATIVE_READER:
@@ -367,16 +333,10 @@ class Conductivity:
         m = q = None
         xu, steps = [], []
         for ts, bounds, cols in frames():
-            if "zu" not in cols:
-                for k, axis in enumerate("xyz"):
-                    cols[axis + "u"] = cols[axis] + cols["i" + axis] * (bounds[k][1] - bounds[k][0])
-            n = len(cols["q"])
-            if seg_off[-1] != n:
-                raise ValueError(f"Length of values ({int(seg_off[-1])}) does not match length of index ({n})")
+            T.unwrap(cols, bounds)
+            check_atom_count(seg_off[-1], len(cols["q"]))
             if m is None:
-                tm = cols[second]
-                m = np.asarray(self.mass, dtype=np.float64)[tm.astype(np.int64) - 1] if self.mass else tm
-                q = cols["q"]
+                m, q = T.masses(cols[second], self.mass), cols["q"]
             xu.append(np.stack([cols["xu"], cols["yu"], cols["zu"]]))
             steps.append(int(ts))
         if not xu:

@@ -20,17 +20,13 @@ import numpy as np
 import pandas as pd
 
 from .. import backend
+from .. import dist as D
 from ..common import constants
-from ..common.com_mols import atom_masses, molecule_layout
+from ..common import trajectory as T
+from ..common.com_mols import check_atom_count, molecule_layout
 from ..io import parse_lammps_dumps, parse_lammps_log  # noqa: F401  (parse_lammps_log: API parity)
 from ..utilities.log import concat_log
 
-
-def _writer():
-    """Only rank 0 writes result files under torch.distributed."""
-    from .. import dist as D
-
-    return D.is_writer()
 
 _COORDS = ["xu", "yu", "zu"]
 _DISPS = ["dx2", "dy2", "dz2"]
@@ -149,8 +145,6 @@ class Diffusion:
 
         if msd_type not in ("allatom", "com"):
             raise ValueError("msd_type must be 'allatom' or 'com'.")
-        from .. import dist as D
-
         times, planes = [], []
         ids = atom_mass = None
         pattern = f"{self.outputs_dir}/{filename}"
@@ -168,7 +162,7 @@ class Diffusion:
                     ids = cols["id"]
                 planes.append(np.ascontiguousarray(np.stack([cols["xu"], cols["yu"], cols["zu"]])))
                 if msd_type == "com":
-                    m = cols["mass"] if not mass else np.asarray(mass, dtype=np.float64)[cols["type"].astype(np.int64) - 1]
+                    m = T.masses(cols["type" if mass else "mass"], mass)
                     if atom_mass is None:
                         atom_mass = m
                     elif not np.array_equal(atom_mass, m):
@@ -186,9 +180,8 @@ class Diffusion:
             D.require_all_nonempty(len(planes), "dump file")  # every rank raises, or none
         if msd_type == "com":
             seg = molecule_layout(num_mols, num_atoms_per_mol)
-            if planes and seg[0][-1] != planes[0].shape[1]:
-                raise ValueError(f"Length of values ({int(seg[0][-1])}) does not match length "
-                                 f"of index ({planes[0].shape[1]})")
+            if planes:
+                check_atom_count(seg[0][-1], planes[0].shape[1])
             com, seg_mass, _ = backend.segment_com(np.stack(planes), atom_mass, seg[0])
             return times, com, dict(type=seg[1], mol_id=seg[2], mass=seg_mass), sharded
         r = np.stack(planes)
@@ -206,22 +199,12 @@ class Diffusion:
         except ImportError:  # libmdhip.so runs on the system ROCm runtime without torch (_lib.py): general route
             return None
 
-        from .. import dist as D
-        from .. import io as mio
-        from .. import stream as S
         from .._lib import default_context
 
-        mine = files if files is not None else mio._sorted_matches(pattern)
-        if not mine or any(str(f).endswith(".gz") for f in mine):
-            return None
-        nd = mio.NativeDumpFile(mine[0])
-        try:
-            names = nd.header(0)[4] if nd.n_frames else []
-        finally:
-            nd.close()
         # the staging batch carries id, ONE per-atom attribute and the three coordinate planes
-        second = "id" if msd_type == "allatom" else ("type" if mass else "mass")
-        if not {"id", "xu", "yu", "zu", second} <= set(names):
+        columns = ("id", "id" if msd_type == "allatom" else ("type" if mass else "mass")) + T.UNWRAPPED
+        mine = T.streamable_files(pattern, columns, files)
+        if mine is None:
             return None
         ctx = default_context()
         dev = torch.device("cuda", ctx.device)
@@ -230,16 +213,12 @@ class Diffusion:
         ids = atom_mass = seg_mass = None
         err = None
         try:
-            stream = S.FrameStream(pattern, files=mine, columns=("id", second, "xu", "yu", "zu"),
-                                   batch_bytes=STREAM_BATCH_BYTES)
-            for batch in stream:
+            for batch in T.stream_reduced(pattern, mine, columns, seg[0][-1] if seg else None, STREAM_BATCH_BYTES):
                 B, _, n = batch.xyz.shape
                 if ids is None:
                     ids = batch.ids[0].copy()
                 if msd_type == "com":
-                    if seg[0][-1] != n:
-                        raise ValueError(f"Length of values ({int(seg[0][-1])}) does not match length of index ({n})")
-                    m = batch.types if not mass else np.asarray(mass, dtype=np.float64)[batch.types.astype(np.int64) - 1]
+                    m = T.masses(batch.types, mass)
                     if atom_mass is None:
                         atom_mass = m[0].copy()
                     if not (m == atom_mass).all():
@@ -274,17 +253,15 @@ class Diffusion:
         (made from x + ix*L when they were not dumped, diffusion.py:62-81)."""
         from .. import io as mio
 
+        def missing(c, _have_unwrapped):  # (the reference asserts on z and iz only; the reader names any other)
+            assert c != "z", "Missing wrapped and unwrapped coordinates (x y z xu yu zu)"
+            assert c != "iz", (
+                "Missing unwrapped coordinates (xu yu zu) and box location (ix iy iz) for converting "
+                "wrapped coordinates (x y z) into unwrapped coordinates. ")
+
         def wanted(names):
             assert "id" in names, "Missing atom id's in dump file."
-            sel = ["id"]
-            if "zu" in names:
-                sel += ["xu", "yu", "zu"]
-            else:
-                assert "z" in names, "Missing wrapped and unwrapped coordinates (x y z xu yu zu)"
-                assert "iz" in names, (
-                    "Missing unwrapped coordinates (xu yu zu) and box location (ix iy iz) for converting "
-                    "wrapped coordinates (x y z) into unwrapped coordinates. ")
-                sel += ["x", "y", "z", "ix", "iy", "iz"]
+            sel = T.unwrapped_columns(names, ["id"], missing, decide_on=("zu",))  # (and tests only zu)
             if msd_type == "com":
                 if not mass:
                     assert "mass" in names, "Missing atom masses in dump file."
@@ -296,11 +273,7 @@ class Diffusion:
         if native:
             for ts, bounds, _lengths, names, planes in mio.iter_native_frames(pattern, wanted, sort_by="id",
                                                                                files=files):
-                cols = dict(zip(wanted(names), planes))
-                if "zu" not in cols:
-                    for k, axis in enumerate("xyz"):
-                        cols[axis + "u"] = cols[axis] + cols["i" + axis] * (bounds[k][1] - bounds[k][0])
-                yield ts, names, cols
+                yield ts, names, T.unwrap(dict(zip(wanted(names), planes)), bounds)
             return
         for dump in parse_lammps_dumps(pattern):
             names = list(dump.data.columns)
@@ -330,8 +303,6 @@ class Diffusion:
                 return got
             # frames out of time order ACROSS ranks: the blocks cannot be reduced where they are; gather them (device
             # to device on RCCL) and go on as one process would
-            from .. import dist as D
-
             counts = D.allgather_counts(len(times))
             times, r = D.allgather_var(times, counts), D.allgather_var(r, counts)
         order = np.argsort(times, kind="stable")  # the reference sorts its (time, id) index
@@ -416,8 +387,6 @@ class Diffusion:
         Returns None when the ranks' blocks are not in time order one after the other (the caller then gathers the
         frames and reduces them as one process).
         """
-        from .. import dist as D
-
         rank, world = D.rank_world()
         counts = D.allgather_counts(len(times_l))
         times = D.allgather_var(np.asarray(times_l, dtype=np.float64), counts)
@@ -529,13 +498,13 @@ class Diffusion:
             table[k] = [fit.slope / (2 * dimension), fit.bse / (2 * dimension), fit.rsquared]
             if save:
                 tag = diff_names[k] if diff_names else k + 1
-                with open(f"{self.diff_dir}/diff_{tag}.txt" if _writer() else os.devnull, "w") as fh:
+                with open(f"{self.diff_dir}/diff_{tag}.txt" if D.is_writer() else os.devnull, "w") as fh:
                     fh.write(str(fit.summary()))
         index = diff_names or [k + 1 for k in range(len(names))]
         diffusion = pd.DataFrame(table, columns=["diffusion (m2/s)", "std", "R2"], index=index)
         if plot:
             self._plot_msd(msd, names, fits, index)
-        if _writer():
+        if D.is_writer():
             diffusion.to_csv(f"{self.diff_dir}/diffusion.csv")
             print("Diffusion results written to a .csv file.")
         return diffusion

@@ -36,21 +36,14 @@ from scipy.special import gamma
 
 from .. import backend
 from .. import io as mio
+from ..common import sayer
+from ..dist import is_writer
 from ..structural.rdf_cn import _calc_atom_type, _load_frames
 
 VERBOSE = False
 
 
-def _say(*args):
-    if VERBOSE:
-        print(*args)
-
-
-def _is_writer():
-    """Only rank 0 writes files under torch.distributed (every rank computes the same tables)."""
-    from .. import dist as D
-
-    return D.is_writer()
+_say = sayer(globals())
 
 
 class ResidenceTime:
@@ -117,7 +110,7 @@ class ResidenceTime:
                 corr = corr / corr[0]                                           # residence_time.py:142
             correlation[atom_pair] = corr
         self.corr_df = pd.DataFrame.from_dict(correlation)
-        if _is_writer():
+        if is_writer():
             self.corr_df.to_csv(self.working_dir + "/auto_correlation.csv")
 
     def fit_auto_correlation(self, cut_percent=0.9, plot=True):
@@ -137,7 +130,7 @@ class ResidenceTime:
         print("Finished computing residence time")
         self.res_time_df = pd.DataFrame(residence_time)
         self.res_time_df.index = ["a", "tau_res", "tau_short", "beta", "r (ps)"]
-        if _is_writer():
+        if is_writer():
             self.res_time_df.to_csv(self.working_dir + "/residence_time.csv")
         return residence_time
 
@@ -157,7 +150,7 @@ class ResidenceTime:
         ax.legend(frameon=False, fontsize=20)
         ax.set_xlabel("Time (ps)", fontsize=20)
         ax.set_ylabel("C(t)", fontsize=20)
-        if _is_writer():
+        if is_writer():
             fig.savefig(self.working_dir + f"/{col}_fit.png", bbox_inches="tight", pad_inches=0.1)
         plt.close()
 
@@ -273,7 +266,7 @@ class Displacement:
             for g, t in enumerate(self.atom_types):
                 dist[t] = hist[g] / (w[g] * self.bin_size)
         self.hist_df = pd.DataFrame(dist)
-        if self.save_mode and _is_writer():
+        if self.save_mode and is_writer():
             self.dist_df.to_csv(self.working_dir + "/displacement.csv")
             self.hist_df.to_csv(self.working_dir + "/displacement_distribution.csv")
         return self.dist_df
@@ -308,7 +301,7 @@ class Displacement:
             gs[t] = pd.DataFrame(cols)
             alpha2[t] = a2[g * n:(g + 1) * n]
         alpha2 = pd.DataFrame(alpha2)
-        if self.save_mode and _is_writer():
+        if self.save_mode and is_writer():
             for t, df in gs.items():
                 df.to_csv(self.working_dir + "/van_hove_%s.csv" % t)
             alpha2.to_csv(self.working_dir + "/alpha2.csv")

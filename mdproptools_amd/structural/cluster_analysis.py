@@ -36,6 +36,7 @@ import pandas as pd
 from .. import backend
 from .. import io as mio
 from ..common.com_mols import check_atom_count, molecule_layout
+from ..common.trajectory import frame_refs, read_frame
 from .rdf_cn import _calc_atom_type
 
 FORCE_CONSTANT = 0.043363 / 16.0  # cluster_analysis.py:29
@@ -59,33 +60,6 @@ def _layout(num_mols, num_atoms_per_mol):
     return mol_of, seg_off, mol_type
 
 
-def _frame_refs(filename):
-    """(file, frame within the file) of every frame, in parse_lammps_dumps order."""
-    refs = []
-    for fname in mio._sorted_matches(filename):
-        if str(fname).endswith(".gz"):
-            n = sum(1 for _ in mio._iter_frames(fname))
-        else:
-            nd = mio.NativeDumpFile(fname)
-            n = nd.n_frames
-            nd.close()
-        refs += [(fname, k) for k in range(n)]
-    return refs
-
-
-def _read_frame(fname, k):
-    """(timestep, bounds [3,2], column names, planes [8, N] of _COLS sorted by id) of frame k of one file."""
-    if str(fname).endswith(".gz"):
-        ts, bounds, _, names, planes = mio._pandas_file_frames(fname, _COLS, "id")[k]
-        return ts, bounds, names, planes
-    nd = mio.NativeDumpFile(fname)
-    try:
-        ts, _, bounds, _, names = nd.header(k)
-        return ts, bounds, names, nd.read(k, _COLS, sort_by="id")
-    finally:
-        nd.close()
-
-
 def _element_column(fname, k):
     """The dump's own `element` column of frame k, in id order (text: the pandas route)."""
     for j, lines in enumerate(mio._iter_frames(fname)):
@@ -97,14 +71,14 @@ def _element_column(fname, k):
 
 def _frames(filename, full_trajectory, frame, refs=None):
     """-> (number of frames processed, iterator of (file, frame in file, timestep, bounds, names, planes)); `refs`:
-    _frame_refs(filename) when the caller has it already."""
-    refs = _frame_refs(filename) if refs is None else refs
+    frame_refs(filename) when the caller has it already."""
+    refs = frame_refs(filename) if refs is None else refs
     if not full_trajectory:
         refs = [refs[frame]]  # dumps[frame] (cluster_analysis.py:104-107): Python indexing, its errors included
 
         def one():
             fname, k = refs[0]
-            yield (fname, k) + _read_frame(fname, k)
+            yield (fname, k) + read_frame(fname, k, _COLS)
 
         return 1, one()
 
@@ -177,14 +151,14 @@ class _Source:
     def reread(self, index):
         """The prepared frame of processed-frame index `index` (after batches()), read again on its own."""
         fname, k = self.refs[index if self.full_trajectory else self.frame]
-        return self.prepare((fname, k) + _read_frame(fname, k))
+        return self.prepare((fname, k) + read_frame(fname, k, _COLS))
 
     def batches(self, same=None):
         """
         -> (number of frames processed, iterator of (index of the batch's first frame, batch)), a batch a list of
         prepared frames with the same centres (and, when given, the same same(frame)) of at most MAX_BATCH_BYTES.
         """
-        self.refs = _frame_refs(self.filename)
+        self.refs = frame_refs(self.filename)
         n_frames, frames = _frames(self.filename, self.full_trajectory, self.frame, self.refs)
 
         def it():

@@ -26,12 +26,13 @@ import numpy as np
 import pandas as pd
 
 from .. import backend
-from .. import io as mio
-from ..common.com_mols import check_atom_count, molecule_layout
+from ..common.com_mols import molecule_layout
+from ..common.trajectory import frame_batches
 
 VERBOSE = False
 COS_CUT = -0.72  # hydration_number.py:35
 MAX_BATCH_BYTES = 1 << 28  # coordinates of the frames handed to the GPU in one call
+_COLS = ["id", "x", "y", "z"]  # the planes of a batch
 
 
 def _layout(cation_type, water_type, num_mols, num_atoms_per_mol):
@@ -49,26 +50,8 @@ def _layout(cation_type, water_type, num_mols, num_atoms_per_mol):
     return int(seg_off[-1]), cations, seg_off[water_mols].astype(np.int32)
 
 
-def _iter_batches(pattern, n_atoms):
-    """Batches of whole frames: (timesteps, box lengths [B,3], xyz [B,3,N], first ids [B,N]), at most MAX_BATCH_BYTES
-    of coordinates each, in parse_lammps_dumps order."""
-    steps, boxes, planes = [], [], []
-    per_frame = 4 * n_atoms * 8
-    for ts, bounds, _, _, pl in mio.iter_native_frames(pattern, ["id", "x", "y", "z"], sort_by="id"):
-        check_atom_count(n_atoms, pl.shape[1])
-        b = np.asarray(bounds, dtype=np.float64)
-        steps.append(int(ts))
-        boxes.append(b[:, 1] - b[:, 0])
-        planes.append(pl)
-        if len(planes) * per_frame >= MAX_BATCH_BYTES:
-            yield steps, np.stack(boxes), planes
-            steps, boxes, planes = [], [], []
-    if planes:
-        yield steps, np.stack(boxes), planes
-
-
 def _xyz(planes):
-    return np.ascontiguousarray(np.stack([p[1:4] for p in planes]))
+    return np.ascontiguousarray(planes[:, 1:4])
 
 
 def get_hydration_number(dump_pattern, cation_type, water_type, r_cut, alter_atom_ids=False, num_mols=None,
@@ -84,7 +67,7 @@ def get_hydration_number(dump_pattern, cation_type, water_type, r_cut, alter_ato
     n_atoms, cations, waters = _layout(cation_type, water_type, num_mols, num_atoms_per_mol)
     rc2 = r_cut ** 2  # hydration_number.py:20
     cosines, factors = [], []
-    for steps, boxes, planes in _iter_batches(os.path.join(working_dir, dump_pattern), n_atoms):
+    for steps, boxes, planes in frame_batches(os.path.join(working_dir, dump_pattern), _COLS, MAX_BATCH_BYTES, n_atoms):
         _, cos, count = backend.hydration_cosines(_xyz(planes), boxes, cations, waters, rc2)
         for j in range(len(planes)):
             if VERBOSE:
@@ -118,7 +101,7 @@ def calc_hydration_orientation(filename, cation_type, water_type, r_cut, num_mol
     hist = np.zeros(n_bins, dtype=np.uint64)
     meta, nw, na = [], [], []
     index = 0
-    for steps, boxes, planes in _iter_batches(filename, n_atoms):
+    for steps, boxes, planes in frame_batches(filename, _COLS, MAX_BATCH_BYTES, n_atoms):
         n_water, n_away, h = backend.hydration_counts(_xyz(planes), boxes, cations, waters, r_cut ** 2, cos_cut, w,
                                                       n_bins)
         hist += h

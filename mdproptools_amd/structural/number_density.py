@@ -29,8 +29,8 @@ import numpy as np
 import pandas as pd
 
 from .. import backend
-from .. import io as mio
-from ..common.com_mols import check_atom_count, molecule_layout
+from ..common.com_mols import molecule_layout
+from ..common.trajectory import frame_batches, same_labels
 from .rdf_cn import _calc_atom_type, _save_rdf
 
 VERBOSE = False
@@ -69,32 +69,13 @@ def _codes(labels, surface_atom, uniq):
     return backend.axis_profile_codes(row, labels == surface_atom)
 
 
-def _iter_batches(pattern, axis, n_atoms=None):
-    """Batches of whole frames in parse_lammps_dumps order, atoms by id: (timesteps, box lengths [B,3], planes
-    [B,3,N] = id, type and the axis coordinate), at most MAX_BATCH_BYTES of coordinates each. A batch holds frames of
-    one size."""
-    steps, boxes, planes = [], [], []
-    for ts, bounds, _, _, pl in mio.iter_native_frames(pattern, ["id", "type", axis], sort_by="id"):
-        if n_atoms is not None:
-            check_atom_count(n_atoms, pl.shape[1])
-        if planes and (pl.shape[1] != planes[0].shape[1] or len(planes) * pl.shape[1] * 8 >= MAX_BATCH_BYTES):
-            yield steps, np.stack(boxes), np.stack(planes)
-            steps, boxes, planes = [], [], []
-        b = np.asarray(bounds, dtype=np.float64)
-        steps.append(int(ts))
-        boxes.append(b[:, 1] - b[:, 0])
-        planes.append(pl)
-    if planes:
-        yield steps, np.stack(boxes), np.stack(planes)
-
-
 def _labels(planes, num_mols, num_atoms_per_mol):
     """Atom labels of a batch, [N] when every frame carries the same ones, else [B,N]."""
     if num_mols and num_atoms_per_mol:
         lab = _calc_atom_type(planes[:, 0], num_mols, num_atoms_per_mol)
     else:
         lab = planes[:, 1]
-    return lab[0] if (lab == lab[0]).all() else lab
+    return same_labels(lab)
 
 
 def _cross_section(box, ax):
@@ -124,7 +105,9 @@ def calc_number_density(dump_pattern, surface_atom, atom_types, bin_size, dist_f
     mode = backend.AP_REF_POS if dist_from_interface > 0 else backend.AP_REF_NEG
     total = np.zeros((len(atom_types), n_bins))
     n_frames = 0
-    for steps, boxes, planes in _iter_batches(os.path.join(working_dir, dump_pattern), axis_norm_interface):
+    # batches of planes [B,3,N]: id, type and the axis coordinate
+    for steps, boxes, planes in frame_batches(os.path.join(working_dir, dump_pattern),
+                                              ["id", "type", axis_norm_interface], MAX_BATCH_BYTES):
         codes = _codes(_labels(planes, num_mols, num_atoms_per_mol), surface_atom, uniq)
         counts, _, outside = backend.axis_profile(np.ascontiguousarray(planes[:, 2]), codes, mode, bin_size,
                                                   dist_from_interface, n_bins, len(uniq))
@@ -176,7 +159,8 @@ def calc_density_profile(filename, surface_atom, atom_types, bin_size, axis, s_m
         seg_off, mol_type, _ = molecule_layout(num_mols, num_atoms_per_mol)
         mol_codes = _codes(mol_type, None, uniq)
     counts_all, extent_all, outside_all, steps_all, box_all, com_all = [], [], [], [], [], []
-    for steps, boxes, planes in _iter_batches(filename, axis, int(seg_off[-1]) if com else None):
+    for steps, boxes, planes in frame_batches(filename, ["id", "type", axis], MAX_BATCH_BYTES,
+                                              int(seg_off[-1]) if com else None):
         x = np.ascontiguousarray(planes[:, 2])
         if com:
             counts, extent, outside, sites = _com_batch(x, planes[:, 1], surface_atom, origin, mass, seg_off,
@@ -222,7 +206,7 @@ def _com_batch(x, types, surface_atom, origin, mass, seg_off, mol_codes, w, s_mi
     import torch
 
     ctx = backend.default_context()
-    lab = types[0] if (types == types[0]).all() else types
+    lab = same_labels(types)
     x = torch.from_numpy(x).to("cuda:%d" % ctx.device)
     _, extent, _ = backend.axis_profile(x, _codes(lab, surface_atom, []), backend.AP_PROFILE, w, s_min, 1, 1, ctx=ctx)
     org = {"top": extent[:, 1], "bottom": extent[:, 0]}[origin] if isinstance(origin, str) \

@@ -29,7 +29,10 @@ import numpy as np
 import pandas as pd
 
 from .. import backend
+from ..common import sayer
 from ..common.com_mols import check_atom_count, molecule_layout
+from ..common.trajectory import same_labels
+from ..dist import is_writer
 from ..io import parse_lammps_dumps
 
 CON_CONSTANT = 1.660538921  # amu/A^3 -> g/cm^3 (rdf_cn.py:30)
@@ -41,9 +44,7 @@ STREAM = True  # parse the next batch of frames (into page-locked staging buffer
 _R_LABEL = "r ($\\AA$)"
 
 
-def _say(*args):
-    if VERBOSE:
-        print(*args)
+_say = sayer(globals())
 
 
 # ------------------------------------------------------------------------------------------------
@@ -80,12 +81,6 @@ def _calc_atom_type(ids, num_mols, num_atoms):
     v[v == 0] = num_atoms[w][v == 0]
     out[inside] = v + np.concatenate(([0], np.cumsum(num_atoms)[:-1]))[w]
     return out
-
-
-def _molecule_layout(num_mols, num_atoms_per_mol):
-    """Segment offsets and molecule type labels implied by the sorted-id order (rdf_cn.py:222-230)."""
-    seg_off, seg_type, _ = molecule_layout(num_mols, num_atoms_per_mol)
-    return seg_off, seg_type.astype(np.int32)
 
 
 def _type_counts(labels):
@@ -238,7 +233,7 @@ def _labels_and_props(batch, altered, num_mols, num_atoms_per_mol, num_types, ma
     labels = [(_calc_atom_type(f.ids, num_mols, num_atoms_per_mol) if altered else f.types) for f in batch]
     props = [_calc_props_memo(f.lengths, lab, lab, num_types, mass, partial_relations, altered, num_atoms_per_mol)
              for f, lab in zip(batch, labels)]
-    return _labels_for(batch, labels), props
+    return same_labels(labels).astype(np.int32), props
 
 
 def _write_csv(df, path_or_buf):
@@ -379,13 +374,6 @@ def _all_frames(per_frame_rows):
     return D.allgather_var(rows, counts=counts)
 
 
-def _is_writer():
-    """Only rank 0 writes files under torch.distributed (every rank returns the same DataFrame)."""
-    from .. import dist as D
-
-    return D.rank_world()[0] == 0
-
-
 class _Batch(list):
     """The frames of one library call; `block` = their coordinates as ONE array [B,3,N] when they already sit in a
     staging buffer (streamed batches), else None."""
@@ -426,14 +414,6 @@ def _batches(frames):
             stop += 1
         yield frames[start:stop]
         start = stop
-
-
-def _labels_for(frames, labels_per_frame):
-    """[N] when every frame carries the same labels, else [F, N]."""
-    first = labels_per_frame[0]
-    if all(np.array_equal(first, lab) for lab in labels_per_frame[1:]):
-        return first.astype(np.int32)
-    return np.stack(labels_per_frame).astype(np.int32)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -483,7 +463,7 @@ def calc_atomic_rdf(r_cut, bin_size, num_types, mass, partial_relations, filenam
         print(f"calc_atomic_rdf: {dropped} pair(s) fell in bin index {num_bins} (== num_bins) and were dropped")
     rdf_full_sum = rdf_full_sum / num_files
     rdf_part_sum = rdf_part_sum / num_files
-    return _save_rdf(radii, relation_matrix, path_or_buff, save_mode and _is_writer(), rdf_part_sum,
+    return _save_rdf(radii, relation_matrix, path_or_buff, save_mode and is_writer(), rdf_part_sum,
                      rdf_full_sum=rdf_full_sum)
 
 
@@ -513,7 +493,7 @@ def calc_atomic_cn(r_cut, bin_size, num_types, mass, partial_relations, filename
     for row in rows:
         cn_sum += row
     cn_sum = cn_sum / num_files
-    return _save_cn(relation_matrix, path_or_buff, cn_sum, save_mode and _is_writer())
+    return _save_cn(relation_matrix, path_or_buff, cn_sum, save_mode and is_writer())
 
 
 def calc_atomic_rdf_cn(r_cut, cn_r_cut, bin_size, num_types, mass, partial_relations, filename, num_mols=None,
@@ -551,9 +531,9 @@ def calc_atomic_rdf_cn(r_cut, cn_r_cut, bin_size, num_types, mass, partial_relat
     cn_sum = _sum_frames(cn_rows) if n_frames else np.zeros(num_relations)
     if dropped:
         print(f"calc_atomic_rdf_cn: {dropped} pair(s) fell in bin index {num_bins} (== num_bins) and were dropped")
-    g = _save_rdf(radii, relation_matrix, rdf_path_or_buff, save_mode and _is_writer(), rdf_part_sum / n_frames,
+    g = _save_rdf(radii, relation_matrix, rdf_path_or_buff, save_mode and is_writer(), rdf_part_sum / n_frames,
                   rdf_full_sum=rdf_full_sum / n_frames)
-    c = _save_cn(relation_matrix, cn_path_or_buff, cn_sum / n_frames, save_mode and _is_writer())
+    c = _save_cn(relation_matrix, cn_path_or_buff, cn_sum / n_frames, save_mode and is_writer())
     return g, c
 
 
@@ -563,7 +543,8 @@ def _same_types(batch):
 
 def _molecular_inputs(batch, num_mols, num_atoms_per_mol, mass):
     """Device-side COM of wrapped coordinates for every frame of the batch (rdf_cn.py:218-241)."""
-    seg_off, seg_type = _molecule_layout(num_mols, num_atoms_per_mol)
+    seg_off, seg_type, _ = molecule_layout(num_mols, num_atoms_per_mol)  # (rdf_cn.py:222-230)
+    seg_type = seg_type.astype(np.int32)
     check_atom_count(seg_off[-1], batch[0].xyz.shape[1])
     xyz = _xyz_block(batch)
     atom_mass = np.asarray(mass, dtype=np.float64)[batch[0].types.astype(np.int64) - 1]
@@ -612,7 +593,7 @@ def calc_molecular_rdf(r_cut, bin_size, num_types, mass, partial_relations, file
     if dropped:
         print(f"calc_molecular_rdf: {dropped} pair(s) fell in bin index {num_bins} (== num_bins) and were dropped")
     rdf_part_sum = rdf_part_sum / num_files
-    return _save_rdf(radii, relation_matrix, path_or_buff, save_mode and _is_writer(), rdf_part_sum)
+    return _save_rdf(radii, relation_matrix, path_or_buff, save_mode and is_writer(), rdf_part_sum)
 
 
 def _per_frame_mol_rdf(batch, sites, seg_type, relation_matrix, r_cut, bin_size, num_bins):
@@ -653,7 +634,7 @@ def calc_molecular_cn(r_cut, bin_size, num_types, mass, partial_relations, filen
     for row in rows:
         cn_sum += row
     cn_sum = cn_sum / num_files
-    return _save_cn(relation_matrix, path_or_buff, cn_sum, save_mode and _is_writer())
+    return _save_cn(relation_matrix, path_or_buff, cn_sum, save_mode and is_writer())
 
 
 def calc_intermolecular_rdf(r_cut, bin_size, num_types, mass, partial_relations, filename, num_mols,
@@ -683,4 +664,4 @@ def calc_intermolecular_rdf(r_cut, bin_size, num_types, mass, partial_relations,
     for row in rows:
         rdf_part_sum += row.reshape(num_relations, num_bins)
     rdf_part_sum = rdf_part_sum / num_files
-    return _save_rdf(radii, relation_matrix, path_or_buff, save_mode and _is_writer(), rdf_part_sum)
+    return _save_rdf(radii, relation_matrix, path_or_buff, save_mode and is_writer(), rdf_part_sum)
