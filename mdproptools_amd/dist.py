@@ -33,7 +33,9 @@ host memory, since gloo gathers only host tensors.
 oracle as the stand-in (tests/test_dist_gloo.py); the product default is the GPU backend.
 """
 
+import contextlib
 import os
+import weakref
 
 import numpy as np
 
@@ -505,8 +507,114 @@ def frame_blocks(n_frames_total, counts=None, world=None):
 
 def frame_owner(n_frames_total, frame, world=None, counts=None):
     """The rank whose contiguous frame block holds `frame`."""
-    blocks = frame_blocks(n_frames_total, counts, world)
+    return _owner_of(frame_blocks(n_frames_total, counts, world), frame)
+
+
+def _owner_of(blocks, frame):
     return next(r for r, (lo, hi) in enumerate(blocks) if lo <= frame < hi)
+
+
+# The shard plan of the MSD paths, _FramePlan and _LagShard: arithmetic only — no process group, no device, no I/O.
+
+
+class _FramePlan:
+    """A trajectory dealt to the ranks in contiguous blocks (frame_blocks) as `rank` sees it: every rank's block and its
+    own [lo, hi); `owner`, the rank that holds origin_frame; `kept_local`, its kept frames (0, tao, 2 tao, ... of the
+    GLOBAL order) as indices into its block, and the first of them, `k0`; `halo_rank`: a window (k - 1, k) belongs to the
+    rank that holds kept frame k, so the window of this rank's first kept frame reaches back to the last kept frame of the
+    nearest rank below that has one — that rank, or None."""
+
+    def __init__(self, n_frames_total, tao, origin_frame, counts, rank, world):
+        self.n_frames, self.tao, self.origin_frame = int(n_frames_total), int(tao), origin_frame
+        self.rank, self.world = rank, world
+        self.blocks = frame_blocks(n_frames_total, counts, world)
+        self.lo, self.hi = self.blocks[rank]
+
+        def kept_of(a, b):  # global indices of the kept frames inside [a, b)
+            return np.arange(-(-a // self.tao) * self.tao, b, self.tao)
+
+        self.kept_local = kept_of(self.lo, self.hi) - self.lo
+        self.k0 = int(self.kept_local[0]) if len(self.kept_local) else 0
+        self.halo_rank = next((q for q in range(rank - 1, -1, -1) if len(kept_of(*self.blocks[q]))), None)
+
+    @property
+    def owner(self):  # (on demand: a caller without a process group needs none)
+        return _owner_of(self.blocks, self.origin_frame)
+
+
+class _LagShard:
+    """This rank's part of every group when the ENTITIES entity_range = (e_lo, e_hi) of the global order are its own:
+    `held`, the groups it holds something of (the others are left out of its call; the held ones are contiguous in the
+    slice, since groups are contiguous globally); `loc_off`, their column offsets in the slice, `cols` the columns they
+    cover, `call_off` the offsets from the first of them (the library call's group_off); `weights` [n_lags, held],
+    origins of a lag x this rank's entities of a group — a mean of the call times its weight is this rank's share of the
+    group's SUM; `counts` [n_lags, G], origins x entities of the whole group: the ranks' weights add up to it."""
+
+    def __init__(self, group_off, entity_range, n_frames, n_lags):
+        e_lo, e_hi = int(entity_range[0]), int(entity_range[1])
+        goff = np.asarray(group_off, dtype=np.int64)
+        self.n_frames, self.n_lags, self.G = int(n_frames), int(n_lags), len(goff) - 1
+        lo = np.clip(goff[:-1], e_lo, e_hi) - e_lo
+        hi = np.clip(goff[1:], e_lo, e_hi) - e_lo
+        self.held = [g for g in range(self.G) if hi[g] > lo[g]]
+        self.sizes = (hi - lo)[np.asarray(self.held, dtype=np.int64)]
+        origins = (self.n_frames - np.arange(self.n_lags)).astype(np.float64)[:, None]
+        self.counts = origins * (goff[1:] - goff[:-1]).astype(np.float64)[None, :]
+        self.weights = origins * self.sizes.astype(np.float64)[None, :]
+        self.loc_off = np.array([lo[g] for g in self.held[:1]] + [hi[g] for g in self.held], dtype=np.int64)
+        self.cols = slice(int(self.loc_off[0]), int(self.loc_off[-1])) if self.held else slice(0, 0)
+        self.call_off = self.loc_off - self.loc_off[:1]
+        self.has_work = bool(self.held) and self.n_frames > 0
+
+
+_LAG_WEIGHTS = {}  # (device, F, n_lags, held sizes, held indices) -> (weights [n_lags, held, 1], index of the held groups)
+
+
+def _lag_weights(shard, dev):
+    """A _LagShard's weights and the index of its held groups as tensors on `dev`. They depend on the shapes only and are
+    kept from call to call: fresh tensors would be synchronous copies from pageable memory in every step."""
+    import torch
+
+    key = (str(dev), shard.n_frames, shard.n_lags, tuple(int(v) for v in shard.sizes), tuple(shard.held))
+    cached = _LAG_WEIGHTS.get(key)
+    if cached is None:
+        if len(_LAG_WEIGHTS) > 16:
+            _LAG_WEIGHTS.clear()
+        cached = _LAG_WEIGHTS[key] = (torch_from(shard.weights[:, :, None], dev), torch.as_tensor(shard.held, device=dev))
+    return cached
+
+
+def torch_from(a, dev):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _weighted_into(dst, means, weights, held):
+    """dst[:, held, :] = means * weights: the means [n_lags, len(held), 4] of a rank's lag call become its share of the
+    per-(lag, group) sums in dst [n_lags, G, 4] (numpy arrays, or tensors with `held` an index tensor). Tensors with every
+    group held: the product lands in dst itself — one kernel."""
+    if _is_tensor(dst) and means.shape[1] == dst.shape[1]:
+        import torch
+
+        torch.mul(means, weights, out=dst)
+    else:
+        dst[:, held, :] = means * weights
+
+
+def _sums_to_means(sums, counts):
+    """Reduced sums [n_lags, G, 4] over the global counts [n_lags, G] (host arrays); 0 where nothing was counted."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(counts[:, :, None] > 0, sums / np.maximum(counts, 1.0)[:, :, None], 0.0)
+
+
+def _halo_window(first, halo, scale):
+    """[E,4] of the one window that reaches back to the rank below, from this rank's first kept frame and the halo frame
+    [3,E]: three planes of arithmetic (the kernel's operations: scale, subtract, square, (dx2 + dy2) + dz2)."""
+    import torch
+
+    d2 = (first * scale - halo * scale) ** 2
+    return torch.stack([d2[0], d2[1], d2[2], (d2[0] + d2[1]) + d2[2]], dim=1)
 
 
 def msd_single_origin_sharded(r_local, n_frames_total, group_off, scale=1.0, origin_frame=0, compute=None, ctx=None,
@@ -521,10 +629,8 @@ def msd_single_origin_sharded(r_local, n_frames_total, group_off, scale=1.0, ori
     (backend.msd_origin); `counts`: per-rank frame counts when the split is not frame_shard's.
     """
     rank, world = rank_world()
-    blocks = frame_blocks(n_frames_total, counts, world)
-    lo, hi = blocks[rank]
-    owner = frame_owner(n_frames_total, origin_frame, world, counts)
-    cnts = [b - a for a, b in blocks]
+    plan = _FramePlan(n_frames_total, 1, origin_frame, counts, rank, world)
+    lo, hi, owner, cnts = plan.lo, plan.hi, plan.owner, [b - a for a, b in plan.blocks]
     E = r_local.shape[2]
     G = len(group_off) - 1
     if int(r_local.shape[0]) != hi - lo:
@@ -565,15 +671,9 @@ def msd_windows_sharded(r_local, n_frames_total, tao, scale=1.0, compute=None, c
     bits may differ from a single-GPU run; inside the rtol 1e-10 bar by orders of magnitude).
     """
     rank, world = rank_world()
-    blocks = frame_blocks(n_frames_total, counts, world)
-    lo, hi = blocks[rank]
+    plan = _FramePlan(n_frames_total, tao, None, counts, rank, world)
+    kept_local, tao = plan.kept_local, plan.tao
     E = int(r_local.shape[2])
-    tao = int(tao)
-
-    def kept_of(a, b):  # global indices of the kept frames inside [a, b)
-        return np.arange(-(-a // tao) * tao, b, tao)
-
-    kept_local = kept_of(lo, hi) - lo
     dev = _is_tensor(r_local) and r_local.is_cuda and compute is None
     if compute is None:
         from . import backend
@@ -586,32 +686,22 @@ def msd_windows_sharded(r_local, n_frames_total, tao, scale=1.0, compute=None, c
 
         zero = torch.zeros((1, 3, E), dtype=torch.float64, device=r_local.device)
         mine = r_local[int(kept_local[-1])][None] if len(kept_local) else zero
-        lasts = allgather_var(mine, counts=[1] * world) if world > 1 else mine
     else:
         r_np = np.asarray(r_local.cpu() if _is_tensor(r_local) else r_local)
         mine = r_np[int(kept_local[-1])][None] if len(kept_local) else np.zeros((1, 3, E))
-        lasts = allgather_var(mine, counts=[1] * world) if world > 1 else mine
         kept = r_np[kept_local]
-    # the halo: the last kept frame of the nearest rank below that has one
-    halo = None
-    for q in range(rank - 1, -1, -1):
-        if len(kept_of(*blocks[q])):
-            halo = lasts[q]
-            break
+    lasts = allgather_var(mine, counts=[1] * world) if world > 1 else mine
+    halo = None if plan.halo_rank is None else lasts[plan.halo_rank]
     if dev:
         from . import backend
 
         sums = torch.zeros((E, 4), dtype=torch.float64, device=r_local.device)
         if len(kept_local):
             # my kept frames lie tao apart from the first one on: the kernel strides over them where they are (no
-            # gathered copy of every tao-th frame) ...
-            k0 = int(kept_local[0])
-            backend.msd_windows(r_local[k0:], tao, scale=scale, ctx=ctx, out=sums)
+            # gathered copy of every tao-th frame); the one window that reaches back to the rank below is added to it
+            backend.msd_windows(r_local[plan.k0:], tao, scale=scale, ctx=ctx, out=sums)
             if halo is not None:
-                # ... and the one window that reaches back to the rank below is three planes of arithmetic
-                # (the kernel's operations: scale, subtract, square, (dx2 + dy2) + dz2)
-                d2 = (r_local[k0] * scale - halo * scale) ** 2
-                sums += torch.stack([d2[0], d2[1], d2[2], (d2[0] + d2[1]) + d2[2]], dim=1)
+                sums += _halo_window(r_local[plan.k0], halo, scale)
         sums = allreduce_tensor(sums)
         return sums if return_device else sums.cpu().numpy()
     block = kept if halo is None else np.concatenate([halo[None], kept])
@@ -648,9 +738,6 @@ def charge_flux_sharded(vel_local, n_frames_total, atom_mass, atom_q, seg_off, s
     return np.moveaxis(allgather_rows(rows, n_frames_total), 0, 2)
 
 
-_LAG_CONST = {}  # lag_msd_sharded: device-resident weights per (device, shapes)
-
-
 def lag_msd_sharded(r_local, entity_range, max_lag, group_off, scale=1.0, compute=None, ctx=None):
     """
     Full lag x origin MSD (mdhip_lag_msd; the compute-bound superset of diffusion.py:225-238) with the ENTITIES
@@ -669,64 +756,33 @@ def lag_msd_sharded(r_local, entity_range, max_lag, group_off, scale=1.0, comput
         def compute(r, ml, goff, sc):
             return backend.lag_msd(r, ml, goff, scale=sc, ctx=ctx)
 
-    e_lo, e_hi = int(entity_range[0]), int(entity_range[1])
-    goff = np.asarray(group_off, dtype=np.int64)
-    G = len(goff) - 1
-    F = int(r_local.shape[0])
     n_lags = int(max_lag) + 1
-    # this rank's part of every group, as local offsets; groups it holds nothing of are left out of the call
-    lo = np.clip(goff[:-1], e_lo, e_hi) - e_lo
-    hi = np.clip(goff[1:], e_lo, e_hi) - e_lo
-    held = [g for g in range(G) if hi[g] > lo[g]]
-    counts = (F - np.arange(n_lags)).astype(np.float64)[:, None] * (goff[1:] - goff[:-1]).astype(np.float64)[None, :]
-    origins = (F - np.arange(n_lags)).astype(np.float64)[:, None]
+    shard = _LagShard(group_off, entity_range, int(r_local.shape[0]), n_lags)
     if dev:
         import torch
 
         from . import backend
 
-        sums = torch.zeros((n_lags, G, 4), dtype=torch.float64, device=r_local.device)
-        if held and F > 0:
-            loc_off = np.array([lo[held[0]]] + [hi[g] for g in held], dtype=np.int64)
-            x = r_local[:, :, int(loc_off[0]):int(loc_off[-1])].contiguous()
-            means = torch.empty((n_lags, len(held), 4), dtype=torch.float64, device=r_local.device)
-            backend.lag_msd(x, int(max_lag), loc_off - loc_off[0], scale=scale, ctx=ctx, out=means)
-            # (the weights and the index of the held groups depend on the shapes only: kept on the device between calls)
-            key = (str(r_local.device), F, n_lags, tuple(int(v) for v in (hi[held] - lo[held])), tuple(held))
-            cached = _LAG_CONST.get(key)
-            if cached is None:
-                w = torch.from_numpy(origins * (hi[held] - lo[held]).astype(np.float64)[None, :]).to(r_local.device)
-                cached = (w[:, :, None].contiguous(), torch.as_tensor(held, device=r_local.device))
-                if len(_LAG_CONST) > 8:
-                    _LAG_CONST.clear()
-                _LAG_CONST[key] = cached
-            if len(held) == G:
-                sums = means * cached[0]
-            else:
-                sums[:, cached[1], :] = means * cached[0]
-        sums = allreduce_tensor(sums).cpu().numpy()
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return np.where(counts[:, :, None] > 0, sums / np.maximum(counts, 1.0)[:, :, None], 0.0)
-    sums = np.zeros((n_lags, G, 4))
-    if held and F > 0:
-        # the held groups are contiguous in the slice (groups are contiguous globally)
-        loc_off = np.array([lo[held[0]]] + [hi[g] for g in held], dtype=np.int64)
-        x = r_local[:, :, int(loc_off[0]):int(loc_off[-1])]
+        sums = torch.zeros((n_lags, shard.G, 4), dtype=torch.float64, device=r_local.device)
+        if shard.has_work:
+            x = r_local[:, :, shard.cols].contiguous()
+            means = torch.empty((n_lags, len(shard.held), 4), dtype=torch.float64, device=r_local.device)
+            backend.lag_msd(x, int(max_lag), shard.call_off, scale=scale, ctx=ctx, out=means)
+            _weighted_into(sums, means, *_lag_weights(shard, r_local.device))
+        return _sums_to_means(allreduce_tensor(sums).cpu().numpy(), shard.counts)
+    sums = np.zeros((n_lags, shard.G, 4))
+    if shard.has_work:
+        x = r_local[:, :, shard.cols]
         if hasattr(x, "contiguous"):
             x = x.contiguous()
-        means = np.asarray(compute(x, int(max_lag), loc_off - loc_off[0], scale))
-        for k, g in enumerate(held):
-            sums[:, g, :] = means[:, k, :] * (origins * float(hi[g] - lo[g]))
+        means = np.asarray(compute(x, int(max_lag), shard.call_off, scale))
+        _weighted_into(sums, means, shard.weights[:, :, None], shard.held)
     if is_distributed():
         import torch
 
         sums = allreduce_tensor(torch.from_numpy(sums)).numpy()
-    with np.errstate(invalid="ignore", divide="ignore"):
-        out = np.where(counts[:, :, None] > 0, sums / counts[:, :, None], 0.0)
-    return out
+    return _sums_to_means(sums, shard.counts)
 
-
-import weakref
 
 # msd_step_sharded: context -> {(device index, post): torch stream}. Keyed on the Context OBJECT (weakly): an id() can be
 # reused by a new context once the old one has been collected, and would hand it a stream it never bound.
@@ -760,27 +816,6 @@ def release_step_stream(ctx):
         ctx.set_stream(None)
 
 
-_LAGW = {}
-
-
-def _lag_weights(origins, g_hi, g_lo, held, dev):
-    """[n_lags, len(held)] origins x entities of this rank's part of every held group, on the device (kept from step to
-    step: a fresh tensor would be a synchronous copy from pageable memory in every step)."""
-    key = (dev.index, len(origins), tuple(int(g_hi[g] - g_lo[g]) for g in held))
-    w = _LAGW.get(key)
-    if w is None:
-        if len(_LAGW) > 16:
-            _LAGW.clear()
-        w = _LAGW[key] = torch_from(origins * (g_hi[held] - g_lo[held]).astype(np.float64)[None, :], dev)
-    return w
-
-
-def torch_from(a, dev):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
 def _pinned_like(t):
     """A page-locked host tensor of t's size (torch's caching host allocator: recycled once the step's results — numpy
     views that keep the tensor alive — are dropped) and its numpy view. Page-locked as TORCH knows it: a non_blocking
@@ -800,13 +835,23 @@ def _post_group():
     so on ONE communicator the next step's pre-exchange — and with it the next step's kernels — would wait for this
     step's kernels, post-processing and collective: no pipelining (measured on the shard of 8: 1.25 ms per step against
     0.95, a one-rank RCCL group). Created collectively by the first fused step of every rank. OPT-IN
-    (MDHIP_STEP_POST_GROUP=1): see the call site."""
+    (MDHIP_STEP_POST_GROUP=1): see _closing_group."""
     d = _dist()
     key = id(d.group.WORLD)
     g = _POST_GROUP.get(key)
     if g is None:
         g = _POST_GROUP[key] = d.new_group(backend=d.get_backend())
     return g
+
+
+def _closing_group():
+    """The communicator of the all-reduce that ends a fused step (and of the one-wait order's agreement word): the default
+    group (None), or the second communicator with MDHIP_STEP_POST_GROUP=1 — read per call. The second communicator is
+    opt-in: collectives of two communicators in flight at once have not been run on more than one GPU here — a one-rank
+    RCCL group and gloo pairs are what the test box allows — and a hang would cost a whole multi-GPU run; on the default
+    group the next step's all-gather queues behind this all-reduce, which is slower but cannot interleave. It applies to
+    both completion orders, so that the two-communicator pattern runs under gloo in the CPU suite."""
+    return _post_group() if os.environ.get("MDHIP_STEP_POST_GROUP", "0") == "1" else None
 
 
 def _allreduce_inplace(t, group=None):
@@ -836,6 +881,278 @@ def _allgather_equal(t):
     return torch.stack(recv).to(t.device)
 
 
+@contextlib.contextmanager
+def _lag_variant(ctx, variant):
+    """Lag calls inside run under lag_variant `variant` (None: as the context stands); the CALLER's own value is put back
+    afterwards (resetting to the default lost it)."""
+    user_variant = ctx.get_option("lag_variant", -1)
+    if variant is not None:
+        ctx.set_option("lag_variant", variant)
+    try:
+        yield
+    finally:
+        if variant is not None:
+            ctx.set_option("lag_variant", user_variant)
+
+
+def _raise_if_ranks_failed(flag):
+    """`flag`: the reduced failure flag of a fused step — the number of ranks whose local calls raised."""
+    if flag != 0.0:
+        raise RuntimeError("%d rank(s) failed on their share of the MSD step; this rank stops with them" % int(round(flag)))
+
+
+class _QueuedCalls:
+    """A fused MSD step of ONE process without a process group: three queued library calls and one wait."""
+
+    def __init__(self, single, fixed, lag):
+        self._handles, self._out = (("single", single), ("fixed", fixed), ("lag", lag)), None
+
+    def wait(self):
+        if self._out is None:
+            out = tuple(h.wait() for _, h in self._handles)  # (single first: the waits complete the calls in issue order)
+            self._out = out + ({key: h.stats() for key, h in self._handles},)
+        return self._out
+
+
+class _MsdStep:
+    """
+    One fused MSD step of a process group in flight: msd_step_sharded_async builds it, runs start() and returns it; wait()
+    runs one of the two completion orders, once. The attributes keep alive everything the queued kernels read — the
+    shards, the gathered frames, the entity slice, the means, the weights, the result buffer — while the step is held.
+
+    ONE flat float64 buffer is all-reduced and copied to the host: single [F,G,4] | win [E,4] | lag [n_lags,G,4] | flag |
+    status. flag: a rank whose local calls raised writes 1 and still takes part in the all-reduce; every rank raises after
+    it, instead of the others waiting in the collective until it times out. status: the lag call's status word
+    (mdhip_lag_msd_status_dev: its error bound, +inf when its result will be rewritten at completion), which every rank
+    reads from the reduced buffer: whether the lag sums must be redone is agreed on without a host wait between the
+    kernels and the collective.
+
+    One host wait per step (round 5): the fused spectral lag path finishes on the device, so everything behind the three
+    calls — the halo window, the weighting of the lag means, the all-reduce, the copy to the host — is QUEUED at issue
+    time (close), and wait_one only waits for the copy. (Round 6: the batched path for series of more than 16 384 padded
+    points finishes on the device too, so the one-wait order holds for every length.) Measured on ONE GPU with the shards
+    one of eight / four ranks holds, both orders in the same process (tools/c4_shard_cost.py, C4_ORDER=two|one,
+    profiles/r05_c4_shard.txt): 1.17 against 1.16 ms per step at 8, 2.01 against 1.83 at 4 — boxes differ by more than
+    that between leases, so orders are compared inside one run. On a multi-GPU node the single wait also covers the
+    collective's wire time. MDHIP_STEP_ONE_WAIT=0 restores round 4's order, wait_two (the stand-ins always take it).
+    """
+
+    def __init__(self, r_f, r_e, frames, lags, group_off, scale, lag_scale, ctx, compute):
+        self.r_f, self.r_e, self.frames, self.lags, self.goff = r_f, r_e, frames, lags, np.asarray(group_off, dtype=np.int64)
+        self.scale, self.lag_scale, self.ctx, self.compute = scale, lag_scale, ctx, compute
+        self.on_gpu, self.dev, self.world = compute is None, r_f.device, frames.world
+        self.one_wait = self.on_gpu and os.environ.get("MDHIP_STEP_ONE_WAIT", "1") != "0"
+        F, E, G, n_lags = frames.n_frames, int(r_f.shape[2]), lags.G, lags.n_lags
+        nS, nW, nL = F * G * 4, E * 4, n_lags * G * 4
+        self.shapes = ((F, G, 4), (E, 4), (n_lags, G, 4))
+        self.parts = (slice(0, nS), slice(nS, nS + nW), slice(nS + nW, nS + nW + nL))
+        self.flag, self.status, self.size = nS + nW + nL, nS + nW + nL + 1, nS + nW + nL + 2
+        self.handles, self.issue_err, self.stats, self._out = {}, None, {}, None
+
+    def views(self, flat):
+        """(single, win, lag sums) as views of the flat buffer `flat`, a tensor or a host array."""
+        return tuple(flat[part].reshape(shape) for part, shape in zip(self.parts, self.shapes))
+
+    def _stream(self, post=False):
+        """torch's current stream := the stream the step is issued on, or (`post`) its second stream; nothing on the CPU."""
+        import torch
+
+        return torch.cuda.stream(_step_stream(self.dev, self.ctx, post=post)) if self.on_gpu else contextlib.nullcontext()
+
+    def start(self):
+        with self._stream():
+            self.exchange()
+            self.issue()
+            if self.one_wait:
+                self.close()
+        return self
+
+    def exchange(self):
+        """THE collective before the kernels: an all-gather of two frames per rank, the origin frame (zeros from every rank
+        but its owner) and the rank's last kept frame (the one-frame halo of the fixed-lag windows)."""
+        import torch
+
+        fp, r_f = self.frames, self.r_f
+        owner = fp.owner
+        owns, keeps = fp.rank == owner, len(fp.kept_local) > 0
+        zero = None if (owns and keeps) else torch.zeros((3, int(r_f.shape[2])), dtype=torch.float64, device=self.dev)
+        mine = torch.stack([r_f[fp.origin_frame - fp.lo] if owns else zero, r_f[int(fp.kept_local[-1])] if keeps else zero])
+        self.allf = _allgather_equal(mine) if self.world > 1 else mine[None]  # [world, 2, 3, E]
+        self.r0 = self.allf[owner, 0].contiguous()
+        self.halo = None if fp.halo_rank is None else self.allf[fp.halo_rank, 1]
+
+    def issue(self):
+        """The result buffer and the three reductions of this rank's shards into its parts of it: *_async library calls on
+        the issue stream, or the stand-ins."""
+        import torch
+
+        fp, ls, r_f, max_lag = self.frames, self.lags, self.r_f, self.lags.n_lags - 1
+        self.res = (torch.empty if self.on_gpu else torch.zeros)(self.size, dtype=torch.float64, device=self.dev)
+        single, self.win, self.lagsum = self.views(self.res)
+        if self.on_gpu:
+            # (only what no kernel of this rank writes is zeroed: the other ranks' single-origin rows, the lag sums of groups
+            # held elsewhere, the two flag words — the window sums, most of the buffer, are written whole by their kernel; a
+            # fill of all 1.9 MB cost the shard-of-8 step 37 us of its ~1 ms)
+            if fp.lo > 0:
+                single[:fp.lo].zero_()
+            if fp.hi < fp.n_frames:
+                single[fp.hi:].zero_()
+            if not len(fp.kept_local):
+                self.win.zero_()
+            self.res[self.parts[2].start:].zero_()
+        self.x = self.r_e[:, :, ls.cols].contiguous() if ls.has_work else None
+        self.means = None
+        if not self.on_gpu:
+            calls = self.compute
+            if fp.hi > fp.lo:
+                single[fp.lo:fp.hi] = torch.as_tensor(calls["origin"](r_f.numpy(), self.r0.numpy(), self.goff, self.scale))
+            if len(fp.kept_local) > 1:
+                self.win.copy_(torch.as_tensor(calls["windows"](r_f[fp.k0:].numpy(), fp.tao, self.scale)))
+            if self.x is not None:
+                self.means = torch.as_tensor(np.asarray(calls["lag"](self.x.numpy(), max_lag, ls.call_off, self.lag_scale)))
+            return
+        from . import backend
+
+        try:
+            if fp.hi > fp.lo:
+                self.handles["single"] = backend.msd_origin(r_f, self.r0, self.goff, scale=self.scale,
+                                                            out=single[fp.lo:fp.hi], ctx=self.ctx, async_=True)
+            if len(fp.kept_local):
+                self.handles["fixed"] = backend.msd_windows(r_f[fp.k0:], fp.tao, scale=self.scale, out=self.win, ctx=self.ctx,
+                                                            async_=True)
+            if self.x is not None:
+                self.means = torch.empty((ls.n_lags, len(ls.held), 4), dtype=torch.float64, device=self.dev)
+                # (one-wait order: the spectral path, no host-side fallback — the status word decides)
+                with _lag_variant(self.ctx, 2 if self.one_wait else None):
+                    self.handles["lag"] = backend.lag_msd(self.x, max_lag, ls.call_off, scale=self.lag_scale, out=self.means,
+                                                          ctx=self.ctx, async_=True,
+                                                          status_out=self.res[self.status:] if self.one_wait else None)
+        except Exception as e:  # (this rank still takes part in the all-reduce; every rank raises behind it)
+            self.issue_err = e
+            self.res[self.flag] = 1.0
+
+    def after_kernels(self):
+        """What follows the kernels on the device (stream-ordered behind the calls): the one window that reaches back to
+        the rank below, and the lag means weighted into this rank's share of the sums."""
+        fp = self.frames
+        if len(fp.kept_local) and self.halo is not None:
+            self.win.add_(_halo_window(self.r_f[fp.k0], self.halo, self.scale))
+        if self.means is not None:
+            self.lag_weights = _lag_weights(self.lags, self.dev)
+            _weighted_into(self.lagsum, self.means, *self.lag_weights)
+
+    def reduce(self):
+        """THE collective after the kernels: an all-reduce of the whole buffer (a single-origin row is non-zero on exactly
+        one rank: the sum IS the gather, exactly; the status becomes the SUM of the ranks' bounds)."""
+        if self.world > 1:
+            _allreduce_inplace(self.res, _closing_group())
+
+    def close(self):
+        """One-wait order, at issue time: after_kernels, reduce and the copy to page-locked memory are queued on the second
+        stream — the next step's kernels queue behind this step's KERNELS only, not behind its dozen small operations and
+        its collective; everything these read is held by this step."""
+        import torch
+
+        ev_kernels = torch.cuda.Event()
+        ev_kernels.record(torch.cuda.current_stream(self.dev))
+        s2 = _step_stream(self.dev, self.ctx, post=True)
+        s2.wait_event(ev_kernels)
+        with torch.cuda.stream(s2):
+            if self.issue_err is None:
+                self.after_kernels()
+            self.reduce()
+            self.flat, self.flat_pinned = _pinned_like(self.res)
+            self.flat_pinned.copy_(self.res, non_blocking=True)
+            self.ev_done = torch.cuda.Event()
+            self.ev_done.record(s2)
+
+    def _complete_calls(self):
+        for key, h in self.handles.items():
+            h.wait()  # (complete: the status of each call, its times; the batched lag path's finish runs here)
+            self.stats[key] = h.stats()
+
+    def wait_one(self):
+        import torch
+
+        self.ev_done.synchronize()  # THE host wait of the step
+        err = self.issue_err
+        try:
+            self._complete_calls()
+        except Exception as e:
+            err = err or e
+        if self.world > 1:
+            # Errors that only show at COMPLETION (a call's deferred re-run failing, EHIP) are not on the reduced
+            # failure flag — that all-reduce ran before the host knew. The ranks agree on them here, before anyone
+            # raises or enters another collective (the redo below, the next step's exchange): one word, summed.
+            # (ADVICE r05: a rank raising alone left the others waiting in their next collective until it timed out.)
+            agree = torch.tensor([0.0 if err is None else 1.0], dtype=torch.float64, device=self.dev)
+            with self._stream(post=True):
+                _allreduce_inplace(agree, _closing_group())
+                n_failed = int(round(float(agree.item())))
+            if n_failed and err is None:
+                err = RuntimeError("%d rank(s) failed completing their share of the MSD step; this rank stops with them"
+                                   % n_failed)
+        if err is not None:
+            raise err
+        _raise_if_ranks_failed(self.flat[self.flag])
+        status = self.flat[self.status]  # (the SUM of the ranks' bounds: at least the largest of them)
+        if not (status <= 1e-10):
+            self.redo_lag(status)
+
+    def redo_lag(self, status):
+        """Some rank's spectral result is not good enough (or was rewritten at completion): every rank sees the same
+        reduced status, so every rank repeats the lag part, together, under lag_variant 3 — the library's own decision per
+        call (round 6): the spectral result stands where the rank's bound holds (the status is the SUM of the ranks' bounds:
+        it can pass the tolerance with every rank inside it), the few lags that miss it are recomputed from the difference
+        form, and only data that misses it broadly goes to the difference kernel."""
+        import torch
+
+        from . import backend
+
+        ls = self.lags
+        self.flat = self.flat.copy()
+        lag_part = torch.zeros(self.parts[2].stop - self.parts[2].start, dtype=torch.float64, device=self.dev)
+        with self._stream(post=True):
+            if self.x is not None:
+                with _lag_variant(self.ctx, 3):
+                    means = torch.empty((ls.n_lags, len(ls.held), 4), dtype=torch.float64, device=self.dev)
+                    backend.lag_msd(self.x, ls.n_lags - 1, ls.call_off, scale=self.lag_scale, out=means, ctx=self.ctx)
+                _weighted_into(lag_part.view(self.shapes[2]), means, *_lag_weights(ls, self.dev))
+            if self.world > 1:
+                _allreduce_inplace(lag_part)
+            self.flat[self.parts[2]] = lag_part.cpu().numpy()
+        self.stats["lag_redone"] = float(status)
+
+    def wait_two(self):
+        """On a stream of its own: the next step's kernels may already be queued on the issue stream, and nothing here has
+        to wait for them (what it reads is complete: the calls are waited for first). A failure is agreed on THROUGH the
+        all-reduce (the flag: no collective of its own)."""
+        with self._stream(post=True):
+            err = self.issue_err
+            try:
+                if err is None:
+                    self._complete_calls()  # (`means` is in place)
+                    self.after_kernels()
+            except Exception as e:
+                err = e
+                self.res[self.flag] = 1.0
+            self.reduce()
+            self.flat = self.res.cpu().numpy()
+            if err is not None:
+                raise err
+            _raise_if_ranks_failed(self.flat[self.flag])
+
+    def results(self):
+        single, win, lagsum = self.views(self.flat)
+        return single, win, _sums_to_means(lagsum, self.lags.counts), self.stats
+
+    def wait(self):
+        if self._out is None:
+            (self.wait_one if self.one_wait else self.wait_two)()
+            self._out = self.results()
+        return self._out
+
+
 def msd_step_sharded_async(r_f, r_e, n_frames_total, entity_range, group_off, tao, scale=1.0, lag_scale=1.0, origin_frame=0,
                      ctx=None, counts=None, compute=None):
     """
@@ -860,282 +1177,37 @@ def msd_step_sharded_async(r_f, r_e, n_frames_total, entity_range, group_off, ta
     `compute` (tests: the exchange logic on CPU over gloo, with the oracle as the stand-in): a dict of
     "origin"(r [f,3,E], r0 [3,E], goff, scale) -> [f,G,4], "windows"(r [f,3,E], tao, scale) -> [E,4] (windows between the
     frames 0, tao, 2 tao ... of r) and "lag"(x [F,3,e], max_lag, loc_off, scale) -> means [F,g,4] on numpy arrays.
+    The plan is _FramePlan and _LagShard, the step in flight _MsdStep.
     """
-    import contextlib
-
-    import torch
-
     rank, world = rank_world()
-    on_gpu = compute is None
-    if on_gpu:
-        from . import backend
+    if compute is None:
         from ._lib import default_context
 
         ctx = ctx or default_context()
     else:
+        import torch
+
         r_f = torch.as_tensor(np.ascontiguousarray(r_f))
         r_e = torch.as_tensor(np.ascontiguousarray(r_e))
     F = int(n_frames_total)
-    blocks = frame_blocks(F, counts, world)
-    lo, hi = blocks[rank]
-    E = int(r_f.shape[2])
-    goff = np.asarray(group_off, dtype=np.int64)
-    G = len(goff) - 1
-    tao = int(tao)
-    max_lag = F - 1
-    n_lags = F
+    frames = _FramePlan(F, tao, origin_frame, counts, rank, world)
+    lags = _LagShard(group_off, entity_range, F, F)
     e_lo, e_hi = int(entity_range[0]), int(entity_range[1])
-    if int(r_f.shape[0]) != hi - lo or int(r_e.shape[0]) != F or int(r_e.shape[2]) != e_hi - e_lo:
+    if int(r_f.shape[0]) != frames.hi - frames.lo or int(r_e.shape[0]) != F or int(r_e.shape[2]) != e_hi - e_lo:
         raise ValueError("shard shapes do not match the frame block / entity range of this rank")
-    # this rank's part of every group of the entity shard (as lag_msd_sharded)
-    g_lo = np.clip(goff[:-1], e_lo, e_hi) - e_lo
-    g_hi = np.clip(goff[1:], e_lo, e_hi) - e_lo
-    held = [g for g in range(G) if g_hi[g] > g_lo[g]]
-    lag_counts = (F - np.arange(n_lags)).astype(np.float64)[:, None] * (goff[1:] - goff[:-1]).astype(np.float64)[None, :]
-    origins = (F - np.arange(n_lags)).astype(np.float64)[:, None]
+    if not is_distributed() and compute is None:
+        from . import backend
 
-    def kept_of(a, b):  # global indices of the kept frames inside [a, b)
-        return np.arange(-(-a // tao) * tao, b, tao)
-
-    kept_local = kept_of(lo, hi) - lo
-    stats = {}
-    if not is_distributed() and on_gpu:
-        h1 = backend.msd_origin(r_f, r_f[origin_frame], goff, scale=scale, ctx=ctx, async_=True)
-        h2 = backend.msd_windows(r_f, tao, scale=scale, ctx=ctx, async_=True)
-        h3 = backend.lag_msd(r_e, max_lag, goff, scale=lag_scale, ctx=ctx, async_=True)
-
-        def finish_local():
-            out = (h1.wait(), h2.wait(), h3.wait())  # (h1 first: the waits complete the calls in issue order)
-            for key, h in (("single", h1), ("fixed", h2), ("lag", h3)):
-                stats[key] = h.stats()
-            return out + (stats,)
-
-        return _Deferred(finish_local)
-    dev = r_f.device
-    owner = frame_owner(F, origin_frame, world, counts)
-    nS, nW, nL = F * G * 4, E * 4, n_lags * G * 4
-    with (torch.cuda.stream(_step_stream(dev, ctx)) if on_gpu else contextlib.nullcontext()):
-        zero = None if (rank == owner and len(kept_local)) else torch.zeros((3, E), dtype=torch.float64, device=dev)
-        mine = torch.stack([r_f[origin_frame - lo] if rank == owner else zero,
-                            r_f[int(kept_local[-1])] if len(kept_local) else zero])
-        allf = _allgather_equal(mine) if world > 1 else mine[None]  # [world, 2, 3, E]
-        r0 = allf[owner, 0].contiguous()
-        halo = None
-        for q in range(rank - 1, -1, -1):
-            if len(kept_of(*blocks[q])):
-                halo = allf[q, 1]
-                break
-        # (+ 2: a failure flag — a rank whose local calls raised still takes part in the all-reduce and every rank raises
-        # after it, instead of the others waiting in the collective until it times out — and the STATUS of the lag call
-        # (mdhip_lag_msd_status_dev: its error bound, +inf when its result will be rewritten at completion), which
-        # every rank reads from the reduced buffer: whether the lag sums must be redone is agreed on without a host
-        # wait between the kernels and the collective)
-        # (only what no kernel of this rank writes is zeroed: the other ranks' single-origin rows, the lag sums of groups
-        # held elsewhere, the two flag words — the window sums, most of the buffer, are written whole by their kernel; a
-        # fill of all 1.9 MB cost the shard-of-8 step 37 us of its ~1 ms)
-        on_dev_fill = on_gpu
-        res = (torch.empty if on_dev_fill else torch.zeros)(nS + nW + nL + 2, dtype=torch.float64, device=dev)
-        single = res[:nS].view(F, G, 4)
-        win = res[nS:nS + nW].view(E, 4)
-        lagsum = res[nS + nW:nS + nW + nL].view(n_lags, G, 4)
-        if on_dev_fill:
-            if lo > 0:
-                single[:lo].zero_()
-            if hi < F:
-                single[hi:].zero_()
-            if not (len(kept_local) and on_gpu):
-                win.zero_()
-            res[nS + nW:].zero_()
-        hs = {}
-        k0 = int(kept_local[0]) if len(kept_local) else 0
-        means, x, loc_off = None, None, None
-        if held and F > 0:
-            loc_off = np.array([g_lo[held[0]]] + [g_hi[g] for g in held], dtype=np.int64)
-            x = r_e[:, :, int(loc_off[0]):int(loc_off[-1])].contiguous()
-        # One host wait per step (round 5): the fused spectral lag path finishes on the device, so everything behind the
-        # three calls — the halo window, the weighting of the lag means, the all-reduce, the copy to the host — is QUEUED
-        # here, at issue time, and finish() only waits for the copy. (Round 6: the batched path for series of more than
-        # 16 384 padded points finishes on the device too, so the one-wait order holds for every length.)
-        # Measured on ONE GPU with the shards one of eight / four ranks holds, both orders in the same process (tools/
-        # c4_shard_cost.py, C4_ORDER=two|one, profiles/r05_c4_shard.txt): 1.17 against 1.16 ms per step at 8, 2.01 against
-        # 1.83 at 4 — boxes differ by more than that between leases, so orders are compared inside one run. On a
-        # multi-GPU node the single wait also covers the collective's wire time. MDHIP_STEP_ONE_WAIT=0 restores round 4's order.
-        one_wait = on_gpu and os.environ.get("MDHIP_STEP_ONE_WAIT", "1") != "0"
-        issue_err = None
-        if on_gpu:
-            try:
-                if hi > lo:
-                    hs["single"] = backend.msd_origin(r_f, r0, goff, scale=scale, out=single[lo:hi], ctx=ctx, async_=True)
-                if len(kept_local):
-                    hs["fixed"] = backend.msd_windows(r_f[k0:], tao, scale=scale, out=win, ctx=ctx, async_=True)
-                if x is not None:
-                    means = torch.empty((n_lags, len(held), 4), dtype=torch.float64, device=dev)
-                    # (the caller's own lag_variant is put back afterwards: ADVICE r05 — resetting to the default lost it)
-                    user_variant = ctx.get_option("lag_variant", -1)
-                    if one_wait:
-                        ctx.set_option("lag_variant", 2)  # (the spectral path, no host-side fallback: the status word decides)
-                    try:
-                        hs["lag"] = backend.lag_msd(x, max_lag, loc_off - loc_off[0], scale=lag_scale, out=means, ctx=ctx,
-                                                    async_=True, status_out=res[nS + nW + nL + 1:] if one_wait else None)
-                    finally:
-                        if one_wait:
-                            ctx.set_option("lag_variant", user_variant)
-            except Exception as e:  # (this rank still takes part in the all-reduce; every rank raises behind it)
-                issue_err = e
-                res[nS + nW + nL] = 1.0
-        else:
-            if hi > lo:
-                single[lo:hi] = torch.as_tensor(compute["origin"](r_f.numpy(), r0.numpy(), goff, scale))
-            if len(kept_local) > 1:
-                win.copy_(torch.as_tensor(compute["windows"](r_f[k0:].numpy(), tao, scale)))
-            if x is not None:
-                means = torch.as_tensor(np.asarray(compute["lag"](x.numpy(), max_lag, loc_off - loc_off[0], lag_scale)))
-
-        def post_ops():
-            """What follows the kernels on the device: the halo window, the lag sums (stream-ordered behind the calls)."""
-            if len(kept_local) and halo is not None:
-                # the one window that reaches back to the rank below: three planes of arithmetic (the kernel's
-                # operations: scale, subtract, square, (dx2 + dy2) + dz2)
-                d2 = (r_f[k0] * scale - halo * scale) ** 2
-                win.add_(torch.stack([d2[0], d2[1], d2[2], (d2[0] + d2[1]) + d2[2]], dim=1))
-            if means is not None:
-                w = _lag_weights(origins, g_hi, g_lo, held, dev)
-                if len(held) == G:
-                    torch.mul(means, w[:, :, None], out=lagsum)  # (one kernel: the product lands in the reduced buffer)
-                else:
-                    lagsum[:, torch.as_tensor(held, device=dev), :] = means * w[:, :, None]
-
-        ev_done, flat_t, flat_np = None, None, None
-        if one_wait:
-            ev_k = torch.cuda.Event()
-            ev_k.record(torch.cuda.current_stream(dev))
-            s2 = _step_stream(dev, ctx, post=True)
-            s2.wait_event(ev_k)
-            # (on the second stream: the next step's kernels queue behind this step's KERNELS only, not behind its dozen
-            # small operations and its collective; everything these read is held by this step until finish())
-            with torch.cuda.stream(s2):
-                if issue_err is None:
-                    post_ops()
-                if world > 1:
-                    # (the second communicator is opt-in, MDHIP_STEP_POST_GROUP=1: collectives of two communicators in
-                    # flight at once have not been run on more than one GPU here — a one-rank RCCL group and gloo pairs
-                    # are what this box allows — and a hang would cost a whole multi-GPU run; on the default group the
-                    # next step's all-gather queues behind this all-reduce, which is slower but cannot interleave)
-                    _allreduce_inplace(res, _post_group() if os.environ.get("MDHIP_STEP_POST_GROUP", "0") == "1" else None)
-                flat_np, flat_t = _pinned_like(res)
-                flat_t.copy_(res, non_blocking=True)
-                ev_done = torch.cuda.Event()
-                ev_done.record(s2)
-    keep = (r_f, r_e, allf, r0, x, means)  # what the queued kernels read stays alive until the step has been waited for
-
-    def finish():
-        if one_wait:
-            ev_done.synchronize()  # THE host wait of the step
-            flat = flat_np
-            err = issue_err
-            try:
-                for key, h in hs.items():
-                    h.wait()  # (complete: the status of each call, its times)
-                    stats[key] = h.stats()
-            except Exception as e:
-                err = err or e
-            if world > 1:
-                # Errors that only show at COMPLETION (a call's deferred re-run failing, EHIP) are not on the reduced
-                # failure flag — that all-reduce ran before the host knew. The ranks agree on them here, before anyone
-                # raises or enters another collective (the redo below, the next step's exchange): one word, summed.
-                # (ADVICE r05: a rank raising alone left the others waiting in their next collective until it timed out.)
-                agree = torch.tensor([0.0 if err is None else 1.0], dtype=torch.float64, device=dev)
-                with torch.cuda.stream(_step_stream(dev, ctx, post=True)):
-                    _allreduce_inplace(agree, _post_group() if os.environ.get("MDHIP_STEP_POST_GROUP", "0") == "1" else None)
-                    n_failed = int(round(float(agree.item())))
-                if n_failed and err is None:
-                    err = RuntimeError("%d rank(s) failed completing their share of the MSD step; this rank stops with them"
-                                       % n_failed)
-            if err is not None:
-                raise err
-            if flat[nS + nW + nL] != 0.0:
-                raise RuntimeError("%d rank(s) failed on their share of the MSD step; this rank stops with them"
-                                   % int(round(flat[nS + nW + nL])))
-            status = flat[nS + nW + nL + 1]  # (the SUM of the ranks' bounds: at least the largest of them)
-            if not (status <= 1e-10):
-                # some rank's spectral result is not good enough (or was rewritten at completion): every rank sees the same
-                # reduced status, so every rank repeats the lag part, together, under lag_variant 3 — the library's own
-                # decision per call (round 6): the spectral result stands where the rank's bound holds (the status is the SUM
-                # of the ranks' bounds: it can pass the tolerance with every rank inside it), the few lags that miss it are
-                # recomputed from the difference form, and only data that misses it broadly goes to the difference kernel
-                flat = flat.copy()
-                lag_part = torch.zeros(nL, dtype=torch.float64, device=dev)
-                with torch.cuda.stream(_step_stream(dev, ctx, post=True)):
-                    if x is not None:
-                        user_variant = ctx.get_option("lag_variant", -1)
-                        ctx.set_option("lag_variant", 3)
-                        try:
-                            m2 = torch.empty((n_lags, len(held), 4), dtype=torch.float64, device=dev)
-                            backend.lag_msd(x, max_lag, loc_off - loc_off[0], scale=lag_scale, out=m2, ctx=ctx)
-                        finally:
-                            ctx.set_option("lag_variant", user_variant)
-                        w = _lag_weights(origins, g_hi, g_lo, held, dev)
-                        lv = lag_part.view(n_lags, G, 4)
-                        if len(held) == G:
-                            lv.copy_(m2 * w[:, :, None])
-                        else:
-                            lv[:, torch.as_tensor(held, device=dev), :] = m2 * w[:, :, None]
-                    if world > 1:
-                        _allreduce_inplace(lag_part)
-                    flat[nS + nW:nS + nW + nL] = lag_part.cpu().numpy()
-                stats["lag_redone"] = float(status)
-        else:
-            # On a stream of its own: the next step's kernels may already be queued on the issue stream, and nothing
-            # here has to wait for them (what it reads is complete: the calls are waited for first).
-            with (torch.cuda.stream(_step_stream(dev, ctx, post=True)) if on_gpu else contextlib.nullcontext()):
-                err = issue_err
-                try:
-                    if err is None:
-                        for key, h in hs.items():
-                            h.wait()  # the calls have completed: `means` is in place (the batched path's finish ran here)
-                            stats[key] = h.stats()
-                        post_ops()
-                except Exception as e:  # agreed on THROUGH the all-reduce (no collective of its own)
-                    err = e
-                    res[nS + nW + nL] = 1.0
-                if world > 1:
-                    # (MDHIP_STEP_POST_GROUP=1: the closing all-reduce on the second communicator, as in the one-wait order
-                    # above — also on this path so that the two-communicator pattern runs under gloo in the CPU suite)
-                    _allreduce_inplace(res, _post_group() if os.environ.get("MDHIP_STEP_POST_GROUP", "0") == "1" else None)
-                flat = res.cpu().numpy()
-                if err is not None:
-                    raise err
-                if flat[nS + nW + nL] != 0.0:
-                    raise RuntimeError("%d rank(s) failed on their share of the MSD step; this rank stops with them"
-                                       % int(round(flat[nS + nW + nL])))
-        assert keep is not None
-        single_h = flat[:nS].reshape(F, G, 4)
-        win_h = flat[nS:nS + nW].reshape(E, 4)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            lag_h = np.where(lag_counts[:, :, None] > 0,
-                             flat[nS + nW:nS + nW + nL].reshape(n_lags, G, 4) / np.maximum(lag_counts, 1.0)[:, :, None],
-                             0.0)
-        return single_h, win_h, lag_h, stats
-
-    return _Deferred(finish)
+        goff = np.asarray(group_off, dtype=np.int64)
+        return _QueuedCalls(backend.msd_origin(r_f, r_f[origin_frame], goff, scale=scale, ctx=ctx, async_=True),
+                            backend.msd_windows(r_f, frames.tao, scale=scale, ctx=ctx, async_=True),
+                            backend.lag_msd(r_e, F - 1, goff, scale=lag_scale, ctx=ctx, async_=True))
+    return _MsdStep(r_f, r_e, frames, lags, group_off, scale, lag_scale, ctx, compute).start()
 
 
 def msd_step_sharded(*args, **kwargs):
     """msd_step_sharded_async, waited for: (single [F,G,4], windows [E,4], lag [F,G,4], per-call kernel times)."""
     return msd_step_sharded_async(*args, **kwargs).wait()
-
-
-class _Deferred:
-    """Handle of a step whose calls have been issued: wait() runs what is left (once) and returns the result."""
-
-    def __init__(self, finish):
-        self._finish, self._out = finish, None
-
-    def wait(self):
-        if self._finish is not None:
-            self._out = self._finish()
-            self._finish = None
-        return self._out
 
 
 def entity_shard(n_entities, rank=None, world=None):

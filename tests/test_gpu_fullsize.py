@@ -514,6 +514,81 @@ def _frame_sharded_worker(rank, world, port, out_dir):
     dist.destroy_process_group()
 
 
+_FUSED_CASES = ((0, 1), (7, 3), (2, 7))  # (origin, tao); (2, 7): the upper shard's only kept frame reaches back across
+
+
+def _fused_case():
+    rng = np.random.default_rng(58)
+    F, E = 11, 300  # shards of 6 + 5 frames, 150 + 150 entities
+    walk = np.cumsum(rng.normal(0, 0.1, (F, 3, E)), axis=0) + rng.uniform(0, 40, (1, 3, E))
+    return F, E, walk, [0, 100, E]  # rank 1 holds nothing of group 0: its lag sums are scattered by index
+
+
+def _fused_step_worker(rank, world, port, out_dir):
+    sys.path.insert(0, REPO)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
+                      LOCAL_RANK="0")
+    import torch
+    import torch.distributed as dist
+
+    from mdproptools_amd import dist as D
+
+    dist.init_process_group("gloo", rank=rank, world_size=world)  # two ranks share the one GPU of the test box
+    F, E, walk, goff = _fused_case()
+    lo, hi = D.frame_shard(F)
+    e_lo, e_hi = D.entity_shard(E)
+    dev = torch.device("cuda", 0)
+    r_f = torch.from_numpy(np.ascontiguousarray(walk[lo:hi])).to(dev)
+    r_e = torch.from_numpy(np.ascontiguousarray(walk[:, :, e_lo:e_hi])).to(dev)
+    res = {"shards": np.array([lo, hi, e_lo, e_hi])}
+    for one_wait in ("1", "0"):
+        os.environ["MDHIP_STEP_ONE_WAIT"] = one_wait  # (read per call)
+        for origin, tao in _FUSED_CASES:
+            single, win, lag, _st = D.msd_step_sharded(r_f, r_e, F, (e_lo, e_hi), goff, tao, scale=1e-10, lag_scale=1.0,
+                                                       origin_frame=origin)
+            key = "w%s_%d_%d_" % (one_wait, origin, tao)
+            res[key + "single"], res[key + "win"], res[key + "lag"] = np.array(single), np.array(win), np.array(lag)
+    np.savez(os.path.join(out_dir, "fused%d.npz" % rank), **res)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_fused_msd_step_two_ranks_real_kernels_both_wait_orders(B, tmp_path):
+    """dist.msd_step_sharded with the HIP kernels behind it, two ranks sharing the GPU over gloo, device-resident shards:
+    11 frames in shards of 6 + 5, 300 entities in two groups of which rank 1 holds only the second (the index-scatter
+    form of the lag sums), the origin in either shard, a tao whose only kept frame of the upper shard reaches back across
+    the boundary — under both completion orders (MDHIP_STEP_ONE_WAIT 1 and 0), against the single-process calls."""
+    import socket
+
+    import torch.multiprocessing as mp
+
+    from mdproptools_amd._lib import Context
+
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    mp.spawn(_fused_step_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    F, E, walk, goff = _fused_case()
+    ctx = Context(0)
+    ctx.set_option("lag_variant", 1)  # the exact-difference kernel as the reference
+    lag = B.lag_msd(walk, F - 1, goff, ctx=ctx)
+    ctx.close()
+    g = [np.load(tmp_path / ("fused%d.npz" % rank)) for rank in range(2)]
+    assert list(g[0]["shards"]) == [0, 6, 0, 150] and list(g[1]["shards"]) == [6, 11, 150, 300]
+    for origin, tao in _FUSED_CASES:
+        single = B.msd_pairs(walk, [(origin, t) for t in range(F)], goff, scale=1e-10)
+        win = B.msd_windows(walk, tao, scale=1e-10)
+        for one_wait in ("1", "0"):
+            key = "w%s_%d_%d_" % (one_wait, origin, tao)
+            for rank in range(2):
+                np.testing.assert_array_equal(g[rank][key + "single"], single)        # a frame's sums come from one rank
+                np.testing.assert_allclose(g[rank][key + "win"], win, rtol=1e-13)     # windows summed rank by rank
+                np.testing.assert_allclose(g[rank][key + "lag"][1:], lag[1:], rtol=1e-10)
+                assert np.all(g[rank][key + "lag"][0] == 0.0)
+            for part in ("single", "win", "lag"):  # both ranks return the same arrays
+                np.testing.assert_array_equal(g[0][key + part], g[1][key + part])
+
+
 def test_frame_sharded_paths_two_ranks_real_kernels(B, tmp_path):
     """cn_sharded, msd_single_origin_sharded (origin in either shard), msd_windows_sharded (one-frame halo),
     charge_flux_sharded and rdf_sharded_per_frame with the HIP kernels behind them — two ranks sharing the GPU over
