@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MDHIP_VERSION 600 /* 0.6.0: + mdhip_pair_plan (which pair kernel a call would run, without a device), mdhip_row_displacement, MDHIP_EUNKNOWN (mdhip_ticket_status of a forgotten ticket), mdhip_lag_msd* finishes on the device at every length; 0.5.0: + mdhip_ticket_status / mdhip_fallbacks / MDHIP_EPENDING (a call's own completion status), mdhip_lag_msd_status_dev; 0.4.0: the *_async entry points with mdhip_sync / mdhip_wait / mdhip_call_stats, mdhip_green_kubo, mdhip_cumtrapz_dev */
+#define MDHIP_VERSION 610 /* 0.6.1: + mdhip_lag_plan (which spectral path a full-lag MSD call would take, without a device); 0.6.0: + mdhip_pair_plan (which pair kernel a call would run, without a device), mdhip_row_displacement, MDHIP_EUNKNOWN (mdhip_ticket_status of a forgotten ticket), mdhip_lag_msd* finishes on the device at every length; 0.5.0: + mdhip_ticket_status / mdhip_fallbacks / MDHIP_EPENDING (a call's own completion status), mdhip_lag_msd_status_dev; 0.4.0: the *_async entry points with mdhip_sync / mdhip_wait / mdhip_call_stats, mdhip_green_kubo, mdhip_cumtrapz_dev */
 
 #define MDHIP_OK 0
 #define MDHIP_EINVAL (-1)  /* bad argument (shape, NULL, unsupported size) */
@@ -237,6 +237,40 @@ int mdhip_pair_plan(const mdhip_ctx *ctx, int op, int64_t n_frames, int64_t n_at
                     const int32_t *rel, double r_cut_sq, double bin_size, int nbins, const double *cn_r_cut_sq, int per_frame,
                     int result_on_device, int xyz_on_device, int cu_count, int64_t lds_bytes, int n_opt,
                     const char *const *opt_key, const int *opt_value, char *text, int text_cap, int32_t *info);
+
+/*
+ * What a full-lag MSD call (mdhip_lag_msd*, lag_variant 2 .. 4) would run on its spectral path, decided from its shape
+ * alone: the library's own decision (csrc/lag_plan.h: lag_choose, the function every such call runs first), with no
+ * device. ctx: NULL (the defaults of a fresh context), or a context whose options and device limits are read (never
+ * changed).
+ *   group_off          host [n_groups + 1], as mdhip_lag_msd
+ *   r_aligned16        the trajectory's device address is a multiple of 16 (host-resident frames are staged: 1)
+ *   cu_count, lds_bytes   the two device limits the decision reads (<= 0: the context's; 256 / 65536 without one)
+ *   opt_key, opt_value [n_opt] overrides as for mdhip_set_option
+ * Out: info[MDHIP_LAG_PLAN_INFO] = { status, path (MDHIP_LAG_*; -1: nothing runs, or the exact kernels answer),
+ *   generation of the power-of-two kernel (1 .. 3) | padded length / 1024 of the one-wave kernel | D of the residue
+ *   classes (4, 8) | fuse level of the batched transforms (0 .. 2),
+ *   m (fused paths: log2 of the packed points at or above (n_frames + max_lag) / 2),
+ *   source of the series (0 the transposed copy, 1 the trajectory in place, 2 / 3 the clusters' staging rings),
+ *   rows per cluster member, staging units per lane and tile (0: not staged),
+ *   template instance, first parameter (12 288-point kernel: QE; generation 3: JJ; 2: QR2; 1: QR; residue paths: 1 .. 3
+ *   msd_power_w1_kernel<n>, 4 msd_power_w12r_kernel<4>, 5 msd_power_w12p_kernel<true>, 6 <false> + msd_power_w12o_kernel),
+ *   second parameter (12 288-point kernel: SHORT; generation 3: QE; residue paths: packed),
+ *   work items (blocks of the power kernel, all batches), batches of series, timed runs of launches as
+ *   mdhip_last_kernel_ms counts them, padded length }; status MDHIP_OK or a negative MDHIP_E* code.
+ * text: the name mdhip_last_kernel_name reports after the call, or the error text. The completion step of a call may
+ * still hand the answer to the exact kernels (lag_variant 3 with the bound missed) and leave their name. Returns
+ * MDHIP_EINVAL for unusable arguments, else MDHIP_OK. A pure function, deterministic.
+ */
+#define MDHIP_LAG_W1 0
+#define MDHIP_LAG_POW2 1
+#define MDHIP_LAG_W12 2
+#define MDHIP_LAG_RESIDUE 3
+#define MDHIP_LAG_BATCHED 4
+#define MDHIP_LAG_PLAN_INFO 13
+int mdhip_lag_plan(const mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, int max_lag, int n_groups,
+                   const int64_t *group_off, int r_aligned16, int cu_count, int64_t lds_bytes, int n_opt,
+                   const char *const *opt_key, const int *opt_value, char *text, int text_cap, int32_t *info);
 
 /* ---- R3: _rdf_loop (+ _calc_rsq, _remove_outliers) ------------------------ */
 /*

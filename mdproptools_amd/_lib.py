@@ -55,6 +55,8 @@ PROTOTYPES = {
                                   C.c_int, c_ip, C.c_double, C.c_double, C.c_int, c_dp, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_char_p,
                                   C.c_int, c_ip]),
+    "mdhip_lag_plan": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int, c_lp, C.c_int, C.c_int, C.c_int64, C.c_int,
+                                 C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.c_char_p, C.c_int, c_ip]),
     "mdhip_rdf_atomic": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_ip, C.c_int64, c_dp, C.c_int,
                                    c_ip, C.c_double, C.c_double, C.c_int, c_dp, C.c_int, c_up, c_up, c_up]),
     "mdhip_rdf_atomic_dev": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_ip, C.c_int64, c_dp, C.c_int,

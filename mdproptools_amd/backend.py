@@ -392,6 +392,30 @@ def lag_msd(r, max_lag, group_off, scale=1.0, ctx=None, out=None, async_=False, 
     return res
 
 
+LAG_PLAN_INFO = ("status", "path", "gen", "m", "source", "Fc", "units", "inst_a", "inst_b", "n_items", "n_batches",
+                 "launches", "L")
+
+
+def lag_plan(F, E, max_lag, group_off, opts=None, ctx=None, cu_count=0, lds_bytes=0, aligned=True):
+    """What `lag_msd` would run on its spectral path for this shape, decided without a device (mdhip_lag_plan) ->
+    dict(kernel=<name last_kernel_name() reports>, **LAG_PLAN_INFO). `ctx`: a context whose options and device limits
+    are read (None: a fresh context's); cu_count / lds_bytes > 0 and `opts` override them."""
+    opts = dict(opts or {})
+    go = _i64(group_off)
+    keys = (C.c_char_p * max(1, len(opts)))(*[k.encode() for k in opts])
+    vals = (C.c_int * max(1, len(opts)))(*[int(v) for v in opts.values()])
+    text = C.create_string_buffer(256)
+    info = np.zeros(len(LAG_PLAN_INFO), np.int32)
+    rc = _lib.load().mdhip_lag_plan(None if ctx is None else ctx.h, int(F), int(E), int(max_lag), len(go) - 1, ptr(go, C.c_int64),
+                               int(aligned), int(cu_count), int(lds_bytes), len(opts), keys, vals, text, len(text),
+                               ptr(info, C.c_int32))
+    if rc != 0:
+        raise _lib.MdhipError(rc, "mdhip_lag_plan: unusable arguments")
+    out = dict(zip(LAG_PLAN_INFO, (int(v) for v in info)))
+    out["kernel"] = text.value.decode()
+    return out
+
+
 def charge_flux(vel, atom_mass, atom_q, seg_off, seg_type, n_types, vel_conv, charge_conv, ctx=None, out=None,
                 async_=False):
     """`conductivity_loop` for every frame (_conductivity.py:11-35): vel [F,3,N] -> j [3,T,F] (`out`: float64 CUDA

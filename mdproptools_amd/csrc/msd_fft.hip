@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "lag_plan.h"
 
 namespace {
 
@@ -2014,143 +2015,205 @@ __global__ void lag_total_kernel(double *__restrict__ out, long long n, double *
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The host part. lag_choose (lag_plan.h) decides what a call runs — the path, where the series come from, the template
+// instance, the batches — from plain values; the three runners below execute that plan and share the mean pre-pass
+// (lag_centre_means) and the device finish (lag_finish). mdhip_lag_plan answers from the same decision without a device.
+namespace lp = lagplan;
+
+static_assert(lp::W12_NW == W12_NW && lp::W12_SUB == W12_SUB && lp::W12_N == W12_N && lp::W12_UN == W12_UN &&
+                  lp::FT_THREADS == FT_THREADS && lp::FT_MAX_M == FT_MAX_M && lp::F3_MIN_M == F3_MIN_M &&
+                  lp::ST_UNITS == ST_UNITS && lp::TSQ_TILES == TSQ_TILES,
+              "lag_plan.h decides with the kernels' own geometry");
+static_assert(sizeof(lp::LagItem) == sizeof(FftItem) && offsetof(lp::LagItem, c_hi) == offsetof(FftItem, c_hi) &&
+                  offsetof(lp::LagItem, step) == offsetof(FftItem, step) && offsetof(lp::LagItem, row) == offsetof(FftItem, row) &&
+                  sizeof(lp::LagStage) == sizeof(FftStage) && offsetof(lp::LagStage, hi) == offsetof(FftStage, hi) &&
+                  offsetof(lp::LagStage, k) == offsetof(FftStage, k) && offsetof(lp::LagStage, cluster) == offsetof(FftStage, cluster),
+              "the plan's items and stages are copied to the device as the kernels' FftItem / FftStage");
+
+// the two device limits, the kernels' LDS needs and the lag_* options as lag_choose takes them
+lp::LagDevice lag_device(const mdhip_ctx *ctx)
+{
+    lp::LagDevice d;
+    d.cu_count = ctx->cu_count;
+    d.lds_max = ctx->lds_max;
+    for (int m = 0; m <= FT_MAX_M; ++m) {
+        d.need.ft[m] = ft_lds_bytes(m);
+        d.need.f2[m] = m >= 9 ? f2_lds_bytes(m) : 0;  // (the decision reads them from m = 9 / F3_MIN_M on)
+        d.need.f3[m] = m >= F3_MIN_M ? f3_lds_bytes(m) : 0;
+    }
+    d.need.w12 = w12_lds_bytes(6);
+    d.need.w1 = w1_lds_bytes(3);
+    d.need.residue = std::max(std::max(w12r_lds_bytes(4), w12p_lds_bytes()), w12o_lds_bytes());
+    d.part_cus0 = lp::lag_part_cus0(ctx->cu_count);
+    return d;
+}
+
+lp::LagOptions lag_options(const mdhip_ctx *ctx)
+{
+    lp::LagOptions o;
+    o.variant = ctx->opt_lag_variant;
+    o.w1 = ctx->opt_lag_w1;
+    o.w12_min_f = ctx->opt_lag_w12_min_f;
+    o.fft_kernel = ctx->opt_lag_fft_kernel;
+    o.direct = ctx->opt_lag_direct;
+    o.residue = ctx->opt_lag_residue;
+    o.overlap = ctx->opt_lag_overlap;
+    o.batch_mb = ctx->opt_lag_batch_mb;
+    o.batched_fuse = ctx->opt_lag_batched_fuse;
+    return o;
+}
+
+lp::LagProblem lag_problem(const mdhip_ctx *ctx, long long F, long long E, int max_lag, long long G, const int64_t *group_off,
+                           bool r_aligned16)
+{
+    lp::LagProblem p;
+    p.F = F;
+    p.E = E;
+    p.max_lag = max_lag;
+    p.G = G;
+    p.group_off = group_off;
+    p.r_aligned16 = r_aligned16;
+    const long long L = lp::lag_pow2_length(F + max_lag);
+    p.two_pass_ok = L < (1LL << 30) && mdhip_fft_power2_plan(ctx, L);
+    return p;
+}
+
+// Consecutive arrays of one workspace block: take<T>(count, align) -> the next `count` T's, the offset rounded up to `align`
+struct Carve {
+    unsigned char *base;
+    size_t off = 0;
+    template <class T>
+    T *take(size_t count, size_t align = alignof(T))
+    {
+        off = (off + align - 1) / align * align;
+        T *p = reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(base) + off);
+        off += count * sizeof(T);
+        return p;
+    }
+};
+
+// one call's arguments, as the runners and lag_finish take them (group_off: the copy in res, which outlives the caller's)
+struct LagCall {
+    long long F, E, G;
+    int max_lag;
+    const double *d_r;
+    double scale;
+    std::shared_ptr<LagFftResult> res;
+    double *out;
+    int out_on_device;
+    long long n_lags() const { return (long long)max_lag + 1; }
+    long long cols() const { return 3 * E; }
+    long long S() const { return 3 * G; }
+};
+
+int lag_run(CallScope &cs, const LagCall &c, const lp::LagPlan &pl);
+
+// frames between two samples of the series' means (col_sum_sample_kernel): ~512 samples of a long trajectory (128 of one of at
+// most 1536 frames); option `lag_mean_sample` 0 = every frame, n > 0 = about n samples
+inline long long lag_mean_stride(const mdhip_ctx *ctx, long long F, long long dflt)
+{
+    if (ctx->opt_lag_mean_sample == 0) return 1;
+    const long long want = ctx->opt_lag_mean_sample > 0 ? ctx->opt_lag_mean_sample : dflt;
+    return std::max<long long>(1, F / want);
+}
+
+// The mean pre-pass of the long-series paths: d_mean [cols] <- scale x the mean of (about `samples` frames of) every column;
+// d_msum [MF_SLABS][cols] is its scratch
+void lag_centre_means(mdhip_ctx *ctx, const LagCall &c, long long samples, double *d_mean, double *d_msum)
+{
+    const long long F = c.F, cols = c.cols(), m_stride = lag_mean_stride(ctx, F, samples);
+    if (m_stride > 1)
+        hipLaunchKernelGGL(col_sum_sample_kernel, dim3((unsigned)((cols + 255) / 256), MF_SLABS), dim3(256), 0, ctx->stream, c.d_r, F,
+                           cols, m_stride, d_msum);
+    else
+        hipLaunchKernelGGL(col_sum_kernel, dim3((unsigned)((cols + 255) / 256), MF_SLABS), dim3(256), 0, ctx->stream, c.d_r, F, cols,
+                           d_msum);
+    hipLaunchKernelGGL(col_mean_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, ctx->stream, d_msum, MF_SLABS,
+                       m_stride > 1 ? sample_count(F, MF_SLABS, m_stride) : F, cols, c.scale, d_mean);
+}
+
+// The finish, on the device (lag_finish_dd_kernel): means into `d_fin`, from there to the caller's buffer on the stream;
+// only the bound of every segment (and the staging rings' stall word) comes back for the completion step.
+// d_corr: the segments' correlations, `corr_stride` doubles apart, to be scaled by `corr_scale`; L_eps: the transform
+// length the error bound is priced with; d_stall (fused staged kernels, else null): set when a cluster member never ran —
+// the completion step then answers with `pl_again` (the same call over the transposed copy) instead.
+int lag_finish(CallScope &cs, const LagCall &c, const KernelTimer &timer, const double *d_Q, const double *d_corr, const double *d_ng,
+               long long corr_stride, double corr_scale, long long L_eps, const unsigned *d_stall, const lp::LagPlan &pl_again)
+{
+    mdhip_ctx *ctx = cs.ctx;
+    const long long F = c.F, G = c.G, S = c.S(), n_lags = c.n_lags();
+    const size_t fin_b = (size_t)n_lags * G * 4 * 8;
+    MD_WS(d_fin_ws, unsigned char, WS_OUT3, fin_b + lag_bound_words(S) * 8 + (size_t)S * (F + 1) * sizeof(DD) + 64);
+    Carve ws{d_fin_ws};
+    double *d_fin = ws.take<double>((size_t)n_lags * G * 4), *d_bound = ws.take<double>(lag_bound_words(S));
+    DD *d_pre = ws.take<DD>((size_t)S * (F + 1), 8);
+    const double eps_l = 4.0 * 2.220446049250313e-16 * std::log2((double)L_eps);
+    hipLaunchKernelGGL(lag_finish_dd_kernel, dim3((unsigned)S), dim3(256), 0, ctx->stream, d_Q, d_corr, corr_stride, corr_scale, F,
+                       n_lags, (int)G, d_ng, eps_l, d_pre, d_fin, d_bound);
+    hipLaunchKernelGGL(lag_total_kernel, dim3((unsigned)((n_lags * G + 255) / 256)), dim3(256), 0, ctx->stream, d_fin,
+                       n_lags * G, d_bound, (int)S, d_stall);
+    ctx->lag_status_dev = d_bound + S;  // (mdhip_lag_msd_status_dev: valid until the next call that uses WS_OUT3)
+    MD_HIP(hipGetLastError());
+    {
+        const int rcr = mdhip_result(cs, c.out, d_fin, fin_b, c.out_on_device);
+        if (rcr) return rcr;
+    }
+    MD_PIN(h_pin, unsigned char, lag_bound_words(S) * 8 + 8);
+    Carve hs{h_pin};
+    double *h_bound = hs.take<double>(lag_bound_words(S));
+    unsigned *h_stall = hs.take<unsigned>(1);
+    *h_stall = 0u;
+    {
+        const int rcc = mdhip_copy_small(ctx, h_bound, d_bound, lag_bound_words(S) * 8, hipMemcpyDeviceToHost);
+        if (rcc) return rcc;
+    }
+    if (d_stall) {
+        const int rcc = mdhip_copy_small(ctx, h_stall, d_stall, 4, hipMemcpyDeviceToHost);
+        if (rcc) return rcc;
+    }
+    cs.defer([=]() {
+        timer.collect();
+        if (*h_stall) {
+            // a cluster member never ran (the grid was not resident as a whole): the same call over the transposed copy,
+            // inside a synchronous call of its own (d_r is the caller's, or the call's staging: valid until completion);
+            // it writes `out` again
+            ++ctx->cur_fallbacks;  // visible: mdhip_ticket_status / mdhip_fallbacks (the 2 s poll is otherwise silent)
+            ++ctx->fallbacks_total;
+            CallScope again(ctx);
+            const int rc2 = lag_run(again, c, pl_again);
+            if (rc2 != MDHIP_OK) return rc2;
+            const int rc3 = again.end();
+            ctx->last_kernel = pl_again.w12() ? "msd_power_w12_kernel (repeated over the transposed copy: a cluster member did not run)"
+                                              : "msd_power_lds_kernel (repeated over the transposed copy: a cluster member did not run)";
+            return rc3;
+        }
+        lag_collect_bounds(c.res.get(), h_bound, S, n_lags);
+        return MDHIP_OK;
+    });
+    return MDHIP_OK;
+}
+
 // The fused LDS path: L = 2^(m+1) <= 16384.
 // w12 (round 5): N = 6144 = 12 x 512, L = 12288 (msd_fft_w12.h) instead of N = 2^m; `m` is ignored then.
 // The means go to `out` (host or device memory) from here: finished on the device, copied on the stream; res->bound is
 // known when the call has completed.
-int lag_msd_fft_fused(CallScope &cs, long long F, long long E, const double *d_r, double scale, int max_lag,
-                      long long G, const int64_t *group_off, int m, const std::shared_ptr<LagFftResult> &res,
-                      double *out, int out_on_device, int src_want = -1 /* -1: the context's option lag_direct */,
-                      bool w12 = false)
+int lag_msd_fft_fused(CallScope &cs, const LagCall &c, const lp::LagPlan &pl)
 {
     mdhip_ctx *ctx = cs.ctx;
-    const long long n_lags = (long long)max_lag + 1, cols = 3 * E, S = 3 * G;
-    const long long N = w12 ? (long long)W12_N : 1LL << m, L = 2 * N;
+    const long long F = c.F, E = c.E, G = c.G, n_lags = c.n_lags(), cols = c.cols(), S = c.S();
+    const double *d_r = c.d_r;
+    const double scale = c.scale;
+    const bool w12 = pl.w12(), staged = pl.staged(), direct = pl.src != 0;
+    const int m = pl.m, n_clusters = pl.n_clusters, Fc = pl.Fc;
+    const long long N = pl.L / 2, L = pl.L;
     const size_t lds_b = w12 ? (size_t)W12_N * 16 + 256 * 16 : ft_lds_bytes(m);
-    // round-3 kernel (conflict-free layout, bilinear spectrum accumulation): N = 2^m a multiple of the block size
-    const bool v2 = !w12 && ctx->opt_lag_fft_kernel != 0 && m >= 9 && f2_lds_bytes(m) <= ctx->lds_max;
-    // second step of round 3 (first pass from registers, wave-private sub-transforms): lag_fft_kernel >= 2
-    const bool v3 = !w12 && ctx->opt_lag_fft_kernel >= 2 && m >= F3_MIN_M && f3_lds_bytes(m) <= ctx->lds_max;
-    // round 4, option `lag_direct` (off by default: measured slower, see ctx.h): that kernel reads the trajectory as it
-    // is, [F][3 E], no transposed copy (see msd_power_lds3_kernel). Needs the blocks in whole clusters of 16 per XCD:
-    // 128 | cu_count.
-    // round 4, option `lag_direct` = 2 (default): no transposed copy either, the clusters of 16 blocks transpose their own
-    // tiles inside the kernel through a small ring (SRC == 2 of msd_power_lds3_kernel): any 16 blocks, rows per member
-    // Fc = F / 16 rounded up to whole 128-byte lines, at most 64 ST_UNITS.
-    const int n_clusters = ctx->cu_count / 16;
-    constexpr int LAG_DIRECT_DEFAULT = 2;  // where the series come from when the option is -1
-    const int src_opt = src_want >= 0 ? src_want : ctx->opt_lag_direct >= 0 ? ctx->opt_lag_direct : LAG_DIRECT_DEFAULT;
-    const int Fc = (int)((((F + 15) / 16) + 15) / 16 * 16);
-    const bool staged = (v3 || w12) && (src_opt == 2 || src_opt == 3) && ctx->cu_count % 16 == 0 && n_clusters >= 1 &&
-                        (w12 ? Fc <= 16 * (W12_NW / 2) * W12_UN
-                             : Fc <= 64 * ST_UNITS && (Fc <= 64 * 5 || (m == 13 && F <= 8192))) &&  // (eight units: the N = 8192 kernels only)
-                        cols >= 16 * (long long)n_clusters &&
-                        (unsigned long long)Fc * (unsigned long long)cols * 8ull < 0xFFFFF000ull &&  // (a member's rows: one buffer)
-                        (reinterpret_cast<unsigned long long>(d_r) & 15ull) == 0ull;  // (16-byte loads of column pairs
-                                                                                     // where the column count is even)
-    const bool direct = staged || (v3 && src_opt == 1 && ctx->cu_count % 128 == 0 && cols >= 16 * (long long)n_clusters);
-    // work items: every non-empty segment gets a share of ~one block per CU, each a contiguous series range — or, for
-    // the direct-read kernel, whole clusters of 16 blocks that walk the segment's 16-column tiles (aligned to 16 columns
-    // of the [F][cols] matrix = one 128-byte line per row), member k taking column 16 T + k
-    std::vector<FftItem> items;
-    std::vector<FftStage> stages;
-    std::vector<int> seg_off((size_t)S + 1, 0);
-    if (!direct) {
-        for (long long s = 0; s < S; ++s) {
-            const long long a = s / G, g = s % G;
-            const long long lo = a * E + group_off[g], hi = a * E + group_off[g + 1], n = hi - lo;
-            seg_off[s] = (int)items.size();
-            if (n <= 0) continue;
-            long long k = (n * ctx->cu_count + cols / 2) / cols;
-            k = std::max<long long>(1, std::min(k, n));
-            for (long long q = 0; q < k; ++q)
-                items.push_back({lo + n * q / k, lo + n * (q + 1) / k, 1, (int)items.size()});
-        }
-        seg_off[S] = (int)items.size();
-    } else {
-        // clusters per segment by largest remainder (every non-empty segment at least one while clusters last)
-        std::vector<long long> seg_n((size_t)S), seg_lo((size_t)S);
-        std::vector<int> seg_c((size_t)S, 0);
-        int nonempty = 0, given = 0;
-        for (long long s = 0; s < S; ++s) {
-            const long long a = s / G, g = s % G;
-            seg_lo[s] = a * E + group_off[g];
-            seg_n[s] = group_off[g + 1] - group_off[g];
-            if (seg_n[s] > 0) ++nonempty;
-        }
-        const bool enough = nonempty <= n_clusters;
-        for (long long s = 0; s < S && enough; ++s)
-            if (seg_n[s] > 0) {
-                seg_c[s] = std::max<int>(1, (int)(seg_n[s] * n_clusters / cols));
-                given += seg_c[s];
-            }
-        while (enough && given > n_clusters) {  // (the floor of 1 can overshoot when many segments are tiny)
-            long long best = -1;
-            for (long long s = 0; s < S; ++s)
-                if (seg_c[s] > 1 && (best < 0 || seg_n[s] * seg_c[best] < seg_n[best] * seg_c[s])) best = s;
-            if (best < 0) break;
-            --seg_c[best];
-            --given;
-        }
-        while (enough && given < n_clusters) {  // the segment with the most columns per cluster takes the next one
-            long long best = -1;
-            for (long long s = 0; s < S; ++s)
-                if (seg_n[s] > 0 && (best < 0 || seg_n[s] * seg_c[best] > seg_n[best] * seg_c[s])) best = s;
-            ++seg_c[best];
-            ++given;
-        }
-        if (!enough || given != n_clusters) {
-            // more non-empty segments than clusters: this shape keeps the transposed path (re-enter without `direct`)
-            return lag_msd_fft_fused(cs, F, E, d_r, scale, max_lag, G, group_off, m, res, out, out_on_device, 0, w12);
-        }
-        // rows (= Qpart / Ppart rows, consecutive per segment): cluster q, member k -> row 16 q + k
-        std::vector<FftItem> rows;
-        if (staged) {
-            // block 16 q + k = member k of cluster q (no placement assumption); c_lo / c_hi = the cluster's tiles
-            for (long long s = 0; s < S; ++s) {
-                seg_off[s] = (int)rows.size();
-                if (seg_c[s] == 0) continue;
-                const long long lo = seg_lo[s], hi = lo + seg_n[s];
-                const long long t0 = lo / 16, t1 = (hi + 15) / 16, nt = t1 - t0;
-                for (int q = 0; q < seg_c[s]; ++q) {
-                    const long long ta = t0 + nt * q / seg_c[s], tb = t0 + nt * (q + 1) / seg_c[s];
-                    for (int k = 0; k < 16; ++k) {
-                        stages.push_back({lo, hi, k, (int)(rows.size() / 16)});
-                        rows.push_back({ta, tb, 1, (int)rows.size()});
-                    }
-                }
-            }
-            seg_off[S] = (int)rows.size();
-            items = rows;
-        } else {
-        for (long long s = 0; s < S; ++s) {
-            seg_off[s] = (int)rows.size();
-            if (seg_c[s] == 0) continue;
-            const long long lo = seg_lo[s], hi = lo + seg_n[s];
-            const long long t0 = lo / 16, t1 = (hi + 15) / 16, nt = t1 - t0;
-            for (int q = 0; q < seg_c[s]; ++q) {
-                const long long ta = t0 + nt * q / seg_c[s], tb = t0 + nt * (q + 1) / seg_c[s];
-                for (int k = 0; k < 16; ++k) {
-                    long long c0 = 16 * ta + k, c1 = 16 * tb;  // columns 16 T + k, ta <= T < tb, inside [lo, hi)
-                    while (c0 < lo) c0 += 16;
-                    c1 = std::min(c1, hi);
-                    rows.push_back({c0, std::max(c0, c1), 16, (int)rows.size()});
-                }
-            }
-        }
-        seg_off[S] = (int)rows.size();
-        // block b runs on XCD b % 8, dispatch round b / 8: the 16 members of a cluster are the blocks of one XCD in 16
-        // consecutive rounds
-        const int per_xcd = ctx->cu_count / 8;  // dispatch rounds = blocks per XCD
-        items.resize(rows.size());
-        for (int b = 0; b < (int)rows.size(); ++b) {
-            const int xcd = b % 8, round = b / 8;
-            const int q = (round / 16) * 8 + xcd, k = round % 16;
-            (void)per_xcd;
-            items[(size_t)b] = rows[(size_t)q * 16 + k];
-        }
-        }
-    }
+    const int fc_arg = pl.src_opt == 3 ? -Fc : Fc;
+    c.res->delivered = true;
+    std::vector<lp::LagItem> items;
+    std::vector<lp::LagStage> stages;
+    std::vector<int> seg_off;
+    lp::lag_fused_items(pl, ctx->cu_count, E, G, c.res->group_off.data(), items, stages, seg_off);
     const long long n_items = (long long)items.size();
 
     // twiddle table of w_L: A[i] = w^(128 i), B[i] = w^i
@@ -2177,38 +2240,56 @@ int lag_msd_fft_fused(CallScope &cs, long long F, long long E, const double *d_r
     const size_t qp_b = (size_t)n_items * F * 8, pp_b = (size_t)n_items * (N + 1) * 8;
     MD_WS(d_part, double, WS_PART, qp_b + pp_b);
     double *d_Qpart = d_part, *d_Ppart = d_part + (size_t)n_items * F;
-    const size_t q_b = (size_t)S * F * 8, p_b = (size_t)S * (N + 1) * 8, c_b = (size_t)S * n_lags * 8;
-    const size_t it_b = (size_t)n_items * sizeof(FftItem), so_b = (((size_t)S + 1) * 4 + 7) / 8 * 8;
-    const size_t sg_b = (stages.size() * sizeof(FftStage) + 7) / 8 * 8, ng_b = (size_t)G * 8;
+    // WS_AUX3: Q | P | correlations | the tables the host fills | the rings' ready counters. The tables — twiddles | items |
+    // segment offsets | stages | entities per group — are laid out once for the device and once for their pinned staging
+    // block (the vectors above are locals), and go over in one copy
+    struct Tables {
+        double2 *tab;
+        FftItem *items;
+        int *seg_off;
+        FftStage *stages;
+        double *ng;
+        size_t bytes;
+    };
+    auto tables = [&](unsigned char *base) {
+        Carve t{base};
+        Tables r;
+        r.tab = t.take<double2>(256, 8);
+        r.items = t.take<FftItem>((size_t)n_items, 8);
+        r.seg_off = t.take<int>((size_t)S + 1);
+        r.stages = t.take<FftStage>(stages.size(), 8);
+        r.ng = t.take<double>((size_t)G, 8);
+        r.bytes = t.off;
+        return r;
+    };
     // ready counters of the rings, a 128-byte line each, and the stall word behind them
-    const size_t rd_b = staged ? ((size_t)n_clusters * ST_BUF * ST_FLAG_STRIDE + ST_FLAG_STRIDE) * 4 : 0;
-    MD_WS(d_small, unsigned char, WS_AUX3, q_b + p_b + c_b + 4096 + it_b + so_b + sg_b + ng_b + rd_b + 256);
-    double *d_Q = reinterpret_cast<double *>(d_small);
-    double *d_P = reinterpret_cast<double *>(d_small + q_b);
-    double *d_corr = reinterpret_cast<double *>(d_small + q_b + p_b);
-    double2 *d_tab = reinterpret_cast<double2 *>(d_small + q_b + p_b + c_b);
-    FftItem *d_items = reinterpret_cast<FftItem *>(d_small + q_b + p_b + c_b + 4096);
-    int *d_seg_off = reinterpret_cast<int *>(d_small + q_b + p_b + c_b + 4096 + it_b);
-    FftStage *d_stages = reinterpret_cast<FftStage *>(d_small + q_b + p_b + c_b + 4096 + it_b + so_b);
-    double *d_ng = reinterpret_cast<double *>(d_small + q_b + p_b + c_b + 4096 + it_b + so_b + sg_b);  // entities per group
-    // (on a 128-byte boundary: d_small is, and so is everything in front once rounded up)
-    const size_t rd_off = (q_b + p_b + c_b + 4096 + it_b + so_b + sg_b + ng_b + 127) / 128 * 128;
-    unsigned *d_ready = reinterpret_cast<unsigned *>(d_small + rd_off);
+    const size_t rd_n = staged ? (size_t)n_clusters * ST_BUF * ST_FLAG_STRIDE + ST_FLAG_STRIDE : 0;
+    const size_t qpc_b = ((size_t)S * F + (size_t)S * (N + 1) + (size_t)S * n_lags) * 8;
+    MD_WS(d_small, unsigned char, WS_AUX3, qpc_b + tables(nullptr).bytes + 128 + rd_n * 4 + 256);
+    Carve ws{d_small};
+    double *d_Q = ws.take<double>((size_t)S * F), *d_P = ws.take<double>((size_t)S * (N + 1)), *d_corr = ws.take<double>((size_t)S * n_lags);
+    const Tables dt = tables(d_small + ws.off);
+    ws.off += dt.bytes;
+    unsigned *d_ready = ws.take<unsigned>(rd_n, 128);  // (on a 128-byte boundary: d_small is)
+    const unsigned *d_stall = staged ? d_ready + (size_t)n_clusters * ST_BUF * ST_FLAG_STRIDE : nullptr;
     {
-        // twiddles | items | segment offsets | stages: one pinned staging block (the vectors above are locals), one copy
-        MD_PIN(h_tab, unsigned char, 4096 + it_b + so_b + sg_b + ng_b);
-        memcpy(h_tab, tab.data(), 4096);
-        memcpy(h_tab + 4096, items.data(), it_b);
-        memcpy(h_tab + 4096 + it_b, seg_off.data(), ((size_t)S + 1) * 4);
-        if (!stages.empty()) memcpy(h_tab + 4096 + it_b + so_b, stages.data(), stages.size() * sizeof(FftStage));
-        double *h_ng = reinterpret_cast<double *>(h_tab + 4096 + it_b + so_b + sg_b);
-        for (long long g = 0; g < G; ++g) h_ng[g] = (double)(group_off[g + 1] - group_off[g]);
+        MD_PIN(h_tab, unsigned char, dt.bytes);
+        const Tables ht = tables(h_tab);
+        memcpy(ht.tab, tab.data(), 4096);
+        memcpy(ht.items, items.data(), items.size() * sizeof(FftItem));
+        memcpy(ht.seg_off, seg_off.data(), ((size_t)S + 1) * 4);
+        if (!stages.empty()) memcpy(ht.stages, stages.data(), stages.size() * sizeof(FftStage));
+        for (long long g = 0; g < G; ++g) ht.ng[g] = (double)(c.res->group_off[g + 1] - c.res->group_off[g]);
         {  // (a kernel on the launch stream, not a copy engine's job: no hand-over between queues — mdhip_copy_small)
-            const int rcc = mdhip_copy_small(ctx, d_tab, h_tab, 4096 + it_b + so_b + sg_b + ng_b, hipMemcpyHostToDevice);
+            const int rcc = mdhip_copy_small(ctx, dt.tab, h_tab, dt.bytes, hipMemcpyHostToDevice);
             if (rcc) return rcc;
         }
-        if (staged) MD_HIP(hipMemsetAsync(d_ready, 0, rd_b, ctx->stream));
+        if (staged) MD_HIP(hipMemsetAsync(d_ready, 0, rd_n * 4, ctx->stream));
     }
+    double2 *d_tab = dt.tab;
+    FftItem *d_items = dt.items;
+    int *d_seg_off = dt.seg_off;
+    FftStage *d_stages = dt.stages;
 
     KernelTimer timer(ctx);
     if (!direct) {
@@ -2216,40 +2297,37 @@ int lag_msd_fft_fused(CallScope &cs, long long F, long long E, const double *d_r
                            0, ctx->stream, d_r, d_x, F, cols, scale);
         MD_HIP(hipGetLastError());
     }
-    const int qr = (int)((F + FT_THREADS - 1) / FT_THREADS);
+    // the launch macros name the template instance the plan chose
     if (w12) {
-        const int qe = std::max(4, (int)(((F + 1) / 2 + W12_SUB - 1) / W12_SUB));  // first-pass inputs that hold data: 4 .. 6
-        const size_t ldsw = w12_lds_bytes(qe);
+        const size_t ldsw = w12_lds_bytes(pl.QE);
 #define MD_W12_GO(QE, SRC, SH, X, SC)                                                                          \
     {                                                                                                          \
         MD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msd_power_w12_kernel<QE, SRC, SH>),          \
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw));                    \
         hipLaunchKernelGGL((msd_power_w12_kernel<QE, SRC, SH>), dim3((unsigned)n_items), dim3(W12_THREADS), ldsw, \
                            ctx->stream, X, (int)F, d_items, d_tab, d_Qpart, d_Ppart, cols, SC, d_stages, d_ring, \
-                           d_ready, src_opt == 3 ? -Fc : Fc);                                                  \
+                           d_ready, fc_arg);                                                                   \
     }
 #define MD_W12_LAUNCH(QE, SH)                                                                                  \
     {                                                                                                          \
         if (staged) MD_W12_GO(QE, 2, SH, d_r, scale)                                                           \
         else MD_W12_GO(QE, 0, SH, d_x, 1.0)                                                                    \
     }
-        if (F < 6 * W12_SUB) MD_W12_LAUNCH(4, true)  // (1536 <= F < 3072: the host's condition, mdhip_lag_msd_fft)
-        else if (qe <= 4) MD_W12_LAUNCH(4, false)
-        else if (qe == 5) MD_W12_LAUNCH(5, false)
+        if (pl.SH) MD_W12_LAUNCH(4, true)
+        else if (pl.QE == 4) MD_W12_LAUNCH(4, false)
+        else if (pl.QE == 5) MD_W12_LAUNCH(5, false)
         else MD_W12_LAUNCH(6, false)
 #undef MD_W12_LAUNCH
 #undef MD_W12_GO
-    } else if (v3) {
+    } else if (pl.gen == 3) {
         const size_t lds3 = f3_lds_bytes(m);
-        const long long s0 = N >> 3;
-        const int qe = (int)(((F + 1) / 2 + s0 - 1) / s0);  // <= 8
 #define MD_F3_GO(JJ, QE, SRC, X, SC)                                                                           \
     {                                                                                                          \
         MD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msd_power_lds3_kernel<JJ, QE, SRC>),         \
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));                    \
         hipLaunchKernelGGL((msd_power_lds3_kernel<JJ, QE, SRC>), dim3((unsigned)n_items), dim3(FT_THREADS), lds3, \
                            ctx->stream, X, (int)F, m, d_items, d_tab, d_Qpart, d_Ppart, cols, SC, d_stages,    \
-                           d_ring, d_ready, src_opt == 3 ? -Fc : Fc);                                          \
+                           d_ring, d_ready, fc_arg);                                                           \
     }
 #define MD_F3_LAUNCH(JJ, QE)                                                                                   \
     {                                                                                                          \
@@ -2264,58 +2342,60 @@ int lag_msd_fft_fused(CallScope &cs, long long F, long long E, const double *d_r
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));                    \
         hipLaunchKernelGGL((msd_power_lds3_kernel<2, QE, 2, 8>), dim3((unsigned)n_items), dim3(FT_THREADS), lds3, \
                            ctx->stream, d_r, (int)F, m, d_items, d_tab, d_Qpart, d_Ppart, cols, scale, d_stages, \
-                           d_ring, d_ready, src_opt == 3 ? -Fc : Fc);                                          \
+                           d_ring, d_ready, fc_arg);                                                           \
     }
-        if (staged && Fc > 64 * 5) {
-            if (qe <= 3) MD_F3_GO8(3)
+        if (pl.units == 8) {
+            if (pl.QE == 3) MD_F3_GO8(3)
             else MD_F3_GO8(4)
-        } else if (s0 > FT_THREADS) {
-            if (qe <= 3) MD_F3_LAUNCH(2, 3)
-            else if (qe <= 4) MD_F3_LAUNCH(2, 4)
+        } else if (pl.JJ == 2) {
+            if (pl.QE == 3) MD_F3_LAUNCH(2, 3)
+            else if (pl.QE == 4) MD_F3_LAUNCH(2, 4)
             else MD_F3_LAUNCH(2, 8)
         } else {
-            if (qe <= 3) MD_F3_LAUNCH(1, 3)
-            else if (qe <= 4) MD_F3_LAUNCH(1, 4)
+            if (pl.QE == 3) MD_F3_LAUNCH(1, 3)
+            else if (pl.QE == 4) MD_F3_LAUNCH(1, 4)
             else MD_F3_LAUNCH(1, 8)
         }
 #undef MD_F3_LAUNCH
 #undef MD_F3_GO8
 #undef MD_F3_GO
-    } else if (v2) {
+    } else if (pl.gen == 2) {
         const size_t lds2 = f2_lds_bytes(m);
-        const int qr2 = (int)(((F + 1) / 2 + FT_THREADS - 1) / FT_THREADS);  // sample pairs per lane, <= N / 512
 #define MD_F2_LAUNCH(QR2)                                                                                      \
-    {                                                                                                          \
+    case QR2: {                                                                                                \
         MD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msd_power_lds2_kernel<QR2>),                 \
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));                    \
         hipLaunchKernelGGL((msd_power_lds2_kernel<QR2>), dim3((unsigned)n_items), dim3(FT_THREADS), lds2,      \
                            ctx->stream, d_x, (int)F, m, d_items, d_tab, d_Qpart, d_Ppart);                     \
-    }
-        // QR2 = sample pairs per lane: ceil(ceil(F / 2) / 512) <= N / 512 = 16
-        if (qr2 <= 1) MD_F2_LAUNCH(1)
-        else if (qr2 <= 2) MD_F2_LAUNCH(2)
-        else if (qr2 <= 3) MD_F2_LAUNCH(3)
-        else if (qr2 <= 5) MD_F2_LAUNCH(5)
-        else if (qr2 <= 8) MD_F2_LAUNCH(8)
-        else MD_F2_LAUNCH(16)  // (F > N: only with max_lag < F - 1)
+    } break;
+        switch (pl.QR2) {  // sample pairs per lane
+            MD_F2_LAUNCH(1)
+            MD_F2_LAUNCH(2)
+            MD_F2_LAUNCH(3)
+            MD_F2_LAUNCH(5)
+            MD_F2_LAUNCH(8)
+            MD_F2_LAUNCH(16)
+        }
 #undef MD_F2_LAUNCH
     } else {
 #define MD_FT_CASE(QR)                                                                                         \
-    {                                                                                                          \
+    case QR: {                                                                                                 \
         MD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msd_power_lds_kernel<QR>),                   \
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));                   \
         hipLaunchKernelGGL(msd_power_lds_kernel<QR>, dim3((unsigned)n_items), dim3(FT_THREADS), lds_b,         \
                            ctx->stream, d_x, (int)F, m, d_items, d_tab, d_Qpart, d_Ppart);                     \
-    }
-    if (qr <= 1) MD_FT_CASE(1)
-    else if (qr <= 2) MD_FT_CASE(2)
-    else if (qr <= 4) MD_FT_CASE(4)
-    else if (qr <= 8) MD_FT_CASE(8)
-    else if (qr <= 10) MD_FT_CASE(10)
-    else if (qr <= 12) MD_FT_CASE(12)
-    else if (qr <= 16) MD_FT_CASE(16)
-    else if (qr <= 24) MD_FT_CASE(24)
-    else MD_FT_CASE(32)
+    } break;
+        switch (pl.QR) {
+            MD_FT_CASE(1)
+            MD_FT_CASE(2)
+            MD_FT_CASE(4)
+            MD_FT_CASE(8)
+            MD_FT_CASE(10)
+            MD_FT_CASE(12)
+            MD_FT_CASE(16)
+            MD_FT_CASE(24)
+            MD_FT_CASE(32)
+        }
 #undef MD_FT_CASE
     }
     MD_HIP(hipGetLastError());
@@ -2336,91 +2416,32 @@ int lag_msd_fft_fused(CallScope &cs, long long F, long long E, const double *d_r
     }
     MD_HIP(hipGetLastError());
     timer.stop();
-    ctx->last_kernel = w12 ? "msd_power_w12_kernel" : "msd_power_lds_kernel";
+    ctx->last_kernel = pl.name;
 
-    // the finish, on the device (lag_finish_dd_kernel): means into `d_fin`, from there to the caller's buffer on the
-    // stream; only the bound of every group (and the ring's stall word) comes back for the completion step
-    const size_t fin_b = (size_t)n_lags * G * 4 * 8;
-    MD_WS(d_fin_ws, unsigned char, WS_OUT3, fin_b + lag_bound_words(S) * 8 + (size_t)S * (F + 1) * sizeof(DD) + 64);
-    double *d_fin = reinterpret_cast<double *>(d_fin_ws), *d_bound = d_fin + (size_t)n_lags * G * 4;
-    DD *d_pre = reinterpret_cast<DD *>(d_bound + lag_bound_words(S));
-    const double eps_l = 4.0 * 2.220446049250313e-16 * std::log2((double)L);
-    hipLaunchKernelGGL(lag_finish_dd_kernel, dim3((unsigned)S), dim3(256), 0, ctx->stream, d_Q, d_corr, n_lags, 1.0, F, n_lags,
-                       (int)G, d_ng, eps_l, d_pre, d_fin, d_bound);
-    hipLaunchKernelGGL(lag_total_kernel, dim3((unsigned)((n_lags * G + 255) / 256)), dim3(256), 0, ctx->stream, d_fin,
-                       n_lags * G, d_bound, (int)S,
-                       staged ? d_ready + (size_t)n_clusters * ST_BUF * ST_FLAG_STRIDE : (const unsigned *)nullptr);
-    ctx->lag_status_dev = d_bound + S;  // (mdhip_lag_msd_status_dev: valid until the next call that uses WS_OUT3)
-    MD_HIP(hipGetLastError());
-    {
-        const int rcr = mdhip_result(cs, out, d_fin, fin_b, out_on_device);
-        if (rcr) return rcr;
-    }
-    MD_PIN(h_bound, double, lag_bound_words(S) * 8 + 8);
-    unsigned *h_stall = reinterpret_cast<unsigned *>(h_bound + lag_bound_words(S));
-    *h_stall = 0u;
-    {
-        const int rcc = mdhip_copy_small(ctx, h_bound, d_bound, lag_bound_words(S) * 8, hipMemcpyDeviceToHost);
-        if (rcc) return rcc;
-    }
+    // a stalled ring: the completion step repeats the call with the series' source forced to the transposed copy
+    lp::LagPlan pl_again = pl;
     if (staged) {
-        const int rcc = mdhip_copy_small(ctx, h_stall, d_ready + (size_t)n_clusters * ST_BUF * ST_FLAG_STRIDE, 4,
-                                         hipMemcpyDeviceToHost);
-        if (rcc) return rcc;
+        lp::LagOptions o = lag_options(ctx);
+        o.direct = 0;
+        pl_again = lp::lag_choose(lag_device(ctx), o, lag_problem(ctx, F, E, c.max_lag, G, c.res->group_off.data(), true));
     }
-    cs.defer([=]() {
-        timer.collect();
-        if (*h_stall) {
-            // a cluster member never ran (the grid was not resident as a whole): the same call over the transposed copy,
-            // inside a synchronous call of its own (d_r is the caller's, or the call's staging: valid until completion);
-            // it writes `out` again
-            ++ctx->cur_fallbacks;  // visible: mdhip_ticket_status / mdhip_fallbacks (the 2 s poll is otherwise silent)
-            ++ctx->fallbacks_total;
-            CallScope again(ctx);
-            const int rc2 = lag_msd_fft_fused(again, F, E, d_r, scale, max_lag, G, res->group_off.data(), m, res, out,
-                                              out_on_device, 0, w12);
-            if (rc2 != MDHIP_OK) return rc2;
-            const int rc3 = again.end();
-            ctx->last_kernel = w12 ? "msd_power_w12_kernel (repeated over the transposed copy: a cluster member did not run)"
-                                   : "msd_power_lds_kernel (repeated over the transposed copy: a cluster member did not run)";
-            return rc3;
-        }
-        lag_collect_bounds(res.get(), h_bound, S, n_lags);
-        return MDHIP_OK;
-    });
-    return MDHIP_OK;
+    return lag_finish(cs, c, timer, d_Q, d_corr, dt.ng, n_lags, 1.0, L, d_stall, pl_again);
 }
 
 // Round 6: series beyond the fused kernels through msd_power_w12r_kernel (msd_fft_w12r.h): padded length L' = 4 x 6144 = 24 576
 // >= F + max_lag, F <= 12 288. The trajectory is transposed and centred batch by batch (transpose_centre64_kernel, as the
 // batched path), every batch's series are dealt to one block per CU, the blocks' partial spectra are folded per segment, and
 // the correlations come from msd_residue_inverse_kernel; the finish is the fused kernels' (lag_finish_dd_kernel).
-// frames between two samples of the series' means (col_sum_sample_kernel): ~512 samples of a long trajectory (128 of one of at
-// most 1536 frames); option
-// `lag_mean_sample` 0 = every frame, n > 0 = about n samples
-inline long long lag_mean_stride(const mdhip_ctx *ctx, long long F, long long dflt = 512)
-{
-    if (ctx->opt_lag_mean_sample == 0) return 1;
-    const long long want = ctx->opt_lag_mean_sample > 0 ? ctx->opt_lag_mean_sample : dflt;
-    return std::max<long long>(1, F / want);
-}
-
-// short_d2 > 0: trajectories BELOW msd_power_w12_kernel's range (F + max_lag <= 3072, F <= 1536) through msd_power_w1_kernel<short_d2>
-// — padded length short_d2 x 1024, one wave per series; the same preparation, folds, inverse and finish.
-int lag_msd_fft_residue(CallScope &cs, long long F, long long E, const double *d_r, double scale, int max_lag, long long G,
-                        const int64_t *group_off, const std::shared_ptr<LagFftResult> &res, double *out, int out_on_device,
-                        int short_d2 = 0)
+// pl.short_d2 > 0: trajectories BELOW msd_power_w12_kernel's range (F + max_lag <= 3072, F <= 1536) through
+// msd_power_w1_kernel<short_d2> — padded length short_d2 x 1024, one wave per series; the same preparation, folds, inverse
+// and finish.
+int lag_msd_fft_residue(CallScope &cs, const LagCall &c, lp::LagPlan pl)
 {
     mdhip_ctx *ctx = cs.ctx;
-    // D = 4: padded length 24 576, the series as they are; D = 8: 49 152, the series folded once by the transposition (rows
-    // [g | h] of 24 576 doubles): the even frequencies by the D = 4 kernel over those rows, the odd ones by msd_power_w12o_kernel
-    const int D = short_d2 ? 4 : (F <= 2LL * W12_N && F + max_lag <= 4LL * W12_N) ? 4 : 8;  // (short: as D = 4 in what follows)
-    const long long LP = short_d2 ? 1024LL * short_d2 : (long long)D * W12_N, K = LP / 2 + 1;
-    const long long LP4 = short_d2 ? LP : 4LL * W12_N;  // the length of the first twiddle table (msd_power_w12p_kernel's)
-    const int rows_per_item = 1;                        // partial spectra a block writes
-    const long long n_lags = (long long)max_lag + 1, cols = 3 * E, S = 3 * G;
-    const long long row_len = D == 4 ? F : 4LL * W12_N;  // doubles per series of the time-major copy
-    res->delivered = true;
+    const long long F = c.F, E = c.E, G = c.G, n_lags = c.n_lags(), cols = c.cols(), S = c.S();
+    const double *d_r = c.d_r;
+    const double scale = c.scale;
+    const int64_t *group_off = c.res->group_off.data();
     // Round 6, `lag_overlap` (an experiment that did not pay; off by default, kept behind its option and its test): the
     // transposition of batch k + 1 on a quarter of the CUs WHILE the transform kernel of batch k (compute-bound, one workgroup
     // per CU) runs on the other three quarters — two CU-masked streams (hipExtStreamCreateWithCUMask), two buffers, at least
@@ -2428,46 +2449,27 @@ int lag_msd_fft_residue(CallScope &cs, long long F, long long E, const double *d
     // not is the premise that a streaming kernel needs few CUs: the transposition moves 4.8 TB/s on 256 CUs and 1.7 TB/s on
     // 64 (a CU cannot hold the ~160 KB in flight that a quarter of the chip would need to cover HBM's latency), so the call
     // takes 16.7 ms instead of 13.2 (profiles/r06_ab_lag_overlap.txt).
-    const bool want_overlap = ctx->opt_lag_overlap != 0 && !short_d2 &&
-                              (cols * row_len * 8 >= (512LL << 20) || ctx->opt_lag_overlap >= 2 /* tests: whatever the size */) &&
-                              mdhip_part_streams(ctx);
-    long long nb_max = std::max<long long>(1, ((long long)ctx->opt_lag_batch_mb << 20) / (row_len * 8) / (want_overlap ? 2 : 1));
-    if (want_overlap) nb_max = std::min(nb_max, std::max<long long>(ctx->opt_lag_overlap >= 2 ? 1 : 4LL * ctx->cu_count, (cols + 5) / 6));
-    const long long n_batches = (cols + nb_max - 1) / nb_max;
-    const long long nb0 = (cols + n_batches - 1) / n_batches;
-    const bool overlap = want_overlap && n_batches >= 3;
-    // (CUs the transform kernel of batch b runs on: it is given one workgroup per CU)
-    auto batch_cus = [&](long long b) { return overlap && b + 1 < n_batches ? ctx->part_cus[0] : ctx->cu_count; };
-    // work items, batch by batch: every (segment, batch) overlap gets its share of ~one block per CU
-    std::vector<FftItem> items;
-    struct Fold {
-        long long batch, seg, c_lo, c_n;  // the segment's columns inside the batch
-        int first, count;                 // its rows of the blocks' partial spectra
-    };
-    std::vector<Fold> folds;
-    std::vector<int> batch_off((size_t)n_batches + 1, 0);
-    int max_items = 0;
-    long long max_tiles = 1;
-    for (long long b = 0; b < n_batches; ++b) {
-        const long long c_first = b * nb0, nb = std::min(nb0, cols - c_first);
-        batch_off[(size_t)b] = (int)items.size();
-        int row = 0;
-        for (long long s = 0; s < S; ++s) {
-            const long long a = s / G, g = s % G;
-            const long long lo = std::max(c_first, a * E + (long long)group_off[g]);
-            const long long hi = std::min(c_first + nb, a * E + (long long)group_off[g + 1]);
-            if (lo >= hi) continue;
-            const long long n = hi - lo;
-            long long k = (n * batch_cus(b) + nb / 2) / nb;
-            k = std::max<long long>(1, std::min(k, n));
-            folds.push_back({b, s, lo, n, row, (int)k});
-            max_tiles = std::max(max_tiles, (n + 64 * TSQ_TILES - 1) / (64 * TSQ_TILES));
-            for (long long q = 0; q < k; ++q)
-                items.push_back({lo - c_first + n * q / k, lo - c_first + n * (q + 1) / k, 1, row++});
-        }
-        max_items = std::max(max_items, row);
+    lp::LagDevice dev = lag_device(ctx);
+    if (pl.want_overlap && !mdhip_part_streams(ctx)) {  // (the streams could not be made: the plan of a device without them)
+        dev.part_cus0 = 0;
+        pl = lp::lag_choose(dev, lag_options(ctx), lag_problem(ctx, F, E, c.max_lag, G, group_off, true));
     }
-    batch_off[(size_t)n_batches] = (int)items.size();
+    if (pl.overlap) dev.part_cus0 = ctx->part_cus[0];
+    const int short_d2 = pl.short_d2, D = pl.D;
+    const bool packed = pl.packed, overlap = pl.overlap;
+    const long long LP = pl.L, K = LP / 2 + 1;
+    const long long LP4 = short_d2 ? LP : 4LL * W12_N;  // the length of the first twiddle table (msd_power_w12p_kernel's)
+    const int rows_per_item = 1;                        // partial spectra a block writes
+    const long long row_len = D == 4 ? F : 4LL * W12_N;  // doubles per series of the time-major copy
+    const long long n_batches = pl.n_batches, nb0 = pl.nb0;
+    c.res->delivered = true;
+    // work items, batch by batch: every (segment, batch) overlap gets its share of ~one block per CU
+    const lp::LagResidueItems ri = lp::lag_residue_items(pl, dev, E, G, group_off);
+    const std::vector<lp::LagItem> &items = ri.items;
+    const std::vector<lp::LagFold> &folds = ri.folds;
+    const std::vector<int> &batch_off = ri.batch_off;
+    const int max_items = ri.max_items;
+    const long long max_tiles = ri.max_tiles;
 
     // twiddle tables: B[i] = w^i (i < 256), A[i] = w^(256 i) of w_24576 (msd_power_w12p_kernel / _w12r_), behind it of w_49152
     const int n_tab4 = 256 + (int)(LP4 / 256), n_tab8 = D == 8 ? 256 + (int)(LP / 256) : 0, n_tab = n_tab4 + n_tab8;
@@ -2489,52 +2491,56 @@ int lag_msd_fft_residue(CallScope &cs, long long F, long long E, const double *d
     double *d_pads[2] = {d_pad0, overlap ? d_pad0 + (((size_t)nb0 * row_len + 31) & ~(size_t)31) : d_pad0};
     MD_WS(d_part, double, WS_PART, (size_t)max_items * rows_per_item * K * 8);
     MD_WS(d_qpart, double, WS_AUX2, (size_t)max_tiles * F * 8);
-    // (Q | P | correlations, the three together rounded up to 16 bytes: the twiddle table behind them is read as double2)
-    const size_t q_b = (size_t)S * F * 8, p_b = (size_t)S * K * 8, c_b = ((size_t)S * (F + K + n_lags) * 8 + 15) / 16 * 16 - q_b - p_b;
-    const size_t tab_b = (size_t)n_tab * 16, it_b = (items.size() * sizeof(FftItem) + 15) / 16 * 16;
-    const size_t go_b = (size_t)(G + 1) * 8, ng_b = (size_t)G * 8;
-    MD_WS(d_small, unsigned char, WS_AUX3, q_b + p_b + c_b + tab_b + it_b + go_b + ng_b + 256);
-    double *d_Q = reinterpret_cast<double *>(d_small);
-    double *d_P = reinterpret_cast<double *>(d_small + q_b);
-    double *d_corr = reinterpret_cast<double *>(d_small + q_b + p_b);
-    double2 *d_tab = reinterpret_cast<double2 *>(d_small + q_b + p_b + c_b);
-    FftItem *d_items = reinterpret_cast<FftItem *>(d_small + q_b + p_b + c_b + tab_b);
-    long long *d_goff = reinterpret_cast<long long *>(d_small + q_b + p_b + c_b + tab_b + it_b);
-    double *d_ng = reinterpret_cast<double *>(d_small + q_b + p_b + c_b + tab_b + it_b + go_b);
-    (void)d_goff;
+    // WS_AUX3: Q | P | correlations | the tables the host fills: twiddles (read as double2: on a 16-byte boundary) | items |
+    // group offsets | entities per group, laid out once for the device and once for their pinned staging block
+    struct Tables {
+        double2 *tab;
+        FftItem *items;
+        long long *goff;
+        double *ng;
+        size_t bytes;
+    };
+    auto tables = [&](unsigned char *base) {
+        Carve t{base};
+        Tables r;
+        r.tab = t.take<double2>((size_t)n_tab, 16);
+        r.items = t.take<FftItem>(items.size(), 16);
+        r.goff = t.take<long long>((size_t)G + 1, 16);
+        r.ng = t.take<double>((size_t)G);
+        r.bytes = t.off;
+        return r;
+    };
+    const size_t q_b = (size_t)S * F * 8, p_b = (size_t)S * K * 8;
+    MD_WS(d_small, unsigned char, WS_AUX3, (size_t)S * (F + K + n_lags) * 8 + 16 + tables(nullptr).bytes + 256);
+    Carve ws{d_small};
+    double *d_Q = ws.take<double>((size_t)S * F), *d_P = ws.take<double>((size_t)S * K), *d_corr = ws.take<double>((size_t)S * n_lags);
+    ws.take<unsigned char>(0, 16);
+    const Tables dt = tables(d_small + ws.off);
+    double2 *d_tab = dt.tab;
+    FftItem *d_items = dt.items;
     {
-        MD_PIN(h_blk, unsigned char, tab_b + it_b + go_b + ng_b);
-        memcpy(h_blk, tab.data(), tab_b);
-        memcpy(h_blk + tab_b, items.data(), items.size() * sizeof(FftItem));
-        memcpy(h_blk + tab_b + it_b, group_off, go_b);
-        double *h_ng = reinterpret_cast<double *>(h_blk + tab_b + it_b + go_b);
-        for (long long g = 0; g < G; ++g) h_ng[g] = (double)(group_off[g + 1] - group_off[g]);
-        const int rcc = mdhip_copy_small(ctx, d_tab, h_blk, tab_b + it_b + go_b + ng_b, hipMemcpyHostToDevice);
+        MD_PIN(h_blk, unsigned char, dt.bytes);
+        const Tables ht = tables(h_blk);
+        memcpy(ht.tab, tab.data(), (size_t)n_tab * 16);
+        memcpy(ht.items, items.data(), items.size() * sizeof(FftItem));
+        memcpy(ht.goff, group_off, (size_t)(G + 1) * 8);
+        for (long long g = 0; g < G; ++g) ht.ng[g] = (double)(group_off[g + 1] - group_off[g]);
+        const int rcc = mdhip_copy_small(ctx, d_tab, h_blk, dt.bytes, hipMemcpyHostToDevice);
         if (rcc) return rcc;
     }
     MD_HIP(hipMemsetAsync(d_Q, 0, q_b + p_b, ctx->stream));  // (Q | P: both are added to, batch by batch)
 
     KernelTimer timer(ctx);
-    const long long m_stride = lag_mean_stride(ctx, F, short_d2 ? 128 : 512);
-    if (m_stride > 1)
-        hipLaunchKernelGGL(col_sum_sample_kernel, dim3((unsigned)((cols + 255) / 256), MF_SLABS), dim3(256), 0, ctx->stream, d_r, F,
-                           cols, m_stride, d_msum);
-    else
-        hipLaunchKernelGGL(col_sum_kernel, dim3((unsigned)((cols + 255) / 256), MF_SLABS), dim3(256), 0, ctx->stream, d_r, F, cols,
-                           d_msum);
-    hipLaunchKernelGGL(col_mean_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, ctx->stream, d_msum, MF_SLABS,
-                       m_stride > 1 ? sample_count(F, MF_SLABS, m_stride) : F, cols, scale, d_mean);
+    lag_centre_means(ctx, c, short_d2 ? 128 : 512, d_mean, d_msum);
     MD_HIP(hipGetLastError());
-    // lag_residue 1 (default): two transforms per series (the even frequencies packed, the odd ones as class 1); 2: three
-    // classes (0, 1, 2), nothing packed — the first form of the kernel, kept for A/B
-    const bool packed = ctx->opt_lag_residue != 2 || D == 8;
     const size_t ldsr = short_d2 ? w1_lds_bytes(short_d2) : packed ? w12p_lds_bytes() : w12r_lds_bytes(4);
-    MD_HIP(hipFuncSetAttribute(short_d2 == 1   ? reinterpret_cast<const void *>(msd_power_w1_kernel<1>)
-                               : short_d2 == 2 ? reinterpret_cast<const void *>(msd_power_w1_kernel<2>)
-                               : short_d2 == 3 ? reinterpret_cast<const void *>(msd_power_w1_kernel<3>)
-                               : !packed       ? reinterpret_cast<const void *>(msd_power_w12r_kernel<4>)
-                               : D == 4        ? reinterpret_cast<const void *>(msd_power_w12p_kernel<true>)
-                                               : reinterpret_cast<const void *>(msd_power_w12p_kernel<false>),
+    const int rk = pl.residue_kernel;
+    MD_HIP(hipFuncSetAttribute(rk == lp::RK_W1_1         ? reinterpret_cast<const void *>(msd_power_w1_kernel<1>)
+                               : rk == lp::RK_W1_2       ? reinterpret_cast<const void *>(msd_power_w1_kernel<2>)
+                               : rk == lp::RK_W1_3       ? reinterpret_cast<const void *>(msd_power_w1_kernel<3>)
+                               : rk == lp::RK_W12R_4     ? reinterpret_cast<const void *>(msd_power_w12r_kernel<4>)
+                               : rk == lp::RK_W12P_SHARE ? reinterpret_cast<const void *>(msd_power_w12p_kernel<true>)
+                                                         : reinterpret_cast<const void *>(msd_power_w12p_kernel<false>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr));
     if (D == 8) {
         MD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(msd_power_w12o_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2566,25 +2572,32 @@ int lag_msd_fft_residue(CallScope &cs, long long F, long long E, const double *d
     auto power_batch = [&](long long b, hipStream_t st, const double *pad) {
         const int n_it = batch_off[(size_t)b + 1] - batch_off[(size_t)b];
         const FftItem *its = d_items + batch_off[(size_t)b];
-        if (short_d2 == 1)
+        switch (rk) {
+        case lp::RK_W1_1:
             hipLaunchKernelGGL(msd_power_w1_kernel<1>, dim3((unsigned)n_it), dim3(W12_THREADS), ldsr, st, pad, (int)F, its, d_tab, d_part);
-        else if (short_d2 == 2)
+            break;
+        case lp::RK_W1_2:
             hipLaunchKernelGGL(msd_power_w1_kernel<2>, dim3((unsigned)n_it), dim3(W12_THREADS), ldsr, st, pad, (int)F, its, d_tab, d_part);
-        else if (short_d2 == 3)
+            break;
+        case lp::RK_W1_3:
             hipLaunchKernelGGL(msd_power_w1_kernel<3>, dim3((unsigned)n_it), dim3(W12_THREADS), ldsr, st, pad, (int)F, its, d_tab, d_part);
-        else if (D == 8) {
+            break;
+        case lp::RK_W12P_FOLD_W12O:
             hipLaunchKernelGGL(msd_power_w12p_kernel<false>, dim3((unsigned)n_it), dim3(W12_THREADS), ldsr, st, pad, row_len, 2 * W12_N,
                                2 * W12_N, 2 * W12_N, 2, (int)K, its, d_tab, d_part);
             hipLaunchKernelGGL(msd_power_w12o_kernel<1>, dim3((unsigned)n_it), dim3(W12_THREADS), w12o_lds_bytes(), st, pad, its,
                                d_tab + n_tab4, d_part);
             hipLaunchKernelGGL(msd_power_w12o_kernel<3>, dim3((unsigned)n_it), dim3(W12_THREADS), w12o_lds_bytes(), st, pad, its,
                                d_tab + n_tab4, d_part);
-        } else if (packed)
+            break;
+        case lp::RK_W12P_SHARE:
             hipLaunchKernelGGL(msd_power_w12p_kernel<true>, dim3((unsigned)n_it), dim3(W12_THREADS), ldsr, st, pad, row_len, (int)F, 0,
                                (int)F, 1, (int)K, its, d_tab, d_part);
-        else
+            break;
+        default:
             hipLaunchKernelGGL((msd_power_w12r_kernel<4>), dim3((unsigned)n_it), dim3(W12_THREADS), ldsr, st, pad, (int)F, its, d_tab,
                                d_part);
+        }
         for (size_t fi = fold_first[(size_t)b]; fi < folds.size() && folds[fi].batch == b; ++fi)
             hipLaunchKernelGGL(power_fold_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, st,
                                d_part + (size_t)folds[fi].first * rows_per_item * K, folds[fi].count * rows_per_item, K,
@@ -2629,153 +2642,64 @@ int lag_msd_fft_residue(CallScope &cs, long long F, long long E, const double *d
                        d_P, (int)LP, (int)n_lags, d_corr);
     MD_HIP(hipGetLastError());
     timer.stop();
-    ctx->last_kernel = short_d2 ? "msd_power_w1_kernel"
-                       : D == 8 ? "msd_power_w12p_kernel + msd_power_w12o_kernel"
-                       : packed ? "msd_power_w12p_kernel"
-                                : "msd_power_w12r_kernel";
-
-    // the finish, on the device, as the fused kernels'
-    const size_t fin_b = (size_t)n_lags * G * 4 * 8;
-    MD_WS(d_fin_ws, unsigned char, WS_OUT3, fin_b + lag_bound_words(S) * 8 + (size_t)S * (F + 1) * sizeof(DD) + 64);
-    double *d_fin = reinterpret_cast<double *>(d_fin_ws), *d_bound = d_fin + (size_t)n_lags * G * 4;
-    DD *d_pre = reinterpret_cast<DD *>(d_bound + lag_bound_words(S));
-    const double eps_l = 4.0 * 2.220446049250313e-16 * std::log2((double)LP);
-    hipLaunchKernelGGL(lag_finish_dd_kernel, dim3((unsigned)S), dim3(256), 0, ctx->stream, d_Q, d_corr, n_lags, 1.0, F, n_lags,
-                       (int)G, d_ng, eps_l, d_pre, d_fin, d_bound);
-    hipLaunchKernelGGL(lag_total_kernel, dim3((unsigned)((n_lags * G + 255) / 256)), dim3(256), 0, ctx->stream, d_fin, n_lags * G,
-                       d_bound, (int)S, (const unsigned *)nullptr);
-    ctx->lag_status_dev = d_bound + S;
-    MD_HIP(hipGetLastError());
-    {
-        const int rcr = mdhip_result(cs, out, d_fin, fin_b, out_on_device);
-        if (rcr) return rcr;
-    }
-    MD_PIN(h_bound, double, lag_bound_words(S) * 8);
-    {
-        const int rcc = mdhip_copy_small(ctx, h_bound, d_bound, lag_bound_words(S) * 8, hipMemcpyDeviceToHost);
-        if (rcc) return rcc;
-    }
-    cs.defer([timer, res, h_bound, S, n_lags]() {
-        timer.collect();
-        lag_collect_bounds(res.get(), h_bound, S, n_lags);
-        return MDHIP_OK;
-    });
-    return MDHIP_OK;
+    ctx->last_kernel = pl.name;
+    return lag_finish(cs, c, timer, d_Q, d_corr, dt.ng, n_lags, 1.0, LP, nullptr, pl);
 }
 
-}  // namespace
-
-// d_r: device [F][3][E]. out: host [max_lag+1][G][4] means as mdhip_lag_msd. *rel_bound: the largest
-// estimated relative rounding error over all (lag >= 1, group, axis) entries with a non-zero value.
-// Both paths — the fused kernels (padded length <= 16384) and the batched transforms below — finish on the device and
-// deliver the means themselves (res->delivered).
-int mdhip_lag_msd_fft(CallScope &cs, int64_t n_frames, int64_t n_ent, const double *d_r, double scale,
-                      int max_lag, int n_groups, const int64_t *group_off, const std::shared_ptr<LagFftResult> &res,
-                      double *out, int out_on_device)
+// The batched transforms (fft_pow2.hip), whatever the length.
+// Round 6 (`lag_batched_fuse`, default): the first transform pass reads the centred series [nb][F] where the transposition
+// left them (implicit zero padding: no padded copy is written or read) and the column sums of |X_k|^2 are taken straight
+// from the packed transform (r2c_power_rows_kernel: the half spectra are never written) — 2.1 -> 1.3 MB of HBM traffic per
+// series at F = 10 000 (profiles/r06_lag_long_kernel_stats.csv before, r06_lag_sizes.txt after). 0: the round-2 sequence.
+// Second step (`lag_batched_fuse` 2, default): the transform in TWO passes, the second one fused with the column sums
+// (fft_power_pass_kernel): the packed transform is never written either — 1.3 -> 0.9 MB per series (one transform buffer).
+// (round 6: this path finishes on the device as well — lag_finish_dd_kernel on Q and the correlations where they are —
+// so that series of more than 16 384 padded points, trajectories of 10^4+ frames, no longer cost two device-to-host
+// copies and a host pass in long double, and carry the same device status word as the fused kernels)
+int lag_msd_fft_batched(CallScope &cs, const LagCall &c, const lp::LagPlan &pl)
 {
     mdhip_ctx *ctx = cs.ctx;
-    const long long F = n_frames, E = n_ent, G = n_groups;
-    res->group_off.assign(group_off, group_off + n_groups + 1);
-    res->out.clear();
-    res->bound = 0.0;
-    const long long n_lags = (long long)max_lag + 1;
-    const long long cols = 3 * E;
-    // round 6: trajectories below msd_power_w12_kernel's range, one wave per series (msd_fft_w12r.h): padded length 1024 / 2048 / 3072
-    // (the residue-class host path launches its transposition and folds per (axis, group) segment: with many groups the
-    // block-wide kernels, which take every segment in one launch, stay the faster choice for calls of a millisecond)
-    if (ctx->opt_lag_variant != 4 && ctx->opt_lag_w1 != 0 && F + max_lag <= 3072 && F <= 1536 && F >= 2 && n_groups <= 16 &&
-        (F < std::max(3 * W12_SUB, ctx->opt_lag_w12_min_f) || ctx->opt_lag_w12_min_f <= 0 || F + max_lag <= 2048) &&
-        w1_lds_bytes(3) <= ctx->lds_max)
-        return lag_msd_fft_residue(cs, F, E, d_r, scale, max_lag, G, group_off, res, out, out_on_device,
-                                   (int)((F + max_lag + 1023) / 1024));
-    if (ctx->opt_lag_variant != 4) {
-        // fused LDS path when the padded series fits: L = power of two >= max(16, F + max_lag)
-        int m = 3;
-        while ((2LL << m) < F + max_lag) ++m;
-        // round 5: padded length 12288 = 3 * 2^12 where 16384 would be the next power of two (msd_fft_w12.h)
-        // round 6: the same kernel for 2048 < F + max_lag <= 8192 (m == 11, 12) from `lag_w12_min_f` frames on (default 1536,
-        // the SHORT instance's lower limit): its twelve register-resident 512-point sub-transforms cost less per series than
-        // the power-of-two kernels' 2048- and 4096-point transforms through LDS although it transforms 1.5-3 x the points
-        // (tools/lag_sizes.py, profiles/r06_lag_sizes_ab.txt: E = 50 000, full lag, F = 1536 3.77 vs 3.78 ms, 2048 3.62 vs
-        // 4.06, 3000 3.79 vs 5.43, 4096 4.02 vs 7.01)
-        const bool w12_long = m == 13 && F >= 6 * W12_SUB;
-        const bool w12_short = (m == 12 || m == 11) && F >= std::max(3 * W12_SUB, ctx->opt_lag_w12_min_f) && ctx->opt_lag_w12_min_f > 0;
-        if (ctx->opt_lag_fft_kernel >= 3 && (w12_long || w12_short) && F + max_lag <= 2 * W12_N && (F + 1) / 2 <= 6 * W12_SUB &&
-            w12_lds_bytes(6) <= ctx->lds_max) {
-            res->delivered = true;
-            return lag_msd_fft_fused(cs, F, E, d_r, scale, max_lag, G, group_off, m, res, out, out_on_device, -1, true);
-        }
-        if (m <= FT_MAX_M && ft_lds_bytes(m) <= ctx->lds_max) {
-            res->delivered = true;
-            return lag_msd_fft_fused(cs, F, E, d_r, scale, max_lag, G, group_off, m, res, out, out_on_device);
-        }
-    }
-    // round 6: 16 384 < F + max_lag <= 24 576 (F <= 12 288) in residue classes of a 4 x 6144-point transform, F + max_lag <=
-    // 49 152 (F <= 24 576) of an 8 x 6144-point one: no transform pass through HBM
-    if (ctx->opt_lag_variant != 4 && ctx->opt_lag_residue != 0 && F + max_lag <= 8LL * W12_N && F <= 4LL * W12_N &&
-        std::max(std::max(w12r_lds_bytes(4), w12p_lds_bytes()), w12o_lds_bytes()) <= ctx->lds_max)
-        return lag_msd_fft_residue(cs, F, E, d_r, scale, max_lag, G, group_off, res, out, out_on_device);
-    const long long L = pow2_length(F + max_lag);
-    MD_REQUIRE(L < (1LL << 30), "series too long for the FFT path (%lld)", L);
-    // (round 6: this path finishes on the device as well — lag_finish_dd_kernel on Q and the correlations where they are —
-    // so that series of more than 16 384 padded points, trajectories of 10^4+ frames, no longer cost two device-to-host
-    // copies and a host pass in long double, and carry the same device status word as the fused kernels)
-    res->delivered = true;
+    const long long F = c.F, E = c.E, G = c.G, cols = c.cols(), S = c.S();
+    const double *d_r = c.d_r;
+    const double scale = c.scale;
+    const int64_t *group_off = c.res->group_off.data();
+    const long long L = pl.L;
+    MD_REQUIRE(!pl.too_long, "series too long for the FFT path (%lld)", L);
+    c.res->delivered = true;
     const long long K = L / 2 + 1;
-    const long long S = 3 * G;  // (axis, group) segments
-
-    // Round 6 (`lag_batched_fuse`, default): the first transform pass reads the centred series [nb][F] where the transposition
-    // left them (implicit zero padding: no padded copy is written or read) and the column sums of |X_k|^2 are taken straight
-    // from the packed transform (r2c_power_rows_kernel: the half spectra are never written) — 2.1 -> 1.3 MB of HBM traffic per
-    // series at F = 10 000 (profiles/r06_lag_long_kernel_stats.csv before, r06_lag_sizes.txt after). 0: the round-2 sequence.
-    // Second step (`lag_batched_fuse` 2, default): the transform in TWO passes, the second one fused with the column sums
-    // (fft_power_pass_kernel): the packed transform is never written either — 1.3 -> 0.9 MB per series (one transform buffer).
-    const bool fuse = ctx->opt_lag_batched_fuse != 0;
-    const bool fuse2 = ctx->opt_lag_batched_fuse >= 2 && mdhip_fft_power2_plan(ctx, L);
+    const bool fuse = pl.fuse != 0, fuse2 = pl.fuse == 2;
     constexpr int MF_SPLITS2 = 128;  // row splits of the fused pass (8-16 tiles of columns each: >= 4 workgroups per CU)
-    // batches of whole series: (padded copy | centred series) + the transform buffers (+ spectrum) <= ~4 GiB
-    const long long per_series = fuse2 ? F * 8 + L * 8 : fuse ? F * 8 + 2 * L * 8 : 2 * L * 8 + K * 16;
-    const long long nb_max = std::max<long long>(1, std::min<long long>(((long long)ctx->opt_lag_batch_mb << 20) / per_series, (1LL << 31) / K));
-    const long long n_batches = (cols + nb_max - 1) / nb_max;
-    const long long nb0 = (cols + n_batches - 1) / n_batches;
+    const long long nb0 = pl.nb0;
 
     MD_WS(d_mean, double, WS_AUX0, (size_t)(MF_SLABS + 1) * cols * 8);
     double *d_msum = d_mean + cols;
     MD_WS(d_pad, double, WS_AUX1, (size_t)nb0 * (fuse ? F : L) * 8);                 // fuse: the centred series [nb][F]
     MD_WS(d_spec, double2, WS_AUX2, fuse ? (size_t)nb0 * L * 8 : (size_t)nb0 * K * 16);  // fuse: the first transform buffer
     MD_WS(d_tmp, double2, WS_FFT_TMP, (size_t)(fuse2 ? S : std::max(nb0, S)) * L * 8 + 64);
-    // Q [S][F] | P [S][K] | complex P [S][K] | correlations [S][L] | group offsets
-    const size_t q_b = (size_t)S * F * 8, p_b = (size_t)S * K * 8, z_b = (size_t)S * K * 16, c_b = (size_t)S * L * 8;
-    MD_WS(d_small, unsigned char, WS_AUX3, q_b + p_b + z_b + c_b + (size_t)(G + 1) * 8 + (size_t)G * 8 + 256);
-    double *d_Q = reinterpret_cast<double *>(d_small);
-    double *d_P = reinterpret_cast<double *>(d_small + q_b);
-    double2 *d_Z = reinterpret_cast<double2 *>(d_small + q_b + p_b);
-    double *d_corr = reinterpret_cast<double *>(d_small + q_b + p_b + z_b);
-    long long *d_goff = reinterpret_cast<long long *>(d_small + q_b + p_b + z_b + c_b);
-    double *d_ng = reinterpret_cast<double *>(d_goff + G + 1);  // entities per group (lag_finish_dd_kernel)
+    // WS_AUX3: Q [S][F] | P [S][K] | complex P [S][K] | correlations [S][L] | group offsets | entities per group
+    MD_WS(d_small, unsigned char, WS_AUX3, ((size_t)S * (F + 3 * K + L) + (size_t)(2 * G + 1)) * 8 + 256);
+    Carve ws{d_small};
+    double *d_Q = ws.take<double>((size_t)S * F), *d_P = ws.take<double>((size_t)S * K);
+    double2 *d_Z = ws.take<double2>((size_t)S * K, 8);
+    double *d_corr = ws.take<double>((size_t)S * L);
+    long long *d_goff = ws.take<long long>((size_t)G + 1);
+    double *d_ng = ws.take<double>((size_t)G);  // entities per group (lag_finish_dd_kernel)
     MD_WS(d_part, double, WS_PART, (size_t)(fuse2 ? MF_SPLITS2 : MF_SPLITS) * K * 8);
 
     {
         // group offsets | entities per group: one pinned block, one copy on the launch stream
         MD_PIN(h_g, unsigned char, (size_t)(2 * G + 1) * 8);
-        memcpy(h_g, group_off, (size_t)(G + 1) * 8);
-        double *h_ng = reinterpret_cast<double *>(h_g + (size_t)(G + 1) * 8);
+        Carve hs{h_g};
+        memcpy(hs.take<long long>((size_t)G + 1), group_off, (size_t)(G + 1) * 8);
+        double *h_ng = hs.take<double>((size_t)G);
         for (long long g = 0; g < G; ++g) h_ng[g] = (double)(group_off[g + 1] - group_off[g]);
         const int rc0 = mdhip_copy_small(ctx, d_goff, h_g, (size_t)(2 * G + 1) * 8, hipMemcpyHostToDevice);
         if (rc0) return rc0;
     }
-    MD_HIP(hipMemsetAsync(d_P, 0, p_b, ctx->stream));
+    MD_HIP(hipMemsetAsync(d_P, 0, (size_t)S * K * 8, ctx->stream));
 
     KernelTimer timer(ctx);
-    const long long m_stride = lag_mean_stride(ctx, F);
-    if (m_stride > 1)
-        hipLaunchKernelGGL(col_sum_sample_kernel, dim3((unsigned)((cols + 255) / 256), MF_SLABS), dim3(256), 0, ctx->stream, d_r, F,
-                           cols, m_stride, d_msum);
-    else
-        hipLaunchKernelGGL(col_sum_kernel, dim3((unsigned)((cols + 255) / 256), MF_SLABS), dim3(256), 0, ctx->stream, d_r, F, cols,
-                           d_msum);
-    hipLaunchKernelGGL(col_mean_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, ctx->stream, d_msum, MF_SLABS,
-                       m_stride > 1 ? sample_count(F, MF_SLABS, m_stride) : F, cols, scale, d_mean);
+    lag_centre_means(ctx, c, 512, d_mean, d_msum);
     hipLaunchKernelGGL(frame_sq_kernel, dim3((unsigned)F, 3), dim3(256), 0, ctx->stream, d_r, d_mean, E, scale,
                        d_goff, (int)G, F, d_Q);
     MD_HIP(hipGetLastError());
@@ -2795,25 +2719,21 @@ int mdhip_lag_msd_fft(CallScope &cs, int64_t n_frames, int64_t n_ent, const doub
                         : mdhip_fft_r2c(ctx, d_pad, d_tmp, d_spec, L, (int)nb);
         if (rc) return rc;
         // the (axis, group) segments this batch touches
-        for (long long s = 0; s < S; ++s) {
-            const long long a = s / G, g = s % G;
-            const long long lo = std::max(c_first, a * E + (long long)group_off[g]);
-            const long long hi = std::min(c_first + nb, a * E + (long long)group_off[g + 1]);
-            if (lo >= hi) continue;
+        lp::lag_segments(E, G, group_off, c_first, nb, [&](long long s, long long lo, long long hi) {
+            if (lo >= hi || rc) return;
             const int splits = (int)std::min<long long>(fuse2 ? MF_SPLITS2 : MF_SPLITS, hi - lo);
-            if (fuse2) {
-                const int rcp = mdhip_fft_power_pass(ctx, d_spec, L, lo - c_first, hi - c_first, splits, d_part);
-                if (rcp) return rcp;
-            } else if (fuse) {
-                const int rcp = mdhip_fft_power_rows(ctx, d_Zp, L, lo - c_first, hi - c_first, splits, d_part);
-                if (rcp) return rcp;
-            } else {
+            if (fuse2)
+                rc = mdhip_fft_power_pass(ctx, d_spec, L, lo - c_first, hi - c_first, splits, d_part);
+            else if (fuse)
+                rc = mdhip_fft_power_rows(ctx, d_Zp, L, lo - c_first, hi - c_first, splits, d_part);
+            else
                 hipLaunchKernelGGL(power_rows_kernel, dim3((unsigned)((K + 255) / 256), (unsigned)splits), dim3(256), 0,
                                    ctx->stream, d_spec, K, lo - c_first, hi - c_first, d_part);
-            }
+            if (rc) return;
             hipLaunchKernelGGL(power_fold_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, ctx->stream,
                                d_part, splits, K, d_P + (size_t)s * K);
-        }
+        });
+        if (rc) return rc;
         MD_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(real_to_complex_kernel, dim3((unsigned)((S * K + 255) / 256)), dim3(256), 0, ctx->stream, d_P,
@@ -2821,34 +2741,99 @@ int mdhip_lag_msd_fft(CallScope &cs, int64_t n_frames, int64_t n_ent, const doub
     int rc = mdhip_fft_c2r(ctx, d_Z, d_tmp, d_corr, L, (int)S);
     if (rc) return rc;
     timer.stop();
-    ctx->last_kernel = "lag_msd_fft";
+    ctx->last_kernel = pl.name;
+    return lag_finish(cs, c, timer, d_Q, d_corr, d_ng, L, 1.0 / (double)L, L, nullptr, pl);
+}
 
-    // the finish, on the device: means into `d_fin`, from there to the caller's buffer on the stream; only the segments'
-    // bounds come back for the completion step (as lag_msd_fft_fused)
-    const size_t fin_b = (size_t)n_lags * G * 4 * 8;
-    MD_WS(d_fin_ws, unsigned char, WS_OUT3, fin_b + lag_bound_words(S) * 8 + (size_t)S * (F + 1) * sizeof(DD) + 64);
-    double *d_fin = reinterpret_cast<double *>(d_fin_ws), *d_bound = d_fin + (size_t)n_lags * G * 4;
-    DD *d_pre = reinterpret_cast<DD *>(d_bound + lag_bound_words(S));
-    const double eps_l = 4.0 * 2.220446049250313e-16 * std::log2((double)L);
-    hipLaunchKernelGGL(lag_finish_dd_kernel, dim3((unsigned)S), dim3(256), 0, ctx->stream, d_Q, d_corr, L, 1.0 / (double)L, F,
-                       n_lags, (int)G, d_ng, eps_l, d_pre, d_fin, d_bound);
-    hipLaunchKernelGGL(lag_total_kernel, dim3((unsigned)((n_lags * G + 255) / 256)), dim3(256), 0, ctx->stream, d_fin,
-                       n_lags * G, d_bound, (int)S, (const unsigned *)nullptr);
-    ctx->lag_status_dev = d_bound + S;  // (mdhip_lag_msd_status_dev: valid until the next call that uses WS_OUT3)
-    MD_HIP(hipGetLastError());
-    {
-        const int rcr = mdhip_result(cs, out, d_fin, fin_b, out_on_device);
-        if (rcr) return rcr;
+int lag_run(CallScope &cs, const LagCall &c, const lp::LagPlan &pl)
+{
+    switch (pl.path) {
+    case lp::LAG_W1:
+    case lp::LAG_RESIDUE:
+        return lag_msd_fft_residue(cs, c, pl);
+    case lp::LAG_POW2:
+    case lp::LAG_W12:
+        return lag_msd_fft_fused(cs, c, pl);
+    default:
+        return lag_msd_fft_batched(cs, c, pl);
     }
-    MD_PIN(h_bound, double, lag_bound_words(S) * 8);
-    {
-        const int rcc = mdhip_copy_small(ctx, h_bound, d_bound, lag_bound_words(S) * 8, hipMemcpyDeviceToHost);
-        if (rcc) return rcc;
-    }
-    cs.defer([timer, res, h_bound, S, n_lags]() {
-        timer.collect();
-        lag_collect_bounds(res.get(), h_bound, S, n_lags);
+}
+
+}  // namespace
+
+// d_r: device [F][3][E]. out: host [max_lag+1][G][4] means as mdhip_lag_msd. *rel_bound: the largest
+// estimated relative rounding error over all (lag >= 1, group, axis) entries with a non-zero value.
+// Every path — one wave per series, the fused kernels (padded length <= 16384), the residue classes and the batched
+// transforms — finishes on the device and delivers the means itself (res->delivered).
+int mdhip_lag_msd_fft(CallScope &cs, int64_t n_frames, int64_t n_ent, const double *d_r, double scale,
+                      int max_lag, int n_groups, const int64_t *group_off, const std::shared_ptr<LagFftResult> &res,
+                      double *out, int out_on_device)
+{
+    mdhip_ctx *ctx = cs.ctx;
+    res->group_off.assign(group_off, group_off + n_groups + 1);
+    res->out.clear();
+    res->bound = 0.0;
+    const LagCall c{n_frames, n_ent, n_groups, max_lag, d_r, scale, res, out, out_on_device};
+    const bool aligned = (reinterpret_cast<unsigned long long>(d_r) & 15ull) == 0ull;
+    const lp::LagPlan pl = lp::lag_choose(lag_device(ctx), lag_options(ctx),
+                                          lag_problem(ctx, n_frames, n_ent, max_lag, n_groups, res->group_off.data(), aligned));
+    return lag_run(cs, c, pl);
+}
+
+extern "C" int mdhip_lag_plan(const mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, int max_lag, int n_groups,
+                              const int64_t *group_off, int r_aligned16, int cu_count, int64_t lds_bytes, int n_opt,
+                              const char *const *opt_key, const int *opt_value, char *text, int text_cap, int32_t *info)
+{
+    if (!text || text_cap < 1 || !info || n_frames < 0 || n_ent < 0 || max_lag < 0 || n_groups < 1 || !group_off) return MDHIP_EINVAL;
+    if (n_frames && max_lag >= n_frames) return MDHIP_EINVAL;
+    if (n_opt < 0 || (n_opt && (!opt_key || !opt_value))) return MDHIP_EINVAL;
+    mdhip_ctx c = ctx ? *ctx : mdhip_ctx();  // (a copy: options and limits only — nothing below touches a device)
+    if (cu_count > 0) c.cu_count = cu_count;
+    if (lds_bytes > 0) c.lds_max = (size_t)lds_bytes;
+    text[0] = 0;
+    for (int k = 0; k < MDHIP_LAG_PLAN_INFO; ++k) info[k] = 0;
+    info[1] = -1;
+    for (int k = 0; k < n_opt; ++k)
+        if (const int rc = mdhip_set_option(&c, opt_key[k], opt_value[k])) {
+            info[0] = rc;
+            snprintf(text, (size_t)text_cap, "%s", c.err.c_str());
+            return MDHIP_OK;
+        }
+    if (group_off[0] < 0 || group_off[n_groups] > n_ent) return MDHIP_EINVAL;
+    for (int g = 0; g < n_groups; ++g)
+        if (group_off[g] > group_off[g + 1]) return MDHIP_EINVAL;
+    if (n_frames == 0 || group_off[n_groups] == group_off[0] || c.opt_lag_variant < 2 || c.opt_lag_variant > 4)
+        return MDHIP_OK;  // nothing runs, or the exact kernels answer (msd.hip): no spectral path
+    const lp::LagDevice dev = lag_device(&c);
+    const lp::LagPlan pl = lp::lag_choose(dev, lag_options(&c), lag_problem(&c, n_frames, n_ent, max_lag, n_groups, group_off, r_aligned16 != 0));
+    if (pl.too_long) {
+        info[0] = MDHIP_EINVAL;
+        snprintf(text, (size_t)text_cap, "series too long for the FFT path (%lld)", pl.L);
         return MDHIP_OK;
-    });
+    }
+    long long n_items = 0;
+    if (pl.path == lp::LAG_POW2 || pl.path == lp::LAG_W12) {
+        std::vector<lp::LagItem> items;
+        std::vector<lp::LagStage> stages;
+        std::vector<int> seg_off;
+        lp::lag_fused_items(pl, dev.cu_count, n_ent, n_groups, group_off, items, stages, seg_off);
+        n_items = (long long)items.size();
+    } else if (pl.path != lp::LAG_BATCHED) {
+        n_items = (long long)lp::lag_residue_items(pl, dev, n_ent, n_groups, group_off).items.size();
+    }
+    const bool fused = pl.path == lp::LAG_POW2 || pl.path == lp::LAG_W12;
+    info[1] = pl.path;
+    info[2] = pl.path == lp::LAG_POW2 ? pl.gen : pl.path == lp::LAG_W1 ? pl.short_d2 : pl.path == lp::LAG_RESIDUE ? pl.D : pl.path == lp::LAG_BATCHED ? pl.fuse : 0;
+    info[3] = fused ? pl.m : 0;
+    info[4] = pl.src;
+    info[5] = fused ? pl.Fc : 0;
+    info[6] = pl.units;
+    info[7] = pl.path == lp::LAG_W12 ? pl.QE : pl.gen == 3 ? pl.JJ : pl.gen == 2 ? pl.QR2 : pl.gen == 1 ? pl.QR : pl.residue_kernel;
+    info[8] = pl.path == lp::LAG_W12 ? (int)pl.SH : pl.gen == 3 ? pl.QE : fused ? 0 : (int)pl.packed;
+    info[9] = (int32_t)n_items;
+    info[10] = (int32_t)pl.n_batches;
+    info[11] = 1;  // (one timed run of launches: what mdhip_last_kernel_ms counts for every spectral path)
+    info[12] = (int32_t)pl.L;
+    snprintf(text, (size_t)text_cap, "%s", pl.name);
     return MDHIP_OK;
 }

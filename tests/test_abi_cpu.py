@@ -19,7 +19,7 @@ def test_header_symbols_are_exported():
     missing = [s for s in sorted(declared) if not hasattr(lib, s)]
     assert not missing, missing
     assert declared == set(_lib.PROTOTYPES), declared ^ set(_lib.PROTOTYPES)
-    assert lib.mdhip_version() == 600
+    assert lib.mdhip_version() == 610
 
 
 def _ref_bin(rsq, ddr):
@@ -344,6 +344,184 @@ def test_pair_plan_picks_what_the_device_ran():
     assert too_many_bins["status"] == -5 and "50000 bins do not fit LDS" in too_many_bins["kernel"]
     # ... and the limits are read: a device with 64 KB of LDS cannot hold C1full's 81 rows in one block
     assert P.plan(P.CASES["C1full"], lds_bytes=65536)["big"] == 0
+
+
+# What the parent commit (e1b4349, "Sharded MSD: one shard plan and a step object replace the closures") reports in
+# last_kernel_name() and as the launch count of last_kernel_ms() for every case of tests/lag_plan_cases.py. NOT a device
+# record: no MI355X could be had while the plan was split off, so the table was derived by reading that commit's
+# mdhip_lag_msd_fft (every spectral path starts ONE KernelTimer: one launch run) and transcribing its path choice by hand,
+# independently of csrc/lag_plan.h. tests/test_gpu_lag_plan.py holds the plan against the real call on a device; a record
+# of P.run() at e1b4349 should replace this table when a device is at hand.
+PARENT_E1B4349_REPORTS = {
+    "w1_2":                 ('msd_power_w1_kernel', 1),
+    "w1_300":               ('msd_power_w1_kernel', 1),
+    "w1_1024":              ('msd_power_w1_kernel', 1),
+    "w1_1025":              ('msd_power_w1_kernel', 1),
+    "w1_1535":              ('msd_power_w1_kernel', 1),
+    "w1_ends_1536":         ('msd_power_w12_kernel', 1),
+    "w1_off":               ('msd_power_lds_kernel', 1),
+    "w1_17_groups":         ('msd_power_lds_kernel', 1),
+    "w12_short_1600":       ('msd_power_w12_kernel', 1),
+    "w12_short_3071":       ('msd_power_w12_kernel', 1),
+    "w12_qe4_3072":         ('msd_power_w12_kernel', 1),
+    "w12_qe5_4097":         ('msd_power_w12_kernel', 1),
+    "w12_qe5_5000":         ('msd_power_w12_kernel', 1),
+    "w12_qe5_5120":         ('msd_power_w12_kernel', 1),
+    "w12_qe6_5121":         ('msd_power_w12_kernel', 1),
+    "w12_qe6_6144":         ('msd_power_w12_kernel', 1),
+    "w12_short_src0":       ('msd_power_w12_kernel', 1),
+    "w12_qe4_src0":         ('msd_power_w12_kernel', 1),
+    "w12_qe6_src0":         ('msd_power_w12_kernel', 1),
+    "w12_min_f_0":          ('msd_power_lds_kernel', 1),
+    "pow2_6145":            ('msd_power_lds_kernel', 1),
+    "pow2_8192":            ('msd_power_lds_kernel', 1),
+    "k0_2100":              ('msd_power_lds_kernel', 1),
+    "k1_2100":              ('msd_power_lds_kernel', 1),
+    "k2_2100":              ('msd_power_lds_kernel', 1),
+    "k0_qr1":               ('msd_power_lds_kernel', 1),
+    "k0_qr2":               ('msd_power_lds_kernel', 1),
+    "k0_qr4":               ('msd_power_lds_kernel', 1),
+    "k0_qr10":              ('msd_power_lds_kernel', 1),
+    "k0_qr12":              ('msd_power_lds_kernel', 1),
+    "k0_qr16":              ('msd_power_lds_kernel', 1),
+    "k0_qr24":              ('msd_power_lds_kernel', 1),
+    "k0_qr32":              ('msd_power_lds_kernel', 1),
+    "k1_qr2_1":             ('msd_power_lds_kernel', 1),
+    "k1_qr2_2":             ('msd_power_lds_kernel', 1),
+    "k1_qr2_5":             ('msd_power_lds_kernel', 1),
+    "k1_qr2_8":             ('msd_power_lds_kernel', 1),
+    "k1_qr2_16":            ('msd_power_lds_kernel', 1),
+    "k2_jj1_qe4":           ('msd_power_lds_kernel', 1),
+    "k2_jj1_qe8":           ('msd_power_lds_kernel', 1),
+    "k2_units5_5120":       ('msd_power_lds_kernel', 1),
+    "k2_units8_5121":       ('msd_power_lds_kernel', 1),
+    "k2_jj2_qe8":           ('msd_power_lds_kernel', 1),
+    "k2_src1":              ('msd_power_lds_kernel', 1),
+    "k2_src1_m13":          ('msd_power_lds_kernel', 1),
+    "k2_src0":              ('msd_power_lds_kernel', 1),
+    "direct_0":             ('msd_power_w12_kernel', 1),
+    "direct_1":             ('msd_power_w12_kernel', 1),
+    "direct_2":             ('msd_power_w12_kernel', 1),
+    "direct_3":             ('msd_power_w12_kernel', 1),
+    "cols_240":             ('msd_power_w12_kernel', 1),
+    "empty_group":          ('msd_power_w12_kernel', 1),
+    "segments_18":          ('msd_power_w12_kernel', 1),
+    "d4_8193":              ('msd_power_w12p_kernel', 1),
+    "d4_12288":             ('msd_power_w12p_kernel', 1),
+    "d8_12289":             ('msd_power_w12p_kernel + msd_power_w12o_kernel', 1),
+    "d8_24576":             ('msd_power_w12p_kernel + msd_power_w12o_kernel', 1),
+    "residue_0":            ('lag_msd_fft', 1),
+    "residue_2":            ('msd_power_w12r_kernel', 1),
+    "residue_3_batches":    ('msd_power_w12p_kernel', 1),
+    "overlap_2":            ('msd_power_w12p_kernel', 1),
+    "batched_24577":        ('lag_msd_fft', 1),
+    "batched_fuse_0":       ('lag_msd_fft', 1),
+    "batched_fuse_1":       ('lag_msd_fft', 1),
+    "batched_3_batches":    ('lag_msd_fft', 1),
+    "variant_4":            ('lag_msd_fft', 1),
+}
+
+
+def test_lag_plan_picks_what_the_device_ran():
+    """mdhip_lag_plan with the MI355X's two limits (256 CUs, 160 KB of LDS) names, for every branch of lag_choose and
+    every template instance the launch code names, the kernel and the launch count the parent commit reports (see the
+    table's own comment for where it comes from)."""
+    import lag_plan_cases as P
+
+    assert set(PARENT_E1B4349_REPORTS) == set(P.CASES)
+    got = {name: P.plan(case) for name, case in P.CASES.items()}
+    for name, (kernel, launches) in PARENT_E1B4349_REPORTS.items():
+        g = got[name]
+        assert g["status"] == 0 and (g["kernel"], g["launches"]) == (kernel, launches), (name, g, kernel, launches)
+    # what the name alone does not show: path, generation | D | fuse level, m, source, rows per member, staging units,
+    # the template instance
+    f = lambda name: tuple(got[name][k] for k in ("path", "gen", "m", "source", "Fc", "units", "inst_a", "inst_b"))  # noqa: E731
+    for name, d2 in (("w1_2", 1), ("w1_300", 1), ("w1_1024", 2), ("w1_1025", 3), ("w1_1535", 3)):
+        assert f(name)[:2] == (P.W1, d2) and got[name]["L"] == 1024 * d2 and f(name)[6] == d2, name
+    assert f("w1_ends_1536") == (P.W12, 0, 11, 2, 96, 4, 4, 1)        # SHORT, staged
+    assert f("w1_off")[:4] == (P.POW2, 2, 9, 0) and f("w1_17_groups")[:4] == (P.POW2, 2, 9, 0)
+    assert f("w12_short_1600")[6:] == (4, 1) and f("w12_short_3071")[6:] == (4, 1) and f("w12_qe4_3072")[6:] == (4, 0)
+    assert f("w12_qe5_4097")[6:] == (5, 0) and f("w12_qe5_5000")[6:] == (5, 0) and f("w12_qe5_5120")[4:] == (320, 4, 5, 0)
+    assert f("w12_qe6_5121")[4:] == (336, 4, 6, 0) and f("w12_qe6_6144")[4:] == (384, 4, 6, 0)
+    for name in ("w12_short_src0", "w12_qe4_src0", "w12_qe6_src0", "direct_0", "direct_1", "cols_240", "segments_18"):
+        assert f(name)[0] == P.W12 and f(name)[3] == 0 and f(name)[5] == 0, name
+    assert f("direct_2")[3] == 2 and f("direct_3")[3] == 3 and f("empty_group")[3] == 2
+    assert got["empty_group"]["n_items"] == 256 and got["segments_18"]["n_items"] < 256 and got["cols_240"]["n_items"] == 240
+    assert f("w12_min_f_0") == (P.POW2, 3, 12, 2, 144, 5, 1, 3)
+    assert f("pow2_6145") == (P.POW2, 3, 13, 2, 400, 8, 2, 4) and f("pow2_8192") == (P.POW2, 3, 13, 2, 512, 8, 2, 4)
+    assert f("k0_2100")[:3] == (P.POW2, 1, 12) and f("k1_2100")[:3] == (P.POW2, 2, 12) and f("k2_2100")[:3] == (P.POW2, 3, 12)
+    for name, qr in (("k0_qr1", 1), ("k0_qr2", 2), ("k0_qr4", 4), ("k0_2100", 8), ("k0_qr10", 10), ("k0_qr12", 12),
+                     ("k0_qr16", 16), ("k0_qr24", 24), ("k0_qr32", 32)):
+        assert f(name)[1] == 1 and f(name)[3] == 0 and f(name)[6] == qr, name
+    for name, qr2 in (("k1_qr2_1", 1), ("k1_qr2_2", 2), ("k1_2100", 3), ("k1_qr2_5", 5), ("k1_qr2_8", 8), ("k1_qr2_16", 16)):
+        assert f(name)[1] == 2 and f(name)[3] == 0 and f(name)[6] == qr2, name
+    assert f("k2_2100")[3:] == (2, 144, 5, 1, 3) and f("k2_jj1_qe4")[3:] == (2, 256, 5, 1, 4)
+    assert f("k2_jj1_qe8")[3:] == (2, 320, 5, 1, 8)
+    assert f("k2_units5_5120")[3:] == (2, 320, 5, 2, 3) and f("k2_units8_5121")[3:] == (2, 336, 8, 2, 3)
+    assert f("k2_jj2_qe8")[3:] == (0, 576, 0, 2, 8)
+    assert f("k2_src1")[3:] == (1, 256, 0, 1, 4) and f("k2_src1_m13")[3:] == (1, 512, 0, 2, 4) and f("k2_src0")[3] == 0
+    assert f("d4_8193")[:2] == (P.RESIDUE, 4) and f("d4_12288")[:2] == (P.RESIDUE, 4) and f("d4_8193")[6:] == (5, 1)
+    assert f("d8_12289")[:2] == (P.RESIDUE, 8) and f("d8_24576")[:2] == (P.RESIDUE, 8) and f("d8_24576")[6:] == (6, 1)
+    assert f("residue_2")[6:] == (4, 0) and f("residue_0")[:2] == (P.BATCHED, 2)
+    assert got["residue_3_batches"]["n_batches"] == 3 and got["overlap_2"]["n_batches"] == 6 and got["d4_8193"]["n_batches"] == 1
+    assert f("batched_24577")[:2] == (P.BATCHED, 2) and got["batched_24577"]["L"] == 65536
+    assert f("batched_fuse_0")[1] == 0 and f("batched_fuse_1")[1] == 1 and got["batched_3_batches"]["n_batches"] == 3
+    assert f("variant_4")[0] == P.BATCHED and got["variant_4"]["L"] == 1024
+    # an unaligned trajectory cannot be staged (16-byte loads); 304 CUs are 19 clusters of 16 (288 columns are too few for
+    # them, 384 are enough) but no multiple of 128
+    assert P.plan(P.CASES["w12_qe5_4097"], aligned=False)["source"] == 0
+    wide = lambda name: dict(P.CASES[name], E=128, go=np.array([0, 128]))  # noqa: E731
+    assert P.plan(P.CASES["w12_qe5_4097"], cu_count=304)["source"] == 0 and P.plan(wide("w12_qe5_4097"), cu_count=304)["source"] == 2
+    assert P.plan(wide("k2_src1"))["source"] == 1 and P.plan(wide("k2_src1"), cu_count=304)["source"] == 0
+    # ... and the limits are read: a device with 64 KB of LDS loses every path whose kernels need more
+    small = {name: P.plan(case, lds_bytes=65536) for name, case in P.CASES.items()}
+    for name in ("w1_300", "w1_1535"):
+        assert small[name]["path"] == P.POW2, name               # the one-wave kernel's 3072-point instance: 155 KB
+    assert (small["w12_short_1600"]["path"], small["w12_short_1600"]["m"]) == (P.POW2, 11)  # no 12 288 points; N = 2048: 39 KB
+    for name in ("w12_qe4_3072", "w12_qe5_4097", "w12_qe6_6144", "pow2_8192", "k0_qr16", "d4_8193", "d8_24576"):
+        assert small[name]["path"] == P.BATCHED, (name, small[name])    # (N = 4096 needs 74 KB, the residue kernels 156 KB)
+    assert small["w1_off"]["path"] == P.POW2 and small["w1_off"]["gen"] == 2   # N = 512: 12.6 KB
+    # nothing spectral to plan: no frames, no entities in any group, or the exact kernels asked for
+    assert P.plan(dict(P.CASES["w1_300"], F=0, max_lag=0))["path"] == -1
+    assert P.plan(dict(P.CASES["w1_300"], go=np.array([0, 0])))["path"] == -1
+    assert P.plan(dict(P.CASES["w1_300"], opts={"lag_variant": 1}))["path"] == -1
+    unknown = P.plan(dict(P.CASES["w1_300"], opts={"no_such_option": 1}))
+    assert unknown["status"] < 0 and unknown["kernel"]
+
+
+def test_bench_lag_fft_plan_agrees_with_the_library():
+    """bench.lag_fft_plan (the roofline's idea of the fused path: padded length and kernel) against mdhip_lag_plan for
+    every fused case of the table that runs with the default kernel choice. bench.py predates the rule that sends
+    2048 < F + max_lag <= 8192 with F >= 1536 to the 12 288-point kernel (lag_w12_min_f): it still prices those shapes
+    as power-of-two transforms. That set is pinned here, shape by shape, so that neither side can drift unnoticed."""
+    import sys
+
+    import lag_plan_cases as P
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    name_of = {(P.W12, 0): "msd_power_w12_kernel", (P.POW2, 3): "msd_power_lds3_kernel", (P.POW2, 2): "msd_power_lds2_kernel",
+               (P.POW2, 1): "msd_power_lds_kernel"}
+    differ = {}
+    n = 0
+    for name, case in P.CASES.items():
+        g = P.plan(case)
+        if g["path"] not in P.FUSED or set(case["opts"]) - {"lag_direct"}:
+            continue
+        n += 1
+        L, _, kernel = bench.lag_fft_plan(case["F"], case["max_lag"])
+        if (L, kernel) != (g["L"], name_of[(g["path"], g["gen"])]):
+            differ[name] = (L, kernel)
+    assert n >= 20
+    assert differ == {
+        "w1_ends_1536": (4096, "msd_power_lds2_kernel"),
+        "w12_short_1600": (4096, "msd_power_lds2_kernel"),
+        "w12_short_3071": (8192, "msd_power_lds3_kernel"),
+        "w12_qe4_3072": (8192, "msd_power_lds3_kernel"),
+        "w12_short_src0": (4096, "msd_power_lds2_kernel"),
+        "w12_qe4_src0": (8192, "msd_power_lds3_kernel"),
+    }, differ
 
 
 def test_row_displacement_is_the_same_in_every_process():
