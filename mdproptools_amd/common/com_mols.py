@@ -22,6 +22,24 @@ def molecule_layout(num_mols, num_atoms_per_mol):
     return seg_off, mol_type, mol_id
 
 
+def calc_atom_type(ids, num_mols, num_atoms):
+    """
+    Atom id -> 1-based index of the atom inside its molecule type, offset by the atom counts of
+    the preceding molecule types (rdf_cn.py:197-215), vectorised over all atoms.
+    """
+    ids = np.asarray(ids, dtype=np.float64)
+    num_atoms = np.asarray(num_atoms)
+    upper = np.cumsum(np.multiply(num_mols, num_atoms))
+    which = np.searchsorted(upper, ids, side="left")  # first molecule type whose range holds the id
+    out = ids.copy()
+    inside = which < len(upper)
+    w = which[inside]
+    v = np.mod(ids[inside] - upper[w], num_atoms[w])  # Python-style modulo of a non-positive number
+    v[v == 0] = num_atoms[w][v == 0]
+    out[inside] = v + np.concatenate(([0], np.cumsum(num_atoms)[:-1]))[w]
+    return out
+
+
 def check_atom_count(n_layout, n_frame):
     """The reference's error (pandas', on assigning the molecule columns) for a frame of another size than the layout."""
     if n_layout != n_frame:

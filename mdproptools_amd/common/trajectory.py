@@ -1,7 +1,8 @@
 """
 Trajectory ingest shared by the drop-in modules: which route can serve a request, which columns to read, and the
-frames themselves — as host batches (`frame_batches`, the native reader) or as page-locked batches from the frame
-stream (`stream_reduced`, mdproptools_amd/stream.py). A new drop-in gets its frames from here.
+frames themselves — as host batches (`frame_batches`, the native reader), as page-locked batches from the frame
+stream (`stream_reduced`, mdproptools_amd/stream.py), or as whole id-sorted frames batched for the pair loops
+(`load_frames`, `batches`, `all_frames`). A new drop-in gets its frames from here.
 """
 
 import numpy as np
@@ -124,3 +125,133 @@ def stream_reduced(pattern, files, columns, n_atoms_expected, batch_bytes=None):
         if n_atoms_expected is not None:
             check_atom_count(n_atoms_expected, batch.xyz.shape[2])
         yield batch
+
+
+# ------------------------------------------------------------------------------------------------
+# whole frames for the pair loops: id-sorted SoA planes, batched for one library call each
+# ------------------------------------------------------------------------------------------------
+
+
+class Frame:
+    """One parsed frame reduced to what the pair loops need (rdf_cn.py:183-194): id-sorted ids, types,
+    xyz planes [3,N] and the box edge lengths."""
+
+    __slots__ = ("timestep", "ids", "types", "xyz", "lengths")
+
+    def __init__(self, timestep, ids, types, xyz, lengths):
+        self.timestep, self.ids, self.types, self.xyz, self.lengths = timestep, ids, types, xyz, lengths
+
+    @classmethod
+    def from_dump(cls, dump):
+        tbl = dump.data[["id", "type", "x", "y", "z"]].sort_values("id").to_numpy(dtype=np.float64)
+        return cls(dump.timestep, tbl[:, 0], tbl[:, 1], np.ascontiguousarray(tbl[:, 2:5].T),
+                   dump.box.to_lattice().lengths)
+
+
+def load_frames(filename, shard=False, stream=False, on_frame=None):
+    """Every frame of `filename` (file or '*' pattern, numeric order). The native reader of libmdhip.so
+    produces the same doubles as the pandas-based one (tests/test_dump_reader_cpu.py), ~10x faster.
+    `on_frame(timestep)` is called as each frame is parsed (the caller's progress line).
+
+    stream=True (what the public functions ask for): a `stream.FrameStream` instead of a list — `batches` then
+    yields batches as the producer thread finishes parsing them, the frames of the trajectory are never all
+    resident on the host (the reference builds the whole list first, rdf_cn.py:176).
+
+    shard=True under torch.distributed (one process per GPU): a rank parses and returns only ITS share of the
+    trajectory — a contiguous block of the files when there are at least as many files as ranks, else a
+    contiguous block of the frames — so that parsing, the usual bottleneck, scales with the ranks too."""
+    from .. import dist as D
+
+    def parsed(frame):
+        if on_frame is not None:
+            on_frame(frame.timestep)
+        return frame
+
+    sharded = shard and D.is_distributed()
+    files = None
+    if sharded and (isinstance(filename, str) or hasattr(filename, "__fspath__")):
+        matches = mio._sorted_matches(str(filename))
+        if len(matches) >= D.rank_world()[1]:
+            files = D.shard_items(matches)
+    is_path = isinstance(filename, str) or hasattr(filename, "__fspath__")
+    if stream and mio.USE_NATIVE_READER and is_path and (not sharded or files is not None):
+        from ..stream import FrameStream
+
+        return FrameStream(str(filename), files=files, on_frame=on_frame)
+    if mio.USE_NATIVE_READER and is_path:
+        frames = [parsed(Frame(ts, planes[0], planes[1], np.ascontiguousarray(planes[2:5]), lengths))
+                  for ts, _b, lengths, _names, planes in
+                  mio.iter_native_frames(str(filename), ["id", "type", "x", "y", "z"], sort_by="id", files=files)]
+    elif files is not None:
+        frames = [parsed(Frame.from_dump(d)) for fn in files for d in mio.parse_lammps_dumps(fn)]
+    else:
+        frames = [parsed(Frame.from_dump(d)) for d in mio.parse_lammps_dumps(filename)]
+    if sharded and files is None:
+        frames = D.shard_items(frames)
+    return frames
+
+
+def all_frames(per_frame_rows):
+    """Per-frame result rows of every rank in frame order (identity without torch.distributed). Ranks hold
+    contiguous blocks of the trajectory, so the concatenation in rank order is the frame order, and summing
+    the gathered rows in that order gives bit for bit what one process gets."""
+    from .. import dist as D
+
+    if len(per_frame_rows) and np.ndim(per_frame_rows[0]) == 2:  # per-batch blocks [B, W]
+        rows = np.concatenate(per_frame_rows)
+    else:
+        rows = np.stack(per_frame_rows) if len(per_frame_rows) else None
+    if not D.is_distributed():
+        return [] if rows is None else rows
+    # Fewer frames than ranks: the ranks without a frame contribute no rows (round 6; they used to make every rank raise).
+    # The row width of an empty rank comes from the others, with the counts, in one small all-gather.
+    mine = (0, 0) if rows is None else (int(rows.shape[0]), int(rows.shape[1]))
+    both = D.allgather_var(np.array([mine], dtype=np.int64), counts=[1] * D.rank_world()[1])
+    counts, width = [int(c) for c in both[:, 0]], int(both[:, 1].max())
+    if sum(counts) == 0:
+        return []
+    if rows is None:
+        rows = np.zeros((0, width))
+    return D.allgather_var(rows, counts=counts)
+
+
+class Batch(list):
+    """The frames of one library call; `block` = their coordinates as ONE array [B,3,N] when they already sit in a
+    staging buffer (streamed batches), else None."""
+
+    block = None
+    uniform_types = False
+    types_ref = None
+    lengths_block = None
+
+
+def lengths_block(batch):
+    lb = getattr(batch, "lengths_block", None)
+    return lb if lb is not None else np.array([f.lengths for f in batch])
+
+
+def xyz_block(batch):
+    return batch.block if getattr(batch, "block", None) is not None else np.stack([f.xyz for f in batch])
+
+
+def batches(frames, max_bytes):
+    """Consecutive frames with the same atom count, capped at `max_bytes` of coordinates. A FrameStream
+    yields its own batches (the staging buffer goes back to the producer when the loop asks for the next one:
+    everything a caller keeps from a batch must be a copy)."""
+    if not isinstance(frames, list):
+        for sb in frames:
+            b = Batch(Frame(fr.timestep, fr.ids, fr.types, fr.xyz, fr.lengths) for fr in sb)  # views into the buffer
+            b.block = sb.xyz
+            b.uniform_types, b.types_ref = getattr(sb, "uniform_types", False), getattr(sb, "types_ref", None)
+            b.lengths_block = np.asarray(sb.lengths, dtype=np.float64)
+            yield b
+        return
+    start = 0
+    while start < len(frames):
+        n = frames[start].xyz.shape[1]
+        cap = max(1, max_bytes // max(1, 24 * n))
+        stop = start + 1
+        while stop < len(frames) and stop - start < cap and frames[stop].xyz.shape[1] == n:
+            stop += 1
+        yield frames[start:stop]
+        start = stop

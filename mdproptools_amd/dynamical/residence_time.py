@@ -8,7 +8,7 @@ What runs where
       (central atom, shell atom) pairs of every frame with the reference's exact single-wrap distance
       (residence_time.py:96-106) and the sum over pairs of the autocovariance numerators
       sum_t h_ij(t) h_ij(t+k) (residence_time.py:111-131) as exact integers.
-  Host: parsing, the pseudo-type relabelling (`_calc_atom_type`), normalisation (1/(n-k), 1/columns, /C(0)),
+  Host: parsing, the pseudo-type relabelling (`calc_atom_type`), normalisation (1/(n-k), 1/columns, /C(0)),
       the stretched-exponential fit (scipy.optimize.curve_fit, as upstream) and the CSV / PNG files.
 
 Deliberate difference: with default ids (no num_mols / num_atoms_per_mol) the reference stops with a
@@ -38,7 +38,8 @@ from .. import backend
 from .. import io as mio
 from ..common import sayer
 from ..dist import is_writer
-from ..structural.rdf_cn import _calc_atom_type, _load_frames
+from ..common.com_mols import calc_atom_type
+from ..common.trajectory import load_frames
 
 VERBOSE = False
 
@@ -76,11 +77,11 @@ class ResidenceTime:
         """Type label of every (id-sorted) atom of one frame: LAMMPS type, or the index of the atom inside
         its molecule type when num_mols / num_atoms_per_mol are given (residence_time.py:85-93)."""
         if self.num_mols and self.num_atoms_per_mol:
-            return _calc_atom_type(frame.ids, self.num_mols, self.num_atoms_per_mol)
+            return calc_atom_type(frame.ids, self.num_mols, self.num_atoms_per_mol)
         return frame.types
 
     def calc_auto_correlation(self):
-        frames = _load_frames(self.filename)
+        frames = load_frames(self.filename)
         n = len(frames)
         correlation = {"Time (ps)": [fr.timestep * self.dt for fr in frames]}
         if n == 0:

@@ -35,9 +35,8 @@ import pandas as pd
 
 from .. import backend
 from .. import io as mio
-from ..common.com_mols import check_atom_count, molecule_layout
+from ..common.com_mols import calc_atom_type, check_atom_count, molecule_layout
 from ..common.trajectory import frame_refs, read_frame
-from .rdf_cn import _calc_atom_type
 
 FORCE_CONSTANT = 0.043363 / 16.0  # cluster_analysis.py:29
 _COLS = ["id", "type", "x", "y", "z", "fx", "fy", "fz"]
@@ -143,7 +142,7 @@ class _Source:
         el = None
         if self.need_elements:
             el = self.el_map[planes[1].astype(np.int64) - 1] if self.elements else _element_column(fname, k)
-        types = _calc_atom_type(planes[0], self.num_mols, self.num_atoms) if self.alter_atom_types else planes[1]
+        types = calc_atom_type(planes[0], self.num_mols, self.num_atoms) if self.alter_atom_types else planes[1]
         lengths = np.asarray(bounds, dtype=np.float64)
         lengths = lengths[:, 1] - lengths[:, 0]
         return ts, lengths, planes, el, np.flatnonzero(types == self.atom_type).astype(np.int32)

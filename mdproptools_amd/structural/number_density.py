@@ -11,7 +11,7 @@ What runs where
 
 The reference's loop comes down to these rules, reproduced exactly:
   * the label of an atom is its type, or with num_mols and num_atoms_per_mol the per-molecule-type atom index of
-    rdf_cn._calc_atom_type; lo, hi = min, max of the axis coordinate over the atoms labelled surface_atom;
+    com_mols.calc_atom_type; lo, hi = min, max of the axis coordinate over the atoms labelled surface_atom;
   * dist_from_interface > 0: the atoms of each type with x - lo < dist_from_interface are binned on
     (x - lo) - (hi - lo); otherwise those with x - lo > dist_from_interface on x - lo;
   * bin k = trunc(b / bin_size), counted with Python indexing: -num_bins <= k < 0 lands in bin k + num_bins (atoms
@@ -29,9 +29,9 @@ import numpy as np
 import pandas as pd
 
 from .. import backend
-from ..common.com_mols import molecule_layout
+from ..common.com_mols import calc_atom_type, molecule_layout
 from ..common.trajectory import frame_batches, same_labels
-from .rdf_cn import _calc_atom_type, _save_rdf
+from .rdf_cn import _save_rdf
 
 VERBOSE = False
 MAX_BATCH_BYTES = 1 << 28  # coordinates of the frames handed to the GPU in one call
@@ -72,7 +72,7 @@ def _codes(labels, surface_atom, uniq):
 def _labels(planes, num_mols, num_atoms_per_mol):
     """Atom labels of a batch, [N] when every frame carries the same ones, else [B,N]."""
     if num_mols and num_atoms_per_mol:
-        lab = _calc_atom_type(planes[:, 0], num_mols, num_atoms_per_mol)
+        lab = calc_atom_type(planes[:, 0], num_mols, num_atoms_per_mol)
     else:
         lab = planes[:, 1]
     return same_labels(lab)

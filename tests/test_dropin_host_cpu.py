@@ -8,8 +8,29 @@ import pytest
 from conftest import load_golden
 
 
+def _normalize_rdf(bin_size, rho_pairs, atom_types, partial_relations, num_relations, num_bins, rdf_part,
+                   rdf_full=None, num_atoms=None, rho=None):
+    """Per-frame normalisation (rdf_cn.py:297-329); operation order kept for bit-identical g(r). The per-frame
+    restatement that the package's `_normalize_rdf_batch` is held to."""
+    from mdproptools_amd.structural.rdf_cn import _shell_volume
+
+    sv = _shell_volume(bin_size, num_bins)
+    if rdf_full is not None:
+        rdf_full = rdf_full / (num_atoms * rho * sv)
+    n_ref = np.array([atom_types[a] for a in partial_relations[0]]).reshape(num_relations, 1)
+    n_ref = np.tile(n_ref, num_bins)
+    rho_b = np.tile(rho_pairs.reshape(num_relations, 1), num_bins)
+    sv_m = np.tile(sv, (num_relations, 1))
+    rdf_part = rdf_part / (n_ref * rho_b * sv_m)
+    return rdf_full, rdf_part
+
+
+def _normalize_cn(atom_types, partial_relations, cn):
+    return cn / [atom_types[a] for a in partial_relations[0]]  # rdf_cn.py:332-338
+
+
 def test_calc_atom_type_vectorised(g_synth):
-    from mdproptools_amd.structural.rdf_cn import _calc_atom_type
+    from mdproptools_amd.common.com_mols import calc_atom_type as _calc_atom_type
 
     nm, na = g_synth["atom_type_num_mols"], g_synth["atom_type_num_atoms"]
     ids = np.arange(1, int(np.dot(nm, na)) + 1, dtype=np.float64)
@@ -28,8 +49,8 @@ def test_normalisation_matches_reference_frame(g_c1):
         fr = g["frames"][f]
         L = tuple((g["bounds"][f][:, 1] - g["bounds"][f][:, 0]).tolist())
         rho, rho_pairs, atom_types, _ = M._calc_props(L, fr[:, 1], fr[:, 1], 9, g["mass"], rel, False)
-        gf, gp = M._normalize_rdf(0.05, rho_pairs, atom_types, rel, 5, 400, g["rdf_def_part"][f].astype(float),
-                                  g["rdf_def_full"][f].astype(float), len(fr), rho)
+        gf, gp = _normalize_rdf(0.05, rho_pairs, atom_types, rel, 5, 400, g["rdf_def_part"][f].astype(float),
+                                g["rdf_def_full"][f].astype(float), len(fr), rho)
         gf_sum, gp_sum = gf_sum + gf, gp_sum + gp
     df = M._save_rdf((np.arange(400) + 0.5) * 0.05, np.asarray(rel).T, None, False, gp_sum / 2, gf_sum / 2)
     np.testing.assert_array_equal(df.to_numpy(), g["rdf_def_df"])
@@ -206,19 +227,23 @@ def test_batch_normalisation_sum_and_csv_are_the_per_frame_code_bit_for_bit(tmp_
     part = rng.integers(0, 50_000, (B, 4, nb)).astype(np.uint64)
     ty = (1 + np.arange(n) % 3).astype(np.float64)
     props = [R._calc_props((30.0 + 0.1 * k, 31.0, 32.0 - 0.05 * k), ty, ty, 3, [1.0, 2.0, 3.0], rel, False) for k in range(B)]
-    memo = [R._calc_props_memo((30.0 + 0.1 * (k // 2), 31.0, 32.0), ty, ty, 3, [1.0, 2.0, 3.0], rel, False) for k in range(B)]
+    cache = R._PropsCache()
+    memo = [cache.props((30.0 + 0.1 * (k // 2), 31.0, 32.0), ty, ty, 3, [1.0, 2.0, 3.0], rel, False) for k in range(B)]
     for k in range(B):  # the memo returns what a fresh call returns (boxes repeat in pairs here)
         fresh = R._calc_props((30.0 + 0.1 * (k // 2), 31.0, 32.0), ty, ty, 3, [1.0, 2.0, 3.0], rel, False)
         assert fresh[0] == memo[k][0] and np.array_equal(fresh[1], memo[k][1]) and fresh[2] == memo[k][2]
     rows = R._normalize_rdf_batch(0.05, props, rel, 4, nb, part, full, [n] * B)
     want = []
     for k in range(B):
-        gf, gp = R._normalize_rdf(0.05, props[k][1], props[k][2], rel, 4, nb, part[k].astype(np.float64),
-                                  full[k].astype(np.float64), n, props[k][0])
+        gf, gp = _normalize_rdf(0.05, props[k][1], props[k][2], rel, 4, nb, part[k].astype(np.float64),
+                                full[k].astype(np.float64), n, props[k][0])
         want.append(np.concatenate([gf, np.ravel(gp)]))
     np.testing.assert_array_equal(rows, np.stack(want))
     only_part = R._normalize_rdf_batch(0.05, props, rel, 4, nb, part)
     np.testing.assert_array_equal(only_part, np.stack(want)[:, nb:])
+    raw = rng.integers(0, 50_000, (B, 4)).astype(np.uint64)
+    np.testing.assert_array_equal(R._normalize_cn_batch(props, rel, raw),
+                                  np.stack([_normalize_cn(props[k][2], rel, raw[k].astype(np.float64)) for k in range(B)]))
     acc = np.zeros(rows.shape[1])
     for r in want:
         acc += r

@@ -471,3 +471,12 @@ def test_calc_intermolecular_rdf(c1_dir):
     # COM sums run in another order on the GPU (rtol 1e-13 on the sites): a COM pair sitting within that of a bin
     # edge could move one count; on these frames none does
     np.testing.assert_allclose(df.to_numpy(), ref["df"], rtol=1e-12, atol=0)
+
+
+def test_molecular_types_that_change_inside_a_batch(tmp_path):
+    """210 atoms, 4 frames, the types of frames 3 and 4 differ from those of 1 and 2 (tests/test_rdf_cn_dropin_cpu.py):
+    calc_molecular_rdf / calc_molecular_cn over all four == the frame-order sum of the four single-file calls over 4,
+    bit for bit, through libmdhip.so."""
+    from test_rdf_cn_dropin_cpu import check_type_runs
+
+    check_type_runs(str(tmp_path))

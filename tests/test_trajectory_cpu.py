@@ -254,3 +254,25 @@ def test_same_labels():
     two = T.same_labels([a, a, b])
     assert two.shape == (3, N) and np.array_equal(two, np.stack([a, a, b]))
     assert T.same_labels([a]).shape == (N,)
+
+
+def test_load_frames_reports_frames_to_on_frame_only(tmp_path, capsys):
+    """The whole-frame loader prints nothing itself, whatever a module's VERBOSE says: the progress line is the caller's
+    `on_frame`, called once per frame in frame order (list route; the stream calls it from its reader)."""
+    from mdproptools_amd import io as mio
+    from mdproptools_amd.structural import rdf_cn
+
+    rng = np.random.default_rng(2)
+    for step in (0, 300, 20):
+        tbl = np.column_stack([rng.permutation(6) + 1, np.ones(6), rng.uniform(0, 5, (6, 3))])
+        mio.write_dump(str(tmp_path / ("d.%d.dump" % step)), step, [[0, 5.0]] * 3, ["id", "type", "x", "y", "z"], tbl)
+    rdf_cn.VERBOSE = True
+    try:
+        frames = T.load_frames(str(tmp_path / "d.*.dump"))
+        assert capsys.readouterr().out == ""
+        seen = []
+        again = T.load_frames(str(tmp_path / "d.*.dump"), on_frame=seen.append)
+    finally:
+        rdf_cn.VERBOSE = False
+    assert seen == [0, 20, 300] == [f.timestep for f in frames] == [f.timestep for f in again]
+    assert [len(b) for b in T.batches(frames, 2 * 24 * 6)] == [2, 1] and frames[0].ids.tolist() == [1, 2, 3, 4, 5, 6]
