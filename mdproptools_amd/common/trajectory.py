@@ -1,7 +1,8 @@
 """
 Trajectory ingest shared by the drop-in modules: which route can serve a request, which columns to read, and the
 frames themselves — as host batches (`frame_batches`, the native reader), as page-locked batches from the frame
-stream (`stream_reduced`, mdproptools_amd/stream.py), or as whole id-sorted frames batched for the pair loops
+stream (`stream_reduced`, mdproptools_amd/stream.py), as two per-atom attributes and three planes from whichever of the
+two can serve (`attribute_batches`: the dynamical drop-ins), or as whole id-sorted frames batched for the pair loops
 (`load_frames`, `batches`, `all_frames`). A new drop-in gets its frames from here.
 """
 
@@ -125,6 +126,82 @@ def stream_reduced(pattern, files, columns, n_atoms_expected, batch_bytes=None):
         if n_atoms_expected is not None:
             check_atom_count(n_atoms_expected, batch.xyz.shape[2])
         yield batch
+
+
+def _keep_row(rows, row):
+    """Appends the per-atom row [N] of one frame to `rows`: the first frame's array itself where the frame repeats it
+    (attributes seldom change, and then nothing is held twice), else a copy."""
+    rows.append(rows[0] if rows and np.array_equal(rows[0], row) else row.copy())
+
+
+def attribute_batches(pattern, leading, planes, n_atoms=None, files=None, stream=True, batch_bytes=None, missing=None,
+                      decide_on=UNWRAPPED, dumps=None):
+    """The frames of `pattern` (or of `files`, a rank's share: native reader only) in parse_lammps_dumps order, atoms by
+    id, reduced to two `leading` per-atom columns and three `planes` — `UNWRAPPED`, or any three columns such as vx vy
+    vz. Returns (streamed, batches): `batches` yields host batches (timesteps [B], first [B,N], second [B,N], planes
+    [B,3,N]) whatever route serves them, and `streamed` says, before the first one, which route was chosen:
+
+    the frame stream, when the caller allows it (`stream`), io.USE_NATIVE_READER is set and `streamable_files` accepts
+    the files: batches of `batch_bytes` (stream.frames_per_batch) that live in staging buffers — what a caller keeps
+    from one must be a copy;
+
+    else the general route — the native reader, or pandas over `dumps` (the caller's own parsed frames; default:
+    parse_lammps_dumps(pattern)) — with every frame in ONE batch (nothing when there is no frame), so that a caller
+    makes one library call there. It makes xu yu zu from x + ix * L where `decide_on` says the dump has none
+    (`unwrapped_columns`, `unwrap`), and hands what the dump lacks to the caller first: `missing([columns], names)`, the
+    columns in the order id, leading, planes. The caller raises there in its own words, or returns and leaves it to
+    the reader. A per-atom row that every frame repeats is held once there: [B,N] is then a read-only view of it. A
+    stream that produced no frame of a whole pattern hands out this route's batch instead.
+
+    Every frame is checked against `n_atoms` (check_atom_count; None: not checked)."""
+    from .com_mols import check_atom_count
+
+    leading, planes = list(leading), list(planes)
+    unwrapped = planes == list(UNWRAPPED)
+    mine = streamable_files(pattern, ["id"] + leading + planes, files) if stream and mio.USE_NATIVE_READER else None
+
+    def wanted(names):  # (the reader's own error names the first column of this list that the dump lacks)
+        sel = unwrapped_columns(names, leading, lambda c, have: None, decide_on) if unwrapped else planes + leading
+        sel = list(dict.fromkeys(sel))  # (a column named twice is read once)
+        lacking = [c for c in dict.fromkeys(["id"] + leading + sel) if c not in names]
+        if lacking and missing is not None:
+            missing(lacking, names)
+        return sel
+
+    def parsed():
+        for dump in dumps if dumps is not None else mio.parse_lammps_dumps(pattern):
+            sel = wanted(list(dump.data.columns))
+            data = dump.data.sort_values(by=["id"])
+            yield dump.timestep, dump.box.bounds, {c: data[c].to_numpy(dtype=np.float64) for c in sel}
+
+    def batches():
+        if mine is not None:
+            served = False
+            for b in stream_reduced(pattern, mine, leading + planes, n_atoms, batch_bytes):
+                served = True
+                yield b.timesteps, b.ids, b.types, b.xyz
+            if served or files is not None:
+                return
+        frames = parsed()
+        if mio.USE_NATIVE_READER:
+            frames = ((ts, bounds, dict(zip(wanted(names), pl))) for ts, bounds, _l, names, pl in
+                      mio.iter_native_frames(pattern, wanted, sort_by="id", files=files))
+        steps, xyz, rows = [], [], {c: [] for c in leading}
+        for ts, bounds, cols in frames:
+            if unwrapped:
+                unwrap(cols, bounds)
+            if n_atoms is not None:
+                check_atom_count(n_atoms, len(cols[planes[0]]))
+            steps.append(int(ts))
+            xyz.append(np.stack([cols[c] for c in planes]))
+            for c in rows:
+                _keep_row(rows[c], cols[c])
+        if steps:
+            held = {c: np.broadcast_to(r[0], (len(r), len(r[0]))) if all(x is r[0] for x in r) else np.stack(r)
+                    for c, r in rows.items()}
+            yield np.array(steps, dtype=np.int64), held[leading[0]], held[leading[1]], np.stack(xyz)
+
+    return mine is not None, batches()
 
 
 # ------------------------------------------------------------------------------------------------

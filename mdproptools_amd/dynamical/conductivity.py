@@ -26,7 +26,7 @@ import pandas as pd
 from .. import backend
 from ..common import constants
 from ..common import trajectory as T
-from ..common.com_mols import check_atom_count, molecule_layout
+from ..common.com_mols import molecule_layout
 from ..io import parse_lammps_dumps
 
 # True: get_charge_flux parses into page-locked staging batches and runs the fused flux kernel on each while the next
@@ -98,76 +98,30 @@ class Conductivity:
 
     def get_charge_flux(self):
         """Charge flux J[3, n_types, n_frames] in SI units; also fills `self.time` (conductivity.py:167-195)."""
-        n_expected = len(glob.glob(f"{self.working_dir}/{self.filename}"))
-        seg_off, mol_type, _ = molecule_layout(self.num_mols, self.num_atoms_per_mol)
+        from .. import dist as D
         from .. import io as mio
 
-        vel, steps = [], []
-        m = q = None
-        from .. import dist as D
-
-        files = None
-        if mio.USE_NATIVE_READER and STREAM:
-            # text -> page-locked batches -> fused flux kernel, the next batch being parsed meanwhile (stream.py)
-            files = D.my_files(f"{self.working_dir}/{self.filename}")
-            got = self._flux_streamed(files, seg_off, mol_type)
-            if got is not None:
-                flux, steps = got
-                return self._finish_flux(flux, steps, files, n_expected)
-        if mio.USE_NATIVE_READER:
-            def wanted(names):
-                return ["vx", "vy", "vz", "q"] + (["type"] if self.mass else ["mass"])
-
-            # under torch.distributed every rank parses and reduces its own share of the files; the per-frame
-            # flux vectors (3 x n_types doubles) are all-gathered below
-            files = D.my_files(f"{self.working_dir}/{self.filename}")
-            frames = ((ts, planes[0:3], planes[3], planes[4]) for ts, _b, _l, _n, planes in
-                      mio.iter_native_frames(f"{self.working_dir}/{self.filename}", wanted, sort_by="id",
-                                             files=files))
-        else:
-            def from_pandas():
-                for dump in self.dumps:
-                    data = dump.data.sort_values(by=["id"])
-                    yield (dump.timestep,
-                           np.ascontiguousarray(data[["vx", "vy", "vz"]].to_numpy(dtype=np.float64).T),
-                           data["q"].to_numpy(dtype=np.float64),
-                           data["type" if self.mass else "mass"].to_numpy(dtype=np.float64))
-
-            frames = from_pandas()
-        for ts, v, qcol, tm in frames:
-            check_atom_count(seg_off[-1], v.shape[1])
-            if m is None:
-                m, q = T.masses(tm, self.mass), qcol
-            vel.append(np.ascontiguousarray(v))
-            steps.append(ts * constants.TIME_CONVERSION[self.units])
-        flux = None
-        if vel:
-            flux = backend.charge_flux(np.stack(vel), m, q, seg_off, (mol_type - 1).astype(np.int32),
-                                       len(self.num_mols), constants.VELOCITY_CONVERSION[self.units],
-                                       constants.CHARGE_CONVERSION[self.units])
-        return self._finish_flux(flux, steps, files, n_expected)
-
-    def _flux_streamed(self, files, seg_off, mol_type):
-        """(flux [3, n_types, F_local] or None, steps) through the frame stream; None when the dumps need the general
-        route (compressed text, a column missing: the general route raises the reference's message)."""
         pattern = f"{self.working_dir}/{self.filename}"
-        # the staging batch carries the charge, ONE more per-atom attribute and the three velocity planes
-        columns = ("q", "type" if self.mass else "mass", "vx", "vy", "vz")
-        mine = T.streamable_files(pattern, ("id",) + columns, files)
-        if mine is None:
-            return None
+        n_expected = len(glob.glob(pattern))
+        seg_off, mol_type, _ = molecule_layout(self.num_mols, self.num_atoms_per_mol)
+        # under torch.distributed every rank parses and reduces its own share of the files; the per-frame flux
+        # vectors (3 x n_types doubles) are all-gathered in _finish_flux
+        files = D.my_files(pattern) if mio.USE_NATIVE_READER else None
         m = q = None
         parts, steps = [], []
-        for batch in T.stream_reduced(pattern, mine, columns, seg_off[-1]):
-            if m is None:  # masses and charges of the first frame, as the general route takes them
-                m, q = T.masses(batch.types[0].copy(), self.mass), batch.ids[0].copy()
-            parts.append(backend.charge_flux(batch.xyz, m, q, seg_off, (mol_type - 1).astype(np.int32),
-                                             len(self.num_mols), constants.VELOCITY_CONVERSION[self.units],
+        # the charge, ONE more per-atom attribute and the three velocity planes; on the frame stream the fused flux
+        # kernel runs on each staging batch while the next one is being parsed (stream.py)
+        _, batches = T.attribute_batches(pattern, ("q", "type" if self.mass else "mass"), ("vx", "vy", "vz"),
+                                         n_atoms=seg_off[-1], files=files, stream=STREAM, dumps=self.dumps)
+        for ts, charge, second, vel in batches:
+            if m is None:  # masses and charges of the first frame
+                m, q = T.masses(second[0].copy(), self.mass), charge[0].copy()
+            parts.append(backend.charge_flux(vel, m, q, seg_off, (mol_type - 1).astype(np.int32), len(self.num_mols),
+                                             constants.VELOCITY_CONVERSION[self.units],
                                              constants.CHARGE_CONVERSION[self.units]))
-            steps.extend((batch.timesteps * constants.TIME_CONVERSION[self.units]).tolist())
-        if not parts:
-            return None if files is None else (None, steps)
-        return np.concatenate(parts, axis=2), steps
+            steps.extend((ts * constants.TIME_CONVERSION[self.units]).tolist())
+        flux = np.concatenate(parts, axis=2) if parts else None
+        return self._finish_flux(flux, steps, files, n_expected)
 
     def _finish_flux(self, flux, steps, files, n_expected):
         from .. import dist as D
@@ -273,79 +227,6 @@ class Conductivity:
 
     # ---- Einstein-Helfand / Nernst-Einstein ------------------------------------------------------------------------
 
-    def _com_frames_streamed(self, seg_off):
-        """([device tensor [B,3,M]], timesteps, molecule charges) through the frame stream, or None when the dumps need
-        the general route (compressed text, no xu yu zu, a column missing: the general route names it)."""
-        import torch
-
-        pattern = f"{self.working_dir}/{self.filename}"
-        columns = ("q", "type" if self.mass else "mass") + T.UNWRAPPED
-        mine = T.streamable_files(pattern, ("id",) + columns)
-        if mine is None:
-            return None
-        ctx = backend.default_context()
-        dev = torch.device("cuda", ctx.device)
-        m = q = q_mol = None
-        parts, steps = [], []
-        M = len(seg_off) - 1
-        for batch in T.stream_reduced(pattern, mine, columns, seg_off[-1]):
-            if m is None:  # masses and charges of the first frame
-                m, q = T.masses(batch.types[0].copy(), self.mass), batch.ids[0].copy()
-            out = torch.empty((len(batch), 3, M), dtype=torch.float64, device=dev)
-            _, _, seg_q = backend.segment_com(batch.xyz, m, seg_off, atom_q=q, out=out, ctx=ctx)
-            if q_mol is None:
-                q_mol = seg_q
-            parts.append(out)
-            steps.extend(int(ts) for ts in batch.timesteps)
-        if not parts:
-            return None
-        return parts, steps, q_mol
-
-    def _com_frames_general(self, seg_off):
-        """The same from whole frames: either reader, xu yu zu as dumped or made from x y z and the image flags."""
-        import torch
-
-        from .. import io as mio
-
-        second = "type" if self.mass else "mass"
-
-        def missing(c, _have_unwrapped):
-            raise ValueError(f"Missing column '{c}' in dump file (no xu yu zu to use instead).")
-
-        def wanted(names):
-            for c in ("id", "q", second):
-                if c not in names:
-                    raise ValueError(f"Missing column '{c}' in dump file.")
-            return T.unwrapped_columns(names, ["q", second], missing)
-
-        def frames():
-            if mio.USE_NATIVE_READER:
-                for ts, bounds, _l, names, planes in mio.iter_native_frames(
-                        f"{self.working_dir}/{self.filename}", wanted, sort_by="id"):
-                    yield ts, bounds, dict(zip(wanted(names), planes))
-            else:
-                for dump in self.dumps:
-                    data = dump.data.sort_values(by=["id"])
-                    sel = wanted(list(data.columns))
-                    yield (dump.timestep, np.asarray(dump.box.bounds, dtype=np.float64),
-                           {c: data[c].to_numpy(dtype=np.float64) for c in sel})
-
-        m = q = None
-        xu, steps = [], []
-        for ts, bounds, cols in frames():
-            T.unwrap(cols, bounds)
-            check_atom_count(seg_off[-1], len(cols["q"]))
-            if m is None:
-                m, q = T.masses(cols[second], self.mass), cols["q"]
-            xu.append(np.stack([cols["xu"], cols["yu"], cols["zu"]]))
-            steps.append(int(ts))
-        if not xu:
-            raise ValueError(f"no frames match {self.working_dir}/{self.filename}")
-        ctx = backend.default_context()
-        out = torch.empty((len(xu), 3, len(seg_off) - 1), dtype=torch.float64, device=torch.device("cuda", ctx.device))
-        _, _, q_mol = backend.segment_com(np.stack(xu), m, seg_off, atom_q=q, out=out, ctx=ctx)
-        return [out], steps, q_mol
-
     @staticmethod
     def frame_times(steps, time_unit):
         """(order, times [s]) of frames with integer timesteps `steps`: sorted by time; ValueError unless they are equally
@@ -367,13 +248,32 @@ class Conductivity:
             return got
         import torch
 
-        from .. import io as mio
-
         seg_off, mol_type, _ = molecule_layout(self.num_mols, self.num_atoms_per_mol)
-        loaded = self._com_frames_streamed(seg_off) if (mio.USE_NATIVE_READER and STREAM) else None
-        if loaded is None:
-            loaded = self._com_frames_general(seg_off)
-        parts, steps, q_mol = loaded
+        pattern = f"{self.working_dir}/{self.filename}"
+
+        def missing(lacking, _names):  # the first column the dump lacks; a coordinate only where xu yu zu are not all there
+            tail = " (no xu yu zu to use instead)" if lacking[0] in T.WRAPPED else ""
+            raise ValueError(f"Missing column '{lacking[0]}' in dump file{tail}.")
+
+        m = q = q_mol = ctx = None
+        parts, steps = [], []
+        # unsharded: every process reads every file. Whatever the route, each batch is reduced to molecule centres
+        # [B,3,M] that stay on the device
+        _, batches = T.attribute_batches(pattern, ("q", "type" if self.mass else "mass"), T.UNWRAPPED,
+                                         n_atoms=seg_off[-1], stream=STREAM, missing=missing, dumps=self.dumps)
+        for ts, charge, second, xyz in batches:
+            if m is None:  # masses and charges of the first frame
+                m, q = T.masses(second[0].copy(), self.mass), charge[0].copy()
+                ctx = backend.default_context()
+            out = torch.empty((len(ts), 3, len(seg_off) - 1), dtype=torch.float64,
+                              device=torch.device("cuda", ctx.device))
+            _, _, seg_q = backend.segment_com(xyz, m, seg_off, atom_q=q, out=out, ctx=ctx)
+            if q_mol is None:
+                q_mol = seg_q
+            parts.append(out)
+            steps.extend(ts.tolist())
+        if not parts:
+            raise ValueError(f"no frames match {pattern}")
         order, times = self.frame_times(steps, constants.TIME_CONVERSION[self.units] * self.timestep)
         com = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
         if np.any(order != np.arange(len(order))):

@@ -15,6 +15,7 @@ Tolerance: means are tree sums on the GPU vs pandas' compensated sums: rtol 1e-1
 """
 
 import os
+from collections import namedtuple
 
 import numpy as np
 import pandas as pd
@@ -23,7 +24,7 @@ from .. import backend
 from .. import dist as D
 from ..common import constants
 from ..common import trajectory as T
-from ..common.com_mols import check_atom_count, molecule_layout
+from ..common.com_mols import molecule_layout
 from ..io import parse_lammps_dumps, parse_lammps_log  # noqa: F401  (parse_lammps_log: API parity)
 from ..utilities.log import concat_log
 
@@ -39,6 +40,11 @@ STREAM_BATCH_BYTES = None  # coordinates per staging batch (None: stream.DEFAULT
 # Under torch.distributed: True = every rank returns the whole `msd_all` (its F x E value columns are gathered, device to
 # device on RCCL) — the frame one process would return; False = every rank returns the rows of ITS frames only.
 MSD_ALL_ON_EVERY_RANK = True
+
+
+# what both forms of get_msd_from_dump need before they reduce: names of the id columns and their values per entity,
+# group labels and offsets, the unit scale of the coordinates, the index of the frame at time 0
+_MsdPlan = namedtuple("_MsdPlan", "id_cols id_vals group_labels group_off scale origin")
 
 
 def _is_device(r):
@@ -99,7 +105,8 @@ class Diffusion:
     # ------------------------------------------------------------------------------------------
     @staticmethod
     def _prepare_unwrapped_coords(dump):
-        """Make xu, yu, zu available, from x + ix*L when they were not dumped (diffusion.py:62-81)."""
+        """Make xu, yu, zu available, from x + ix*L when they were not dumped (diffusion.py:62-81). Kept for callers
+        that subclass, like the two methods below; the product path unwraps in common/trajectory.py (`unwrap`)."""
         cols = dump.data.columns
         if "zu" not in cols:  # the reference's `"xu" and "yu" and "zu" not in ...` tests only zu
             assert "z" in cols, "Missing wrapped and unwrapped coordinates (x y z xu yu zu)"
@@ -140,149 +147,77 @@ class Diffusion:
     def _entity_frames(self, filename, msd_type, num_mols, num_atoms_per_mol, mass):
         """Parse this process's frames and reduce them to entity coordinates [F_local, 3, E] in LAMMPS length units.
         Returns (times, r, meta, sharded): under torch.distributed every rank parses ITS share of the files and
-        `sharded` is True — r then holds only those frames (get_msd_from_dump reduces them where they are)."""
+        `sharded` is True — r then holds only those frames (get_msd_from_dump reduces them where they are).
+        When the frame stream serves the request (common/trajectory.py `attribute_batches`), r is a DEVICE tensor:
+        frames go text -> page-locked batch -> GPU while the next batch is parsed, and 'com' reduces every batch to
+        molecule centres on the way (`mdhip_segment_com` with a device destination), so only [F,3,M] stays. Otherwise
+        (wrapped coordinates to unwrap, compressed text, the pandas reader, STREAM off) r is a host array."""
         from .. import io as mio
+        from .._lib import default_context
 
         if msd_type not in ("allatom", "com"):
             raise ValueError("msd_type must be 'allatom' or 'com'.")
-        times, planes = [], []
-        ids = atom_mass = None
-        pattern = f"{self.outputs_dir}/{filename}"
-        # under torch.distributed every rank parses its own share of the files (parsing is the bottleneck);
-        # the reduced frames are all-gathered below and the rest runs replicated
-        files = D.my_files(pattern) if mio.USE_NATIVE_READER else None
-        if STREAM and mio.USE_NATIVE_READER:
-            got = self._entity_frames_streamed(pattern, files, msd_type, num_mols, num_atoms_per_mol, mass)
-            if got is not None:
-                return got
-        err = None
-        try:
-            for step, names, cols in self._frame_columns(pattern, msd_type, mass, mio.USE_NATIVE_READER, files=files):
-                if ids is None:
-                    ids = cols["id"]
-                planes.append(np.ascontiguousarray(np.stack([cols["xu"], cols["yu"], cols["zu"]])))
-                if msd_type == "com":
-                    m = T.masses(cols["type" if mass else "mass"], mass)
-                    if atom_mass is None:
-                        atom_mass = m
-                    elif not np.array_equal(atom_mass, m):
-                        raise ValueError("atom masses change between frames")
-                times.append(step * self.timestep * constants.TIME_CONVERSION[self.units])
-        except Exception as e:  # noqa: BLE001
-            if files is None:
-                raise
-            err = e  # (a rank's own parse error: the ranks agree on it before anyone enters a collective)
-        if files is not None:
-            D.raise_together(err, "parsing its dump files")
-        times = np.asarray(times, dtype=np.float64)
-        sharded = files is not None and D.is_distributed()
-        if files is not None:
-            D.require_all_nonempty(len(planes), "dump file")  # every rank raises, or none
-        if msd_type == "com":
-            seg = molecule_layout(num_mols, num_atoms_per_mol)
-            if planes:
-                check_atom_count(seg[0][-1], planes[0].shape[1])
-            com, seg_mass, _ = backend.segment_com(np.stack(planes), atom_mass, seg[0])
-            return times, com, dict(type=seg[1], mol_id=seg[2], mass=seg_mass), sharded
-        r = np.stack(planes)
-        # (id: an integer column, as the reference's parser reads it)
-        return times, r, dict(id=np.asarray(ids).astype(np.int64)), sharded
-
-    def _entity_frames_streamed(self, pattern, files, msd_type, num_mols, num_atoms_per_mol, mass):
-        """The same (times, r [F,3,E], meta) with r a DEVICE tensor: frames go text -> page-locked batch -> GPU while
-        the next batch is parsed; 'com' reduces every batch to molecule centres on the way (`mdhip_segment_com` with a
-        device destination), so only [F,3,M] stays. None when the dumps need the general route (wrapped coordinates
-        to unwrap, compressed text, a column missing — whose error the general route raises in the reference's
-        words)."""
         try:
             import torch
         except ImportError:  # libmdhip.so runs on the system ROCm runtime without torch (_lib.py): general route
-            return None
+            torch = None
 
-        from .._lib import default_context
+        def missing(lacking, _names):  # (the reference asserts on z and iz only; the reader names any other)
+            assert "id" not in lacking, "Missing atom id's in dump file."
+            assert "z" not in lacking, "Missing wrapped and unwrapped coordinates (x y z xu yu zu)"
+            assert "iz" not in lacking, (
+                "Missing unwrapped coordinates (xu yu zu) and box location (ix iy iz) for converting "
+                "wrapped coordinates (x y z) into unwrapped coordinates. ")
+            assert "mass" not in lacking, "Missing atom masses in dump file."
 
-        # the staging batch carries id, ONE per-atom attribute and the three coordinate planes
-        columns = ("id", "id" if msd_type == "allatom" else ("type" if mass else "mass")) + T.UNWRAPPED
-        mine = T.streamable_files(pattern, columns, files)
-        if mine is None:
-            return None
-        ctx = default_context()
-        dev = torch.device("cuda", ctx.device)
-        seg = molecule_layout(num_mols, num_atoms_per_mol) if msd_type == "com" else None
-        times, blocks = [], []
-        ids = atom_mass = seg_mass = None
-        err = None
+        com = msd_type == "com"
+        seg = molecule_layout(num_mols, num_atoms_per_mol) if com else None
+        pattern = f"{self.outputs_dir}/{filename}"
+        # under torch.distributed every rank parses its own share of the files (parsing is the bottleneck)
+        files = D.my_files(pattern) if mio.USE_NATIVE_READER else None
+        # id, ONE more per-atom attribute and the three coordinate planes
+        streamed, batches = T.attribute_batches(
+            pattern, ("id", ("type" if mass else "mass") if com else "id"), T.UNWRAPPED,
+            n_atoms=seg[0][-1] if com else None, files=files, stream=STREAM and torch is not None,
+            batch_bytes=STREAM_BATCH_BYTES, missing=missing, decide_on=("zu",))  # (the reference tests only zu)
+        steps, blocks = [], []
+        ids = second0 = atom_mass = seg_mass = ctx = err = None
         try:
-            for batch in T.stream_reduced(pattern, mine, columns, seg[0][-1] if seg else None, STREAM_BATCH_BYTES):
-                B, _, n = batch.xyz.shape
+            for ts, id_rows, second, xyz in batches:
                 if ids is None:
-                    ids = batch.ids[0].copy()
-                if msd_type == "com":
-                    m = T.masses(batch.types, mass)
-                    if atom_mass is None:
-                        atom_mass = m[0].copy()
-                    if not (m == atom_mass).all():
+                    ids, second0 = id_rows[0].copy(), second[0].copy()
+                    atom_mass = T.masses(second0, mass) if com else None
+                out = None
+                if streamed:  # what is kept from a staging batch is a copy: on the device
+                    ctx = ctx or default_context()
+                    out = torch.empty((len(ts), 3, len(seg[0]) - 1 if com else xyz.shape[2]), dtype=torch.float64,
+                                      device=torch.device("cuda", ctx.device))
+                if com:  # (rows that repeat the first frame's carry its masses; any other row is looked up)
+                    if not (second == second0).all() and not (T.masses(second, mass) == atom_mass).all():
                         raise ValueError("atom masses change between frames")
-                    out = torch.empty((B, 3, len(seg[0]) - 1), dtype=torch.float64, device=dev)
-                    _, seg_mass, _ = backend.segment_com(batch.xyz, atom_mass, seg[0], out=out, ctx=ctx)
+                    out, seg_mass, _ = backend.segment_com(xyz, atom_mass, seg[0], out=out, ctx=ctx)
+                elif streamed:
+                    out.copy_(torch.from_numpy(xyz))  # synchronous DMA from the page-locked batch
                 else:
-                    out = torch.empty((B, 3, n), dtype=torch.float64, device=dev)
-                    out.copy_(torch.from_numpy(batch.xyz))  # synchronous DMA from the page-locked batch
+                    out = xyz
                 blocks.append(out)
-                times.extend(batch.timesteps.tolist())
+                steps.extend(ts.tolist())
         except Exception as e:  # noqa: BLE001
             if files is None:
                 raise
             err = e  # (this rank's own parse / reduce error: agreed on below, before the first collective)
         if files is not None:
-            D.raise_together(err, "streaming its dump files")
-        times = np.asarray(times, dtype=np.float64) * self.timestep * constants.TIME_CONVERSION[self.units]
-        if files is not None:
-            D.require_all_nonempty(len(times), "dump file")  # every rank raises, or none
-        elif not blocks:
-            return None
-        r = torch.cat(blocks) if len(blocks) > 1 else blocks[0]
+            D.raise_together(err, "streaming its dump files" if streamed else "parsing its dump files")
+            D.require_all_nonempty(len(steps), "dump file")  # every rank raises, or none
+        if not blocks:
+            raise ValueError("need at least one array to stack")  # (no frame at all: numpy's words for it, as ever)
+        times = np.asarray(steps, dtype=np.float64) * self.timestep * constants.TIME_CONVERSION[self.units]
+        r = blocks[0] if len(blocks) == 1 else torch.cat(blocks)  # (only the stream cuts batches)
         del blocks
         sharded = files is not None and D.is_distributed()
-        if msd_type == "com":
+        if com:
             return times, r, dict(type=seg[1], mol_id=seg[2], mass=seg_mass), sharded
         return times, r, dict(id=ids.astype(np.int64)), sharded  # an integer column, as the reference's parser reads it
-
-    def _frame_columns(self, pattern, msd_type, mass, native, files=None):
-        """Yields (timestep, column names, {name: id-sorted float64 column}) with xu, yu, zu present
-        (made from x + ix*L when they were not dumped, diffusion.py:62-81)."""
-        from .. import io as mio
-
-        def missing(c, _have_unwrapped):  # (the reference asserts on z and iz only; the reader names any other)
-            assert c != "z", "Missing wrapped and unwrapped coordinates (x y z xu yu zu)"
-            assert c != "iz", (
-                "Missing unwrapped coordinates (xu yu zu) and box location (ix iy iz) for converting "
-                "wrapped coordinates (x y z) into unwrapped coordinates. ")
-
-        def wanted(names):
-            assert "id" in names, "Missing atom id's in dump file."
-            sel = T.unwrapped_columns(names, ["id"], missing, decide_on=("zu",))  # (and tests only zu)
-            if msd_type == "com":
-                if not mass:
-                    assert "mass" in names, "Missing atom masses in dump file."
-                    sel.append("mass")
-                else:
-                    sel.append("type")
-            return sel
-
-        if native:
-            for ts, bounds, _lengths, names, planes in mio.iter_native_frames(pattern, wanted, sort_by="id",
-                                                                               files=files):
-                yield ts, names, T.unwrap(dict(zip(wanted(names), planes)), bounds)
-            return
-        for dump in parse_lammps_dumps(pattern):
-            names = list(dump.data.columns)
-            sel = wanted(names)
-            dump.data = dump.data.sort_values(by=["id"])
-            dump.data.reset_index(inplace=True)
-            dump = self._prepare_unwrapped_coords(dump)
-            want = set(sel) | {"xu", "yu", "zu"}
-            yield dump.timestep, names, {c: dump.data[c].to_numpy(dtype=np.float64) for c in want}
 
     def get_msd_from_dump(self, filename, msd_type="com", num_mols=None, num_atoms_per_mol=None, mass=None,
                           com_drift=False, avg_interval=False, tao_coeff=4):
@@ -309,40 +244,47 @@ class Diffusion:
         if not np.array_equal(order, np.arange(len(order))):
             times, r = times[order], _take_frames(r, order)
         F, _, E = r.shape
-        id_cols, id_vals, group_off, group_labels = self._groups(meta, msd_type, E)
-        dist = constants.DISTANCE_CONVERSION[self.units]
-        scale = dist
+        plan = self._msd_plan(times, meta, msd_type, E)
+        group_off, scale, origin = plan.group_off, plan.scale, plan.origin
         if msd_type == "com" and com_drift:
             if _is_device(r):  # small ([F,3,M]) and host arithmetic: same doubles as the load-everything route
                 r = r.cpu().numpy()
-            r = self._remove_drift(r * dist, meta["mass"] * constants.MASS_CONVERSION[self.units], group_off)
+            r = self._remove_drift(r * scale, meta["mass"] * constants.MASS_CONVERSION[self.units], group_off)
             scale = 1.0
-        origin = np.flatnonzero(times == 0)
-        if len(origin) == 0:
-            raise KeyError(0)  # the reference selects the time-0 rows with .xs(0, 0)
-        origin = int(origin[0])
         pairs = np.column_stack([np.full(F, origin), np.arange(F)]).astype(np.int32)
         # the per-entity values come back as the four COLUMNS of msd_all (one contiguous block each); the frame wraps
         # them, the time column and the tiled id columns without consolidating them into a second copy
         col_block = np.empty((4, F * E))
         sums = backend.msd_pairs_cols(r, pairs, group_off, col_block, scale=scale)
-        msd_all = self._msd_all_frame(times, E, id_cols, id_vals, col_block)
-        msd = self._msd_frame(times, sums, group_off, group_labels, msd_type)
-        if not avg_interval:
-            return msd, msd_all
-
-        n_kept = len(np.arange(F)[::tao_coeff])  # diffusion.py:226-228: every tao-th time is kept
-        win = backend.msd_windows(r, tao_coeff, scale=scale)  # (the kernel strides over the kept frames in place)
-        return msd, msd_all, self._msd_int_frame(win, n_kept, E, id_cols, id_vals)
+        # (the window kernel strides over the kept frames in place)
+        win = backend.msd_windows(r, tao_coeff, scale=scale) if avg_interval else None
+        return self._msd_results(times, times, sums, col_block, win, tao_coeff, plan, msd_type)
 
     # ------------------------------------------------------------------------------------------
-    @staticmethod
-    def _groups(meta, msd_type, E):
+    def _msd_plan(self, times, meta, msd_type, E):
+        """The `_MsdPlan` of frames at `times`; KeyError(0) when none is at time 0."""
+        origin = np.flatnonzero(times == 0)
+        if len(origin) == 0:
+            raise KeyError(0)  # the reference selects the time-0 rows with .xs(0, 0)
+        scale, origin = constants.DISTANCE_CONVERSION[self.units], int(origin[0])
         if msd_type == "allatom":
-            return ["id"], [meta["id"]], np.array([0, E], dtype=np.int64), None
+            return _MsdPlan(["id"], [meta["id"]], None, np.array([0, E], dtype=np.int64), scale, origin)
         counts = np.bincount(meta["type"])[1:]
         group_off = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
-        return ["type", "mol_id"], [meta["type"], meta["mol_id"]], group_off, np.arange(1, len(counts) + 1)
+        return _MsdPlan(["type", "mol_id"], [meta["type"], meta["mol_id"]], np.arange(1, len(counts) + 1), group_off,
+                        scale, origin)
+
+    def _msd_results(self, times, times_all, sums, col_block, win, tao_coeff, plan, msd_type):
+        """(msd, msd_all[, msd_int]) from the group sums [F,G,4] of the frames at `times`, the per-entity value columns
+        [4, rows] of the frames at `times_all`, and the window sums [E,4] (None: no msd_int)."""
+        id_cols, id_vals, group_labels, group_off = plan.id_cols, plan.id_vals, plan.group_labels, plan.group_off
+        E = len(id_vals[0])
+        msd_all = self._msd_all_frame(times_all, E, id_cols, id_vals, col_block)
+        msd = self._msd_frame(times, sums, group_off, group_labels, msd_type)
+        if win is None:
+            return msd, msd_all
+        n_kept = len(np.arange(len(times))[::tao_coeff])  # diffusion.py:226-228: every tao-th time is kept
+        return msd, msd_all, self._msd_int_frame(win, n_kept, E, id_cols, id_vals)
 
     @staticmethod
     def _msd_all_frame(times, E, id_cols, id_vals, col_block):
@@ -394,23 +336,17 @@ class Diffusion:
             return None
         F, F_l, E = int(sum(counts)), int(r_l.shape[0]), int(r_l.shape[2])
         lo = int(sum(counts[:rank]))
-        id_cols, id_vals, group_off, group_labels = self._groups(meta, msd_type, E)
-        dist = constants.DISTANCE_CONVERSION[self.units]
-        scale = dist
+        plan = self._msd_plan(times, meta, msd_type, E)
+        group_off, scale, origin = plan.group_off, plan.scale, plan.origin
         if msd_type == "com" and com_drift:
             # per-type drift: this rank's frames against the per-type centre of the FIRST frame (rank 0's first)
             if _is_device(r_l):
                 r_l = r_l.cpu().numpy()
-            ent_mass = meta["mass"] * constants.MASS_CONVERSION[self.units]
-            r_si = r_l * dist
-            com_l = self._type_com(r_si, ent_mass, group_off)  # [F_l, 3, G]
+            r_si = r_l * scale
+            com_l = self._type_com(r_si, meta["mass"] * constants.MASS_CONVERSION[self.units], group_off)  # [F_l, 3, G]
             com0 = D.broadcast_array(com_l[0] if rank == 0 else None, 0, (3, len(group_off) - 1))
             r_l = self._subtract_drift(r_si, com_l - com0[None], group_off)
             scale = 1.0
-        origin = np.flatnonzero(times == 0)
-        if len(origin) == 0:
-            raise KeyError(0)  # the reference selects the time-0 rows with .xs(0, 0)
-        origin = int(origin[0])
         on_dev = _is_device(r_l)
         if on_dev:
             import torch
@@ -421,21 +357,15 @@ class Diffusion:
         sums = D.msd_single_origin_sharded(r_l, F, group_off, scale=scale, origin_frame=origin, counts=counts,
                                            cols=cols_l)
         if MSD_ALL_ON_EVERY_RANK:
-            col_block = np.empty((4, F * E))
+            times_all, col_block = times, np.empty((4, F * E))
             for k in range(4):  # column k of every rank's frames, in rank (= time) order
                 g = D.allgather_var(cols_l[k].reshape(F_l, E), counts)
                 col_block[k] = (g.cpu().numpy() if on_dev else g).reshape(-1)
-            msd_all = self._msd_all_frame(times, E, id_cols, id_vals, col_block)
         else:
-            col_block = cols_l.cpu().numpy() if on_dev else cols_l
-            msd_all = self._msd_all_frame(times[lo:lo + F_l], E, id_cols, id_vals, col_block)
+            times_all, col_block = times[lo:lo + F_l], (cols_l.cpu().numpy() if on_dev else cols_l)
         del cols_l
-        msd = self._msd_frame(times, sums, group_off, group_labels, msd_type)
-        if not avg_interval:
-            return msd, msd_all
-        n_kept = len(np.arange(F)[::tao_coeff])
-        win = D.msd_windows_sharded(r_l, F, tao_coeff, scale=scale, counts=counts)
-        return msd, msd_all, self._msd_int_frame(win, n_kept, E, id_cols, id_vals)
+        win = D.msd_windows_sharded(r_l, F, tao_coeff, scale=scale, counts=counts) if avg_interval else None
+        return self._msd_results(times, times_all, sums, col_block, win, tao_coeff, plan, msd_type)
 
     @staticmethod
     def _type_com(r_si, ent_mass, group_off):
@@ -458,13 +388,8 @@ class Diffusion:
     def _remove_drift(r_si, ent_mass, group_off):
         """Per-type mass-weighted COM minus the same at the first frame, subtracted from every
         molecule of that type (diffusion.py:83-96). r_si [F,3,E]."""
-        out = r_si.copy()
-        for g in range(len(group_off) - 1):
-            lo, hi = group_off[g], group_off[g + 1]
-            m = ent_mass[lo:hi]
-            com = (r_si[:, :, lo:hi] @ m) / m.sum()  # [F,3]
-            out[:, :, lo:hi] -= (com - com[0])[:, :, None]
-        return out
+        com = Diffusion._type_com(r_si, ent_mass, group_off)
+        return Diffusion._subtract_drift(r_si, com - com[:1], group_off)
 
     # ------------------------------------------------------------------------------------------
     def get_msd_from_log(self, log_pattern):

@@ -144,20 +144,21 @@ def test_diffusion_streamed_equals_load_all(small_dir, kw, monkeypatch):
         monkeypatch.setattr(dm, "STREAM", on)
         monkeypatch.setattr(dm, "STREAM_BATCH_BYTES", 2 * 24 * n)  # two frames per batch
         made = []
-        orig = dm.Diffusion._entity_frames_streamed
+        orig = dm.Diffusion._entity_frames
 
         def spy(self, *a, **k):
             out = orig(self, *a, **k)
-            made.append(out)
+            made.append(out[1])
             return out
 
-        monkeypatch.setattr(dm.Diffusion, "_entity_frames_streamed", spy)
+        monkeypatch.setattr(dm.Diffusion, "_entity_frames", spy)
         res[on] = d.get_msd_from_dump("dump.nvt.*.dump", avg_interval=True, tao_coeff=3, **kw)
-        monkeypatch.setattr(dm.Diffusion, "_entity_frames_streamed", orig)
+        monkeypatch.setattr(dm.Diffusion, "_entity_frames", orig)
+        assert len(made) == 1
         if on:
-            assert made and made[0] is not None and made[0][1].is_cuda  # the device-resident route was taken
+            assert made[0].is_cuda  # the device-resident route was taken
         else:
-            assert not made
+            assert isinstance(made[0], np.ndarray)
     for a, b in zip(res[True], res[False]):
         assert list(a.columns) == list(b.columns)
         np.testing.assert_array_equal(a.to_numpy(), b.to_numpy())

@@ -115,46 +115,45 @@ def test_unwrapped_columns_selection_and_the_callers_raise():
 
 
 def test_no_coordinates_at_all_raises_each_callers_own_error(tmp_path):
-    """The texts are the parent commit's, copied as literals."""
+    """The texts are the parent commit's, copied as literals; both callers raise them from the callback they hand to
+    `attribute_batches`, before anything is asked of a GPU."""
     from mdproptools_amd.dynamical.conductivity import Conductivity
     from mdproptools_amd.dynamical.diffusion import Diffusion
 
-    pattern = _write(tmp_path, ["id", "type", "q", "mass"])
+    _write(tmp_path, ["id", "type", "q", "mass"])
     d = Diffusion(outputs_dir=str(tmp_path), diff_dir=str(tmp_path))
     with pytest.raises(AssertionError) as e:
-        next(d._frame_columns(pattern, "com", None, True))
+        d.get_msd_from_dump("dump.*.dump", msd_type="com", num_mols=NUM_MOLS, num_atoms_per_mol=ATOMS_PER_MOL)
     assert str(e.value) == "Missing wrapped and unwrapped coordinates (x y z xu yu zu)"
     c = Conductivity("dump.*.dump", NUM_MOLS, ATOMS_PER_MOL, 1000.0, working_dir=str(tmp_path))
     with pytest.raises(ValueError) as e:
-        c._com_frames_general(np.array([0, 2, 4, 7]))
+        c.einstein()
     assert str(e.value) == "Missing column 'x' in dump file (no xu yu zu to use instead)."
     # z without the image flags: Diffusion's second text; Conductivity names the first column it lacks
     sub = tmp_path / "no_images"
     sub.mkdir()
-    pattern = _write(sub, ["id", "type", "q", "mass", "x", "y", "z"])
+    _write(sub, ["id", "type", "q", "mass", "x", "y", "z"])
     with pytest.raises(AssertionError) as e:
-        next(Diffusion(outputs_dir=str(sub), diff_dir=str(sub))._frame_columns(pattern, "allatom", None, True))
+        Diffusion(outputs_dir=str(sub), diff_dir=str(sub)).get_msd_from_dump("dump.*.dump", msd_type="allatom")
     assert str(e.value) == ("Missing unwrapped coordinates (xu yu zu) and box location (ix iy iz) for converting "
                             "wrapped coordinates (x y z) into unwrapped coordinates. ")
     with pytest.raises(ValueError) as e:
-        Conductivity("dump.*.dump", NUM_MOLS, ATOMS_PER_MOL, 1000.0, working_dir=str(sub))._com_frames_general(
-            np.array([0, 2, 4, 7]))
+        Conductivity("dump.*.dump", NUM_MOLS, ATOMS_PER_MOL, 1000.0, working_dir=str(sub)).nernst()
     assert str(e.value) == "Missing column 'ix' in dump file (no xu yu zu to use instead)."
 
 
 def test_adapters_unwrap_wrapped_dumps_like_dumped_unwrapped_ones(wrapped):
-    """Diffusion._frame_columns on the native route: xu yu zu of a wrapped dump are x + ix * L of its id-sorted rows."""
-    from mdproptools_amd.dynamical.diffusion import Diffusion
-
+    """`attribute_batches` as Diffusion calls it, on the native route: xu yu zu of a wrapped dump are x + ix * L of its
+    id-sorted rows, every frame in one batch of the general route."""
     tables = _tables()
-    d = Diffusion(outputs_dir=os.path.dirname(wrapped), diff_dir=os.path.dirname(wrapped))
-    got = list(d._frame_columns(wrapped, "com", MASS, True))
-    assert [g[0] for g in got] == STEPS
-    for (ts, names, cols), t in zip(got, tables):
-        assert sorted(cols) == sorted(["id", "type", "x", "y", "z", "ix", "iy", "iz", "xu", "yu", "zu"])
+    streamed, batches = T.attribute_batches(wrapped, ("id", "type"), T.UNWRAPPED, n_atoms=N, decide_on=("zu",))
+    ((steps, ids, types, planes),) = batches
+    assert not streamed and steps.tolist() == STEPS and planes.shape == (5, 3, N)
+    assert np.array_equal(ids, np.tile(np.arange(1.0, N + 1), (5, 1))) and np.array_equal(types, np.tile(TYPES, (5, 1)))
+    for f, t in enumerate(tables):
         for k, axis in enumerate("xyz"):
             want = t[axis] + t["i" + axis].astype(np.float64) * (BOUNDS[k][1] - BOUNDS[k][0])
-            assert cols[axis + "u"].tobytes() == want.tobytes()
+            assert planes[f, k].tobytes() == want.tobytes()
 
 
 # ---- masses ----------------------------------------------------------------------------------------------------------
