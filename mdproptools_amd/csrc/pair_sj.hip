@@ -253,24 +253,30 @@ __device__ __forceinline__ int sj_item(const PairArgs &a, FastCtx &c, const unsi
 // pair changes. Lane-parallel draining makes the exact chain cost ~1/64 of what an inline fallback would.
 //
 // Keeping the f32 error small, and the wrap out of the pair loop: the j atoms are stored relative to the centre c
-// of the box of their tile of 256 sorted atoms (64-atom blocks were slower: retired in round 4), and every lane moves
-// its own i atom to the periodic image nearest to that centre, once per neighbour tile:
+// of the box of their tile of 256 sorted atoms (64-atom blocks were slower: retired in round 4), and the wave moves its
+// i atoms to ONE periodic image of that centre, once per neighbour tile and axis:
 //   xr_j = f32(x_j - c)                          (pre-pass, |xr_j| <= half extent h of the block)
-//   q    = x_i - c;  xr_i = f32(q - L rint(q/L)) (f64 per lane and block, |xr_i| <= L/2)
-// so that d' = xr_i - xr_j is d = x_i - x_j moved by a whole number of box lengths, |d'| <= L/2 + e (e = how far
-// the group's atoms reach from c). With |d| < 1.5 L the reference's single wrap yields the nearest image of d, and
+//   n    = rint((c_wave - c) / L)                (the same for all 64 lanes: the image of the wave box's centre)
+//   q    = x_i - c;  xr_i = f32(fma(-n, L, q))   (f64 per lane and block, |xr_i| <= L/2 + h_wave)
+// so that d' = xr_i - xr_j is d = x_i - x_j moved by a whole number of box lengths. With |d| < 1.5 L the reference's
+// single wrap yields the nearest image of d, and for ANY integer image d' of d
 //   |d'| <= L/2            : d' IS that nearest image;
-//   L/2 < |d'| <= L/2 + e  : the nearest image is L - |d'| away.
+//   L/2 < |d'| < L         : the nearest image is L - |d'| away.
 // So wherever |d'| <= L - r_cut - margin the plain difference is enough: either d' is the nearest image, or both d'
-// and the nearest image exceed the cutoff on that axis alone and the pair counts nowhere either way. The wave tests
-// this per (wave box, group box) and axis, lane-parallel over the groups of a tile: when all its lanes sit at the
-// same image n (the wave box does not straddle a wrap boundary of this centre), d' ranges over
-// [wlo' - ghi', whi' - glo'] (primed = relative to c, the wave box moved by n L). Only groups where that interval
-// reaches beyond L - r_cut (cutoffs close to L/2: the far corner of a neighbour at the edge of the cutoff) take the
-// per-pair f32 wrap d' - L rint(d'/L) on that axis (VAR bit). Blocks that the bound does not cover — some
-// |x_i - x_j| >= 1.5 L (atoms box lengths outside the cell, where the reference's single wrap is not the nearest
-// image) or |xr_i| + h beyond s_cap — are swept by the exact f64 chain (sweep_group_sj<., 2, 7>: general wrap,
-// valid for every d).
+// and the nearest image exceed the cutoff on that axis alone and the pair counts nowhere either way. Nothing in this
+// asks for the lane's own nearest image; and because every lane sits at the wave's n, d' ranges over
+// [D - s, D + s] with D = c_wave - n L - c_group and s = h_wave + h_group for every (wave box, group box) — also for a
+// wave box that straddles a +-L/2 plane of this centre. (Every lane used to take its own rint(q / L), and the box
+// bound held only where all 64 agreed: a wave box is 11 A wide in C2's 50 A cell and straddles a fifth of the time per
+// axis, and every group of such a tile then wrapped on that axis — 0.45 of the 0.52 wrapped axes per swept group,
+// tools/wrap_share.py.) The wave tests |D| + s <= L - r_cut - margin per group and axis, lane-parallel over the groups
+// of a tile. Only groups where that interval reaches beyond L - r_cut (cutoffs close to L/2: the far corner of a
+// neighbour at the edge of the cutoff) take the per-pair f32 wrap d' - L rint(d'/L) on that axis (VAR bit). Tiles that
+// the bound does not cover — some |x_i - x_j| >= 1.5 L (atoms box lengths outside the cell, where the reference's single
+// wrap is not the nearest image) or |xr_i| + h beyond s_cap — are swept by the exact f64 chain (sweep_group_sj<., 2, 7>:
+// general wrap, valid for every d). Where only the wave's one image leaves s_cap (a wave box about a box length wide:
+// atoms outside the cell) the axis falls back to the per-lane nearest image, |xr_i| <= L/2, with every group of the
+// tile wrapping on it, so that no tile reaches the exact chain that did not before.
 // ------------------------------------------------------------------------------------------------
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -284,7 +290,7 @@ constexpr int PK_WAVES_PER_SIMD = 6;  // HIP's second launch bound: the register
 constexpr int PK_BIG_THREADS = 1024;
 
 struct PkCtx {
-    f32x2 x2, y2, z2;     // this lane's i atom (its image nearest to the j block's centre) relative to that centre,
+    f32x2 x2, y2, z2;     // this lane's i atom (at the wave's image of the j block's centre) relative to that centre,
                           // both halves equal
     f32x2 Lx2, Ly2, Lz2;  // box lengths (f32) for the axes that still need the per-pair wrap
     f32x2 iLx2, iLy2, iLz2;  // and their reciprocals
@@ -777,28 +783,40 @@ __device__ __forceinline__ int sj_item_pk(const PairArgs &a, FastCtx &c, const u
         const unsigned long long nm = CNG ? __builtin_amdgcn_ballot_w64(g2 < cn_reach2) : 0ull;
         const float *rtile = rel_f + (long long)J * TILE * 4;
         const bool diag = a.tri && J == I_u;
-        // (wave box, tile centre c), one axis per lane: do all lanes of the wave sit at the same image n relative to c
-        // — the rint of both ends of the box agree, with 1e-3 of slack so that every lane's own f64 rint agrees too —,
-        // the wave's centre moved there, the threshold for |d'| (-1 = no group is plain on this axis), and whether
-        // the error bound covers the tile: every |x_i - x_j| < 1.5 L (single wrap = nearest image), |xr_i| + |xr_j|
-        // within s_cap, |d'| <= L/2 + h < 1.5 L for the per-pair wrap.
+        // (wave box, tile centre c), one axis per lane: the image n of the wave box's centre relative to c — the image
+        // of all 64 lanes —, the wave's centre moved there, the threshold for |d'| (-1 = no group is plain on this axis),
+        // and whether the error bound covers the tile: every |x_i - x_j| < 1.5 L (single wrap = nearest image),
+        // |xr_i| + |xr_j| within s_cap, |d'| < 1.5 L for the per-pair wrap (|rel - n L| <= |rel|: the first clause of
+        // ok_a bounds |d'| <= wmax + he as well).
         const float c_a = (float)cd_a, he_a = (float)hd_a;
         const float rel_a = cw_a - c_a;
-        const float n0 = __builtin_rintf(__builtin_fmaf(rel_a - hw_a, iL_a, -1.0e-3f));
-        const float n1 = __builtin_rintf(__builtin_fmaf(rel_a + hw_a, iL_a, 1.0e-3f));
-        const bool same = n0 == n1;
-        const float cwn_a = __builtin_fmaf(-n0, L_a, cw_a);
+        float nu_a = __builtin_rintf(rel_a * iL_a);
         // (c is rounded to f32 here: 2^-24 |c| on each difference — nothing next to the margin inside th for
         // coordinates within a few box lengths of the origin, but subtracted so that the test stays conservative)
-        const float thc_a = same ? __builtin_fmaf(-1.0e-6f, __builtin_fabsf(c_a), th_a) : -1.0f;
-        // the largest |xr_i| of the wave: its box at image n0, or L/2 when the wave straddles a wrap boundary
-        const float wmax_a = same ? __builtin_fabsf(__builtin_fmaf(-n0, L_a, rel_a)) + hw_a : 0.5000001f * L_a;
+        float thc_a = __builtin_fmaf(-1.0e-6f, __builtin_fabsf(c_a), th_a);
+        // the largest |xr_i| of the wave: its box at image n
+        float wmax_a = __builtin_fabsf(__builtin_fmaf(-nu_a, L_a, rel_a)) + hw_a;
+        unsigned long long fbm = 0ull;  // axes on the per-lane fallback
+        if (__builtin_amdgcn_ballot_w64(!(wmax_a + he_a < cap_a)) & 7ull) {  // wave-uniform, rare
+            // One image does not fit the error bound's cover on some axis. Where the box straddles a wrap boundary of this
+            // centre (the rint of both ends of the box differ, with 1e-3 of slack so that every lane's own f64 rint falls
+            // between them) and the per-lane nearest image, |xr_i| <= L/2, does fit, the axis takes that one, as every
+            // straddling wave did before the wave-uniform image: no box bound, every group wraps on the axis.
+            const float n0 = __builtin_rintf(__builtin_fmaf(rel_a - hw_a, iL_a, -1.0e-3f));
+            const float n1 = __builtin_rintf(__builtin_fmaf(rel_a + hw_a, iL_a, 1.0e-3f));
+            const bool fb_a = n0 != n1 && !(wmax_a + he_a < cap_a) && (0.5000001f * L_a + he_a < cap_a);
+            thc_a = fb_a ? -1.0f : thc_a;
+            wmax_a = fb_a ? 0.5000001f * L_a : wmax_a;
+            fbm = __builtin_amdgcn_ballot_w64(fb_a) & 7ull;
+        }
+        const float cwn_a = __builtin_fmaf(-nu_a, L_a, cw_a);
         const bool ok_a = (__builtin_fabsf(rel_a) + hw_a + he_a < 1.49f * L_a) && (wmax_a + he_a < cap_a) &&
                           (he_a < 0.9f * L_a);
         const bool covered = (__builtin_amdgcn_ballot_w64(ok_a) & 7ull) == 7ull;
 #define PK_LANE(V, K) __int_as_float(__builtin_amdgcn_readlane(__float_as_int(V), K))
         const float cwnx = PK_LANE(cwn_a, 0), cwny = PK_LANE(cwn_a, 1), cwnz = PK_LANE(cwn_a, 2);
         const float thcx = PK_LANE(thc_a, 0), thcy = PK_LANE(thc_a, 1), thcz = PK_LANE(thc_a, 2);
+        const float nux = PK_LANE(nu_a, 0), nuy = PK_LANE(nu_a, 1), nuz = PK_LANE(nu_a, 2);
 #undef PK_LANE
         // per group and axis: does the plain difference d' = xr_i - xr_j suffice for every pair of (wave box, group
         // box)? |d'| <= |c_wave - n L - c_group| + h_wave + h_group must stay within th. The axes that fail take the
@@ -832,13 +850,19 @@ __device__ __forceinline__ int sj_item_pk(const PairArgs &a, FastCtx &c, const u
                 }
                 continue;
             }
-            // this lane's i atom at the periodic image nearest to the tile's centre
+            // this lane's i atom at the wave's image of the tile's centre (fallback axes: at its own nearest image)
             // (the i atom is re-read per tile rather than kept live through the pair loop: 8 VGPRs)
             const double4 me = ats[ig];
             const double qx = me.x - cb[0], qy = me.y - cb[1], qz = me.z - cb[2];
-            const double wx = __builtin_fma(-__builtin_rint(qx * iLx), L.Lx, qx);
-            const double wy = __builtin_fma(-__builtin_rint(qy * iLy), L.Ly, qy);
-            const double wz = __builtin_fma(-__builtin_rint(qz * iLz), L.Lz, qz);
+            double ndx = (double)nux, ndy = (double)nuy, ndz = (double)nuz;
+            if (fbm) {  // wave-uniform, rare
+                if (fbm & 1ull) ndx = __builtin_rint(qx * iLx);
+                if (fbm & 2ull) ndy = __builtin_rint(qy * iLy);
+                if (fbm & 4ull) ndz = __builtin_rint(qz * iLz);
+            }
+            const double wx = __builtin_fma(-ndx, L.Lx, qx);
+            const double wy = __builtin_fma(-ndy, L.Ly, qy);
+            const double wz = __builtin_fma(-ndz, L.Lz, qz);
             {
                 const float xr = real_i ? (float)wx : -1.0e18f;
                 const float yr = real_i ? (float)wy : -1.0e18f;
@@ -895,8 +919,9 @@ __device__ __forceinline__ int sj_item_pk(const PairArgs &a, FastCtx &c, const u
                 PK_PIPELINED(km & ~wrapm & ~nm, false, 0, false)
                 if constexpr (CNG) PK_PIPELINED(km & ~wrapm & nm, true, 0, false)
                 // the groups that take the per-pair wrap on some axis run the same software pipeline, variant by variant
-                // (round 3: their records were loaded and waited for group by group before — at C2, where a third of the
-                // swept groups wrap on some axis, 3.04 -> 2.82 ms build against build; C3, which has none, -0.9 %)
+                // (round 3: their records were loaded and waited for group by group before — at C2, where 47 % of the swept
+                // groups wrapped on some axis then and 30 % do with the wave-uniform image, 3.04 -> 2.82 ms build against
+                // build; C3, which has none, -0.9 %)
                 if (km & wrapm & ~nm) {
                     PK_PIPELINED(variant(1u) & ~nm, false, 1, false)
                     PK_PIPELINED(variant(2u) & ~nm, false, 2, false)
