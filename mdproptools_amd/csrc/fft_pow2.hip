@@ -37,6 +37,13 @@ constexpr int FFT_MAX_PASSES = 8;  // PassPlan::logR slots: H <= 2^32 at the sma
 constexpr int FFT_LOGC = 4;      // C = 16 columns per tile
 constexpr int FFT_MAX_BATCH = 32768;  // series per launch (grid.y)
 
+__host__ __device__ inline int ilog2(long long n)  // n a power of two
+{
+    int l = 0;
+    while ((1LL << l) < n) ++l;
+    return l;
+}
+
 __device__ __forceinline__ double2 cmul(double2 a, double2 b)
 {
     return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
@@ -98,39 +105,170 @@ struct PassIo {
     const double2 *zb;     // IN_SPEC: the second series' transform [batch][H] (nullptr: autocorrelation, Zb = Za = `in`)
 };
 
-// grid (H/R/C tiles, batch). in/out [batch][H].
+// ---- steps that more than one kernel takes, each written once ------------------------------------------------------
+
+// The R/2 roots of unity e^{-2 pi i t/R} that a network reads, into LDS (both networks; this lane is `lane` of `lanes`)
+__device__ __forceinline__ void net8_fill_roots(double2 *tw, const TwTab &tt, int logR, int lane, int lanes)
+{
+    for (int t = lane; t < ((1 << logR) >> 1); t += lanes) tw[t] = tw_lookup(tt, (unsigned long long)t, logR);
+}
+
+// The real-spectrum step: xk = X(k), xh = X(H-k) of a real series from zk = Z(k), zh = Z(H-k) of its transform as complex
+// pairs; w = e^{-2 pi i k/L}. E = (zk + conj zh)/2, O = (zk - conj zh)/(2i), X(k) = E + w O, X(H-k) = conj(E - w O).
+__device__ __forceinline__ void half_spectrum(const double2 w, const double2 zk, const double2 zh, double2 &xk, double2 &xh)
+{
+    const double2 E = make_double2(0.5 * (zk.x + zh.x), 0.5 * (zk.y - zh.y));
+    const double2 O = make_double2(0.5 * (zk.y + zh.y), -0.5 * (zk.x - zh.x));
+    const double2 wo = cmul(w, O);
+    xk = make_double2(E.x + wo.x, E.y + wo.y);
+    xh = make_double2(E.x - wo.x, -(E.y - wo.y));
+}
+
+__device__ __forceinline__ double2 mul_conj(double2 a, double2 b)  // a conj(b)
+{
+    return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y);
+}
+
+// The inverse-input step: from sk = S(k), sh = S(H-k) of a Hermitian half spectrum the points wk = W(k), wh = W(H-k) of
+// W = conj Y, the input of the forward transform that stands for the inverse one (Y: the head of this file);
+// w = e^{-2 pi i k/L}. Y(k) = se + i conj(w) sd, Y(H-k) = conj(se) + i w conj(sd). (k = 0 and k = H/2 are their own
+// partners: a caller stores wk alone there.)
+template <bool WK = true, bool WH = true>  // (spec_input asks for one of the two)
+__device__ __forceinline__ void inverse_input_pair(const double2 w, const double2 sk, const double2 sh, double2 &wk, double2 &wh)
+{
+    const double2 se = make_double2(sk.x + sh.x, sk.y - sh.y);  // S(k) + conj S(H-k)
+    const double2 sd = make_double2(sk.x - sh.x, sk.y + sh.y);  // S(k) - conj S(H-k)
+    if (WK) {
+        const double2 t = cmul(make_double2(w.x, -w.y), sd);  // e^{+2 pi i k/L} sd
+        wk = make_double2(se.x - t.y, -(se.y + t.x));
+    }
+    if (WH) {
+        const double2 u = cmul(w, make_double2(sd.x, -sd.y));
+        wh = make_double2(se.x - u.y, -(-se.y + u.x));
+    }
+}
+
+// IN_SPEC: the inverse transform's first pass computes its own input — what xcorr_spectrum_kernel writes in place, W(o) =
+// conj Y(o) from the half spectra of Za, Zb (the zero-padded series' transforms read as complex pairs) — from Z(o) and
+// Z(H - o) of both series, so that the spectrum never makes a round trip through HBM: 32 MB read instead of 16 read +
+// 16 written + 16 read per 10^6-sample series. (Thread k of that kernel owns the points k and H - k; here every point
+// is computed by the lane that loads it.)
+__device__ __forceinline__ double2 spec_input(const double2 *__restrict__ Za, const double2 *__restrict__ Zb, long long o,
+                                              long long H, const TwTab &tt)
+{
+    const long long om = (H - o) & (H - 1);
+    const bool upper = o > om;              // o = H - k with k < H/2: the mirror point of the pair
+    const long long k = upper ? om : o, kk = upper ? o : om;
+    const double2 w = tw_lookup(tt, (unsigned long long)k, tt.logL);  // e^{-2 pi i k/L}
+    double2 ak, ah, bk, bh, wk, wh;
+    half_spectrum(w, Za[k], Za[kk], ak, ah);
+    if (Zb == Za) {
+        bk = ak;
+        bh = ah;
+    } else {
+        half_spectrum(w, Zb[k], Zb[kk], bk, bh);
+    }
+    const double2 sk = mul_conj(ak, bk), sh = mul_conj(ah, bh);
+    if (!upper) {
+        inverse_input_pair<true, false>(w, sk, sh, wk, wh);
+        return wk;
+    }
+    inverse_input_pair<false, true>(w, sk, sh, wk, wh);
+    return wh;
+}
+
+// Where fft_pass_kernel keeps point (row k, column cc) of its R x C tile, and the row that holds output j once its network
+// is done (bit-reversed). Net8Tile answers the same two questions for the radix-8 kernel: pass_load and pass_store, the
+// first and the last stage of a pass, are written against either.
+struct Net4Tile {
+    int logR, logC;
+    __device__ __forceinline__ int pos(int k, int cc) const { return (k << logC) | cc; }  // (cc < C)
+    __device__ __forceinline__ int row(int j) const { return (int)bit_reverse((unsigned)j, logR); }
+};
+
+// First stage of a pass: the tile's points (row k < R, column c0 + cc of the [R][H/R] view of the input) into LDS.
+template <int IN, class Tile>
+__device__ __forceinline__ void pass_load(const Tile &T, double2 *buf, const double2 *in, const PassIo &io, const TwTab &tt,
+                                          long long H, long long c0, int lane, int lanes)
+{
+    const int logR = T.logR, logC = T.logC, R = 1 << logR, C = 1 << logC;
+    const long long cols = H >> logR;
+    const double *x = io.series + (size_t)blockIdx.y * io.n;  // IN_PAD
+    const double2 *za = in + (size_t)blockIdx.y * H;           // IN_SPEC (and the plain input)
+    const double2 *zb = io.zb ? io.zb + (size_t)blockIdx.y * H : za;
+    for (int idx = lane; idx < (R << logC); idx += lanes) {
+        const int k = idx >> logC, cc = idx & (C - 1);
+        const long long c = c0 + cc + (long long)k * cols;
+        double2 v = make_double2(0.0, 0.0);
+        if (IN == IN_PAD) {
+            if (2 * c < io.n) {  // (rows k >= R/2 lie in the zero padding: L >= 2n)
+                v.x = x[2 * c];
+                if (2 * c + 1 < io.n) v.y = x[2 * c + 1];
+            }
+        } else if (IN == IN_SPEC) {
+            v = spec_input(za, zb, c, H, tt);
+        } else {
+            v = za[c];
+        }
+        buf[T.pos(k, cc)] = v;
+    }
+}
+
+// Last stage of a pass (n, s = 2^logS): output j of column c = c0 + cc, times the pass twiddle e^{-2 pi i j p/n}, goes to
+// (c mod s) + s (R p + j), p = c div s: into `out` as it is, conjugated (OUT_CONJ), or as scaled lags (OUT_LAGS).
+template <int OUT, class Tile>
+__device__ __forceinline__ void pass_store(const Tile &T, const double2 *buf, double2 *out, const PassIo &io, const TwTab &tt,
+                                           long long H, long long c0, int logS, long long n, int lane, int lanes)
+{
+    const int logR = T.logR, logC = T.logC, R = 1 << logR, C = 1 << logC;
+    const long long s = 1LL << logS;
+    const bool last = n == R;  // p = 0 for every column: no twiddle
+    const int logn = 63 - __builtin_clzll((unsigned long long)n);
+    // store order: columns fastest when a tile's columns share their p (s >= C: runs of C points), output index
+    // fastest otherwise (first pass, s = 1: the tile's outputs are one contiguous block of R*C points)
+    const bool col_fast = s >= C;
+    out += (size_t)blockIdx.y * H;
+    double *lags = OUT == OUT_LAGS ? io.lags + (size_t)blockIdx.y * io.n_lags : nullptr;
+    for (int idx = lane; idx < (R << logC); idx += lanes) {
+        int cc, j;
+        if (col_fast) {
+            cc = idx & (C - 1);
+            j = idx >> logC;
+        } else {
+            j = idx & (R - 1);
+            cc = idx >> logR;
+        }
+        double2 v = buf[T.pos(T.row(j), cc)];
+        const long long c = c0 + cc;
+        const long long p = c >> logS, q = c & (s - 1);
+        if (!last && j != 0 && p != 0) v = cmul(v, tw_lookup(tt, (unsigned long long)j * (unsigned long long)p, logn));
+        const long long o = q + s * (((long long)p << logR) + j);
+        if (OUT == OUT_LAGS) {
+            const long long t = 2 * o;
+            if (t < io.n_lags) lags[t] = ((v.x / io.L) / (double)(io.n - t)) * io.scale;
+            if (t + 1 < io.n_lags) lags[t + 1] = ((-v.y / io.L) / (double)(io.n - t - 1)) * io.scale;
+        } else {
+            if (OUT == OUT_CONJ) v.y = -v.y;
+            out[o] = v;
+        }
+    }
+}
+
+// grid (H/R/C tiles, batch). in/out [batch][H]. (IN_SPEC and OUT_PERM belong to the radix-8 kernel: launch_pass never
+// starts this one with them, and its instances for them read and write plainly.)
 template <int IN, int OUT>
 __global__ __launch_bounds__(FFT_THREADS) void fft_pass_kernel(const double2 *__restrict__ in,
                                                                double2 *__restrict__ out, long long H, int logR,
                                                                int logC, int logS, long long n, PassIo io, TwTab tt)
 {
-    const long long s = 1LL << logS;
     extern __shared__ double2 lds[];
     const int R = 1 << logR, C = 1 << logC;
+    const Net4Tile T{logR, logC};
     double2 *buf = lds;              // [R][C]
     double2 *tw = lds + (R << logC);  // [R/2]
-    const long long cols = H >> logR;
     const long long c0 = (long long)blockIdx.x << logC;
-    if (IN == IN_PAD) {
-        const double *x = io.series + (size_t)blockIdx.y * io.n;
-        for (int idx = threadIdx.x; idx < (R << logC); idx += FFT_THREADS) {
-            const int k = idx >> logC, cc = idx & (C - 1);
-            const long long e = 2 * (c0 + cc + (long long)k * cols);
-            double2 v = make_double2(0.0, 0.0);
-            if (e < io.n) {  // (rows k >= R/2 lie in the zero padding: L >= 2n)
-                v.x = x[e];
-                if (e + 1 < io.n) v.y = x[e + 1];
-            }
-            buf[idx] = v;
-        }
-    } else {
-        in += (size_t)blockIdx.y * H;
-        for (int idx = threadIdx.x; idx < (R << logC); idx += FFT_THREADS) {
-            const int k = idx >> logC, cc = idx & (C - 1);
-            buf[idx] = in[c0 + cc + (long long)k * cols];
-        }
-    }
-    for (int t = threadIdx.x; t < (R >> 1); t += FFT_THREADS) tw[t] = tw_lookup(tt, (unsigned long long)t, logR);
+    pass_load<IN == IN_SPEC ? IN_PLAIN : IN>(T, buf, in, io, tt, H, c0, threadIdx.x, FFT_THREADS);
+    net8_fill_roots(tw, tt, logR, threadIdx.x, FFT_THREADS);
     __syncthreads();
     // Gentleman-Sande network over the rows, two radix-2 stages per LDS round trip (a radix-4 butterfly in registers:
     // the same operations in the same order as the two stages one after the other, half the LDS traffic and barriers);
@@ -171,37 +309,7 @@ __global__ __launch_bounds__(FFT_THREADS) void fft_pass_kernel(const double2 *__
         }
         __syncthreads();
     }
-    const bool last = n == R;  // p = 0 for every column: no twiddle
-    const int logn = 63 - __builtin_clzll((unsigned long long)n);
-    // store order: columns fastest when a tile's columns share their p (s >= C: runs of C points), output index
-    // fastest otherwise (first pass, s = 1: the tile's outputs are one contiguous block of R*C points)
-    const bool col_fast = s >= C;
-    out += (size_t)blockIdx.y * H;
-    double *lags = OUT == OUT_LAGS ? io.lags + (size_t)blockIdx.y * io.n_lags : nullptr;
-    for (int idx = threadIdx.x; idx < (R << logC); idx += FFT_THREADS) {
-        int cc, j;
-        if (col_fast) {
-            cc = idx & (C - 1);
-            j = idx >> logC;
-        } else {
-            j = idx & (R - 1);
-            cc = idx >> logR;
-        }
-        const int r = (int)bit_reverse((unsigned)j, logR);
-        double2 v = buf[(r << logC) + cc];
-        const long long c = c0 + cc;
-        const long long p = c >> logS, q = c & (s - 1);
-        if (!last && j != 0 && p != 0) v = cmul(v, tw_lookup(tt, (unsigned long long)j * (unsigned long long)p, logn));
-        const long long o = q + s * (((long long)p << logR) + j);
-        if (OUT == OUT_LAGS) {
-            const long long t = 2 * o;
-            if (t < io.n_lags) lags[t] = ((v.x / io.L) / (double)(io.n - t)) * io.scale;
-            if (t + 1 < io.n_lags) lags[t + 1] = ((-v.y / io.L) / (double)(io.n - t - 1)) * io.scale;
-        } else {
-            if (OUT == OUT_CONJ) v.y = -v.y;
-            out[o] = v;
-        }
-    }
+    pass_store<OUT>(T, buf, out, io, tt, H, c0, logS, n, threadIdx.x, FFT_THREADS);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -316,202 +424,144 @@ __device__ __forceinline__ double2 net8_root(const double2 *tw, int m, int half)
     return m & half ? make_double2(-w.x, -w.y) : w;
 }
 
-// IN_SPEC: the inverse transform's first pass computes its own input — what xcorr_spectrum_kernel writes in place, W(o) =
-// conj Y(o) from the half spectra of Za, Zb (the zero-padded series' transforms read as complex pairs) — from Z(o) and
-// Z(H - o) of both series, so that the spectrum never makes a round trip through HBM: 32 MB read instead of 16 read +
-// 16 written + 16 read per 10^6-sample series. Same operations in the same order as that kernel (thread k of it owns
-// the points k and H - k; here every point is computed by the lane that loads it).
-__device__ __forceinline__ double2 spec_input(const double2 *__restrict__ Za, const double2 *__restrict__ Zb, long long o,
-                                              long long H, const TwTab &tt)
+// A radix-8 tile in LDS: point (row k, column cc) at net8_pos — rows C points apart, C points of padding after every final
+// sub-transform of 2^lf rows — net8_points in all, the R/2 roots behind them. The host sizes the launch by the same
+// function (net8_lds_bytes).
+__host__ __device__ constexpr int net8_pos(int k, int cc, int lf, int logC) { return ((k + (k >> lf)) << logC) + cc; }
+__host__ __device__ constexpr int net8_points(int logR, int logC, int lf)
 {
-    const long long om = (H - o) & (H - 1);
-    const bool upper = o > om;              // o = H - k with k < H/2: the mirror point of the pair
-    const long long k = upper ? om : o, kk = upper ? o : om;
-    const double2 w = tw_lookup(tt, (unsigned long long)k, tt.logL);  // e^{-2 pi i k/L}
-    auto half_spectrum = [&](const double2 zk, const double2 zh, double2 &xk, double2 &xh) {
-        const double2 E = make_double2(0.5 * (zk.x + zh.x), 0.5 * (zk.y - zh.y));
-        const double2 O = make_double2(0.5 * (zk.y + zh.y), -0.5 * (zk.x - zh.x));
-        const double2 wo = cmul(w, O);
-        xk = make_double2(E.x + wo.x, E.y + wo.y);
-        xh = make_double2(E.x - wo.x, -(E.y - wo.y));
-    };
-    double2 ak, ah, bk, bh;
-    half_spectrum(Za[k], Za[kk], ak, ah);
-    if (Zb == Za) {
-        bk = ak;
-        bh = ah;
-    } else {
-        half_spectrum(Zb[k], Zb[kk], bk, bh);
-    }
-    const double2 sk = make_double2(ak.x * bk.x + ak.y * bk.y, ak.y * bk.x - ak.x * bk.y);
-    const double2 sh = make_double2(ah.x * bh.x + ah.y * bh.y, ah.y * bh.x - ah.x * bh.y);
-    const double2 se = make_double2(sk.x + sh.x, sk.y - sh.y);
-    const double2 sd = make_double2(sk.x - sh.x, sk.y + sh.y);
-    if (!upper) {
-        const double2 t = cmul(make_double2(w.x, -w.y), sd);
-        return make_double2(se.x - t.y, -(se.y + t.x));
-    }
-    const double2 u = cmul(w, make_double2(sd.x, -sd.y));
-    return make_double2(se.x - u.y, -(-se.y + u.x));
+    return ((1 << logR) << logC) + (((1 << logR) >> lf) << logC);
 }
 
-// grid (H/R/C tiles, batch), R·C/8 lanes (at most 1024). in/out [batch][H]. LDS: (R·C + (R >> lf)·C) points + R/2 roots.
-template <int IN, int OUT>
-__global__ __launch_bounds__(1024) void fft_pass8_kernel(const double2 *__restrict__ in, double2 *__restrict__ out,
-                                                         long long H, int logR, int logC, int logS, long long n,
-                                                         PassIo io, TwTab tt)
+// What Net4Tile is to fft_pass_kernel: where fft_pass8_kernel keeps a point, and the row of output j after its rounds
+struct Net8Tile {
+    int logR, logC;
+    Net8Plan pl;
+    __device__ __forceinline__ int pos(int k, int cc) const { return net8_pos(k, cc, pl.lf, logC); }
+    __device__ __forceinline__ int row(int j) const { return net8_row(j, logR, pl); }
+};
+
+// Tiles narrower than a 128-byte line (C = 4 points) share every line with a neighbour: workgroups are dealt to the
+// XCDs round robin, so the neighbours are given to the SAME XCD, one dispatch round apart (w = 8 m + x -> tile
+// (m & 1) + 2 x + 16 (m >> 1)); dealt in launch order the two halves of a line were fetched by two L2s (FETCH_SIZE
+// twice the algorithmic bytes).
+__device__ __forceinline__ long long net8_tile_of_block()
 {
-    const long long s = 1LL << logS;
-    extern __shared__ double2 lds[];
-    const int R = 1 << logR, C = 1 << logC, NT = blockDim.x;
-    const Net8Plan pl = net8_plan(logR);
-    const int lf = pl.lf;
-    double2 *buf = lds;                                        // point (row k, column cc) at P(k, cc)
-    double2 *tw = lds + (R << logC) + ((R >> lf) << logC);     // [R/2]
-#define NET8_P(k, cc) ((((k) + ((k) >> lf)) << logC) + (cc))
-    const long long cols = H >> logR;
-    // Tiles narrower than a 128-byte line (C = 4 points) share every line with a neighbour: workgroups are dealt to the
-    // XCDs round robin, so the neighbours are given to the SAME XCD, one dispatch round apart (w = 8 m + x -> tile
-    // (m & 1) + 2 x + 16 (m >> 1)); dealt in launch order the two halves of a line were fetched by two L2s (FETCH_SIZE
-    // twice the algorithmic bytes).
     long long tile = blockIdx.x;
     if ((gridDim.x & 15u) == 0u) {
         const unsigned m = blockIdx.x >> 3, xc = blockIdx.x & 7u;
         tile = (long long)((m & 1u) + 2u * xc) + 16LL * (m >> 1);
     }
-    const long long c0 = tile << logC;
-    if (IN == IN_PAD) {
-        const double *x = io.series + (size_t)blockIdx.y * io.n;
-        for (int idx = threadIdx.x; idx < (R << logC); idx += NT) {
-            const int k = idx >> logC, cc = idx & (C - 1);
-            const long long e = 2 * (c0 + cc + (long long)k * cols);
-            double2 v = make_double2(0.0, 0.0);
-            if (e < io.n) {
-                v.x = x[e];
-                if (e + 1 < io.n) v.y = x[e + 1];
-            }
-            buf[NET8_P(k, cc)] = v;
-        }
-    } else if (IN == IN_SPEC) {
-        const double2 *za = in + (size_t)blockIdx.y * H;
-        const double2 *zb = io.zb ? io.zb + (size_t)blockIdx.y * H : za;
-        for (int idx = threadIdx.x; idx < (R << logC); idx += NT) {
-            const int k = idx >> logC, cc = idx & (C - 1);
-            buf[NET8_P(k, cc)] = spec_input(za, zb, c0 + cc + (long long)k * cols, H, tt);
-        }
+    return tile;
+}
+
+// One radix-8 butterfly of a round with twiddles, number b < R C / 8 of the tile, on sub-transforms of length 2^logn: rows
+// i + e 2^(logn-3) of block blk, output digit d times W_len^(i d). TRANSPOSED: the same round of the transposed network,
+// twiddles BEFORE the butterfly.
+template <bool TRANSPOSED>
+__device__ __forceinline__ void net8_butterfly(double2 *buf, const double2 *tw, int b, int logn, int logR, int logC, int lf)
+{
+    const int R = 1 << logR, C = 1 << logC;
+    const int lst = logn - 3;  // log2 of the butterfly stride (rows)
+    const int cc = b & (C - 1), bf = b >> logC;
+    const int i = bf & ((1 << lst) - 1), blk = bf >> lst;
+    const int row0 = (blk << logn) + i;
+    double2 a[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] = buf[net8_pos(row0 + (e << lst), cc, lf, logC)];
+    if (!TRANSPOSED) net_dft8(a);
+    // W_len^(i d) = W_R^(i d R/len): the powers 1, 2, 4 from the table, the others products
+    const int sh = logR - logn;
+    const double2 w1 = net8_root(tw, i << sh, R >> 1), w2 = net8_root(tw, (2 * i) << sh, R >> 1),
+                  w4 = net8_root(tw, (4 * i) << sh, R >> 1);
+    const double2 w3 = cmul(w1, w2), w5 = cmul(w4, w1), w6 = cmul(w4, w2), w7 = cmul(w4, w3);
+    a[1] = cmul(a[1], w1);
+    a[2] = cmul(a[2], w2);
+    a[3] = cmul(a[3], w3);
+    a[4] = cmul(a[4], w4);
+    a[5] = cmul(a[5], w5);
+    a[6] = cmul(a[6], w6);
+    a[7] = cmul(a[7], w7);
+    if (TRANSPOSED) net_dft8(a);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) buf[net8_pos(row0 + (e << lst), cc, lf, logC)] = a[e];
+}
+
+// The last round: a transform of 2^lf consecutive rows per item, without twiddles. net_dft16 leaves frequency f0 + 4 f1
+// at 4 f0 + f1, the smaller ones are in natural order; TRANSPOSED (the last round's transpose, which the inverse network
+// starts with) carries that digit swap on the way in and on the way out and is otherwise the same.
+template <bool TRANSPOSED>
+__device__ __forceinline__ void net8_last_round(double2 *buf, int b, int logC, int lf)
+{
+    const int C = 1 << logC;
+    const int cc = b & (C - 1), row0 = (b >> logC) << lf;
+    if (lf == 4) {
+        double2 x[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) x[e] = buf[net8_pos(row0 + (TRANSPOSED ? 4 * (e & 3) + (e >> 2) : e), cc, lf, logC)];
+        net_dft16(x);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) buf[net8_pos(row0 + e, cc, lf, logC)] = x[TRANSPOSED ? 4 * (e & 3) + (e >> 2) : e];
+    } else if (lf == 3) {
+        double2 x[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] = buf[net8_pos(row0 + e, cc, lf, logC)];
+        net_dft8(x);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) buf[net8_pos(row0 + e, cc, lf, logC)] = x[e];
+    } else if (lf == 2) {
+        double2 y0, y1, y2, y3;
+        net_dft4(buf[net8_pos(row0, cc, lf, logC)], buf[net8_pos(row0 + 1, cc, lf, logC)], buf[net8_pos(row0 + 2, cc, lf, logC)],
+                 buf[net8_pos(row0 + 3, cc, lf, logC)], y0, y1, y2, y3);
+        buf[net8_pos(row0, cc, lf, logC)] = y0;
+        buf[net8_pos(row0 + 1, cc, lf, logC)] = y1;
+        buf[net8_pos(row0 + 2, cc, lf, logC)] = y2;
+        buf[net8_pos(row0 + 3, cc, lf, logC)] = y3;
     } else {
-        in += (size_t)blockIdx.y * H;
-        for (int idx = threadIdx.x; idx < (R << logC); idx += NT) {
-            const int k = idx >> logC, cc = idx & (C - 1);
-            buf[NET8_P(k, cc)] = in[c0 + cc + (long long)k * cols];
-        }
+        const double2 u = buf[net8_pos(row0, cc, lf, logC)], v = buf[net8_pos(row0 + 1, cc, lf, logC)];
+        buf[net8_pos(row0, cc, lf, logC)] = cadd(u, v);
+        buf[net8_pos(row0 + 1, cc, lf, logC)] = csub(u, v);
     }
-    for (int t = threadIdx.x; t < (R >> 1); t += NT) tw[t] = tw_lookup(tt, (unsigned long long)t, logR);
+}
+
+// grid (H/R/C tiles, batch), R·C/8 lanes (at most 1024). in/out [batch][H]. LDS: net8_points + R/2 roots.
+template <int IN, int OUT>
+__global__ __launch_bounds__(1024) void fft_pass8_kernel(const double2 *__restrict__ in, double2 *__restrict__ out,
+                                                         long long H, int logR, int logC, int logS, long long n,
+                                                         PassIo io, TwTab tt)
+{
+    extern __shared__ double2 lds[];
+    const int R = 1 << logR, NT = blockDim.x;
+    const Net8Plan pl = net8_plan(logR);
+    const int lf = pl.lf;
+    double2 *buf = lds, *tw = lds + net8_points(logR, logC, lf);
+    const Net8Tile T{logR, logC, pl};
+    const long long c0 = net8_tile_of_block() << logC;
+    pass_load<IN>(T, buf, in, io, tt, H, c0, threadIdx.x, NT);
+    net8_fill_roots(tw, tt, logR, threadIdx.x, NT);
     __syncthreads();
-    // ---- rounds with twiddles: radix 8 ----
-    int logn = logR;  // log2 of the current sub-transform length
-    for (int q = 0; q < pl.n8; ++q) {
-        const int lst = logn - 3;  // log2 of the butterfly stride (rows)
-        for (int b = threadIdx.x; b < (R >> 3 << logC); b += NT) {
-            const int cc = b & (C - 1), bf = b >> logC;
-            const int i = bf & ((1 << lst) - 1), blk = bf >> lst;
-            const int row0 = (blk << logn) + i;
-            double2 a[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) a[e] = buf[NET8_P(row0 + (e << lst), cc)];
-            net_dft8(a);
-            // output digit d times W_len^(i d) = W_R^(i d R/len): the powers 1, 2, 4 from the table, the others products
-            const int sh = logR - logn;
-            const double2 w1 = net8_root(tw, i << sh, R >> 1), w2 = net8_root(tw, (2 * i) << sh, R >> 1),
-                          w4 = net8_root(tw, (4 * i) << sh, R >> 1);
-            const double2 w3 = cmul(w1, w2), w5 = cmul(w4, w1), w6 = cmul(w4, w2), w7 = cmul(w4, w3);
-            a[1] = cmul(a[1], w1);
-            a[2] = cmul(a[2], w2);
-            a[3] = cmul(a[3], w3);
-            a[4] = cmul(a[4], w4);
-            a[5] = cmul(a[5], w5);
-            a[6] = cmul(a[6], w6);
-            a[7] = cmul(a[7], w7);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) buf[NET8_P(row0 + (e << lst), cc)] = a[e];
-        }
+    for (int q = 0, logn = logR; q < pl.n8; ++q, logn -= 3) {  // logn: log2 of the current sub-transform length
+        for (int b = threadIdx.x; b < (R >> 3 << logC); b += NT) net8_butterfly<false>(buf, tw, b, logn, logR, logC, lf);
         __syncthreads();
-        logn -= 3;
     }
-    // ---- last round: 2^lf consecutive rows per lane, no twiddles ----
-    for (int b = threadIdx.x; b < (R >> lf << logC); b += NT) {
-        const int cc = b & (C - 1), row0 = (b >> logC) << lf;
-        if (lf == 4) {
-            double2 x[16];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) x[e] = buf[NET8_P(row0 + e, cc)];
-            net_dft16(x);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) buf[NET8_P(row0 + e, cc)] = x[e];
-        } else if (lf == 3) {
-            double2 x[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = buf[NET8_P(row0 + e, cc)];
-            net_dft8(x);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) buf[NET8_P(row0 + e, cc)] = x[e];
-        } else if (lf == 2) {
-            double2 y0, y1, y2, y3;
-            net_dft4(buf[NET8_P(row0, cc)], buf[NET8_P(row0 + 1, cc)], buf[NET8_P(row0 + 2, cc)], buf[NET8_P(row0 + 3, cc)],
-                     y0, y1, y2, y3);
-            buf[NET8_P(row0, cc)] = y0;
-            buf[NET8_P(row0 + 1, cc)] = y1;
-            buf[NET8_P(row0 + 2, cc)] = y2;
-            buf[NET8_P(row0 + 3, cc)] = y3;
-        } else {
-            const double2 u = buf[NET8_P(row0, cc)], v = buf[NET8_P(row0 + 1, cc)];
-            buf[NET8_P(row0, cc)] = cadd(u, v);
-            buf[NET8_P(row0 + 1, cc)] = csub(u, v);
-        }
-    }
+    for (int b = threadIdx.x; b < (R >> lf << logC); b += NT) net8_last_round<false>(buf, b, logC, lf);
     __syncthreads();
-    const bool last = n == R;  // p = 0 for every column: no twiddle
-    const int logn_p = 63 - __builtin_clzll((unsigned long long)n);
-    const bool col_fast = s >= C;
-    out += (size_t)blockIdx.y * H;
-    double *lags = OUT == OUT_LAGS ? io.lags + (size_t)blockIdx.y * io.n_lags : nullptr;
     if (OUT == OUT_PERM) {
         // (s = 1, the host's condition: a column's R outputs are one run of R points; lanes walk its POSITIONS)
+        const bool last = n == R;
+        const int logn = 63 - __builtin_clzll((unsigned long long)n);
+        out += (size_t)blockIdx.y * H;
         for (int idx = threadIdx.x; idx < (R << logC); idx += NT) {
             const int x = idx & (R - 1), cc = idx >> logR;
             const int j = pair_logical(x, R);
-            double2 v = buf[NET8_P(net8_row(j, logR, pl), cc)];
+            double2 v = buf[T.pos(T.row(j), cc)];
             const long long c = c0 + cc;
-            if (!last && j != 0 && c != 0) v = cmul(v, tw_lookup(tt, (unsigned long long)j * (unsigned long long)c, logn_p));
+            if (!last && j != 0 && c != 0) v = cmul(v, tw_lookup(tt, (unsigned long long)j * (unsigned long long)c, logn));
             (out + (c << logR))[x] = v;
         }
         return;
     }
-    for (int idx = threadIdx.x; idx < (R << logC); idx += NT) {
-        int cc, j;
-        if (col_fast) {
-            cc = idx & (C - 1);
-            j = idx >> logC;
-        } else {
-            j = idx & (R - 1);
-            cc = idx >> logR;
-        }
-        const int r = net8_row(j, logR, pl);
-        double2 v = buf[NET8_P(r, cc)];
-        const long long c = c0 + cc;
-        const long long p = c >> logS, q = c & (s - 1);
-        if (!last && j != 0 && p != 0) v = cmul(v, tw_lookup(tt, (unsigned long long)j * (unsigned long long)p, logn_p));
-        const long long o = q + s * (((long long)p << logR) + j);
-        if (OUT == OUT_LAGS) {
-            const long long t = 2 * o;
-            if (t < io.n_lags) lags[t] = ((v.x / io.L) / (double)(io.n - t)) * io.scale;
-            if (t + 1 < io.n_lags) lags[t + 1] = ((-v.y / io.L) / (double)(io.n - t - 1)) * io.scale;
-        } else {
-            if (OUT == OUT_CONJ) v.y = -v.y;
-            out[o] = v;
-        }
-    }
-#undef NET8_P
+    pass_store<OUT>(T, buf, out, io, tt, H, c0, logS, n, threadIdx.x, NT);
 }
 
 // Round 5: the middle of a TWO-pass autocorrelation in one launch — the forward transform's second pass, the spectrum
@@ -520,7 +570,7 @@ __global__ __launch_bounds__(1024) void fft_pass8_kernel(const double2 *__restri
 // H = Ra Rb. The first pass (radix Ra, OUT_PERM) left in[Ra r + pair_phys(j)] = output j of column r; this kernel's
 // tile is C neighbouring positions x of every row r < Rb: the columns c = pair_logical(x) of the second pass, whose
 // outputs are the frequencies k = c + Ra j. H - k = (Ra - c) + Ra (Rb - 1 - j) (c > 0) lies in the column next door,
-// Ra (Rb - j) (c = 0) in the same one: the spectrum step (xcorr_spectrum_kernel's operations, SAME) works in place on
+// Ra (Rb - j) (c = 0) in the same one: the spectrum step (as xcorr_spectrum_kernel<true>) works in place on
 // the tile, each pair by the lane that owns its lower frequency. The forward network (decimation in frequency, as
 // fft_pass8_kernel) leaves frequency j in row net8_row(j); the inverse runs the TRANSPOSED network — the rounds in
 // reverse order, twiddles before the butterflies — which takes exactly that order and ends in natural order (F = P A
@@ -534,89 +584,24 @@ __global__ __launch_bounds__(1024) void fft_mid_acf_kernel(const double2 *__rest
     const int R = 1 << logR, C = 1 << logC, NT = blockDim.x, Ra = 1 << logRa;
     const Net8Plan pl = net8_plan(logR);
     const int lf = pl.lf;
-    double2 *buf = lds;
-    double2 *tw = lds + (R << logC) + ((R >> lf) << logC);
-#define NET8_P(k, cc) ((((k) + ((k) >> lf)) << logC) + (cc))
-    long long tile = blockIdx.x;
-    if ((gridDim.x & 15u) == 0u) {  // (half-line tiles: the two halves of a line to the same XCD, as fft_pass8_kernel)
-        const unsigned m = blockIdx.x >> 3, xc = blockIdx.x & 7u;
-        tile = (long long)((m & 1u) + 2u * xc) + 16LL * (m >> 1);
-    }
-    const int x0 = (int)(tile << logC);
+    double2 *buf = lds, *tw = lds + net8_points(logR, logC, lf);
+    const int x0 = (int)(net8_tile_of_block() << logC);
     in += (size_t)blockIdx.y * H;
     out += (size_t)blockIdx.y * H;
     for (int idx = threadIdx.x; idx < (R << logC); idx += NT) {
         const int k = idx >> logC, cc = idx & (C - 1);
-        buf[NET8_P(k, cc)] = in[x0 + cc + (long long)k * Ra];
+        buf[net8_pos(k, cc, lf, logC)] = in[x0 + cc + (long long)k * Ra];
     }
-    for (int t = threadIdx.x; t < (R >> 1); t += NT) tw[t] = tw_lookup(tt, (unsigned long long)t, logR);
+    net8_fill_roots(tw, tt, logR, threadIdx.x, NT);
     __syncthreads();
-    // ---- forward: radix-8 rounds with twiddles, then the last round (fft_pass8_kernel) ----
-    int logn = logR;
-    for (int q = 0; q < pl.n8; ++q) {
-        const int lst = logn - 3;
-        for (int b = threadIdx.x; b < (R >> 3 << logC); b += NT) {
-            const int cc = b & (C - 1), bf = b >> logC;
-            const int i = bf & ((1 << lst) - 1), blk = bf >> lst;
-            const int row0 = (blk << logn) + i;
-            double2 a[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) a[e] = buf[NET8_P(row0 + (e << lst), cc)];
-            net_dft8(a);
-            const int sh = logR - logn;
-            const double2 w1 = net8_root(tw, i << sh, R >> 1), w2 = net8_root(tw, (2 * i) << sh, R >> 1),
-                          w4 = net8_root(tw, (4 * i) << sh, R >> 1);
-            const double2 w3 = cmul(w1, w2), w5 = cmul(w4, w1), w6 = cmul(w4, w2), w7 = cmul(w4, w3);
-            a[1] = cmul(a[1], w1);
-            a[2] = cmul(a[2], w2);
-            a[3] = cmul(a[3], w3);
-            a[4] = cmul(a[4], w4);
-            a[5] = cmul(a[5], w5);
-            a[6] = cmul(a[6], w6);
-            a[7] = cmul(a[7], w7);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) buf[NET8_P(row0 + (e << lst), cc)] = a[e];
-        }
+    // ---- forward: the network of fft_pass8_kernel ----
+    for (int q = 0, logn = logR; q < pl.n8; ++q, logn -= 3) {
+        for (int b = threadIdx.x; b < (R >> 3 << logC); b += NT) net8_butterfly<false>(buf, tw, b, logn, logR, logC, lf);
         __syncthreads();
-        logn -= 3;
     }
-    // the last round and its transpose: net_dft16 leaves frequency f0 + 4 f1 at 4 f0 + f1 (sg16: that digit swap), the
-    // smaller ones are in natural order. PRE: the rows are permuted on the way in, POST: on the way out.
-    auto last_round = [&](bool transposed) {
-        for (int b = threadIdx.x; b < (R >> lf << logC); b += NT) {
-            const int cc = b & (C - 1), row0 = (b >> logC) << lf;
-            if (lf == 4) {
-                double2 x[16];
-#pragma unroll
-                for (int e = 0; e < 16; ++e) x[e] = buf[NET8_P(row0 + (transposed ? 4 * (e & 3) + (e >> 2) : e), cc)];
-                net_dft16(x);
-#pragma unroll
-                for (int e = 0; e < 16; ++e) buf[NET8_P(row0 + e, cc)] = x[transposed ? 4 * (e & 3) + (e >> 2) : e];
-            } else if (lf == 3) {
-                double2 x[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) x[e] = buf[NET8_P(row0 + e, cc)];
-                net_dft8(x);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) buf[NET8_P(row0 + e, cc)] = x[e];
-            } else if (lf == 2) {
-                double2 y0, y1, y2, y3;
-                net_dft4(buf[NET8_P(row0, cc)], buf[NET8_P(row0 + 1, cc)], buf[NET8_P(row0 + 2, cc)], buf[NET8_P(row0 + 3, cc)],
-                         y0, y1, y2, y3);
-                buf[NET8_P(row0, cc)] = y0;
-                buf[NET8_P(row0 + 1, cc)] = y1;
-                buf[NET8_P(row0 + 2, cc)] = y2;
-                buf[NET8_P(row0 + 3, cc)] = y3;
-            } else {
-                const double2 u = buf[NET8_P(row0, cc)], v = buf[NET8_P(row0 + 1, cc)];
-                buf[NET8_P(row0, cc)] = cadd(u, v);
-                buf[NET8_P(row0 + 1, cc)] = csub(u, v);
-            }
-        }
-    };
-    last_round(false);
+    for (int b = threadIdx.x; b < (R >> lf << logC); b += NT) net8_last_round<false>(buf, b, logC, lf);
     __syncthreads();
-    // ---- spectrum step, in place (xcorr_spectrum_kernel<true>, pair by pair) ----
+    // ---- spectrum step, in place (what xcorr_spectrum_kernel<true> does, pair by pair) ----
     // (k = c + Ra j <= H / 2 exactly for j < Rb / 2, whatever the column — and for the one point H / 2 itself, c = 0,
     // j = Rb / 2, which rides as one more item of the tile that holds column 0: every item is a pair to do)
     const int n_items = (R >> 1 << logC) + (x0 == 0 ? 1 : 0);
@@ -627,67 +612,32 @@ __global__ __launch_bounds__(1024) void fft_mid_acf_kernel(const double2 *__rest
         const long long k = (long long)c + (long long)Ra * j;
         const int ccp = (x < 2 ? x : x ^ 1) - x0;
         const int jp = c == 0 ? (R - j) & (R - 1) : R - 1 - j;
-        const int pos = NET8_P(net8_row(j, logR, pl), cc), posp = NET8_P(net8_row(jp, logR, pl), ccp);
+        const int pos = net8_pos(net8_row(j, logR, pl), cc, lf, logC), posp = net8_pos(net8_row(jp, logR, pl), ccp, lf, logC);
         const double2 zk = buf[pos], zh = buf[posp];
         const double2 w = tw_lookup(tt, (unsigned long long)k, tt.logL);  // e^{-2 pi i k/L}
-        const double2 E = make_double2(0.5 * (zk.x + zh.x), 0.5 * (zk.y - zh.y));
-        const double2 O = make_double2(0.5 * (zk.y + zh.y), -0.5 * (zk.x - zh.x));
-        const double2 wo = cmul(w, O);
-        const double2 ak = make_double2(E.x + wo.x, E.y + wo.y);     // X(k)
-        const double2 ah = make_double2(E.x - wo.x, -(E.y - wo.y));  // X(H-k)
-        const double2 sk = make_double2(ak.x * ak.x + ak.y * ak.y, ak.y * ak.x - ak.x * ak.y);  // A conj(A), as mul_conj
-        const double2 sh = make_double2(ah.x * ah.x + ah.y * ah.y, ah.y * ah.x - ah.x * ah.y);
-        const double2 se = make_double2(sk.x + sh.x, sk.y - sh.y);
-        const double2 sd = make_double2(sk.x - sh.x, sk.y + sh.y);
-        const double2 t = cmul(make_double2(w.x, -w.y), sd);
-        buf[pos] = make_double2(se.x - t.y, -(se.y + t.x));
-        if (k != 0 && 2 * k != H) {
-            const double2 u = cmul(w, make_double2(sd.x, -sd.y));
-            buf[posp] = make_double2(se.x - u.y, -(-se.y + u.x));
-        }
+        double2 ak, ah, wk, wh;
+        half_spectrum(w, zk, zh, ak, ah);
+        inverse_input_pair(w, mul_conj(ak, ak), mul_conj(ah, ah), wk, wh);
+        buf[pos] = wk;
+        if (k != 0 && 2 * k != H) buf[posp] = wh;
     }
     __syncthreads();
-    // ---- inverse: the transposed network — last round first, then the radix-8 rounds, twiddles BEFORE the butterflies ----
-    last_round(true);
+    // ---- inverse: the transposed network — last round first, then the radix-8 rounds in reverse order ----
+    for (int b = threadIdx.x; b < (R >> lf << logC); b += NT) net8_last_round<true>(buf, b, logC, lf);
     __syncthreads();
     for (int q = pl.n8 - 1; q >= 0; --q) {
-        logn = logR - 3 * q;
-        const int lst = logn - 3;
-        for (int b = threadIdx.x; b < (R >> 3 << logC); b += NT) {
-            const int cc = b & (C - 1), bf = b >> logC;
-            const int i = bf & ((1 << lst) - 1), blk = bf >> lst;
-            const int row0 = (blk << logn) + i;
-            double2 a[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) a[e] = buf[NET8_P(row0 + (e << lst), cc)];
-            const int sh = logR - logn;
-            const double2 w1 = net8_root(tw, i << sh, R >> 1), w2 = net8_root(tw, (2 * i) << sh, R >> 1),
-                          w4 = net8_root(tw, (4 * i) << sh, R >> 1);
-            const double2 w3 = cmul(w1, w2), w5 = cmul(w4, w1), w6 = cmul(w4, w2), w7 = cmul(w4, w3);
-            a[1] = cmul(a[1], w1);
-            a[2] = cmul(a[2], w2);
-            a[3] = cmul(a[3], w3);
-            a[4] = cmul(a[4], w4);
-            a[5] = cmul(a[5], w5);
-            a[6] = cmul(a[6], w6);
-            a[7] = cmul(a[7], w7);
-            net_dft8(a);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) buf[NET8_P(row0 + (e << lst), cc)] = a[e];
-        }
+        for (int b = threadIdx.x; b < (R >> 3 << logC); b += NT) net8_butterfly<true>(buf, tw, b, logR - 3 * q, logR, logC, lf);
         __syncthreads();
     }
     // ---- the inverse's first pass ends: twiddle e^{-2 pi i j c / H}, a column's outputs one run of Rb points ----
-    int logH = 0;
-    while ((1LL << logH) < H) ++logH;
+    const int logH = ilog2(H);
     for (int idx = threadIdx.x; idx < (R << logC); idx += NT) {
         const int j = idx & (R - 1), cc = idx >> logR;
         const int c = pair_logical(x0 + cc, Ra);
-        double2 v = buf[NET8_P(j, cc)];
+        double2 v = buf[net8_pos(j, cc, lf, logC)];
         if (j != 0 && c != 0) v = cmul(v, tw_lookup(tt, (unsigned long long)j * (unsigned long long)c, logH));
         (out + ((long long)c << logR))[j] = v;
     }
-#undef NET8_P
 }
 
 // spec[b][k], k = 0..H, from Z = FFT_H of the reals read as complex pairs. grid (ceil((H/2+1)/256), batch)
@@ -698,19 +648,16 @@ __global__ void r2c_post_kernel(const double2 *__restrict__ Z, double2 *__restri
     Z += (size_t)blockIdx.y * H;
     spec += (size_t)blockIdx.y * (H + 1);
     const long long kk = (H - k) & (H - 1);
-    const double2 zk = Z[k], zh = Z[kk];
-    const double2 E = make_double2(0.5 * (zk.x + zh.x), 0.5 * (zk.y - zh.y));
-    const double2 O = make_double2(0.5 * (zk.y + zh.y), -0.5 * (zk.x - zh.x));  // (zk - conj zh) / (2i)
-    const double2 w = tw_lookup(tt, (unsigned long long)k, tt.logL);
-    const double2 wo = cmul(w, O);
-    spec[k] = make_double2(E.x + wo.x, E.y + wo.y);
-    spec[H - k] = make_double2(E.x - wo.x, -(E.y - wo.y));  // X(H-k) = conj(E - w O); k = 0 -> X(H)
+    double2 xk, xh;
+    half_spectrum(tw_lookup(tt, (unsigned long long)k, tt.logL), Z[k], Z[kk], xk, xh);
+    spec[k] = xk;
+    spec[H - k] = xh;  // (k = 0 -> X(H))
 }
 
 // r2c_post_kernel and the column sums of |X_k|^2 in one pass over Z (round 6: the full-lag MSD of series too long for the
 // fused kernels wrote the half spectra only to read them once): partial[split][k], k = 0..H, = the sum over the split's
-// rows of |X_row(k)|^2, X from Z exactly as r2c_post_kernel makes it (the same operations in the same order, the rows
-// added alternately into two sums as power_rows_kernel of msd_fft.hip did: bit-identical results).
+// rows of |X_row(k)|^2, X from Z by half_spectrum as r2c_post_kernel makes it, the rows added alternately into two sums
+// as power_rows_kernel of msd_fft.hip did: bit-identical results.
 // grid (ceil((H/2+1)/256), splits); rows [row0, row1) of Z [.][H].
 __global__ __launch_bounds__(256) void r2c_power_rows_kernel(const double2 *__restrict__ Z, long long H, long long row0,
                                                              long long row1, double *__restrict__ partial, TwTab tt)
@@ -723,12 +670,8 @@ __global__ __launch_bounds__(256) void r2c_power_rows_kernel(const double2 *__re
     const double2 w = tw_lookup(tt, (unsigned long long)k, tt.logL);
     double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;  // |X_k|^2 and |X_(H-k)|^2, even / odd rows
     for (long long q = ra; q < rb; ++q) {
-        const double2 zk = Z[(size_t)q * H + k], zh = Z[(size_t)q * H + kk];
-        const double2 E = make_double2(0.5 * (zk.x + zh.x), 0.5 * (zk.y - zh.y));
-        const double2 O = make_double2(0.5 * (zk.y + zh.y), -0.5 * (zk.x - zh.x));
-        const double2 wo = cmul(w, O);
-        const double2 xk = make_double2(E.x + wo.x, E.y + wo.y);
-        const double2 xh = make_double2(E.x - wo.x, -(E.y - wo.y));
+        double2 xk, xh;
+        half_spectrum(w, Z[(size_t)q * H + k], Z[(size_t)q * H + kk], xk, xh);
         const double pk = xk.x * xk.x + xk.y * xk.y, ph = xh.x * xh.x + xh.y * xh.y;
         if ((q - ra) & 1) {
             a1 += pk;
@@ -762,18 +705,11 @@ __global__ __launch_bounds__(((1 << logR) << logC) >> 3, 3) void fft_power_pass_
     const int Ra = 1 << logRa;
     constexpr Net8Plan pl = net8_plan(logR);
     constexpr int lf = pl.lf;
-    double2 *buf = lds;
-    double2 *tw = lds + (R << logC) + ((R >> lf) << logC);
-#define NET8_P(k, cc) ((((k) + ((k) >> lf)) << logC) + (cc))
-    long long tile = blockIdx.x;
-    if ((gridDim.x & 15u) == 0u) {  // (half-line tiles: the two halves of a line to the same XCD, as fft_pass8_kernel)
-        const unsigned m = blockIdx.x >> 3, xc = blockIdx.x & 7u;
-        tile = (long long)((m & 1u) + 2u * xc) + 16LL * (m >> 1);
-    }
-    const int x0 = (int)(tile << logC);
+    double2 *buf = lds, *tw = lds + net8_points(logR, logC, lf);
+    const int x0 = (int)(net8_tile_of_block() << logC);
     const long long n_rows = row1 - row0;
     const long long ra = row0 + n_rows * blockIdx.y / gridDim.y, rb = row0 + n_rows * (blockIdx.y + 1) / gridDim.y;
-    for (int t = threadIdx.x; t < (R >> 1); t += NT) tw[t] = tw_lookup(tt, (unsigned long long)t, logR);
+    net8_fill_roots(tw, tt, logR, threadIdx.x, NT);
     // This lane's four pairs (item idx = lane + i NT < R/2 * C: column cc = idx mod C, output j = idx div C < R/2) and, for
     // lane 0 of the tile that holds column 0, the point H/2 (c = 0, j = R/2: its own partner). The sums are the BILINEAR ones
     // of the fused kernels (msd_fft.hip, msd_power_lds2_kernel): S = |Z_k|^2, S' = |Z_(H-k)|^2, T = Im(Z_k Z_(H-k)) per series —
@@ -788,17 +724,18 @@ __global__ __launch_bounds__(((1 << logR) << logC) >> 3, 3) void fft_power_pass_
         const int x = x0 + cc, c = pair_logical(x, Ra);
         const int ccp = (x < 2 ? x : x ^ 1) - x0;
         const int jp = c == 0 ? (R - j) & (R - 1) : R - 1 - j;
-        pos[i] = NET8_P(net8_row(j, logR, pl), cc);
-        posp[i] = NET8_P(net8_row(jp, logR, pl), ccp);
+        pos[i] = net8_pos(net8_row(j, logR, pl), cc, lf, logC);
+        posp[i] = net8_pos(net8_row(jp, logR, pl), ccp, lf, logC);
         sk[i] = sh[i] = tk[i] = 0.0;
     }
     const bool has_mid = x0 == 0 && threadIdx.x == 0;
-    const int pos_mid = NET8_P(net8_row(R >> 1, logR, pl), 0);
+    const int pos_mid = net8_pos(net8_row(R >> 1, logR, pl), 0, lf, logC);
     double s_mid = 0.0;
     double2 v[8];
     // (`lane` = threadIdx.x through an opaque copy made inside the series loop: every address, LDS position and twiddle of
     // the transform is the same for all series, and hoisted out of the loop they would fill the register budget — 100+
-    // spilled registers; recomputed per series they are a few integer operations)
+    // spilled registers; recomputed per series they are a few integer operations. The network helpers take `lane` for
+    // that reason and never read threadIdx.x themselves.)
     auto fetch = [&](long long q, int lane) {
         const double2 *row = in + (size_t)q * H + x0;
 #pragma unroll
@@ -817,68 +754,14 @@ __global__ __launch_bounds__(((1 << logR) << logC) >> 3, 3) void fft_power_pass_
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int idx = lane + i * NT;
-            buf[NET8_P(idx >> logC, idx & (C - 1))] = v[i];
+            buf[net8_pos(idx >> logC, idx & (C - 1), lf, logC)] = v[i];
         }
         __syncthreads();
-        int logn = logR;
-        for (int r8 = 0; r8 < pl.n8; ++r8) {
-            const int lst = logn - 3;
-            {  // (R/8 * C butterflies = NT: one per lane)
-                const int b = lane;
-                const int cc = b & (C - 1), bf = b >> logC;
-                const int i = bf & ((1 << lst) - 1), blk = bf >> lst;
-                const int rw0 = (blk << logn) + i;
-                double2 a[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) a[e] = buf[NET8_P(rw0 + (e << lst), cc)];
-                net_dft8(a);
-                const int sft = logR - logn;
-                const double2 w1 = net8_root(tw, i << sft, R >> 1), w2 = net8_root(tw, (2 * i) << sft, R >> 1),
-                              w4 = net8_root(tw, (4 * i) << sft, R >> 1);
-                const double2 w3 = cmul(w1, w2), w5 = cmul(w4, w1), w6 = cmul(w4, w2), w7 = cmul(w4, w3);
-                a[1] = cmul(a[1], w1);
-                a[2] = cmul(a[2], w2);
-                a[3] = cmul(a[3], w3);
-                a[4] = cmul(a[4], w4);
-                a[5] = cmul(a[5], w5);
-                a[6] = cmul(a[6], w6);
-                a[7] = cmul(a[7], w7);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) buf[NET8_P(rw0 + (e << lst), cc)] = a[e];
-            }
+        for (int r8 = 0, logn = logR; r8 < pl.n8; ++r8, logn -= 3) {
+            net8_butterfly<false>(buf, tw, lane, logn, logR, logC, lf);  // (R/8 * C butterflies = NT: one per lane)
             __syncthreads();
-            logn -= 3;
         }
-        for (int b = lane; b < (R >> lf << logC); b += NT) {
-            const int cc = b & (C - 1), rw0 = (b >> logC) << lf;
-            if (lf == 4) {
-                double2 x[16];
-#pragma unroll
-                for (int e = 0; e < 16; ++e) x[e] = buf[NET8_P(rw0 + e, cc)];
-                net_dft16(x);
-#pragma unroll
-                for (int e = 0; e < 16; ++e) buf[NET8_P(rw0 + e, cc)] = x[e];
-            } else if (lf == 3) {
-                double2 x[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) x[e] = buf[NET8_P(rw0 + e, cc)];
-                net_dft8(x);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) buf[NET8_P(rw0 + e, cc)] = x[e];
-            } else if (lf == 2) {
-                double2 y0, y1, y2, y3;
-                net_dft4(buf[NET8_P(rw0, cc)], buf[NET8_P(rw0 + 1, cc)], buf[NET8_P(rw0 + 2, cc)], buf[NET8_P(rw0 + 3, cc)],
-                         y0, y1, y2, y3);
-                buf[NET8_P(rw0, cc)] = y0;
-                buf[NET8_P(rw0 + 1, cc)] = y1;
-                buf[NET8_P(rw0 + 2, cc)] = y2;
-                buf[NET8_P(rw0 + 3, cc)] = y3;
-            } else {
-                const double2 u = buf[NET8_P(rw0, cc)], w = buf[NET8_P(rw0 + 1, cc)];
-                buf[NET8_P(rw0, cc)] = cadd(u, w);
-                buf[NET8_P(rw0 + 1, cc)] = csub(u, w);
-            }
-        }
+        for (int b = lane; b < (R >> lf << logC); b += NT) net8_last_round<false>(buf, b, logC, lf);
         __syncthreads();
         if (q + 1 < rb) fetch(q + 1, lane);  // (the next series' tile lands under the sums and the barrier)
 #pragma unroll
@@ -914,7 +797,6 @@ __global__ __launch_bounds__(((1 << logR) << logC) >> 3, 3) void fft_power_pass_
         }
     }
     if (has_mid) p[H >> 1] = s_mid;  // X_(H/2) = conj Z_(H/2)
-#undef NET8_P
 }
 
 // W = conj Y (the input of the forward transform that stands for the inverse one) from the Hermitian half spectrum
@@ -926,22 +808,14 @@ __global__ void c2r_pre_kernel(const double2 *__restrict__ S, double2 *__restric
     S += (size_t)blockIdx.y * (H + 1);
     W += (size_t)blockIdx.y * H;
     const double2 sk = S[k], sh = S[H - k];
-    const double2 w = tw_lookup(tt, (unsigned long long)k, tt.logL);  // e^{-2 pi i k/L}
-    const double2 se = make_double2(sk.x + sh.x, sk.y - sh.y);       // S(k) + conj S(H-k)
-    const double2 sd = make_double2(sk.x - sh.x, sk.y + sh.y);       // S(k) - conj S(H-k)
-    const double2 t = cmul(make_double2(w.x, -w.y), sd);             // e^{+2 pi i k/L} sd
-    const double2 yk = make_double2(se.x - t.y, se.y + t.x);         // se + i t
-    W[k] = make_double2(yk.x, -yk.y);
-    if (k != 0 && 2 * k != H) {
-        // Y(H-k) = conj(se) - i w (S(H-k) - conj S(k)) = conj(se) + i w conj(sd)
-        const double2 u = cmul(w, make_double2(sd.x, -sd.y));
-        const double2 yh = make_double2(se.x - u.y, -se.y + u.x);
-        W[H - k] = make_double2(yh.x, -yh.y);
-    }
+    double2 wk, wh;
+    inverse_input_pair(tw_lookup(tt, (unsigned long long)k, tt.logL), sk, sh, wk, wh);
+    W[k] = wk;
+    if (k != 0 && 2 * k != H) W[H - k] = wh;
 }
 
 // The correlation pipeline's one pointwise step, in place: Za, Zb = FFT_H of the two zero-padded series read as
-// complex pairs  ->  half spectra A, B (as r2c_post_kernel)  ->  S = A conj(B)  ->  W = conj Y (as c2r_pre_kernel),
+// complex pairs  ->  half spectra A, B (half_spectrum)  ->  S = A conj(B)  ->  W = conj Y (inverse_input_pair),
 // written over Za (thread k owns the points k and H-k of both inputs and of the output). SAME: Zb is Za.
 template <bool SAME>
 __global__ void xcorr_spectrum_kernel(double2 *__restrict__ Za, const double2 *__restrict__ Zb, long long H, TwTab tt)
@@ -952,31 +826,17 @@ __global__ void xcorr_spectrum_kernel(double2 *__restrict__ Za, const double2 *_
     Zb += (size_t)blockIdx.y * H;
     const long long kk = (H - k) & (H - 1);
     const double2 w = tw_lookup(tt, (unsigned long long)k, tt.logL);  // e^{-2 pi i k/L}
-    auto half_spectrum = [&](const double2 zk, const double2 zh, double2 &xk, double2 &xh) {
-        const double2 E = make_double2(0.5 * (zk.x + zh.x), 0.5 * (zk.y - zh.y));
-        const double2 O = make_double2(0.5 * (zk.y + zh.y), -0.5 * (zk.x - zh.x));
-        const double2 wo = cmul(w, O);
-        xk = make_double2(E.x + wo.x, E.y + wo.y);     // X(k)
-        xh = make_double2(E.x - wo.x, -(E.y - wo.y));  // X(H-k)
-    };
-    double2 ak, ah, bk, bh;
-    half_spectrum(Za[k], Za[kk], ak, ah);
+    double2 ak, ah, bk, bh, wk, wh;
+    half_spectrum(w, Za[k], Za[kk], ak, ah);
     if (SAME) {
         bk = ak;
         bh = ah;
     } else {
-        half_spectrum(Zb[k], Zb[kk], bk, bh);
+        half_spectrum(w, Zb[k], Zb[kk], bk, bh);
     }
-    const double2 sk = make_double2(ak.x * bk.x + ak.y * bk.y, ak.y * bk.x - ak.x * bk.y);  // A conj(B), as mul_conj
-    const double2 sh = make_double2(ah.x * bh.x + ah.y * bh.y, ah.y * bh.x - ah.x * bh.y);
-    const double2 se = make_double2(sk.x + sh.x, sk.y - sh.y);
-    const double2 sd = make_double2(sk.x - sh.x, sk.y + sh.y);
-    const double2 t = cmul(make_double2(w.x, -w.y), sd);
-    Za[k] = make_double2(se.x - t.y, -(se.y + t.x));
-    if (k != 0 && 2 * k != H) {
-        const double2 u = cmul(w, make_double2(sd.x, -sd.y));
-        Za[kk] = make_double2(se.x - u.y, -(-se.y + u.x));
-    }
+    inverse_input_pair(w, mul_conj(ak, bk), mul_conj(ah, bh), wk, wh);
+    Za[k] = wk;
+    if (k != 0 && 2 * k != H) Za[kk] = wh;
 }
 
 __global__ void conj_copy_kernel(const double2 *__restrict__ in, double2 *__restrict__ out, long long count)
@@ -989,8 +849,7 @@ __global__ void conj_copy_kernel(const double2 *__restrict__ in, double2 *__rest
 bool fft_twiddle_table(mdhip_ctx *ctx, long long H, TwTab &tt)
 {
     const long long L = 2 * H;
-    int logL = 0;
-    while ((1LL << logL) < L) ++logL;
+    const int logL = ilog2(L);
     const long long nA = L > 1024 ? L >> 10 : 1, nB = L > 1024 ? 1024 : L;
     double2 *tab = (double2 *)mdhip_ws(ctx, WS_FFT_TW, (size_t)(nA + nB) * sizeof(double2));
     if (!tab) return false;
@@ -1014,8 +873,7 @@ struct PassPlan {
 
 PassPlan plan_passes(const mdhip_ctx *ctx, long long H, int batch)
 {
-    int logH = 0;
-    while ((1LL << logH) < H) ++logH;
+    const int logH = ilog2(H);
     int max_logr = std::min(std::max(ctx->opt_fft_logr, 4), FFT_MAX_LOGR);
     // a one-column tile of the radix (R + R/2 complex points) must fit the CU's LDS
     while (max_logr > 4 && ((size_t)24 << max_logr) > ctx->lds_max) --max_logr;
@@ -1039,22 +897,52 @@ PassPlan plan_passes(const mdhip_ctx *ctx, long long H, int batch)
     return p;
 }
 
+// A radix-8 tile of 2^logC columns: its LDS bytes (points and roots), its butterflies (one lane each) and the lanes of its
+// workgroup
+size_t net8_lds_bytes(int logR, int logC)
+{
+    return ((size_t)net8_points(logR, logC, net8_plan(logR).lf) + ((size_t)1 << logR >> 1)) * sizeof(double2);
+}
+long long net8_butterflies(int logR, int logC) { return ((1LL << logR) << logC) >> 3; }
+int net8_threads(int logR, int logC) { return (int)std::min<long long>(1024, std::max<long long>(64, net8_butterflies(logR, logC))); }
+
 // Tile width (log2 columns) and LDS bytes of a radix-2^logR pass through the radix-8 network; false when that pass runs the
 // radix-4 network instead (small radix, switched off, or no tile fits)
 bool net8_tile(const mdhip_ctx *ctx, long long H, int logR, int &logC, size_t &lds)
 {
     if (logR < NET8_MIN_LOGR || ctx->opt_fft_net8 == 0) return false;
     const long long cols = H >> logR;
-    const int lf = net8_plan(logR).lf;
-    auto bytes = [&](int lc) {
-        return ((((size_t)1 << logR) + ((size_t)1 << logR >> lf)) << lc) * sizeof(double2) + ((size_t)1 << logR >> 1) * sizeof(double2);
-    };
     // two workgroups per CU (their loads, transforms and stores overlap), i.e. <= 78 KB of LDS each
     const size_t cap = ctx->opt_fft_net8 == 2 ? ctx->lds_max : (size_t)78 * 1024;  // (2: one workgroup per CU, A/B)
     logC = NET8_MAX_LOGC;
-    while (logC > 0 && (bytes(logC) > cap || (1LL << logC) > cols)) --logC;
-    lds = bytes(logC);
+    while (logC > 0 && (net8_lds_bytes(logR, logC) > cap || (1LL << logC) > cols)) --logC;
+    lds = net8_lds_bytes(logR, logC);
     return lds <= ctx->lds_max;
+}
+
+// A launch with `lds` bytes of dynamic LDS (more than the 64 KB a kernel gets unasked); false with the error set
+template <typename... Params, typename... Args>
+bool launch_lds(mdhip_ctx *ctx, void (*kernel)(Params...), dim3 grid, int threads, size_t lds, int logR, Args... args)
+{
+    const hipError_t e =
+        hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) {
+        mdhip_fail(ctx, MDHIP_EHIP, "fft pass of radix 2^%d needs %zu bytes of LDS: %s", logR, lds, hipGetErrorString(e));
+        return false;
+    }
+    hipLaunchKernelGGL(kernel, grid, dim3((unsigned)threads), lds, ctx->stream, args...);
+    return true;
+}
+
+// fn(b0, nb) for every part of at most FFT_MAX_BATCH series (grid.y) of `batch`; stops at the first non-zero return
+template <typename Fn>
+int for_batches(int batch, Fn fn)
+{
+    for (int b0 = 0; b0 < batch; b0 += FFT_MAX_BATCH) {
+        const int rc = fn(b0, std::min(FFT_MAX_BATCH, batch - b0));
+        if (rc) return rc;
+    }
+    return MDHIP_OK;
 }
 
 template <int IN, int OUT>
@@ -1062,43 +950,34 @@ bool launch_pass(mdhip_ctx *ctx, const double2 *in, double2 *out, long long H, i
                  const PassIo &io, const TwTab &tt)
 {
     const long long cols = H >> logR;
-    {
-        int logC;
-        size_t lds;
-        if (net8_tile(ctx, H, logR, logC, lds)) {
-            const int threads = (int)std::min<long long>(1024, std::max<long long>(64, ((1LL << logR) << logC) >> 3));
-            const dim3 grid((unsigned)(cols >> logC), (unsigned)batch);
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fft_pass8_kernel<IN, OUT>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) {
-                mdhip_fail(ctx, MDHIP_EHIP, "fft pass of radix 2^%d needs %zu bytes of LDS: %s", logR, lds, hipGetErrorString(e));
-                return false;
-            }
-            hipLaunchKernelGGL((fft_pass8_kernel<IN, OUT>), grid, dim3((unsigned)threads), lds, ctx->stream, in, out, H, logR,
-                               logC, logS, H >> logS, io, tt);
-            return true;
-        }
-    }
+    int logC;
+    size_t lds;
+    if (net8_tile(ctx, H, logR, logC, lds))
+        return launch_lds(ctx, fft_pass8_kernel<IN, OUT>, dim3((unsigned)(cols >> logC), (unsigned)batch), net8_threads(logR, logC),
+                          lds, logR, in, out, H, logR, logC, logS, H >> logS, io, tt);
     if (IN == IN_SPEC) {  // (callers ask for the fused spectrum input only when net8_tile says the first pass takes it)
         mdhip_fail(ctx, MDHIP_EHIP, "internal: spectrum-input pass of radix 2^%d has no radix-8 tile", logR);
         return false;
     }
     // 16 columns per tile (256-byte runs) while the tile fits 64 KB of LDS, fewer for the larger radices
-    int logC = std::min(std::max(ctx->opt_fft_logc, 0), 6);
+    logC = std::min(std::max(ctx->opt_fft_logc, 0), 6);
     while (logC > 0 && ((size_t)16 << logR << logC) > (size_t)128 * 1024) --logC;
     while ((1LL << logC) > cols) --logC;
-    const size_t lds = ((size_t)(1 << logR << logC) + (size_t)(1 << logR >> 1)) * sizeof(double2);
-    const dim3 grid((unsigned)(cols >> logC), (unsigned)batch);
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fft_pass_kernel<IN, OUT>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-        mdhip_fail(ctx, MDHIP_EHIP, "fft pass of radix 2^%d needs %zu bytes of LDS: %s", logR, lds, hipGetErrorString(e));
-        return false;
-    }
-    hipLaunchKernelGGL((fft_pass_kernel<IN, OUT>), grid, dim3(FFT_THREADS), lds, ctx->stream, in, out, H, logR, logC,
-                       logS, H >> logS, io, tt);
-    return true;
+    lds = ((size_t)(1 << logR << logC) + (size_t)(1 << logR >> 1)) * sizeof(double2);
+    return launch_lds(ctx, fft_pass_kernel<IN, OUT>, dim3((unsigned)(cols >> logC), (unsigned)batch), FFT_THREADS, lds, logR, in,
+                      out, H, logR, logC, logS, H >> logS, io, tt);
 }
+
+// The (input, output) kinds a pass of fft_forward can have, and the launch of each
+using PassLaunch = bool (*)(mdhip_ctx *, const double2 *, double2 *, long long, int, int, int, const PassIo &, const TwTab &);
+constexpr struct {
+    int in, out;
+    PassLaunch launch;
+} PASS_KINDS[] = {
+    {IN_SPEC, OUT_PLAIN, launch_pass<IN_SPEC, OUT_PLAIN>},   {IN_SPEC, OUT_LAGS, launch_pass<IN_SPEC, OUT_LAGS>},
+    {IN_PAD, OUT_PLAIN, launch_pass<IN_PAD, OUT_PLAIN>},     {IN_PLAIN, OUT_LAGS, launch_pass<IN_PLAIN, OUT_LAGS>},
+    {IN_PLAIN, OUT_CONJ, launch_pass<IN_PLAIN, OUT_CONJ>},   {IN_PLAIN, OUT_PLAIN, launch_pass<IN_PLAIN, OUT_PLAIN>},
+};
 
 // FFT_H of `batch` series. The passes alternate between the two buffers; returns the buffer that holds the result
 // (x after an even number of passes, y after an odd one), nullptr when a pass could not be launched (error set).
@@ -1122,14 +1001,14 @@ double2 *fft_forward(mdhip_ctx *ctx, double2 *x, double2 *y, long long H, int ba
     int s = 0;  // log2 of the product of the radices done
     for (int i = 0; i < p.n_pass; ++i) {
         const int im = i == 0 ? in_mode : IN_PLAIN, om = i == p.n_pass - 1 ? out_mode : OUT_PLAIN;
-        bool ok;
-        if (im == IN_SPEC && om == OUT_PLAIN) ok = launch_pass<IN_SPEC, OUT_PLAIN>(ctx, src, dst, H, batch, p.logR[i], s, io, tt);
-        else if (im == IN_SPEC && om == OUT_LAGS) ok = launch_pass<IN_SPEC, OUT_LAGS>(ctx, src, dst, H, batch, p.logR[i], s, io, tt);
-        else if (im == IN_PAD && om == OUT_PLAIN) ok = launch_pass<IN_PAD, OUT_PLAIN>(ctx, src, dst, H, batch, p.logR[i], s, io, tt);
-        else if (im == IN_PLAIN && om == OUT_LAGS) ok = launch_pass<IN_PLAIN, OUT_LAGS>(ctx, src, dst, H, batch, p.logR[i], s, io, tt);
-        else if (im == IN_PLAIN && om == OUT_CONJ) ok = launch_pass<IN_PLAIN, OUT_CONJ>(ctx, src, dst, H, batch, p.logR[i], s, io, tt);
-        else ok = launch_pass<IN_PLAIN, OUT_PLAIN>(ctx, src, dst, H, batch, p.logR[i], s, io, tt);
-        if (!ok) return nullptr;
+        PassLaunch launch = nullptr;
+        for (const auto &k : PASS_KINDS)
+            if (k.in == im && k.out == om) launch = k.launch;
+        if (!launch) {
+            mdhip_fail(ctx, MDHIP_EHIP, "internal: no transform pass reads kind %d and writes kind %d", im, om);
+            return nullptr;
+        }
+        if (!launch(ctx, src, dst, H, batch, p.logR[i], s, io, tt)) return nullptr;
         s += p.logR[i];
         std::swap(src, dst);
     }
@@ -1146,22 +1025,17 @@ int mdhip_fft_r2c(mdhip_ctx *ctx, double *d_real, double2 *d_tmp, double2 *d_spe
 {
     MD_REQUIRE(L >= 2 && (L & (L - 1)) == 0, "transform length %lld is not a power of two", L);
     const long long H = L / 2;
-    if (batch > FFT_MAX_BATCH) {  // grid.y
-        for (int b0 = 0; b0 < batch; b0 += FFT_MAX_BATCH) {
-            const int rc = mdhip_fft_r2c(ctx, d_real + (size_t)b0 * L, d_tmp + (size_t)b0 * H,
-                                         d_spec + (size_t)b0 * (H + 1), L, std::min(FFT_MAX_BATCH, batch - b0));
-            if (rc) return rc;
-        }
+    return for_batches(batch, [&](int b0, int nb) -> int {
+        TwTab tt;
+        if (!fft_twiddle_table(ctx, H, tt)) return MDHIP_ENOMEM;
+        double2 *Z = fft_forward(ctx, reinterpret_cast<double2 *>(d_real + (size_t)b0 * L), d_tmp + (size_t)b0 * H, H, nb, IN_PLAIN,
+                                 OUT_PLAIN, PassIo{}, tt);
+        if (!Z) return MDHIP_EHIP;
+        hipLaunchKernelGGL(r2c_post_kernel, dim3((unsigned)((H / 2 + 1 + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, Z,
+                           d_spec + (size_t)b0 * (H + 1), H, tt);
+        MD_HIP(hipGetLastError());
         return MDHIP_OK;
-    }
-    TwTab tt;
-    if (!fft_twiddle_table(ctx, H, tt)) return MDHIP_ENOMEM;
-    double2 *Z = fft_forward(ctx, reinterpret_cast<double2 *>(d_real), d_tmp, H, batch, IN_PLAIN, OUT_PLAIN, PassIo{}, tt);
-    if (!Z) return MDHIP_EHIP;
-    hipLaunchKernelGGL(r2c_post_kernel, dim3((unsigned)((H / 2 + 1 + 255) / 256), (unsigned)batch), dim3(256), 0,
-                       ctx->stream, Z, d_spec, H, tt);
-    MD_HIP(hipGetLastError());
-    return MDHIP_OK;
+    });
 }
 
 // Z[b][0..L/2) = FFT_(L/2) of the zero-padded real series d_series[b][0..n) read as complex pairs — the transform WITHOUT
@@ -1176,15 +1050,16 @@ int mdhip_fft_r2c_packed(mdhip_ctx *ctx, const double *d_series, long long n, do
     TwTab tt;
     if (!fft_twiddle_table(ctx, H, tt)) return MDHIP_ENOMEM;
     const double2 *Z = nullptr;
-    for (int b0 = 0; b0 < batch; b0 += FFT_MAX_BATCH) {  // (grid.y)
+    const int rc = for_batches(batch, [&](int b0, int nb) -> int {
         PassIo io{};
         io.series = d_series + (size_t)b0 * n;
         io.n = n;
-        double2 *z = fft_forward(ctx, d_buf0 + (size_t)b0 * H, d_buf1 + (size_t)b0 * H, H, std::min(FFT_MAX_BATCH, batch - b0),
-                                 IN_PAD, OUT_PLAIN, io, tt);
+        double2 *z = fft_forward(ctx, d_buf0 + (size_t)b0 * H, d_buf1 + (size_t)b0 * H, H, nb, IN_PAD, OUT_PLAIN, io, tt);
         if (!z) return MDHIP_EHIP;
-        if (b0 == 0) Z = z - (size_t)b0 * H;  // (the same number of passes for every part: the same buffer)
-    }
+        if (b0 == 0) Z = z;  // (the same number of passes for every part: the same buffer)
+        return MDHIP_OK;
+    });
+    if (rc) return rc;
     *Z_out = Z;
     MD_HIP(hipGetLastError());
     return MDHIP_OK;
@@ -1217,22 +1092,17 @@ struct Power2Plan {
 
 bool power2_plan(const mdhip_ctx *ctx, long long H, Power2Plan &pp)
 {
-    int logH = 0;
-    while ((1LL << logH) < H) ++logH;
+    const int logH = ilog2(H);
     if (logH < 10 || logH > 22) return false;
     pp.logRa = (logH + 1) / 2;
     pp.logRb = logH - pp.logRa;
-    auto bytes = [](int logR, int lc) {
-        const int lf = net8_plan(logR).lf;
-        return ((((size_t)1 << logR) + ((size_t)1 << logR >> lf)) << lc) * sizeof(double2) + ((size_t)1 << logR >> 1) * sizeof(double2);
-    };
     // tiles of <= 40 KB: four workgroups per CU, whose loads, transforms and sums overlap; 16 columns (256-byte runs) at most,
     // R C / 8 lanes between 64 and 1024
     auto pick = [&](int logR, int &lc, size_t &lds) {
         lc = 4;
-        while (lc > 1 && (bytes(logR, lc) > (size_t)40 * 1024 || ((1 << logR << lc) >> 3) > 512)) --lc;
-        lds = bytes(logR, lc);
-        return lds <= ctx->lds_max && ((1 << logR << lc) >> 3) >= 64 && ((1 << logR << lc) >> 3) <= 512;
+        while (lc > 1 && (net8_lds_bytes(logR, lc) > (size_t)40 * 1024 || net8_butterflies(logR, lc) > 512)) --lc;
+        lds = net8_lds_bytes(logR, lc);
+        return lds <= ctx->lds_max && net8_butterflies(logR, lc) >= 64 && net8_butterflies(logR, lc) <= 512;
     };
     if (!pick(pp.logRa, pp.lc1, pp.lds1) || !pick(pp.logRb, pp.lc2, pp.lds2)) return false;
     bool have = false;
@@ -1256,18 +1126,18 @@ int mdhip_fft_first_perm(mdhip_ctx *ctx, const double *d_series, long long n, do
     MD_REQUIRE((L & (L - 1)) == 0 && n <= L && power2_plan(ctx, H, pp), "no two-pass plan for the transform length %lld", L);
     TwTab tt;
     if (!fft_twiddle_table(ctx, H, tt)) return MDHIP_ENOMEM;
-    MD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fft_pass8_kernel<IN_PAD, OUT_PERM>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp.lds1));
     const long long cols = H >> pp.logRa;
-    const int threads = (1 << pp.logRa << pp.lc1) >> 3;
-    for (int b0 = 0; b0 < batch; b0 += FFT_MAX_BATCH) {  // (grid.y)
+    const int rc = for_batches(batch, [&](int b0, int nb) -> int {
         PassIo io{};
         io.series = d_series + (size_t)b0 * n;
         io.n = n;
-        hipLaunchKernelGGL((fft_pass8_kernel<IN_PAD, OUT_PERM>), dim3((unsigned)(cols >> pp.lc1), (unsigned)std::min(FFT_MAX_BATCH, batch - b0)),
-                           dim3((unsigned)threads), pp.lds1, ctx->stream, (const double2 *)nullptr, d_buf + (size_t)b0 * H, H,
-                           pp.logRa, pp.lc1, 0, H, io, tt);
-    }
+        return launch_lds(ctx, fft_pass8_kernel<IN_PAD, OUT_PERM>, dim3((unsigned)(cols >> pp.lc1), (unsigned)nb),
+                          net8_threads(pp.logRa, pp.lc1), pp.lds1, pp.logRa, (const double2 *)nullptr, d_buf + (size_t)b0 * H, H,
+                          pp.logRa, pp.lc1, 0, H, io, tt)
+                   ? MDHIP_OK
+                   : MDHIP_EHIP;
+    });
+    if (rc) return rc;
     MD_HIP(hipGetLastError());
     return MDHIP_OK;
 }
@@ -1280,13 +1150,11 @@ int mdhip_fft_power_pass(mdhip_ctx *ctx, const double2 *d_buf, long long L, long
     MD_REQUIRE((L & (L - 1)) == 0 && power2_plan(ctx, H, pp), "no two-pass plan for the transform length %lld", L);
     TwTab tt;
     if (!fft_twiddle_table(ctx, H, tt)) return MDHIP_ENOMEM;
-    const int threads = (1 << pp.logRb << pp.lc2) >> 3;
 #define MD_POWER_PASS(LR, LC)                                                                                                 \
     if (pp.logRb == LR && pp.lc2 == LC) {                                                                                     \
-        MD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fft_power_pass_kernel<LR, LC>),                             \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp.lds2));                                \
-        hipLaunchKernelGGL((fft_power_pass_kernel<LR, LC>), dim3((unsigned)((1LL << pp.logRa) >> pp.lc2), (unsigned)splits),  \
-                           dim3((unsigned)threads), pp.lds2, ctx->stream, d_buf, H, pp.logRa, row0, row1, d_partial, tt);     \
+        if (!launch_lds(ctx, fft_power_pass_kernel<LR, LC>, dim3((unsigned)((1LL << pp.logRa) >> LC), (unsigned)splits),      \
+                        net8_threads(LR, LC), pp.lds2, LR, d_buf, H, pp.logRa, row0, row1, d_partial, tt))                    \
+            return MDHIP_EHIP;                                                                                                \
         MD_HIP(hipGetLastError());                                                                                            \
         return MDHIP_OK;                                                                                                      \
     }
@@ -1302,32 +1170,26 @@ int mdhip_fft_c2r(mdhip_ctx *ctx, const double2 *d_spec, double2 *d_tmp, double 
 {
     MD_REQUIRE(L >= 2 && (L & (L - 1)) == 0, "transform length %lld is not a power of two", L);
     const long long H = L / 2;
-    if (batch > FFT_MAX_BATCH) {  // grid.y
-        for (int b0 = 0; b0 < batch; b0 += FFT_MAX_BATCH) {
-            const int rc = mdhip_fft_c2r(ctx, d_spec + (size_t)b0 * (H + 1), d_tmp + (size_t)b0 * H,
-                                         d_real + (size_t)b0 * L, L, std::min(FFT_MAX_BATCH, batch - b0));
-            if (rc) return rc;
-        }
+    return for_batches(batch, [&](int b0, int nb) -> int {
+        const PassPlan p = plan_passes(ctx, H, nb);
+        MD_REQUIRE(p.n_pass >= 0, "transform length %lld needs more than %d passes", L, FFT_MAX_PASSES);
+        // the result must land in d_real: start in d_real for an even number of buffer hops, in d_tmp for an odd one
+        // (H = 1: one hop, the conjugating copy)
+        const int hops = p.n_pass == 0 ? 1 : p.n_pass;
+        double2 *real_c = reinterpret_cast<double2 *>(d_real + (size_t)b0 * L), *tmp = d_tmp + (size_t)b0 * H;
+        double2 *first = hops % 2 == 0 ? real_c : tmp, *second = hops % 2 == 0 ? tmp : real_c;
+        TwTab tt;
+        if (!fft_twiddle_table(ctx, H, tt)) return MDHIP_ENOMEM;
+        hipLaunchKernelGGL(c2r_pre_kernel, dim3((unsigned)((H / 2 + 1 + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream,
+                           d_spec + (size_t)b0 * (H + 1), first, H, tt);
+        // W = conj Y went in; y = conj FFT(W): conjugate on the way out. c[2j] = Re y[j], c[2j+1] = Im y[j]: the complex
+        // result read as reals IS the series.
+        double2 *res = fft_forward(ctx, first, second, H, nb, IN_PLAIN, OUT_CONJ, PassIo{}, tt);
+        if (!res) return MDHIP_EHIP;
+        MD_HIP(hipGetLastError());
+        if (res != real_c) return mdhip_fail(ctx, MDHIP_EHIP, "internal: inverse transform landed in the wrong buffer");
         return MDHIP_OK;
-    }
-    const PassPlan p = plan_passes(ctx, H, batch);
-    MD_REQUIRE(p.n_pass >= 0, "transform length %lld needs more than %d passes", L, FFT_MAX_PASSES);
-    // the result must land in d_real: start in d_real for an even number of buffer hops, in d_tmp for an odd one
-    // (H = 1: one hop, the conjugating copy)
-    const int hops = p.n_pass == 0 ? 1 : p.n_pass;
-    double2 *real_c = reinterpret_cast<double2 *>(d_real);
-    double2 *first = hops % 2 == 0 ? real_c : d_tmp, *second = hops % 2 == 0 ? d_tmp : real_c;
-    TwTab tt;
-    if (!fft_twiddle_table(ctx, H, tt)) return MDHIP_ENOMEM;
-    hipLaunchKernelGGL(c2r_pre_kernel, dim3((unsigned)((H / 2 + 1 + 255) / 256), (unsigned)batch), dim3(256), 0,
-                       ctx->stream, d_spec, first, H, tt);
-    // W = conj Y went in; y = conj FFT(W): conjugate on the way out. c[2j] = Re y[j], c[2j+1] = Im y[j]: the complex
-    // result read as reals IS the series.
-    double2 *res = fft_forward(ctx, first, second, H, batch, IN_PLAIN, OUT_CONJ, PassIo{}, tt);
-    if (!res) return MDHIP_EHIP;
-    MD_HIP(hipGetLastError());
-    if (res != real_c) return mdhip_fail(ctx, MDHIP_EHIP, "internal: inverse transform landed in the wrong buffer");
-    return MDHIP_OK;
+    });
 }
 
 // The whole FFT estimator of `batch` series pairs (xcorr.hip): lags[b][t] = sum_u a[b][u+t] b[b][u] / (n - t),
@@ -1345,34 +1207,27 @@ int mdhip_fft_xcorr(mdhip_ctx *ctx, const double *d_a, const double *d_b, long l
     PassIo io{};
     io.n = n;
     io.series = d_a;
+    io.lags = d_lags;  // (read by the last pass of the inverse alone, which writes the scaled lags)
+    io.n_lags = n_lags;
+    io.L = (double)L;
+    io.scale = out_scale;
     TwTab tt;
     if (!fft_twiddle_table(ctx, H, tt)) return MDHIP_ENOMEM;
     const bool same = d_a == d_b;
+    const PassPlan fp = plan_passes(ctx, H, batch);
     {
         // Autocorrelation in THREE launches where the transform runs in two passes of the radix-8 network (round 5,
         // fft_mid_acf_kernel): first pass (pairs next to each other) | second pass + spectrum + inverse's first | last
-        const PassPlan fp = plan_passes(ctx, H, batch);
         int lc1 = 0, lcm = 0;
         size_t lds1 = 0, ldsm = 0;
         if (same && ctx->opt_fft_mid != 0 && fp.n_pass == 2 && net8_tile(ctx, H, fp.logR[0], lc1, lds1) &&
             net8_tile(ctx, H, fp.logR[1], lcm, ldsm) && lcm >= 1) {
             const int logRa = fp.logR[0], logRb = fp.logR[1];
-            if (ctx->opt_fft_mid == 2 && lcm > 1) {  // (A/B: tiles half as wide, more workgroups per CU)
-                --lcm;
-                ldsm = ((((size_t)1 << logRb) + ((size_t)1 << logRb >> net8_plan(logRb).lf)) << lcm) * sizeof(double2) +
-                       ((size_t)1 << logRb >> 1) * sizeof(double2);
-            }
+            if (ctx->opt_fft_mid == 2 && lcm > 1) ldsm = net8_lds_bytes(logRb, --lcm);  // (A/B: tiles half as wide)
             if (!launch_pass<IN_PAD, OUT_PERM>(ctx, buf0, buf1, H, batch, logRa, 0, io, tt)) return MDHIP_EHIP;
-            const int threads = (int)std::min<long long>(1024, std::max<long long>(64, ((1LL << logRb) << lcm) >> 3));
-            MD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fft_mid_acf_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsm));
-            hipLaunchKernelGGL(fft_mid_acf_kernel, dim3((unsigned)((1LL << logRa) >> lcm), (unsigned)batch),
-                               dim3((unsigned)threads), ldsm, ctx->stream, buf1, buf0, H, logRa, logRb, lcm, tt);
-            io.lags = d_lags;
-            io.n_lags = n_lags;
-            io.L = (double)L;
-            io.scale = out_scale;
-            io.zb = nullptr;
+            if (!launch_lds(ctx, fft_mid_acf_kernel, dim3((unsigned)((1LL << logRa) >> lcm), (unsigned)batch),
+                            net8_threads(logRb, lcm), ldsm, logRb, buf1, buf0, H, logRa, logRb, lcm, tt))
+                return MDHIP_EHIP;
             if (!launch_pass<IN_PLAIN, OUT_LAGS>(ctx, buf0, buf1, H, batch, logRa, logRb, io, tt)) return MDHIP_EHIP;
             MD_HIP(hipGetLastError());
             return MDHIP_OK;
@@ -1388,10 +1243,9 @@ int mdhip_fft_xcorr(mdhip_ctx *ctx, const double *d_a, const double *d_b, long l
     }
     // the pointwise step (half spectra, product, inverse-transform input) rides on the inverse transform's first pass when
     // that pass runs the radix-8 network (IN_SPEC); else it is a kernel of its own, in place
-    const PassPlan ip = plan_passes(ctx, H, batch);
     int lc_;
     size_t lds_;
-    const bool fuse = ctx->opt_fft_specfuse != 0 && ip.n_pass >= 1 && net8_tile(ctx, H, ip.logR[0], lc_, lds_);
+    const bool fuse = ctx->opt_fft_specfuse != 0 && fp.n_pass >= 1 && net8_tile(ctx, H, fp.logR[0], lc_, lds_);
     if (!fuse) {
         const dim3 grid((unsigned)((H / 2 + 1 + 255) / 256), (unsigned)batch);
         if (same)
@@ -1399,10 +1253,6 @@ int mdhip_fft_xcorr(mdhip_ctx *ctx, const double *d_a, const double *d_b, long l
         else
             hipLaunchKernelGGL(xcorr_spectrum_kernel<false>, grid, dim3(256), 0, ctx->stream, Za, Zb, H, tt);
     }
-    io.lags = d_lags;
-    io.n_lags = n_lags;
-    io.L = (double)L;
-    io.scale = out_scale;
     io.zb = same ? nullptr : Zb;
     if (!fft_forward(ctx, Za, Za == buf0 ? buf1 : buf0, H, batch, fuse ? IN_SPEC : IN_PLAIN, OUT_LAGS, io, tt)) return MDHIP_EHIP;
     MD_HIP(hipGetLastError());

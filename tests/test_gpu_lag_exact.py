@@ -232,6 +232,27 @@ def test_batched_transforms(B, ctx):
     spectral(B, ctx, c, 3000, 0.5, 131072, BATCHED, lag_variant=4)
 
 
+# (radix, tile width) instance of fft_power_pass_kernel -> the smallest call that selects it: the second pass of the fused
+# form (lag_batched_fuse=2) has radix 2^(logH - ceil(logH / 2)), H = L / 2. The calls above and in the other tests reach
+# (5,4), (7,4) and (8,3) through L = 4096, 2^15 .. 2^18; these are the other four the library is built with.
+FUSED_PASS_INSTANCES = [((6, 4), "white", 3000, 2000, 8192, {"lag_variant": 4}), ((9, 2), "spikes", (1 << 18) + 1, 8, 1 << 19, {}),
+                        ((10, 1), "white", (1 << 20) + 1, 8, 1 << 21, {}), ((11, 1), "spikes", (1 << 22) + 1, 8, 1 << 23, {})]
+
+
+@pytest.mark.parametrize("inst,gen,F,max_lag,L,opts", FUSED_PASS_INSTANCES, ids=["%d-%d" % c[0] for c in FUSED_PASS_INSTANCES])
+def test_batched_transforms_fused_pass_instances(B, ctx, inst, gen, F, max_lag, L, opts):
+    """One series per call, nine lags at the long lengths: exact sums at every lag for each instance of the fused second
+    pass. The shape must still plan to the padded length that selects the instance (a change of the plan's rule fails here
+    rather than emptying the case)."""
+    opts = {"lag_batched_fuse": 2, **opts}
+    plan = B.lag_plan(F, 1, max_lag, [0, 1], opts={"lag_variant": 2, **opts}, ctx=ctx)
+    logH = L.bit_length() - 2
+    assert (plan["kernel"], plan["L"]) == (BATCHED, L) and logH - (logH + 1) // 2 == inst[0], (plan, inst)
+    c = Case(gen, F, 1, [0, 1], max_lag, seed=12)
+    assert X.sums_fit_double(c.S), "the data must keep every sum exact in float64"
+    spectral(B, ctx, c, max_lag, 1.0, L, BATCHED, **opts)
+
+
 # ------------------------------------------------------------------------------------------- groups, batches, centring
 def test_many_groups_every_path(B, ctx):
     """17 and 40 groups (ragged, empty, one-entity) on every path that takes more than 16: the 12 288-point kernel, the

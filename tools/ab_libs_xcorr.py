@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""tools/ab_libs_xcorr.py LIB.so [LIB.so ...] [n] — direct ACF kernel time through several BUILDS of libmdhip.so in one
-process (one 1e6-sample series by default), results compared."""
+"""tools/ab_libs_xcorr.py LIB.so [LIB.so ...] [n] [fft] [cross] — direct ACF kernel time through several BUILDS of libmdhip.so
+in one process (one 1e6-sample series by default), results compared. `cross`: correlate with a second series instead."""
 import os
 import sys
 
@@ -30,12 +30,13 @@ for c_, o_ in zip(ctxs, opts):
     for k_, v_ in o_.items():
         c_.set_option(k_, int(v_))
 x = torch.from_numpy(np.random.default_rng(0).standard_normal((3, n))).cuda()
+y = torch.from_numpy(np.random.default_rng(1).standard_normal((3, n))).cuda() if "cross" in sys.argv[1:] else None
 ref = None
 for rnd in range(2):
     for k_lib, (p, ctx) in enumerate(zip(libs, ctxs)):
         best = 1e9
         for rep in range(3 if METHOD == B.XCORR_DIRECT else 10):
-            out = B.xcorr(x, method=METHOD, ctx=ctx)
+            out = B.xcorr(x, y, method=METHOD, ctx=ctx)
             best = min(best, ctx.last_kernel_ms()[0])
         if ref is None:
             ref = out
