@@ -708,6 +708,37 @@ int mdhip_hydration_counts(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, co
                            const int32_t *waters, double r_cut_sq, double cos_cut, double bin_width, int32_t n_bins,
                            int32_t *n_water, int32_t *n_away, uint64_t *hist);
 
+/* ---- bond-angle histograms (angular_distribution.py calc_angular_distribution; not in the reference) ---- */
+/*
+ * The distribution of the angle A-C-B at a centre atom C between two of its shell neighbours, for a batch of frames:
+ * coordinates xyz [F][3][n_atoms] (host or device memory as xyz_on_device says), box [F][3], the centre atoms
+ * centres[n_centres] with their class centre_class[n_centres], the candidate atoms cand[n_cand] (every atom that can
+ * be a neighbour) with their class cand_class[n_cand], mol_of[n_atoms] (NULL: no exclusion), the triplets
+ * triplet_class[n_triplets][3] = (class_a, class_c, class_b) with their squared cutoffs triplet_rsq[n_triplets][2] =
+ * (r_ca ** 2, r_cb ** 2), and the table cos_edges[n_bins] = cos(m * bin_size), strictly decreasing.
+ * For one frame, one centre c of class class_c and one triplet t:
+ *   neighbour j of c in role A: j != c, class[j] == class_a, rsq(c, j) < r_ca ** 2 (the reference's single-wrap rsq,
+ *     rdf_cn.py:36-58, strict), and mol_of[j] != mol_of[c] under exclusion; role B the same with class_b and r_cb;
+ *   d_j = x_j - x_c wrapped once per axis (d > L/2 ? d - L : (d < -L/2 ? d + L : d)), n_j = sqrt((dx dx + dy dy) + dz dz),
+ *   cos = ((dxj dxk + dyj dyk) + dzj dzk) / (n_j * n_k), unfused, correctly rounded sqrt and division;
+ *   bin = the number of m in [1, n_bins) with cos <= cos_edges[m]: the angle is in [m D, (m + 1) D), the last bin is
+ *     closed at 180 degrees, a cosine an ulp outside +-1 falls in the first or last bin; a NaN cosine (a neighbour on
+ *     the centre) is in no bin and counts in n_degenerate[t];
+ *   a symmetric triplet (class_a == class_b and r_ca ** 2 == r_cb ** 2) counts every unordered pair {j, k}, j != k, of
+ *     role-A neighbours once; an asymmetric one every ordered (j, k), j != k, j in role A and k in role B.
+ *   hist [n_triplets][n_bins], n_degenerate [n_triplets] (uint64, summed over all frames and centres), exact;
+ *   count [F][n_centres]: the candidates other than c (and, under exclusion, its molecule) within the largest cutoff
+ *     of the triplets of c's class, exact even when it exceeds cap. A row with count > cap adds NOTHING to hist and
+ *     n_degenerate: call again with cap >= the largest count.
+ * 1 <= n_triplets <= 8, n_triplets * n_bins <= 4096, 1 <= cap <= 512. Outputs are host memory. The call's aux time
+ * (mdhip_last_aux_ms) is that of the gather and the search; the rest of its kernel time is the angle pass.
+ */
+int mdhip_angle_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int xyz_on_device,
+                     const double *box, int32_t n_centres, const int32_t *centres, const int32_t *centre_class,
+                     int32_t n_cand, const int32_t *cand, const int32_t *cand_class, const int32_t *mol_of,
+                     int32_t n_triplets, const int32_t *triplet_class, const double *triplet_rsq, int32_t n_bins,
+                     const double *cos_edges, int32_t cap, uint64_t *hist, uint64_t *n_degenerate, int32_t *count);
+
 /* ---- atom counts along the axis normal to a surface (number_density.py calc_number_density) ---- */
 /*
  * Replaces the per-type selections and the counting loop of calc_number_density   structural/number_density.py:76-105

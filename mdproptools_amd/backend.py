@@ -747,6 +747,89 @@ def hydration_counts(xyz, box, cations, waters, r_cut_sq, cos_cut, bin_width, n_
     return n_water, n_away, hist
 
 
+ANGLE_CAP = 64  # first-try neighbours per (frame, centre) row of angle_hist; a batch with a larger row is run again
+ANGLE_MAX_CAP = 512  # what the angle kernel stages (include/mdhip.h: mdhip_angle_hist)
+ANGLE_MAX_TRIPLETS = 8
+ANGLE_MAX_CELLS = 4096  # n_triplets * n_bins
+
+
+def angle_cos_edges(bin_size):
+    """The cosine table of angle_hist: E[m] = cos(radians(m * bin_size)), m = 0 .. ceil(180 / bin_size) - 1; ValueError
+    unless it is strictly decreasing (a bin_size so small that two edges round to one cosine)."""
+    bin_size = float(bin_size)
+    if not 0.0 < bin_size <= 180.0:
+        raise ValueError("bin_size must be in (0, 180] degrees")
+    n_bins = int(np.ceil(180.0 / bin_size))
+    if not np.cos(np.radians(bin_size)) < 1.0:  # (the table is flattest at its ends: checked before it is built)
+        raise ValueError("bin_size=%r: the cosine table is not strictly decreasing" % bin_size)
+    if n_bins > ANGLE_MAX_CELLS:
+        raise ValueError("bin_size=%r gives %d bins; at most %d" % (bin_size, n_bins, ANGLE_MAX_CELLS))
+    edges = np.cos(np.radians(np.arange(n_bins) * bin_size))
+    if not np.all(np.diff(edges) < 0):
+        raise ValueError("bin_size=%r: the cosine table is not strictly decreasing" % bin_size)
+    return edges
+
+
+def angle_hist(xyz, box, types, triplets, r_cut_sq, cos_edges, mol_of=None, cap=ANGLE_CAP, ctx=None):
+    """
+    Bond-angle histograms (include/mdhip.h: mdhip_angle_hist): xyz [F,3,N], box [F,3], types [N] (the same in every
+    frame), triplets [T] of (type_a, type_c, type_b), r_cut_sq [T,2] = (r_ca**2, r_cb**2), cos_edges [n_bins] from
+    angle_cos_edges, mol_of [N] (None: no molecule exclusion) -> (hist uint64 [T,n_bins], n_degenerate uint64 [T],
+    count int32 [F,C], centres int32 [C]). The centres are the atoms whose type is the type_c of a triplet, ascending;
+    the candidates those whose type is a type_a or type_b. count[f, c] is the number of candidates within the largest
+    cutoff of the centre's triplets. A batch with a row of more than `cap` neighbours is run once more with a cap of
+    the largest count; more than 512 is a ValueError.
+    """
+    ctx = ctx or default_context()
+    F, _, N = _shape3(xyz, "xyz")
+    typ = _i32(types).ravel()
+    if len(typ) != N:
+        raise ValueError("types must hold one type per atom")
+    trip = _i32(triplets).reshape(-1, 3)
+    T = len(trip)
+    rc2 = _f64(r_cut_sq).reshape(-1, 2)
+    if len(rc2) != T:
+        raise ValueError("one (r_ca**2, r_cb**2) per triplet is required")
+    edges = _f64(cos_edges).ravel()
+    n_bins = len(edges)
+    if n_bins < 1 or not np.all(np.diff(edges) < 0):
+        raise ValueError("cos_edges must be strictly decreasing")
+    mol = None
+    if mol_of is not None:
+        mol = _i32(mol_of).ravel()
+        if len(mol) != N:
+            raise ValueError("mol_of must hold one molecule index per atom")
+    cen = np.flatnonzero(np.isin(typ, trip[:, 1])).astype(np.int32)
+    cand = np.flatnonzero(np.isin(typ, np.concatenate([trip[:, 0], trip[:, 2]]))).astype(np.int32)
+    cen_cls, cand_cls = np.ascontiguousarray(typ[cen]), np.ascontiguousarray(typ[cand])
+    bx = _f64(box).reshape(F, 3)
+    xp, x_dev, keep = as_input(xyz, ctx)
+
+    def run(k):
+        hist = np.zeros((T, n_bins), dtype=np.uint64)
+        degen = np.zeros(T, dtype=np.uint64)
+        count = np.zeros((F, len(cen)), dtype=np.int32)
+        ctx.check(ctx.lib.mdhip_angle_hist(
+            ctx.h, F, N, xp, x_dev, ptr(bx), len(cen), ptr(cen, C.c_int32), ptr(cen_cls, C.c_int32), len(cand),
+            ptr(cand, C.c_int32), ptr(cand_cls, C.c_int32), None if mol is None else ptr(mol, C.c_int32), T,
+            ptr(trip, C.c_int32), ptr(rc2), n_bins, ptr(edges), int(k), ptr(hist, C.c_uint64),
+            ptr(degen, C.c_uint64), ptr(count, C.c_int32)))
+        return hist, degen, count
+
+    cap = int(cap)
+    hist, degen, count = run(cap)
+    big = int(count.max()) if count.size else 0
+    if big > cap:
+        if big > ANGLE_MAX_CAP:
+            f, c = np.unravel_index(int(count.argmax()), count.shape)
+            raise ValueError("angle_hist: frame %d, centre atom %d has %d neighbours; at most %d are supported "
+                             "(smaller cutoffs?)" % (f, int(cen[c]), big, ANGLE_MAX_CAP))
+        hist, degen, again = run(big)  # (the first call's histograms are discarded)
+        if not np.array_equal(again, count):
+            raise RuntimeError("angle_hist: the re-run found other row sizes than the first sweep")
+    return hist, degen, count, cen
+
+
 AP_REF_POS, AP_REF_NEG, AP_PROFILE = 0, 1, 2  # binning modes of axis_profile (include/mdhip.h: MDHIP_AP_*)
 AP_SURFACE = 0x4000  # code bit: the atom belongs to the surface
 AP_NONE = 0x3FFF     # row field of an atom that counts in no row
