@@ -5,7 +5,7 @@
 // One frame, one centre c, one triplet t = (type_a, type_c, type_b, r_ca, r_cb):
 //   neighbour j of c in role A: j != c, type[j] == type_a, shell::rsq(c, j) < r_ca**2 (strict; the |d| form of the
 //     single wrap), and mol_of[j] != mol_of[c] under exclusion; role B the same with type_b and r_cb;
-//   d_j = wrap(x_j - x_c) (signed: d > L/2 ? d - L : (d < -L/2 ? d + L : d)), n_j = sqrt((dx dx + dy dy) + dz dz),
+//   d_j = shell::wrap_signed(x_j - x_c), n_j = sqrt((dx dx + dy dy) + dz dz),
 //   cos = ((dxj dxk + dyj dyk) + dzj dzk) / (n_j * n_k), unfused, correctly rounded sqrt and division;
 //   bin = the number of m in [1, n_bins) with cos <= E[m], E[m] = cos(m * bin_size) from the host, strictly
 //     decreasing (theta in [m D, (m + 1) D), the last bin closed, no clamp, no acos); a NaN cosine is in no bin and
@@ -18,8 +18,8 @@
 //     reads coalesced planes of only the atoms that can be a neighbour.
 //  2. ang_search_kernel: the sweep of shell_search.h with the largest cutoff of all. A hit (rare) that is not the
 //     centre itself, not of its molecule under exclusion, and within the largest cutoff of the centre's class is
-//     appended to the row (frame, centre); count stays exact past `cap`. Which of those tests a call needs at all is
-//     decided on the host.
+//     appended to the row (frame, centre) (shell::append). Which of those tests a call needs at all is decided on
+//     the host.
 //  3. ang_pair_kernel: one wave per row. The row is staged in LDS in tiles of ANG_TILE neighbours (d, the norm and a
 //     mask of the (triplet, role) pairs the neighbour serves); the lanes walk the pairs j < k of a tile pair, test the
 //     two masks against each other, and only a pair that counts somewhere computes its cosine, finds the bin by binary
@@ -40,13 +40,6 @@ constexpr int ANG_MAX_TRIPLETS = 8;
 constexpr int ANG_MAX_CELLS = 4096;  // n_triplets * n_bins: the block's histogram (16 KB) and E (up to 32 KB) in LDS
 constexpr int ANG_MAX_CAP = 512;
 constexpr int ANG_TILE = 64;         // neighbours per staged tile (two tiles: 4.5 KB)
-
-// the signed wrap (the cosine needs the direction): d - sign(d) L when d > L/2 or d < -L/2
-__device__ __forceinline__ double ang_wrap(double d, double L)
-{
-    const double h = 0.5 * L;
-    return d > h ? d - L : (d < -h ? d + L : d);
-}
 
 // The triplet table (by value: wave-uniform loads). Classes are the caller's atom types.
 struct AngTriplets {
@@ -75,39 +68,26 @@ __global__ __launch_bounds__(256) void ang_gather_kernel(const double *__restric
 constexpr int ANG_TEST_ATOM = 1;    // the candidate's atom is looked up: it may be the centre, or of its molecule
 constexpr int ANG_TEST_RADIUS = 2;  // the centres' largest cutoffs differ: rsq again, against the centre's own
 
-// Candidate a of the frame's planes q is within the sweep's cutoff of centre c (atom centres[c], row `row`): appended
-// unless it is the centre, of the centre's molecule (mol_of != nullptr), or beyond the largest cutoff of the centre's
-// class.
-__device__ __forceinline__ void ang_hit(const double *__restrict__ q, long long n_cand, const int *__restrict__ cand,
-                                        const int *__restrict__ mol_of, const int *__restrict__ centres,
-                                        const double *__restrict__ cen_rmax2, int tests, long long a, int c, double cx,
-                                        double cy, double cz, double Lx, double Ly, double Lz, int cap, size_t row,
-                                        int *__restrict__ idx, int *__restrict__ count)
-{
-    if (tests & ANG_TEST_ATOM) {
-        const int aj = cand[a], ci = centres[c];
-        if (aj == ci) return;
-        if (mol_of && mol_of[aj] == mol_of[ci]) return;
-    }
-    if ((tests & ANG_TEST_RADIUS) &&
-        !(shell::rsq(cx, cy, cz, q[a], q[n_cand + a], q[2 * n_cand + a], Lx, Ly, Lz) < cen_rmax2[c]))
-        return;
-    const int slot = atomicAdd(&count[row], 1);
-    if (slot < cap) idx[row * (size_t)cap + (size_t)slot] = (int)a;
-}
-
+// A candidate within the sweep's cutoff of a row's centre is appended unless it is the centre, of the centre's molecule
+// (mol_of != nullptr), or beyond the largest cutoff of the centre's class.
 __global__ __launch_bounds__(shell::THREADS) void ang_search_kernel(
     const double *__restrict__ xyz, long long n, const double *__restrict__ planes, long long n_cand,
     const double *__restrict__ box, const int *__restrict__ centres, int n_c, const int *__restrict__ cand,
     const int *__restrict__ mol_of, const double *__restrict__ cen_rmax2, int tests, double rc2, int cap,
     shell::Grid g, int *__restrict__ idx, int *__restrict__ count)
 {
-    shell::sweep(xyz, n, centres, n_c, planes, 3, n_cand, box, rc2, g,
-                 [=](long long f, size_t row, long long a, double cx, double cy, double cz, double Lx, double Ly,
-                     double Lz) {
-                     ang_hit(planes + (size_t)f * 3 * (size_t)n_cand, n_cand, cand, mol_of, centres, cen_rmax2, tests,
-                             a, (int)(row - (size_t)f * (size_t)n_c), cx, cy, cz, Lx, Ly, Lz, cap, row, idx, count);
-                 });
+    shell::sweep(xyz, n, centres, n_c, planes, 3, n_cand, box, rc2, g, [=](const shell::Row &r, size_t row, long long a) {
+        if (tests & ANG_TEST_ATOM) {
+            const int aj = cand[a];
+            if (aj == r.ci) return;
+            if (mol_of && mol_of[aj] == mol_of[r.ci]) return;
+        }
+        const double *q = planes + (size_t)r.f * 3 * (size_t)n_cand;
+        if ((tests & ANG_TEST_RADIUS) &&
+            !(shell::rsq(r.cx, r.cy, r.cz, q[a], q[n_cand + a], q[2 * n_cand + a], r.Lx, r.Ly, r.Lz) < cen_rmax2[r.c]))
+            return;
+        shell::append(count, idx, row, cap, (int)a);
+    });
 }
 
 // One staged tile of a row: d, the norm, and the mask (bit t: role A of triplet t, bit 8 + t: role B of an asymmetric
@@ -119,14 +99,15 @@ struct AngTile {
 
 __device__ __forceinline__ void ang_stage(const AngTile &s, int lane, int m, const int *__restrict__ r,
                                           const double *__restrict__ q, long long n_cand,
-                                          const int *__restrict__ cand_class, int cc, const AngTriplets &tr, double cx,
-                                          double cy, double cz, double Lx, double Ly, double Lz)
+                                          const int *__restrict__ cand_class, int cc, const AngTriplets &tr,
+                                          const shell::Row &c)
 {
     if (lane < m) {
         const long long a = r[lane];
         const double x = q[a], y = q[n_cand + a], z = q[2 * n_cand + a];
-        const double dx = ang_wrap(x - cx, Lx), dy = ang_wrap(y - cy, Ly), dz = ang_wrap(z - cz, Lz);
-        const double rsq = shell::rsq(cx, cy, cz, x, y, z, Lx, Ly, Lz);
+        const double dx = shell::wrap_signed(x - c.cx, c.Lx), dy = shell::wrap_signed(y - c.cy, c.Ly),
+                     dz = shell::wrap_signed(z - c.cz, c.Lz);
+        const double rsq = shell::rsq(c.cx, c.cy, c.cz, x, y, z, c.Lx, c.Ly, c.Lz);
         const int cls = cand_class[a];
         unsigned mask = 0;
 #pragma unroll
@@ -196,25 +177,21 @@ __global__ __launch_bounds__(64) void ang_pair_kernel(const double *__restrict__
             pending = 0;
         }
         pending += inc;
-        const long long f = row / n_c;
-        const int c = (int)(row % n_c);
-        const int ci = centres[c], cc = cen_class[c];
-        const double *px = xyz + (size_t)f * 3 * (size_t)n;
-        const double *q = planes + (size_t)f * 3 * (size_t)n_cand;
-        const double Lx = box[3 * f], Ly = box[3 * f + 1], Lz = box[3 * f + 2];
-        const double cx = px[ci], cy = px[n + ci], cz = px[2 * n + ci];
+        const shell::Row c = shell::row_of(xyz, n, box, centres, row / n_c, (int)(row % n_c));
+        const int cc = cen_class[c.c];
+        const double *q = planes + (size_t)c.f * 3 * (size_t)n_cand;
         const int *r = idx + (size_t)row * (size_t)cap;
         const int n_tiles = (k + ANG_TILE - 1) / ANG_TILE;
         for (int ta = 0; ta < n_tiles; ++ta) {
             const int ma = k - ta * ANG_TILE < ANG_TILE ? k - ta * ANG_TILE : ANG_TILE;
             __syncthreads();  // (the pairs of the tiles before have been read)
-            ang_stage(tj, lane, ma, r + ta * ANG_TILE, q, n_cand, cand_class, cc, tr, cx, cy, cz, Lx, Ly, Lz);
+            ang_stage(tj, lane, ma, r + ta * ANG_TILE, q, n_cand, cand_class, cc, tr, c);
             for (int tb = ta; tb < n_tiles; ++tb) {
                 const int mb = k - tb * ANG_TILE < ANG_TILE ? k - tb * ANG_TILE : ANG_TILE;
                 const bool same = tb == ta;
                 if (!same) {
                     __syncthreads();
-                    ang_stage(tk, lane, mb, r + tb * ANG_TILE, q, n_cand, cand_class, cc, tr, cx, cy, cz, Lx, Ly, Lz);
+                    ang_stage(tk, lane, mb, r + tb * ANG_TILE, q, n_cand, cand_class, cc, tr, c);
                 }
                 __syncthreads();
                 AngTile sk;  // (the K tile is the J tile on the diagonal)
@@ -267,18 +244,19 @@ int mdhip_angle_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const do
     MD_REQUIRE(n_triplets >= 1 && n_triplets <= ANG_MAX_TRIPLETS, "n_triplets must be in [1, %d]", ANG_MAX_TRIPLETS);
     MD_REQUIRE(n_bins >= 1 && (int64_t)n_triplets * n_bins <= ANG_MAX_CELLS,
                "n_triplets * n_bins must be in [1, %d]", ANG_MAX_CELLS);
-    MD_REQUIRE(cap >= 1 && cap <= ANG_MAX_CAP, "cap must be in [1, %d]", ANG_MAX_CAP);
+    shell::RowSet rs;
+    int rc;
+    if ((rc = shell::take_rows(ctx, n_frames, n_centres, cap, ANG_MAX_CAP, rs))) return rc;
     MD_REQUIRE(triplet_class && triplet_rsq && cos_edges && hist && n_degenerate, "NULL array");
     for (int32_t m = 1; m < n_bins; ++m)
         MD_REQUIRE(cos_edges[m] < cos_edges[m - 1], "cos_edges must be strictly decreasing (edge %d)", (int)m);
     memset(hist, 0, (size_t)n_triplets * (size_t)n_bins * 8);
     memset(n_degenerate, 0, (size_t)n_triplets * 8);
-    if (n_frames == 0 || n_centres == 0) return cs.end();
+    if (rs.n_rows == 0) return cs.end();
     MD_REQUIRE(centre_class && count, "NULL array");
     MD_REQUIRE(cand || n_cand == 0, "NULL array");
     MD_REQUIRE(cand_class || n_cand == 0, "NULL array");
-    for (int32_t w = 0; w < n_cand; ++w)
-        MD_REQUIRE(cand[w] >= 0 && cand[w] < n_atoms, "candidate %d: atom index %d out of range", (int)w, (int)cand[w]);
+    if ((rc = shell::check_indices(ctx, "candidate", n_cand, cand, 1, n_atoms))) return rc;
 
     AngTriplets tr;
     memset(&tr, 0, sizeof tr);
@@ -292,14 +270,10 @@ int mdhip_angle_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const do
         rc2 = std::max(rc2, std::max(tr.ra2[t], tr.rb2[t]));
     }
     shell::Inputs in;
-    int rc;
     if ((rc = shell::stage(ctx, "centre", n_frames, n_atoms, xyz, xyz_on_device, box, n_centres, centres, in)))
         return rc;
-    const size_t n_rows = (size_t)n_frames * (size_t)n_centres;
-    MD_WS(d_count, int, WS_AUX0, n_rows * 4);
-    MD_HIP(hipMemsetAsync(d_count, 0, n_rows * 4, ctx->stream));
     if (n_cand == 0) {  // (no atom can be a neighbour: every count is 0)
-        if ((rc = mdhip_result(cs, count, d_count, n_rows * 4, 0))) return rc;
+        if ((rc = shell::row_results(cs, rs, nullptr, count))) return rc;
         return cs.end();
     }
 
@@ -339,7 +313,6 @@ int mdhip_angle_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const do
 
     const size_t n_cells = (size_t)n_triplets * (size_t)n_bins + (size_t)n_triplets;
     MD_WS(d_planes, double, WS_AUX1, (size_t)n_frames * 3 * (size_t)n_cand * 8);
-    MD_WS(d_idx, int, WS_OUT, n_rows * (size_t)cap * 4);
     MD_WS(d_hist, unsigned long long, WS_HIST, n_cells * 8);
     MD_HIP(hipMemsetAsync(d_hist, 0, n_cells * 8, ctx->stream));
 
@@ -354,27 +327,20 @@ int mdhip_angle_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const do
     const shell::Grid g = shell::sweep_grid(ctx, n_frames, n_centres, n_cand);
     hipLaunchKernelGGL(ang_search_kernel, dim3(g.grid), dim3(shell::THREADS), 0, ctx->stream, in.xyz,
                        (long long)n_atoms, d_planes, (long long)n_cand, in.box, in.centres, (int)n_centres, d_cand, d_mol,
-                       d_rmax2, tests, rc2, (int)cap, g, d_idx, d_count);
+                       d_rmax2, tests, rc2, (int)cap, g, rs.idx, rs.count);
     MD_HIP(hipGetLastError());
     search.stop();
     const size_t lds = ((size_t)n_bins + 8 * ANG_TILE) * 8 + (n_cells + 2 * ANG_TILE) * 4;
-    const unsigned pgrid = (unsigned)std::min<size_t>(n_rows, (size_t)ctx->cu_count * 16);
-    hipLaunchKernelGGL(ang_pair_kernel, dim3(pgrid), dim3(64), lds, ctx->stream, in.xyz, (long long)n_atoms, d_planes,
-                       (long long)n_cand, in.box, in.centres, d_cen_class, (int)n_centres, d_cand_class, d_idx, d_count,
-                       (long long)n_rows, (int)cap, tr, d_edges, (int)n_bins, d_hist);
+    hipLaunchKernelGGL(ang_pair_kernel, dim3(rs.grid(ctx, 16)), dim3(64), lds, ctx->stream, in.xyz, (long long)n_atoms,
+                       d_planes, (long long)n_cand, in.box, in.centres, d_cen_class, (int)n_centres, d_cand_class, rs.idx,
+                       rs.count, (long long)rs.n_rows, (int)cap, tr, d_edges, (int)n_bins, d_hist);
     MD_HIP(hipGetLastError());
     timer.stop();
     if ((rc = mdhip_result(cs, hist, d_hist, (size_t)n_triplets * (size_t)n_bins * 8, 0))) return rc;
     if ((rc = mdhip_result(cs, n_degenerate, d_hist + (size_t)n_triplets * (size_t)n_bins, (size_t)n_triplets * 8, 0)))
         return rc;
-    if ((rc = mdhip_result(cs, count, d_count, n_rows * 4, 0))) return rc;
-    cs.defer([timer, search, ctx]() {
-        const double aux = search.collect();
-        timer.collect();
-        ctx->last_aux_ms = aux;
-        return MDHIP_OK;
-    });
-    return cs.end();
+    if ((rc = shell::row_results(cs, rs, nullptr, count))) return rc;
+    return shell::finish(cs, timer, &search);
 }
 
 }  // extern "C"

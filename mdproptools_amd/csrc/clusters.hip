@@ -9,8 +9,8 @@
 //  1. shell_hits_kernel: the sweep of shell_search.h, every centre against every atom of its frame. A hit is counted
 //     for its molecule only when it is the molecule's FIRST hit in id order: the atoms before it in the same molecule
 //     (molecules are contiguous id ranges) are tested again, and any earlier hit means another lane counts the
-//     molecule. So every shell molecule is appended exactly once — count[f][c] is the true number of shell molecules
-//     even when it exceeds the row's capacity `cap` (the host then re-runs those frames with a larger one).
+//     molecule. So every shell molecule is appended (shell::append) exactly once: count[f][c] is the number of shell
+//     molecules.
 //  2. shell_sort_kernel: one wave per (frame, centre) row puts the row's molecule indices in ascending order (the row
 //     pass of shell_search.h: the values are distinct) and pads the row to `cap` with -1.
 //  3. mol_kahan_kernel: one lane per (frame, attribute, molecule), the compensated sum of pandas' groupby().sum() over
@@ -36,8 +36,7 @@ __device__ __noinline__ void sh_hit(const double *__restrict__ px, const double 
     const int m = mol_of[a];
     for (long long b = a - 1; b >= 0 && mol_of[b] == m; --b)
         if (shell::rsq(cx, cy, cz, px[b], py[b], pz[b], Lx, Ly, Lz) < rc2) return;
-    const int slot = atomicAdd(&count[row], 1);
-    if (slot < cap) mols[row * (size_t)cap + (size_t)slot] = m;
+    shell::append(count, mols, row, cap, m);
 }
 
 __global__ __launch_bounds__(shell::THREADS) void shell_hits_kernel(
@@ -46,10 +45,8 @@ __global__ __launch_bounds__(shell::THREADS) void shell_hits_kernel(
     int *__restrict__ count)
 {
     shell::sweep(xyz, n, centres, n_c, xyz, 3, n, box, rc2, g,
-                 [=](long long f, size_t row, long long a, double cx, double cy, double cz, double Lx, double Ly,
-                     double Lz) {
-                     const double *px = xyz + (size_t)f * 3 * (size_t)n, *py = px + n, *pz = py + n;
-                     sh_hit(px, py, pz, mol_of, a, cx, cy, cz, Lx, Ly, Lz, rc2, cap, row, mols, count);
+                 [=](const shell::Row &r, size_t row, long long a) {
+                     sh_hit(r.px, r.py, r.pz, mol_of, a, r.cx, r.cy, r.cz, r.Lx, r.Ly, r.Lz, rc2, cap, row, mols, count);
                  });
 }
 
@@ -96,33 +93,28 @@ int mdhip_shell_members(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const
     if (!ctx) return MDHIP_EINVAL;
     CallScope cs(ctx);
     MD_REQUIRE(n_frames >= 0 && n_atoms >= 0 && n_centres >= 0, "negative sizes");
-    MD_REQUIRE(cap >= 1 && cap <= shell::MAX_CAP, "cap must be in [1, %d]", shell::MAX_CAP);
-    if (n_frames == 0 || n_centres == 0) return cs.end();
+    shell::RowSet rs;
+    int rc;
+    if ((rc = shell::take_rows(ctx, n_frames, n_centres, cap, shell::MAX_CAP, rs))) return rc;
+    if (rs.n_rows == 0) return cs.end();
     MD_REQUIRE(mol_of && mols && count, "NULL array");
     shell::Inputs in;
-    int rc;
     if ((rc = shell::stage(ctx, "centre", n_frames, n_atoms, xyz, xyz_on_device, box, n_centres, centres, in)))
         return rc;
-    const size_t n_rows = (size_t)n_frames * (size_t)n_centres;
     MD_WS(d_mol, int, WS_TYPE_J, (size_t)n_atoms * 4);
     if ((rc = mdhip_h2d_small(ctx, d_mol, mol_of, (size_t)n_atoms * 4))) return rc;
-    MD_WS(d_count, int, WS_AUX0, n_rows * 4);
-    MD_WS(d_mols, int, WS_OUT, n_rows * (size_t)cap * 4);
-    MD_HIP(hipMemsetAsync(d_count, 0, n_rows * 4, ctx->stream));
 
     const shell::Grid g = shell::sweep_grid(ctx, n_frames, n_centres, n_atoms);
     KernelTimer timer(ctx, 2);
     ctx->last_kernel = "shell_hits_kernel";
     hipLaunchKernelGGL(shell_hits_kernel, dim3(g.grid), dim3(shell::THREADS), 0, ctx->stream, in.xyz,
-                       (long long)n_atoms, in.box, in.centres, (int)n_centres, d_mol, r_cut_sq, (int)cap, g, d_mols, d_count);
+                       (long long)n_atoms, in.box, in.centres, (int)n_centres, d_mol, r_cut_sq, (int)cap, g, rs.idx, rs.count);
     MD_HIP(hipGetLastError());
-    const unsigned sort_grid = (unsigned)std::min<size_t>(n_rows, (size_t)ctx->cu_count * 32);
-    hipLaunchKernelGGL(shell_sort_kernel, dim3(sort_grid), dim3(64), (size_t)cap * 4, ctx->stream, d_mols, d_count,
-                       (long long)n_rows, (int)cap);
+    hipLaunchKernelGGL(shell_sort_kernel, dim3(rs.grid(ctx, 32)), dim3(64), (size_t)cap * 4, ctx->stream, rs.idx, rs.count,
+                       (long long)rs.n_rows, (int)cap);
     MD_HIP(hipGetLastError());
     timer.stop();
-    if ((rc = mdhip_result(cs, mols, d_mols, n_rows * (size_t)cap * 4, 0))) return rc;
-    if ((rc = mdhip_result(cs, count, d_count, n_rows * 4, 0))) return rc;
+    if ((rc = shell::row_results(cs, rs, mols, count))) return rc;
     return shell::finish(cs, timer);
 }
 

@@ -11,9 +11,8 @@
 //     is dropped when its molecule is the centre's own or fails the pass mask (the force filter's verdict, [F][M]),
 //     and, as in clusters.hip, unless it is the molecule's FIRST hit in id order. The lane walks the whole molecule
 //     once for both: whether an earlier atom is within r_shell too, and, per coordination class, the atoms with
-//     rsq < r_coord_sq: eight 8-bit counters in one 64-bit
-//     word (a molecule has at most 255 atoms, so no counter wraps). One atomicAdd on count[row] gives the record's
-//     slot; count is exact even past `cap`.
+//     rsq < r_coord_sq: eight 8-bit counters in one 64-bit word (a molecule has at most 255 atoms, so no counter
+//     wraps). shell::append gives the record's slot.
 //  2. coord_rank_kernel: one wave per (frame, centre) row puts the row's records in (molecule type, word, molecule)
 //     order (the keyed row pass of shell_search.h) and pads the row with -1 / ~0. A row then has one form whatever
 //     order the atomics landed in, and two rows are the same configuration exactly when their (type, word) sequences
@@ -52,12 +51,10 @@ struct CoordTable {
 __device__ __noinline__ void co_hit(const CoordTable *__restrict__ tab, long long f, size_t row, long long a)
 {
     const CoordTable &t = *tab;
-    const int m = t.mol_of[a], ci = t.centres[row - (size_t)f * (size_t)t.n_c];
-    if (m == t.mol_of[ci]) return;
+    const shell::Row r = shell::row_of(t.xyz, t.n, t.box, t.centres, f, (int)(row - (size_t)f * (size_t)t.n_c));
+    const int m = t.mol_of[a];
+    if (m == t.mol_of[r.ci]) return;
     if (t.passes && !t.passes[(size_t)f * (size_t)t.n_mols + (size_t)m]) return;
-    const double *px = t.xyz + (size_t)f * 3 * (size_t)t.n, *py = px + t.n, *pz = py + t.n;
-    const double Lx = t.box[3 * f], Ly = t.box[3 * f + 1], Lz = t.box[3 * f + 2];
-    const double cx = px[ci], cy = py[ci], cz = pz[ci];
     // one walk over the molecule, every load unconditional so that the loads of several atoms are in flight together
     // (a lane is alone here, and a chain of dependent loads per atom is what the block would wait for)
     const long long b0 = t.seg_off[m], b1 = t.seg_off[m + 1];
@@ -66,16 +63,13 @@ __device__ __noinline__ void co_hit(const CoordTable *__restrict__ tab, long lon
     bool earlier = false;
     for (long long b = b0; b < b1; ++b) {
         const unsigned c = t.cls[b];
-        const double r = shell::rsq(cx, cy, cz, px[b], py[b], pz[b], Lx, Ly, Lz);
-        earlier |= b < a && r < rs2;
-        word += (c != NO_CLASS && r < rc2) ? 1ull << (8u * (c & 7u)) : 0ull;
+        const double d2 = shell::rsq(r.cx, r.cy, r.cz, r.px[b], r.py[b], r.pz[b], r.Lx, r.Ly, r.Lz);
+        earlier |= b < a && d2 < rs2;
+        word += (c != NO_CLASS && d2 < rc2) ? 1ull << (8u * (c & 7u)) : 0ull;
     }
     if (earlier) return;  // (that atom's lane appends the molecule)
-    const int slot = atomicAdd(&t.count[row], 1);
-    if (slot < t.cap) {
-        t.mols[row * (size_t)t.cap + (size_t)slot] = m;
-        t.words[row * (size_t)t.cap + (size_t)slot] = word;
-    }
+    const int slot = shell::append(t.count, t.mols, row, t.cap, m);
+    if (slot >= 0) t.words[row * (size_t)t.cap + (size_t)slot] = word;
 }
 
 __global__ __launch_bounds__(shell::THREADS) void coord_hits_kernel(
@@ -83,9 +77,7 @@ __global__ __launch_bounds__(shell::THREADS) void coord_hits_kernel(
     int n_c, double rs2, shell::Grid g, const CoordTable *__restrict__ tab)
 {
     shell::sweep(xyz, n, centres, n_c, xyz, 3, n, box, rs2, g,
-                 [=](long long f, size_t row, long long a, double, double, double, double, double, double) {
-                     co_hit(tab, f, row, a);
-                 });
+                 [=](const shell::Row &r, size_t row, long long a) { co_hit(tab, r.f, row, a); });
 }
 
 // One wave per row; LDS: the row [cap] (16-byte records).
@@ -127,9 +119,12 @@ int mdhip_shell_coordination(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, 
     if (!ctx) return MDHIP_EINVAL;
     CallScope cs(ctx);
     MD_REQUIRE(n_frames >= 0 && n_atoms >= 0 && n_centres >= 0 && n_mols >= 0, "negative sizes");
-    MD_REQUIRE(cap >= 1 && cap <= shell::MAX_KEYED_CAP, "cap must be in [1, %d]: a row of more records does not fit in LDS",
-               shell::MAX_KEYED_CAP);
-    if (n_frames == 0 || n_centres == 0) return cs.end();
+    shell::RowSet rs;
+    int rc;
+    if ((rc = shell::take_rows(ctx, n_frames, n_centres, cap, shell::MAX_KEYED_CAP, rs,
+                               ": a row of more records does not fit in LDS")))
+        return rc;
+    if (rs.n_rows == 0) return cs.end();
     MD_REQUIRE(mol_of && seg_off && mol_type && cls && mols && words && count, "NULL array");
     // the kernels index seg_off, mol_type and passes by mol_of, and shift by the class: all of it checked here
     MD_REQUIRE(n_mols > 0 && n_mols < (1ll << 31), "the number of molecules must be in [1, 2^31)");
@@ -147,10 +142,8 @@ int mdhip_shell_coordination(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, 
         MD_REQUIRE(cls[a] == NO_CLASS || cls[a] < MAX_CLASSES, "atom %lld: class %d (at most %d classes, or 255)",
                    (long long)a, (int)cls[a], MAX_CLASSES);
     shell::Inputs in;
-    int rc;
     if ((rc = shell::stage(ctx, "centre", n_frames, n_atoms, xyz, xyz_on_device, box, n_centres, centres, in)))
         return rc;
-    const size_t n_rows = (size_t)n_frames * (size_t)n_centres;
     MD_WS(d_mol, int, WS_TYPE_J, (size_t)n_atoms * 4);
     if ((rc = mdhip_h2d_small(ctx, d_mol, mol_of, (size_t)n_atoms * 4))) return rc;
     MD_WS(d_off, long long, WS_TABLES, ((size_t)n_mols + 1) * 8);
@@ -165,14 +158,11 @@ int mdhip_shell_coordination(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, 
         if ((rc = mdhip_h2d_small(ctx, d_p, passes, (size_t)n_frames * (size_t)n_mols))) return rc;
         d_pass = d_p;
     }
-    MD_WS(d_count, int, WS_AUX0, n_rows * 4);
-    MD_WS(d_mols, int, WS_OUT, n_rows * (size_t)cap * 4);
-    MD_WS(d_words, unsigned long long, WS_OUT2, n_rows * (size_t)cap * 8);
-    MD_HIP(hipMemsetAsync(d_count, 0, n_rows * 4, ctx->stream));
+    MD_WS(d_words, unsigned long long, WS_OUT2, rs.n_rows * (size_t)cap * 8);
 
     const shell::Grid g = shell::sweep_grid(ctx, n_frames, n_centres, n_atoms);
     const CoordTable table{in.xyz, in.box, in.centres, d_mol, d_off, d_cls, d_pass, (long long)n_atoms, (long long)n_mols,
-                           r_shell_sq, r_coord_sq, (int)n_centres, (int)cap, d_mols, d_count, d_words};
+                           r_shell_sq, r_coord_sq, (int)n_centres, (int)cap, rs.idx, rs.count, d_words};
     MD_WS(d_table, CoordTable, WS_MISC, sizeof(CoordTable));
     if ((rc = mdhip_h2d_small(ctx, d_table, &table, sizeof(CoordTable)))) return rc;
     KernelTimer timer(ctx, 2);
@@ -180,14 +170,12 @@ int mdhip_shell_coordination(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, 
     hipLaunchKernelGGL(coord_hits_kernel, dim3(g.grid), dim3(shell::THREADS), 0, ctx->stream, in.xyz,
                        (long long)n_atoms, in.box, in.centres, (int)n_centres, r_shell_sq, g, d_table);
     MD_HIP(hipGetLastError());
-    const unsigned rank_grid = (unsigned)std::min<size_t>(n_rows, (size_t)ctx->cu_count * 32);
-    hipLaunchKernelGGL(coord_rank_kernel, dim3(rank_grid), dim3(64), (size_t)cap * 16, ctx->stream, d_mols, d_words,
-                       d_count, d_type, (long long)n_rows, (int)cap);
+    hipLaunchKernelGGL(coord_rank_kernel, dim3(rs.grid(ctx, 32)), dim3(64), (size_t)cap * 16, ctx->stream, rs.idx,
+                       d_words, rs.count, d_type, (long long)rs.n_rows, (int)cap);
     MD_HIP(hipGetLastError());
     timer.stop();
-    if ((rc = mdhip_result(cs, mols, d_mols, n_rows * (size_t)cap * 4, 0))) return rc;
-    if ((rc = mdhip_result(cs, words, d_words, n_rows * (size_t)cap * 8, 0))) return rc;
-    if ((rc = mdhip_result(cs, count, d_count, n_rows * 4, 0))) return rc;
+    if ((rc = mdhip_result(cs, words, d_words, rs.n_rows * (size_t)cap * 8, 0))) return rc;
+    if ((rc = shell::row_results(cs, rs, mols, count))) return rc;
     return shell::finish(cs, timer);
 }
 

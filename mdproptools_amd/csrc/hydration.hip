@@ -11,8 +11,7 @@
 //     group sum, (0 + H1) + H2.
 //  2. hy_search_kernel<COUNTS>: the sweep of shell_search.h, every cation against the O of every water of its frame
 //     (the |d| form of the wrap: the same rsq as d - sign(d) L). What a hit (rare) does:
-//       list mode: the water index is appended to the row (frame, cation); count stays exact past `cap` (the host then
-//         re-runs the frames that overflowed with a larger cap);
+//       list mode: the water index is appended to the row (frame, cation) (shell::append);
 //       counts mode: the cosine is computed at once; n_water, n_away (cos < cos_cut) per row and an exact histogram
 //         (bin trunc((cos + 1) / w) clamped to n_bins - 1, NaN in no bin) kept per block in LDS, added to the global
 //         uint64 bins once per block.
@@ -32,20 +31,13 @@ namespace {
 
 constexpr int HY_MAX_BINS = 4096;  // the counts pass keeps its histogram in LDS (32 KB)
 
-// the signed wrap itself (the cosine needs the direction): d - sign(d) L when d > L/2 or d < -L/2
-__device__ __forceinline__ double hy_wrap(double d, double L)
-{
-    const double h = 0.5 * L;
-    return d > h ? d - L : (d < -h ? d + L : d);
-}
-
 // cosine of (cation - O, wrapped) and v of water w of the frame's planes p (ox oy oz vx vy vz, each n_w long)
 __device__ __noinline__ double hy_cos(double cx, double cy, double cz, const double *__restrict__ p, long long n_w,
                                       long long w, double Lx, double Ly, double Lz)
 {
-    const double dx = hy_wrap(cx - p[w], Lx);
-    const double dy = hy_wrap(cy - p[n_w + w], Ly);
-    const double dz = hy_wrap(cz - p[2 * n_w + w], Lz);
+    const double dx = shell::wrap_signed(cx - p[w], Lx);
+    const double dy = shell::wrap_signed(cy - p[n_w + w], Ly);
+    const double dz = shell::wrap_signed(cz - p[2 * n_w + w], Lz);
     const double vx = p[3 * n_w + w], vy = p[4 * n_w + w], vz = p[5 * n_w + w];
     const double dot = ((0.0 + dx * vx) + dy * vy) + dz * vz;
     const double n1 = __builtin_sqrt((dx * dx + dy * dy) + dz * dz);
@@ -96,10 +88,10 @@ __global__ __launch_bounds__(shell::THREADS) void hy_search_kernel(
         __syncthreads();
     }
     shell::sweep(xyz, n, cations, n_c, wat, 6, n_w, box, rc2, g,
-                 [=](long long f, size_t row, long long w, double cx, double cy, double cz, double Lx, double Ly,
-                     double Lz) {
+                 [=](const shell::Row &r, size_t row, long long w) {
                      if constexpr (COUNTS) {
-                         const double c = hy_cos(cx, cy, cz, wat + (size_t)f * 6 * (size_t)n_w, n_w, w, Lx, Ly, Lz);
+                         const double c = hy_cos(r.cx, r.cy, r.cz, wat + (size_t)r.f * 6 * (size_t)n_w, n_w, w, r.Lx,
+                                                 r.Ly, r.Lz);
                          atomicAdd(&o.count[row], 1);
                          if (c < o.cos_cut) atomicAdd(&o.n_away[row], 1);
                          if (c == c) {
@@ -108,8 +100,7 @@ __global__ __launch_bounds__(shell::THREADS) void hy_search_kernel(
                              atomicAdd(&s_hist[b], 1ull);
                          }
                      } else {
-                         const int slot = atomicAdd(&o.count[row], 1);
-                         if (slot < o.cap) o.idx[row * (size_t)o.cap + (size_t)slot] = (int)w;
+                         shell::append(o.count, o.idx, row, o.cap, (int)w);
                      }
                  });
     if constexpr (COUNTS) {
@@ -127,19 +118,15 @@ __global__ __launch_bounds__(64) void hy_row_kernel(const double *__restrict__ x
                                                     double *__restrict__ cosv, long long n_rows, int cap)
 {
     for (long long row = blockIdx.x; row < n_rows; row += gridDim.x) {
-        const long long f = row / n_c;
-        const int ci = cations[row % n_c];
-        const double *px = xyz + (size_t)f * 3 * (size_t)n;
-        const double *pw = wat + (size_t)f * 6 * (size_t)n_w;
-        const double Lx = box[3 * f], Ly = box[3 * f + 1], Lz = box[3 * f + 2];
-        const double cx = px[ci], cy = px[n + ci], cz = px[2 * n + ci];
+        const shell::Row c = shell::row_of(xyz, n, box, cations, row / n_c, (int)(row % n_c));
+        const double *pw = wat + (size_t)c.f * 6 * (size_t)n_w;
         int *r = idx + (size_t)row * (size_t)cap;
         double *o = cosv + (size_t)row * (size_t)cap;
         shell::rank_row(
             r, count[row], cap,
             [&](int rank, int v) {
                 r[rank] = v;
-                o[rank] = hy_cos(cx, cy, cz, pw, n_w, v, Lx, Ly, Lz);
+                o[rank] = hy_cos(c.cx, c.cy, c.cz, pw, n_w, v, c.Lx, c.Ly, c.Lz);
             },
             [&](int i) {
                 r[i] = -1;
@@ -162,9 +149,7 @@ int hy_stage(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xy
     if ((rc = shell::stage(ctx, "cation", n_frames, n_atoms, xyz, xyz_on_device, box, n_cations, cations, in)))
         return rc;
     MD_REQUIRE(waters || n_waters == 0, "NULL array");
-    for (int32_t w = 0; w < n_waters; ++w)
-        MD_REQUIRE(waters[w] >= 0 && (int64_t)waters[w] + 2 < n_atoms, "water %d: atoms %d..%d out of range", (int)w,
-                   (int)waters[w], (int)waters[w] + 2);
+    if ((rc = shell::check_indices(ctx, "water", n_waters, waters, 3, n_atoms))) return rc;
     if (n_waters == 0) return MDHIP_OK;
     MD_WS(d_widx, int, WS_TYPE_J, (size_t)n_waters * 4);
     if ((rc = mdhip_h2d_small(ctx, d_widx, waters, (size_t)n_waters * 4))) return rc;
@@ -205,32 +190,27 @@ int mdhip_hydration_cosines(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, c
     if (!ctx) return MDHIP_EINVAL;
     CallScope cs(ctx);
     MD_REQUIRE(n_frames >= 0 && n_atoms >= 0 && n_cations >= 0 && n_waters >= 0, "negative sizes");
-    MD_REQUIRE(cap >= 1 && cap <= shell::MAX_CAP, "cap must be in [1, %d]", shell::MAX_CAP);
-    if (n_frames == 0 || n_cations == 0) return cs.end();
+    shell::RowSet rs;
+    int rc;
+    if ((rc = shell::take_rows(ctx, n_frames, n_cations, cap, shell::MAX_CAP, rs))) return rc;
+    if (rs.n_rows == 0) return cs.end();
     MD_REQUIRE(idx && cosines && count, "NULL array");
     HyInputs in;
-    int rc;
     if ((rc = hy_stage(ctx, n_frames, n_atoms, xyz, xyz_on_device, box, n_cations, cations, n_waters, waters, in)))
         return rc;
-    const size_t n_rows = (size_t)n_frames * (size_t)n_cations;
-    MD_WS(d_count, int, WS_AUX0, n_rows * 4);
-    MD_WS(d_idx, int, WS_OUT, n_rows * (size_t)cap * 4);
-    MD_WS(d_cos, double, WS_OUT2, n_rows * (size_t)cap * 8);
-    MD_HIP(hipMemsetAsync(d_count, 0, n_rows * 4, ctx->stream));
+    MD_WS(d_cos, double, WS_OUT2, rs.n_rows * (size_t)cap * 8);
     KernelTimer timer(ctx, 3);
     ctx->last_kernel = "hy_search_kernel<false>";
     if ((rc = hy_launch<false>(ctx, n_frames, n_atoms, n_cations, n_waters, in, r_cut_sq, 0,
-                               HyList{(int)cap, d_idx, d_count})))
+                               HyList{(int)cap, rs.idx, rs.count})))
         return rc;
-    const unsigned row_grid = (unsigned)std::min<size_t>(n_rows, (size_t)ctx->cu_count * 32);
-    hipLaunchKernelGGL(hy_row_kernel, dim3(row_grid), dim3(64), (size_t)cap * 4, ctx->stream, in.xyz,
-                       (long long)n_atoms, in.wat, (long long)n_waters, in.box, in.centres, (int)n_cations, d_idx, d_count,
-                       d_cos, (long long)n_rows, (int)cap);
+    hipLaunchKernelGGL(hy_row_kernel, dim3(rs.grid(ctx, 32)), dim3(64), (size_t)cap * 4, ctx->stream, in.xyz,
+                       (long long)n_atoms, in.wat, (long long)n_waters, in.box, in.centres, (int)n_cations, rs.idx, rs.count,
+                       d_cos, (long long)rs.n_rows, (int)cap);
     MD_HIP(hipGetLastError());
     timer.stop();
-    if ((rc = mdhip_result(cs, idx, d_idx, n_rows * (size_t)cap * 4, 0))) return rc;
-    if ((rc = mdhip_result(cs, cosines, d_cos, n_rows * (size_t)cap * 8, 0))) return rc;
-    if ((rc = mdhip_result(cs, count, d_count, n_rows * 4, 0))) return rc;
+    if ((rc = mdhip_result(cs, cosines, d_cos, rs.n_rows * (size_t)cap * 8, 0))) return rc;
+    if ((rc = shell::row_results(cs, rs, idx, count))) return rc;
     return shell::finish(cs, timer);
 }
 

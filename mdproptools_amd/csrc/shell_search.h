@@ -1,9 +1,16 @@
-// shell_search.h — the per-centre shell search that clusters.hip and hydration.hip share: for each centre atom of each
-// frame, every candidate point within r_cut under the reference's single-wrap rsq (rdf_cn.py:44-57), handed to a
-// functor; and the row pass that puts what a row collected in ascending order.
+// shell_search.h — the per-centre shell search and what its four consumers do around it. For each centre atom of each
+// frame, the sweep hands every candidate point within r_cut under the reference's single-wrap rsq (rdf_cn.py:44-57) to
+// a functor. All four run the sweep, append hits to capped rows (append; on the host RowSet) and begin and end their
+// entry points with stage and finish. Beyond that:
+//   clusters.hip        every atom a candidate, rows of molecules; rank_row puts them in order
+//   configurations.hip  every atom a candidate, rows of (molecule, word) records; row_of in its hit, rank_row_keyed
+//   hydration.hip       the water O (check_indices) as candidates; wrap_signed for the cosines; row_of and rank_row
+//                       in its row pass; its counts mode keeps no rows (plain counters)
+//   angles.hip          gathered candidates (check_indices); wrap_signed; row_of in its pair pass; finish with the
+//                       search's aux timer
 // The reference's arithmetic is unfused: an including .hip puts `#pragma clang fp contract(off)` AHEAD of this include
-// (it has to be in force where wrap_abs / rsq are instantiated). residence.hip (rt_wrap_abs) and pair_common.h
-// (wrap_abs) keep copies of the wrap: the committed counter runs are tied to those files byte for byte.
+// (it has to be in force where wrap_abs / wrap_signed / rsq are instantiated). residence.hip (rt_wrap_abs) and
+// pair_common.h (wrap_abs) keep copies of the wrap: the committed counter runs are tied to those files byte for byte.
 #pragma once
 
 #include <algorithm>
@@ -37,6 +44,44 @@ __device__ __forceinline__ double rsq(double cx, double cy, double cz, double x,
     return (ax * ax + ay * ay) + az * az;
 }
 
+// the signed wrap itself (a cosine needs the direction): d - sign(d) L when d > L/2 or d < -L/2
+__device__ __forceinline__ double wrap_signed(double d, double L)
+{
+    const double h = 0.5 * L;
+    return d > h ? d - L : (d < -h ? d + L : d);
+}
+
+// A row: centre c (atom ci) of frame f, with the frame's three coordinate planes [n], its box edges and the centre's
+// coordinates. Plain pointers and doubles: it lives in registers and is never handed to a call that is not inlined.
+struct Row {
+    long long f;
+    int c, ci;
+    const double *px, *py, *pz;
+    double Lx, Ly, Lz, cx, cy, cz;
+};
+
+__device__ __forceinline__ Row row_of(const double *__restrict__ xyz, long long n, const double *__restrict__ box,
+                                      const int *__restrict__ centres, long long f, int c)
+{
+    Row r;
+    r.f = f, r.c = c, r.ci = centres[c];
+    r.px = xyz + (size_t)f * 3 * (size_t)n, r.py = r.px + n, r.pz = r.py + n;
+    r.Lx = box[3 * f], r.Ly = box[3 * f + 1], r.Lz = box[3 * f + 2];
+    r.cx = r.px[r.ci], r.cy = r.py[r.ci], r.cz = r.pz[r.ci];
+    return r;
+}
+
+// The capped append: v goes to the next slot of idx[row][cap]. Returns the slot, or -1 when the row is full: count[row]
+// stays exact past `cap` (every hit adds to it), which is how the host learns that a row overflowed and by how much, and
+// runs it again with a larger cap.
+__device__ __forceinline__ int append(int *__restrict__ count, int *__restrict__ idx, size_t row, int cap, int v)
+{
+    const int slot = atomicAdd(&count[row], 1);
+    if (slot >= cap) return -1;
+    idx[row * (size_t)cap + (size_t)slot] = v;
+    return slot;
+}
+
 // the sweep's steps (host: sweep_grid) and the blocks that share them
 struct Grid {
     long long n_tiles, n_chunks, n_blocks;
@@ -47,7 +92,7 @@ struct Grid {
 // flattened block index (no launch dimension grows with the frames). Centres: atoms centres[0 .. n_c) of the planes
 // xyz[f][3][n]; candidates: the first three of the planes cand[f][cand_planes][n_cand]. The tile's centre coordinates
 // are wave-uniform loads; the lanes walk the chunk on coalesced planes and test each candidate against every centre
-// of the tile, strictly rsq < rc2. Per hit (rare): hit(f, row = f * n_c + centre, candidate, cx, cy, cz, Lx, Ly, Lz).
+// of the tile, strictly rsq < rc2. Per hit (rare): hit(the centre's Row, row = f * n_c + centre, candidate).
 template <class Hit>
 __device__ __forceinline__ void sweep(const double *__restrict__ xyz, long long n, const int *__restrict__ centres,
                                       int n_c, const double *__restrict__ cand, int cand_planes, long long n_cand,
@@ -56,19 +101,18 @@ __device__ __forceinline__ void sweep(const double *__restrict__ xyz, long long 
     for (long long blk = blockIdx.x; blk < g.n_blocks; blk += gridDim.x) {
         const long long chunk = blk % g.n_chunks, rest = blk / g.n_chunks;
         const long long tile = rest % g.n_tiles, f = rest / g.n_tiles;
-        const double *px = xyz + (size_t)f * 3 * (size_t)n, *py = px + n, *pz = py + n;
-        const double *qx = cand + (size_t)f * (size_t)cand_planes * (size_t)n_cand, *qy = qx + n_cand,
-                     *qz = qy + n_cand;
-        const double Lx = box[3 * f], Ly = box[3 * f + 1], Lz = box[3 * f + 2];
         const int c0 = (int)tile * TC;
         const int nc = n_c - c0 < TC ? n_c - c0 : TC;
+        const Row r0 = row_of(xyz, n, box, centres, f, c0);  // (the frame's planes and box; centre k = 0)
+        const double *qx = cand + (size_t)f * (size_t)cand_planes * (size_t)n_cand, *qy = qx + n_cand,
+                     *qz = qy + n_cand;
         double cx[TC], cy[TC], cz[TC];
 #pragma unroll
         for (int k = 0; k < TC; ++k) {
             const int ci = centres[k < nc ? c0 + k : c0];  // (a short last tile repeats its first centre; hits masked)
-            cx[k] = px[ci];
-            cy[k] = py[ci];
-            cz[k] = pz[ci];
+            cx[k] = r0.px[ci];
+            cy[k] = r0.py[ci];
+            cz[k] = r0.pz[ci];
         }
         const long long a_end = (chunk + 1) * CHUNK < n_cand ? (chunk + 1) * CHUNK : n_cand;
         for (long long a = chunk * CHUNK + threadIdx.x; a < a_end; a += THREADS) {
@@ -76,13 +120,12 @@ __device__ __forceinline__ void sweep(const double *__restrict__ xyz, long long 
             unsigned hits = 0;
 #pragma unroll
             for (int k = 0; k < TC; ++k)
-                if (rsq(cx[k], cy[k], cz[k], x, y, z, Lx, Ly, Lz) < rc2) hits |= 1u << k;
+                if (rsq(cx[k], cy[k], cz[k], x, y, z, r0.Lx, r0.Ly, r0.Lz) < rc2) hits |= 1u << k;
             hits &= (nc >= 32 ? ~0u : (1u << nc) - 1u);
             while (__builtin_expect(hits != 0, 0)) {  // (rare: a few candidates per centre in a whole frame)
                 const int k = __builtin_ctz(hits);
                 hits &= hits - 1u;
-                const int ci = centres[c0 + k];
-                hit(f, (size_t)f * (size_t)n_c + (size_t)(c0 + k), a, px[ci], py[ci], pz[ci], Lx, Ly, Lz);
+                hit(row_of(xyz, n, box, centres, f, c0 + k), (size_t)f * (size_t)n_c + (size_t)(c0 + k), a);
             }
         }
     }
@@ -145,6 +188,18 @@ struct Inputs {  // on the device
     const int *centres = nullptr;
 };
 
+// A table of atom indices from the caller: entry k names the atoms idx[k] .. idx[k] + span - 1.
+inline int check_indices(mdhip_ctx *ctx, const char *noun, int32_t n, const int32_t *idx, int span, int64_t n_atoms)
+{
+    for (int32_t k = 0; k < n; ++k) {
+        const bool ok = idx[k] >= 0 && (int64_t)idx[k] + span - 1 < n_atoms;
+        if (span > 1)
+            MD_REQUIRE(ok, "%s %d: atoms %d..%d out of range", noun, (int)k, (int)idx[k], (int)idx[k] + span - 1);
+        MD_REQUIRE(ok, "%s %d: atom index %d out of range", noun, (int)k, (int)idx[k]);
+    }
+    return MDHIP_OK;
+}
+
 // What every entry point checks and stages (no launch); `noun` names a centre in the error texts.
 inline int stage(mdhip_ctx *ctx, const char *noun, int64_t n_frames, int64_t n_atoms, const double *xyz,
                  int xyz_on_device, const double *box, int32_t n_centres, const int32_t *centres, Inputs &in)
@@ -152,11 +207,9 @@ inline int stage(mdhip_ctx *ctx, const char *noun, int64_t n_frames, int64_t n_a
     MD_REQUIRE(n_atoms > 0, "%ss without atoms", noun);
     MD_REQUIRE(xyz && box && centres, "NULL array");
     MD_REQUIRE(n_atoms < (1ll << 31), "at most 2^31 - 1 atoms");
-    for (int32_t c = 0; c < n_centres; ++c)
-        MD_REQUIRE(centres[c] >= 0 && centres[c] < n_atoms, "%s %d: atom index %d out of range", noun, (int)c,
-                   (int)centres[c]);
-    MD_HIP(hipSetDevice(ctx->device));
     int rc;
+    if ((rc = check_indices(ctx, noun, n_centres, centres, 1, n_atoms))) return rc;
+    MD_HIP(hipSetDevice(ctx->device));
     in.xyz = (const double *)mdhip_stage(ctx, WS_XYZ_I, xyz, (size_t)n_frames * 3 * (size_t)n_atoms * 8,
                                          xyz_on_device, &rc);
     if (rc) return rc;
@@ -175,10 +228,48 @@ inline Grid sweep_grid(const mdhip_ctx *ctx, int64_t n_frames, int32_t n_centres
     return {n_tiles, n_chunks, n_blocks, (unsigned)std::min<long long>(n_blocks, (long long)ctx->cu_count * 64)};
 }
 
-// The end of an entry point whose launches ran under `timer`: the time is read when the call completes.
-inline int finish(CallScope &cs, const KernelTimer &timer)
+// The rows of a capped call on the device: count [n_rows] (WS_AUX0), zeroed, and the row buffer idx [n_rows][cap]
+// (WS_OUT).
+struct RowSet {
+    size_t n_rows = 0;
+    int cap = 0;
+    int *count = nullptr, *idx = nullptr;
+    // blocks of a row pass: one row at a time each, `per_cu` of them on a CU
+    unsigned grid(const mdhip_ctx *ctx, int per_cu) const { return (unsigned)std::min(n_rows, (size_t)ctx->cu_count * per_cu); }
+};
+
+// Checks `cap` against the caller's limit (`why`: what the limit is for, appended to the error text) and takes the
+// buffers; a call without rows takes none.
+inline int take_rows(mdhip_ctx *ctx, int64_t n_frames, int32_t n_centres, int32_t cap, int max_cap, RowSet &rs,
+                     const char *why = "")
 {
-    cs.defer([timer]() {
+    MD_REQUIRE(cap >= 1 && cap <= max_cap, "cap must be in [1, %d]%s", max_cap, why);
+    rs.n_rows = (size_t)n_frames * (size_t)n_centres;
+    rs.cap = (int)cap;
+    if (rs.n_rows == 0) return MDHIP_OK;
+    MD_HIP(hipSetDevice(ctx->device));
+    MD_WS(d_count, int, WS_AUX0, rs.n_rows * 4);
+    MD_WS(d_idx, int, WS_OUT, rs.n_rows * (size_t)cap * 4);
+    MD_HIP(hipMemsetAsync(d_count, 0, rs.n_rows * 4, ctx->stream));
+    rs.count = d_count;
+    rs.idx = d_idx;
+    return MDHIP_OK;
+}
+
+// Queues the rows' results: idx (unless the caller has no use for the rows themselves: nullptr) and count.
+inline int row_results(CallScope &cs, const RowSet &rs, int32_t *idx, int32_t *count)
+{
+    int rc;
+    if (idx && (rc = mdhip_result(cs, idx, rs.idx, rs.n_rows * (size_t)rs.cap * 4, 0))) return rc;
+    return mdhip_result(cs, count, rs.count, rs.n_rows * 4, 0);
+}
+
+// The end of an entry point whose launches ran under `timer` (and some of them under `aux`, whose time becomes the
+// call's aux time): the times are read when the call completes.
+inline int finish(CallScope &cs, const KernelTimer &timer, const KernelTimer *aux = nullptr)
+{
+    cs.defer([timer, has_aux = aux != nullptr, a = aux ? *aux : timer]() {
+        if (has_aux) timer.ctx->last_aux_ms = a.collect();
         timer.collect();
         return MDHIP_OK;
     });

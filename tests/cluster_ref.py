@@ -78,6 +78,35 @@ def shell(xyz, lengths, p, mol_of, r_cut_sq):
     return np.unique(mol_of[rsq(xyz[:, p], xyz, lengths) < r_cut_sq])
 
 
+def chunk_straddling_system(rng, n_frames=2, L=(40.0, 41.0, 42.0)):
+    """
+    A uniform random system of about 4 150 atoms in ragged molecules, built around atom 4096: the first candidate of the
+    second chunk of the shell sweep (shell::CHUNK of csrc/shell_search.h). Molecule K owns the atoms 4094..4097, on both
+    sides of the chunk edge. Of the 17 centres (one more than a tile), in the last frame, the first (atom 5) is 1.0 and
+    0.5 away from atoms 4095 and 4096 of K and 5.0 from the other two; the last (the last atom) is 1.0 away from atom
+    4097 and at least 6.5 from the others. With a cutoff of 3, K is a first hit at 4095 and a later hit at 4096, on
+    either side of the edge, for the one, and a first hit behind the edge for the other.
+    -> (xyz [F, 3, N], box [F, 3], mol_of [N], seg_off [M + 1], centres [17], K)
+    """
+    sizes = rng.integers(1, 9, 2000)
+    sizes = sizes[:np.searchsorted(np.cumsum(sizes), 4094, side="right")]
+    sizes = np.concatenate((sizes, [4094 - sizes.sum()] if sizes.sum() < 4094 else [], [4], rng.integers(1, 9, 10)))
+    sizes = sizes.astype(np.int64)
+    seg_off = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+    mol_of = np.repeat(np.arange(len(sizes)), sizes).astype(np.int32)
+    K = int(mol_of[4094])
+    assert seg_off[K] == 4094 and seg_off[K + 1] == 4098
+    N = len(mol_of)
+    box = np.tile(np.asarray(L, dtype=np.float64), (n_frames, 1))
+    xyz = rng.uniform(0, 1, (n_frames, 3, N)) * box[0][None, :, None]
+    last = xyz[-1]
+    for a, x in ((4094, 10.0), (4095, 14.0), (4096, 14.5), (4097, 20.0), (5, 15.0), (N - 1, 21.0)):
+        last[:, a] = [x, 10.0, 10.0]
+    others = 6 + rng.choice(4094 - 6, 15, replace=False)
+    centres = np.concatenate(([5], others, [N - 1])).astype(np.int32)
+    return xyz, box, mol_of, seg_off, centres, K
+
+
 def padded(i, n):
     return "0" * (len(str(n)) - len(str(i))) + str(i)
 

@@ -161,6 +161,18 @@ def test_shell_members_uniform_and_overflow(B):
     _check(m3, c3, want)
 
 
+def test_shell_members_across_a_chunk_edge(B):
+    xyz, box, mol_of, _, centres, K = R.chunk_straddling_system(np.random.default_rng(5))
+    rc2 = 3.0 ** 2
+    hits = [np.flatnonzero(R.rsq(xyz[1][:, p], xyz[1], box[1])[4094:4098] < rc2) + 4094 for p in centres[[0, 16]]]
+    assert hits[0].tolist() == [4095, 4096] and hits[1].tolist() == [4097]
+    want = _oracle_shells(xyz, box, centres, mol_of, rc2)
+    for cap in (B.SHELL_CAP, 1):  # the default, and every row with more than one molecule re-run
+        mols, count = B.shell_members(xyz, box, centres, mol_of, rc2, cap=cap)
+        _check(mols, count, want)
+        assert (mols[1, 0] == K).sum() == 1 and (mols[1, 16] == K).sum() == 1
+
+
 def test_shell_members_past_launch_limit(B):
     F = 65535 * 2 + 3
     rng = np.random.default_rng(3)

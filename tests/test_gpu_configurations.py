@@ -188,6 +188,27 @@ def test_shell_coordination_overflow(B):
     _check(*B.shell_coordination(torch.from_numpy(xyz).cuda(), *args, passes=passes, cap=3), want)
 
 
+def test_shell_coordination_across_a_chunk_edge(B):
+    rng = np.random.default_rng(5)
+    xyz, box, mol_of, seg_off, centres, K = R.chunk_straddling_system(rng)
+    n_mols = len(seg_off) - 1
+    mol_type = rng.integers(1, 4, n_mols).astype(np.int32)
+    cls = rng.choice(np.array([0, 1, 2, 0xFF], dtype=np.uint8), len(mol_of))
+    cls[4094:4098] = [0, 1, 2, 1]
+    passes = rng.uniform(size=(2, n_mols)) < 0.7
+    passes[:, K] = True
+    rs2, rc2 = 3.0 ** 2, 2.0 ** 2
+    hits = [np.flatnonzero(R.rsq(xyz[1][:, p], xyz[1], box[1])[4094:4098] < rs2) + 4094 for p in centres[[0, 16]]]
+    assert hits[0].tolist() == [4095, 4096] and hits[1].tolist() == [4097]
+    want = CR.coordination_rows(xyz, box, centres, mol_of, seg_off, mol_type, cls, rs2, rc2, passes)
+    assert (K, (1 << 8) + (1 << 16)) in want[1][0] and (K, 1 << 8) in want[1][16]
+    for cap in (B.SHELL_CAP, 1):  # the default, and every row with more than one record re-run
+        mols, words, count = B.shell_coordination(xyz, box, centres, mol_of, seg_off, mol_type, cls, rs2, rc2,
+                                                  passes=passes, cap=cap)
+        _check(mols, words, count, want)
+        assert (mols[1, 0] == K).sum() == 1 and (mols[1, 16] == K).sum() == 1
+
+
 def test_shell_coordination_past_launch_limit(B):
     F = 65535 * 2 + 3
     rng = np.random.default_rng(3)

@@ -126,10 +126,7 @@ def test_random_systems_with_edges(B):
         assert c in sel
 
 
-def test_counts_match_lists_and_restatement(B):
-    rng = np.random.default_rng(11)
-    xyz, box, ions, wat = _system(rng, 4, 37, 900, [16.0, 16.0, 6.0])
-    idx, cos, count = B.hydration_cosines(xyz, box, ions, wat, 3.5 ** 2)
+def _check_counts(B, xyz, box, ions, wat, cos, count):
     n_water, n_away, hist = B.hydration_counts(xyz, box, ions, wat, 3.5 ** 2, -0.72, 0.02, 100)
     assert np.array_equal(n_water, count)
     valid = np.arange(cos.shape[2])[None, None, :] < count[:, :, None]
@@ -138,8 +135,30 @@ def test_counts_match_lists_and_restatement(B):
     c = c[~np.isnan(c)]
     want = np.bincount(np.clip(np.trunc((c + 1.0) / 0.02).astype(np.int64), 0, 99), minlength=100)
     assert np.array_equal(hist.astype(np.int64), want)
-    rw, ra, rh = R.counts(_frames(xyz, box), 1, 2, 3.5, [37, 900], [1, 3])
+    rw, ra, rh = R.counts(_frames(xyz, box), 1, 2, 3.5, [len(ions), len(wat)], [1, 3])
     assert np.array_equal(n_water, rw) and np.array_equal(n_away, ra) and np.array_equal(hist.astype(np.int64), rh)
+
+
+def test_counts_match_lists_and_restatement(B):
+    rng = np.random.default_rng(11)
+    xyz, box, ions, wat = _system(rng, 4, 37, 900, [16.0, 16.0, 6.0])
+    _, cos, count = B.hydration_cosines(xyz, box, ions, wat, 3.5 ** 2)
+    _check_counts(B, xyz, box, ions, wat, cos, count)
+
+
+def test_waters_past_one_chunk(B):
+    """4097 waters: the O of the last one is candidate 4096, the first of the sweep's second chunk (shell::CHUNK of
+    csrc/shell_search.h). The last cation (alone in the short last tile of centres) has the last two waters in its
+    row: candidates of both chunks, appended by different blocks."""
+    rng = np.random.default_rng(13)
+    xyz, box, ions, wat = _system(rng, 2, 17, 4097, [16.0, 16.0, 6.0], edges=False)
+    xyz[1][:, ions[16]] = [8.0, 8.0, 3.0]
+    xyz[1][:, wat[4095]] = [9.0, 8.0, 3.0]
+    xyz[1][:, wat[4096]] = [8.0, 9.5, 3.0]
+    idx, cos, count, _ = _check_lists(B, xyz, box, ions, wat, 3.5, cap=4)  # every row overflows and is re-run
+    row = idx[1, 16, :count[1, 16]]
+    assert 4095 in row and 4096 in row and (row < 4095).any()
+    _check_counts(B, xyz, box, ions, wat, cos, count)
 
 
 def test_a_million_cosines_against_numpy(B):
