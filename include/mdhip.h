@@ -739,6 +739,33 @@ int mdhip_angle_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const do
                      int32_t n_triplets, const int32_t *triplet_class, const double *triplet_rsq, int32_t n_bins,
                      const double *cos_edges, int32_t cap, uint64_t *hist, uint64_t *n_degenerate, int32_t *count);
 
+/* ---- connected components of a contact graph (aggregates.py calc_aggregates; not in the reference) ---- */
+/*
+ * Which nodes (molecules, or atoms) hang together through contacts between listed atoms, for a batch of frames:
+ * coordinates xyz [F][3][n_atoms] (host or device memory as xyz_on_device says), box [F][3], a list A of atoms
+ * atoms_a[n_a] with a class class_a[n_a] in [0, n_ca), a list B of atoms atoms_b[n_b] with a class class_b[n_b] in
+ * [0, n_cb) (the two lists may share atoms), the squared cutoff of every class pair rsq_cut[n_ca][n_cb] (a value <= 0:
+ * that pair never links), and node_of[n_atoms] (read only for listed atoms; values in [0, n_nodes)).
+ * In frame f, atom i of A and atom j of B are in contact when
+ *   node_of[i] != node_of[j], and
+ *   rsq(i, j) < rsq_cut[class_a[i]][class_b[j]] (the reference's single-wrap rsq, rdf_cn.py:36-58, strict, unfused).
+ * Each contact makes the two nodes neighbours.
+ *   label [F][n_nodes] (int32): the smallest node index of the connected component of that node in that frame; a node
+ *     without a contact is its own label;
+ *   n_components [F] (int32): the number of nodes with label == index;
+ *   n_contacts [F] (uint64): the number of (position in A, position in B) pairs in contact; a pair of atoms listed on
+ *     both sides counts once for each position pair in contact (twice when both atoms are in both lists).
+ * 1 <= n_ca, n_cb <= 16, n_nodes < 2^31, at least one positive cutoff, every atom index in [0, n_atoms). There is no
+ * capacity: nothing in this call can overflow. Outputs are host memory. The call's aux time (mdhip_last_aux_ms) is that
+ * of the gather and the union sweep; the rest of its kernel time is the initialisation of the parent rows and the
+ * label pass.
+ */
+int mdhip_contact_components(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int xyz_on_device,
+                             const double *box, int32_t n_a, const int32_t *atoms_a, const int32_t *class_a,
+                             int32_t n_b, const int32_t *atoms_b, const int32_t *class_b, int32_t n_ca, int32_t n_cb,
+                             const double *rsq_cut, int64_t n_nodes, const int32_t *node_of, int32_t *label,
+                             int32_t *n_components, uint64_t *n_contacts);
+
 /* ---- atom counts along the axis normal to a surface (number_density.py calc_number_density) ---- */
 /*
  * Replaces the per-type selections and the counting loop of calc_number_density   structural/number_density.py:76-105

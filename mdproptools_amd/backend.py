@@ -830,6 +830,42 @@ def angle_hist(xyz, box, types, triplets, r_cut_sq, cos_edges, mol_of=None, cap=
     return hist, degen, count, cen
 
 
+CONTACT_MAX_CLASSES = 16  # classes per side of contact_components (include/mdhip.h: mdhip_contact_components)
+
+
+def contact_components(xyz, box, atoms_a, class_a, atoms_b, class_b, rsq_cut, node_of, n_nodes, ctx=None):
+    """
+    Connected components of the contact graph (include/mdhip.h: mdhip_contact_components): xyz [F,3,N] (numpy, or a
+    torch device tensor), box [F,3], the atoms of list A [n_a] with their class [n_a], those of list B [n_b] with their
+    class [n_b], rsq_cut [n_ca,n_cb] (squared cutoffs; <= 0: never links), node_of [N] (read for listed atoms only)
+    -> (label int32 [F,n_nodes], n_components int32 [F], n_contacts uint64 [F]). label[f, m] is the smallest node of
+    the component of m in frame f. No capacity: nothing in this call can overflow.
+    """
+    ctx = ctx or default_context()
+    F, _, N = _shape3(xyz, "xyz")
+    aa, ca = _i32(atoms_a).ravel(), _i32(class_a).ravel()
+    ab, cb = _i32(atoms_b).ravel(), _i32(class_b).ravel()
+    if len(aa) != len(ca) or len(ab) != len(cb):
+        raise ValueError("one class per listed atom is required")
+    cut = _f64(rsq_cut)
+    if cut.ndim != 2:
+        raise ValueError("rsq_cut must be a [n_ca, n_cb] table")
+    node = _i32(node_of).ravel()
+    if len(node) != N:
+        raise ValueError("node_of must hold one node index per atom")
+    n_nodes = int(n_nodes)
+    bx = _f64(box).reshape(F, 3)
+    xp, x_dev, keep = as_input(xyz, ctx)
+    label = result_array((F, max(n_nodes, 0)), np.int32)
+    n_comp = np.zeros(F, dtype=np.int32)
+    n_con = np.zeros(F, dtype=np.uint64)
+    ctx.check(ctx.lib.mdhip_contact_components(
+        ctx.h, F, N, xp, x_dev, ptr(bx), len(aa), ptr(aa, C.c_int32), ptr(ca, C.c_int32), len(ab),
+        ptr(ab, C.c_int32), ptr(cb, C.c_int32), cut.shape[0], cut.shape[1], ptr(cut), n_nodes, ptr(node, C.c_int32),
+        ptr(label, C.c_int32), ptr(n_comp, C.c_int32), ptr(n_con, C.c_uint64)))
+    return label, n_comp, n_con
+
+
 AP_REF_POS, AP_REF_NEG, AP_PROFILE = 0, 1, 2  # binning modes of axis_profile (include/mdhip.h: MDHIP_AP_*)
 AP_SURFACE = 0x4000  # code bit: the atom belongs to the surface
 AP_NONE = 0x3FFF     # row field of an atom that counts in no row
