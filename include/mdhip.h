@@ -178,6 +178,45 @@ int mdhip_device_name(mdhip_ctx *ctx, char *buf, int buflen);
  *                  into a blocking wait after 100 ms), 0 block at once */
 int mdhip_set_option(mdhip_ctx *ctx, const char *key, int value);
 
+/* ---- Non-finite input ("NaN stays home") ------------------------------------------------------ */
+/*
+ * A run that blew up writes nan, -nan and inf into its dump; the reader passes them on (strtod) and no entry point
+ * refuses a non-finite coordinate or sample, as the reference does not. What comes out is defined, per family
+ * (tests/test_nonfinite_cpu.py, tests/test_gpu_nonfinite.py):
+ *
+ *   Pair counts — RDF, CN, RDF + CN in one sweep, atoms x sites, shell residence, shell members, shell coordination,
+ *   contact components, angles, hydration. rdf_cn.py:36-69: a non-finite difference leaves rsq at NaN or +inf and
+ *   rsq < r_cut^2 false, so the pair is in no cutoff; every pair without such an atom counts as before. The integers of
+ *   a frame with K poisoned atoms are those of the frame with the K atoms deleted. This holds on every route: the
+ *   spatial sort clamps its keys in the integer domain (a non-finite atom lands in cell 0), bounding boxes leave NaN out
+ *   (fmin / fmax) and become unbounded for +-Inf or 1e300 — such a tile is never culled, and the packed-f32 sweep hands
+ *   it to its exact f64 chain ("not covered") —, and every bin index is formed under rsq < r_cut^2 only. A finite
+ *   coordinate of 1e300 behaves the same (rsq overflows to +inf) except towards an atom at the same value.
+ *
+ *   Sums — segment COM, charge flux, msd_pairs / origin / windows, lag_msd, correlations, integrals. A non-finite value
+ *   enters exactly the sums the value enters in plain numpy, and no others: its segment's COM on its plane in its frame
+ *   (its type's flux component); its entity's row, its group's sum on its axis and the total, at the pairs, frames and
+ *   windows that touch its frame; every other output is bit-identical to the call on clean data.
+ *     lag_msd, difference kernels (lag_variant 0, 1): a sample at frame t* makes the lags k <= max(t*, F - 1 - t*) of its
+ *       (group, axis) and of that group's total non-finite, nothing else.
+ *     lag_msd, spectral paths forced (lag_variant 2, 4): the transform spreads the sample over every lag, so the affected
+ *       (group, axis) column and its total may be NaN THROUGHOUT (lag 0 stays 0); every other column keeps its bound. The
+ *       reported bound (mdhip_last_rel_bound, mdhip_lag_msd_status_dev) is +infinity: there is none.
+ *     lag_msd, default (lag_variant 3): +infinity misses the 1e-10 bound like any other, so the call is answered by the
+ *       difference kernel and the whole result is the difference kernel's.
+ *     xcorr, direct: the non-finite lags are those of the plain sums c[k] = sum_t a[t+k] b[t] (a sample of b at t reaches
+ *       the lags k < n - t, a sample of a at t the lags k <= t); a row with a non-finite lag is summed once more, every
+ *       lag over its own range in time order (the sweep's zero padding times a NaN would reach the other lags too). The
+ *       other series of the batch are bit-identical. xcorr, FFT: the poisoned row is non-finite at every lag, as
+ *       numpy's rfft / irfft of such a series is; the other rows are bit-identical.
+ *     cumtrapz: I[k] is non-finite from the first increment that holds the bad sample on, +-Inf or NaN as a sequential
+ *       cumsum of the increments gives (a finite series whose running sum overflows included); the integrals before it,
+ *       and the series after it in the batch, are untouched. green_kubo is the chain of the separate calls, masks
+ *       included.
+ *
+ * Not covered: NaN in box lengths, types or masses.
+ */
+
 /* ---- R2/R3 binning table ------------------------------------------------ */
 /*
  * Exact bin edges of the reference's binning rule
@@ -471,7 +510,9 @@ int mdhip_msd_windows_dev(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const
  * Tolerance: rtol 1e-10 against the plain double sum. The default evaluates S1(k) - 2 S2(k) with S2 from the power
  * spectrum (O(F log F)) whenever the rounding bound it computes for the data is <= 1e-10 relative to the MSD
  * (mdhip_last_rel_bound reports it); otherwise — e.g. coordinates far from the origin against a small displacement —
- * the difference kernel sums (r(t0+k) - r(t0))^2 directly.
+ * the difference kernel sums (r(t0+k) - r(t0))^2 directly. A NaN / Inf sample (or squares that overflow) gives a bound of
+ * +infinity, i.e. the difference kernel by default; with lag_variant 2 / 4 its (group, axis) column and that group's total
+ * may be NaN at every lag ("Non-finite input" above).
  */
 int mdhip_lag_msd(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const double *r, int on_device,
                   double scale, int max_lag, int n_groups, const int64_t *group_off, double *out);

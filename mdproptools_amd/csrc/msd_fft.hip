@@ -1990,12 +1990,18 @@ __global__ __launch_bounds__(256) void lag_finish_dd_kernel(const double *__rest
             if (ends_s[w][2] != 0.0 && (ok == 0.0 || ends_s[w][2] < ok)) ok = ends_s[w][2];
         }
         double *ends = bound + gridDim.x + 2 + 3 * s;  // (behind the S bounds and the two status words)
+        // A NaN / Inf sample (or squares that overflow) makes the energy, and with it every lag of this segment, non-finite:
+        // the comparisons above are all false for NaN and would report a bound of 0. There is no bound then — +infinity,
+        // for the lags "that keep the bound" too, so that lag_variant 3 hands the call to the difference form, whose NaN
+        // stays at the lags the sample enters.
+        const double INF = __longlong_as_double(0x7ff0000000000000LL);
+        const bool no_bound = !(__builtin_fabs(e2) < INF) || m != m || ok != ok;
         ends[0] = lo;
         ends[1] = hi;
-        ends[2] = ok > 0.0 ? e2 / ok : 0.0;
+        ends[2] = no_bound ? INF : ok > 0.0 ? e2 / ok : 0.0;
         // the transform's rounding error in S2(k) scales with the energy of the WHOLE series at every lag: the worst
         // relative error is at the lag with the smallest |v| (2 pre[F] >= S1(k), equal at small lags)
-        bound[s] = m > 0.0 ? eps_l * (2.0 * (tot.hi + tot.lo)) / m : 0.0;
+        bound[s] = no_bound ? INF : m > 0.0 ? eps_l * (2.0 * (tot.hi + tot.lo)) / m : 0.0;
     }
 }
 

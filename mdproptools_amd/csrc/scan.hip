@@ -128,8 +128,11 @@ __global__ __launch_bounds__(SC_THREADS) void trap_scan_onepass_kernel(
         if (lane >= d) incl += up;
     }
     if (lane == 63) s_w[wv] = incl;
+    // the exclusive prefix is the lane below's inclusive one, NOT incl - run: a lane whose own run holds a NaN / Inf
+    // (or overflows) would make that NaN and spoil its integrals BEFORE the bad sample, which a sequential cumsum keeps
+    double before = __shfl_up(incl, 1, 64);
+    if (lane == 0) before = 0.0;
     __syncthreads();  // (also: every lane has read its samples, s_v can take the results)
-    double before = incl - run;
     for (int w = 0; w < wv; ++w) before += s_w[w];
     double tile_total = 0.0;
     if (tid == SC_THREADS - 1) {

@@ -178,8 +178,9 @@ __global__ __launch_bounds__(DX_THREADS) void xcorr_direct_kernel(
     }
 }
 
+// (a non-finite sum raises the row's word in `redo`: xcorr_redo_rows_kernel below)
 __global__ void xcorr_finish_kernel(const double *__restrict__ partial, double *__restrict__ out,
-                                    long long n, long long lag0, long long n_lags, int n_slabs)
+                                    long long n, long long lag0, long long n_lags, int n_slabs, int *__restrict__ redo)
 {
     const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_lags) return;
@@ -187,6 +188,31 @@ __global__ void xcorr_finish_kernel(const double *__restrict__ partial, double *
     double s = 0.0;
     for (int r = 0; r < n_slabs; ++r) s += partial[(size_t)r * n_lags + k];
     out[(size_t)blockIdx.y * n_lags + k] = s / (double)(n - (lag0 + k));
+    if (!(__builtin_fabs(s) < __builtin_inf())) redo[blockIdx.y] = 1;
+}
+
+// Rows with a non-finite lag, once more with the range of every lag's sum written out. The sweep above lets the lanes
+// of a tile run over one time range and relies on a[t + k] = 0 beyond the series; a NaN or Inf in b[t] times that zero is
+// NaN, so a bad sample reached the lags k >= n - t as well, where the plain sum does not contain it. Only rows that hold a
+// non-finite value come here (none, for finite data: every block reads its rows' words and leaves), and those are summed
+// in time order, one lag per lane: slow, and right. On exact data the finite lags equal the sweep's.
+__global__ __launch_bounds__(256) void xcorr_redo_rows_kernel(const double *__restrict__ a, const double *__restrict__ b,
+                                                              long long n, long long lag0, long long n_lags, int n_rows,
+                                                              const int *__restrict__ redo, double *__restrict__ out)
+{
+    // items = (row, chunk of 256 lags), dealt to the blocks in turn: a flagged row is spread over the whole grid
+    const long long chunks = (n_lags + 255) / 256, items = (long long)n_rows * chunks;
+    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+        const int row = (int)(it / chunks);
+        if (redo[row] == 0) continue;
+        const long long q = (it % chunks) * 256 + threadIdx.x;
+        if (q >= n_lags) continue;
+        const double *ar = a + (size_t)row * n, *br = b + (size_t)row * n;
+        const long long k = lag0 + q;
+        double s = 0.0;
+        for (long long t = 0; t + k < n; ++t) s = __builtin_fma(ar[t + k], br[t], s);
+        out[(size_t)row * n_lags + q] = s / (double)(n - k);
+    }
 }
 
 int xcorr_direct(mdhip_ctx *ctx, long long n, int n_pairs, const double *d_a, const double *d_b,
@@ -209,16 +235,23 @@ int xcorr_direct(mdhip_ctx *ctx, long long n, int n_pairs, const double *d_a, co
     if (n_slabs < 1) n_slabs = 1;
     group = (int)std::max<long long>(1, std::min<long long>(group, (1LL << 30) / (slab_b * n_slabs)));
     MD_WS(d_partial, double, WS_PART, (size_t)group * n_slabs * slab_b);
+    MD_WS(d_redo, int, WS_MISC, (size_t)group * 4);
     for (int p0 = 0; p0 < n_pairs; p0 += group) {
         const int np = std::min(group, n_pairs - p0);
         // a slab can be empty for short tiles: start from zeros
         MD_HIP(hipMemsetAsync(d_partial, 0, (size_t)np * n_slabs * slab_b, ctx->stream));
+        MD_HIP(hipMemsetAsync(d_redo, 0, (size_t)np * 4, ctx->stream));
         hipLaunchKernelGGL(xcorr_direct_kernel, dim3((unsigned)n_blocks, (unsigned)n_slabs, (unsigned)np),
                            dim3(DX_THREADS), 0, ctx->stream, d_a + (size_t)p0 * n, d_b + (size_t)p0 * n, n,
                            lag0, n_lags, n_tiles, n_slabs, d_partial);
         MD_HIP(hipGetLastError());
         hipLaunchKernelGGL(xcorr_finish_kernel, dim3((unsigned)((n_lags + 255) / 256), (unsigned)np), dim3(256), 0,
-                           ctx->stream, d_partial, d_out + (size_t)p0 * n_lags, n, lag0, n_lags, n_slabs);
+                           ctx->stream, d_partial, d_out + (size_t)p0 * n_lags, n, lag0, n_lags, n_slabs, d_redo);
+        MD_HIP(hipGetLastError());
+        hipLaunchKernelGGL(xcorr_redo_rows_kernel, dim3((unsigned)std::min<long long>((long long)np * ((n_lags + 255) / 256), 8LL * ctx->cu_count)), dim3(256), 0,
+                           ctx->stream,
+                           d_a + (size_t)p0 * n, d_b + (size_t)p0 * n, n, lag0, n_lags, np, d_redo,
+                           d_out + (size_t)p0 * n_lags);
         MD_HIP(hipGetLastError());
     }
     return MDHIP_OK;
