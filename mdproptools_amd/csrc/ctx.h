@@ -224,9 +224,10 @@ struct mdhip_ctx {
                               // 64 frames, C2 1.60 against 1.70 ms
     int opt_rdf_guard = 0;    // overflow guard of the 32-bit LDS histogram words: neighbour tiles a block may sweep
                               // per launch (0 = the real bound, 2^32 / (64 * 256) with margin; tests lower it)
+    // The four seg_* options are read in one place, seg_plan (seg_plan.h), for the COM and the flux alike
     int opt_seg_cap = 0;      // segment kernels: atoms per block stage: 0 = 1024 or 512 by the shape of the segment table (by-frame
                               // kernel, pick_seg_cap), 1024 for the staged one; 1024, 512, or 256 = one wave per block (A/B)
-    int opt_seg_vec = 1;      // segment kernels: 16-byte loads when alignment allows (default), 0 = 8-byte loads (A/B)
+    int opt_seg_vec = 1;      // staged segment kernels: 16-byte loads when alignment allows (default), 0 = 8-byte loads (A/B)
     int opt_fft_logr = 10;    // fft_pow2.hip: largest radix of a pass (log2, 4..10); passes of radix >= 2^9 run the radix-8
                               // network (fft_pass8_kernel), so that 2^20 points take two passes (round 2: 8 = three passes)
     int opt_fft_net8 = 1;     // 0: radix-4 network for every radix (A/B)
@@ -235,9 +236,9 @@ struct mdhip_ctx {
     int opt_fft_mid = 1;      // mdhip_fft_xcorr, autocorrelation through a two-pass transform: 1 (default) three launches
                               // (fft_mid_acf_kernel: second pass + spectrum + inverse's first pass in one), 0 four
     int opt_fft_logc = 3;     // fft_pow2.hip: columns per tile (log2); 8 columns = 128-byte runs measured best (tools/ab_fft.py)
-    int opt_seg_gy = 0;       // staged segment kernels (COM and flux): frame slices per block run (0 = auto)
-    int opt_seg_frame = 1;    // mdhip_segment_com: one (run, frame) per block, nothing carried between frames (A/B: 0 =
-                              // the software-pipelined staged kernel)
+    int opt_seg_gy = 0;       // staged segment kernels: frame slices per block run (0 = auto) (seg_plan)
+    int opt_seg_frame = 1;    // segment kernels: one (run, frame) per block, nothing carried between frames (A/B: 0 =
+                              // the software-pipelined staged kernel) (seg_plan)
     int opt_xcorr_tile = 0;
     int opt_lag_residue = 1;      // full-lag MSD with 16 384 < F + max_lag <= 24 576: 1 (default) the residue-class kernel (msd_fft_w12r.h), 0 the batched transforms
     int opt_lag_mean_sample = -1; // long-series paths: the series are centred on the mean of about this many sampled frames (-1: 512; 0: every frame)

@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "ctx.h"
+#include "seg_plan.h"
 
 #pragma clang fp contract(off)
 
@@ -23,12 +24,8 @@ namespace {
 // multiplied by their mass and parked in LDS; then one lane per segment adds its atoms up in index
 // order from LDS and divides by the mass sum. Same operations in the same order as one lane walking
 // its segment in global memory (the fallback below, kept for segments longer than SC_CAP), but every
-// HBM byte is fetched once by a full-width load.
-struct SegBlock {
-    long long s0, s1;  // segments [s0, s1)
-};
-constexpr int SC_CAP_MAX = 1024;   // atoms per block stage (CAP of the kernel: 1024 or 512)
-constexpr int SC_PLANES = 3;   // attribute planes staged together (x, y, z): one barrier pair per frame
+// HBM byte is fetched once by a full-width load. The runs (SegBlock) and the stage sizes come from seg_plan.h.
+
 // LDS index with one pad double per 32: lanes whose segments start 4, 8, 16, ... atoms apart would otherwise
 // all hit the same banks
 __device__ __forceinline__ int sc_pad(int i) { return i + (i >> 5); }
@@ -165,15 +162,10 @@ __global__ __launch_bounds__(NT) void segment_staged_kernel(
 }
 
 // One (run of segments, frame, plane group) per block and nothing carried between frames (round 3; option seg_frame):
-// the run's table entry holds its atom range, the per-segment mass sums come from the host's index-order sums
-// (mdhip_segment_com computes them anyway), the masses are re-read per block (L2 hits: 8 B per atom against 24 B of
+// the run's table entry (SegRun) holds its atom range, the per-segment mass sums come from the host's index-order sums
+// (seg_sums; mdhip_segment_com computes them anyway), the masses are re-read per block (L2 hits: 8 B per atom against 24 B of
 // coordinates from HBM). No software pipeline, no register double buffer: the loads of many small blocks overlap
 // instead, as in msd_pairs_kernel. Same products, same additions in the same order, one division.
-struct SegRun {
-    long long s0, s1, a0;
-    int na, pad_;
-};
-
 // (88 / 100 VGPRs: 5 / 4 blocks per CU where LDS would hold 6; forcing 80 registers spills 3 / 11 of them and measured
 // 5 % / 20 % slower.)
 template <bool FLUX, int SC_CAP>
@@ -278,50 +270,6 @@ __global__ __launch_bounds__(256) void segment_frame_kernel(
     }
 }
 
-// Runs of whole segments with <= SC_CAP atoms and <= 256 segments each; false when a segment is longer.
-bool build_seg_blocks(int64_t n_seg, const int64_t *seg_off, std::vector<SegBlock> &blocks, int SC_CAP = SC_CAP_MAX,
-                      int max_segs = 256)
-{
-    blocks.clear();
-    int64_t s0 = 0;
-    while (s0 < n_seg) {
-        int64_t s1 = s0;
-        while (s1 < n_seg && s1 - s0 < max_segs && seg_off[s1 + 1] - seg_off[s0] <= SC_CAP) ++s1;
-        if (s1 == s0) return false;  // segment s0 alone exceeds the LDS stage
-        blocks.push_back({(long long)s0, (long long)s1});
-        s0 = s1;
-    }
-    return true;
-}
-
-// Stage size of the by-frame kernel for a segment table (round 5; measured at C4 size, tools/ab_seg_cap.py): 1024 atoms per
-// block unless that leaves the block's second phase — one lane per (segment, plane) sum, 256 lanes a round — mostly idle
-// rounds (10-atom molecules: 102 segments x 3 planes = 306 sums = two rounds for 1.2 rounds' worth: 0.515 -> 0.478 ms with
-// 512-atom stages) or the stage mostly empty (3-atom molecules: the 256-segment limit fills 768 of 1024: 0.722 -> 0.69).
-// Molecules of 4, 16, 40 atoms and mixes of them keep 1024 (512: 2-7 % slower).
-int pick_seg_cap(int64_t n_seg, const int64_t *seg_off, int n_attr, std::vector<SegBlock> &blocks)
-{
-    if (!build_seg_blocks(n_seg, seg_off, blocks, SC_CAP_MAX, 256)) {
-        blocks.clear();  // (a segment longer than the stage: the caller takes the one-lane-per-segment kernel)
-        return SC_CAP_MAX;
-    }
-    const int planes = n_attr < SC_PLANES ? n_attr : SC_PLANES;
-    double rounds = 0.0, tasks = 0.0, atoms = 0.0;
-    for (const SegBlock &b : blocks) {
-        const double t = (double)planes * (double)(b.s1 - b.s0);
-        rounds += std::ceil(t / 256.0);
-        tasks += t;
-        atoms += (double)(seg_off[b.s1] - seg_off[b.s0]);
-    }
-    const bool idle_rounds = rounds > (double)blocks.size() && rounds * 256.0 > 1.5 * tasks;
-    const bool empty_stage = atoms < 0.85 * (double)SC_CAP_MAX * (double)blocks.size() && blocks.size() > 1;
-    if (!(idle_rounds || empty_stage)) return SC_CAP_MAX;
-    std::vector<SegBlock> half;
-    if (!build_seg_blocks(n_seg, seg_off, half, 512, 256)) return SC_CAP_MAX;
-    blocks.swap(half);
-    return 512;
-}
-
 // Fallback: one lane per (segment, frame) walking global memory
 __global__ __launch_bounds__(256) void segment_com_kernel(
     const double *__restrict__ attr, const double *__restrict__ mass,
@@ -400,6 +348,77 @@ int check_segments(mdhip_ctx *ctx, int64_t n_atoms, int64_t n_seg, const int64_t
     return MDHIP_OK;
 }
 
+// What a segment kernel is given, whichever of them runs
+struct SegArgs {
+    const double *attr, *mass, *q;  // q: the flux's charges (staged and walk forms)
+    const long long *seg_off;
+    double *out;
+    int n_attr;
+    long long n_atoms, n_seg, n_frames;
+    double vel_conv, charge_conv;  // the COM: 1.0
+    // seg_stage_tables: the SegBlock | SegRun table and, by frame, the per-segment sums behind it
+    const void *table = nullptr;
+    const double *seg_msum = nullptr, *seg_qsi = nullptr;
+};
+
+SegOptions seg_options(const mdhip_ctx *ctx) { return {ctx->opt_seg_cap, ctx->opt_seg_frame, ctx->opt_seg_gy, ctx->opt_seg_vec}; }
+
+// Only the table the chosen kernel reads goes to the device, into workspace slot `slot` (the callers' slots differ:
+// the flux's result of this kernel lives in WS_AUX3). Staged: the SegBlock runs. By frame: the SegRun runs, then the
+// n_sums per-segment sums (n_seg mass sums | + n_seg charge sums x charge_conv). The tables are the caller's locals:
+// through pinned staging of the call.
+int seg_stage_tables(mdhip_ctx *ctx, int slot, const SegPlan &pl, const double *sums, size_t n_sums, SegArgs &a)
+{
+    if (pl.form == SEG_WALK) return MDHIP_OK;
+    const bool by_frame = pl.form == SEG_FRAME;
+    const size_t tb = by_frame ? pl.runs.size() * sizeof(SegRun) : pl.blocks.size() * sizeof(SegBlock);
+    const size_t sb = by_frame ? n_sums * 8 : 0;
+    MD_WS(d_tab, unsigned char, slot, tb + sb);
+    a.table = d_tab;
+    int rc = mdhip_h2d_small(ctx, d_tab, by_frame ? (const void *)pl.runs.data() : (const void *)pl.blocks.data(), tb);
+    if (rc || !by_frame) return rc;
+    a.seg_msum = reinterpret_cast<const double *>(d_tab + tb);
+    a.seg_qsi = n_sums > (size_t)a.n_seg ? a.seg_msum + a.n_seg : nullptr;
+    return mdhip_h2d_small(ctx, d_tab + tb, sums, sb);
+}
+
+constexpr int seg_case(int form, int cap) { return form == SEG_WALK ? 0 : form * 2048 + cap; }
+
+// The one place that launches a segment kernel: the plan's (form, stage size) names the instance
+template <bool FLUX>
+int seg_launch(mdhip_ctx *ctx, const SegPlan &pl, const SegArgs &a)
+{
+    const dim3 grid(pl.gx, pl.gy), block((unsigned)pl.threads);
+    ctx->last_kernel = pl.name;
+#define SEG_STAGED(CAP, NT)                                                                                              \
+    hipLaunchKernelGGL((segment_staged_kernel<FLUX, CAP, NT>), grid, block, 0, ctx->stream, a.attr, a.mass, a.q, a.seg_off, \
+                       (const SegBlock *)a.table, a.out, a.n_attr, a.n_atoms, a.n_seg, a.n_frames, a.vel_conv,           \
+                       a.charge_conv, pl.vec)
+#define SEG_FRAME(CAP)                                                                                                   \
+    hipLaunchKernelGGL((segment_frame_kernel<FLUX, CAP>), grid, block, 0, ctx->stream, a.attr, a.mass, a.seg_msum,        \
+                       a.seg_qsi, a.seg_off, (const SegRun *)a.table, a.out, a.n_attr, a.n_atoms, a.n_seg, pl.n_steps,    \
+                       a.vel_conv)
+    switch (seg_case(pl.form, pl.cap)) {
+    case seg_case(SEG_FRAME, 512): SEG_FRAME(512); break;
+    case seg_case(SEG_FRAME, 1024): SEG_FRAME(1024); break;
+    case seg_case(SEG_STAGED, 256): SEG_STAGED(256, 64); break;
+    case seg_case(SEG_STAGED, 512): SEG_STAGED(512, 256); break;
+    case seg_case(SEG_STAGED, 1024): SEG_STAGED(1024, 256); break;
+    case seg_case(SEG_WALK, 0):
+        if constexpr (FLUX)
+            hipLaunchKernelGGL(mol_flux_kernel, grid, block, 0, ctx->stream, a.attr, a.mass, a.q, a.seg_off, a.out, a.n_atoms,
+                               a.n_seg, a.n_frames, a.vel_conv, a.charge_conv);
+        else
+            hipLaunchKernelGGL(segment_com_kernel, grid, block, 0, ctx->stream, a.attr, a.mass, a.seg_off, a.out, a.n_attr,
+                               a.n_atoms, a.n_seg, a.n_frames);
+        break;
+    default: MD_REQUIRE(false, "no segment kernel of form %d with a stage of %d atoms", pl.form, pl.cap);
+    }
+#undef SEG_STAGED
+#undef SEG_FRAME
+    return MDHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -416,17 +435,9 @@ int mdhip_segment_com(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, int n_a
     int rc = check_segments(ctx, n_atoms, n_seg, seg_off);
     if (rc) return rc;
     // sums that do not depend on the frame are done on the host, in index order
-    std::vector<double> msum_h((size_t)n_seg);
-    for (int64_t s = 0; s < n_seg; ++s) {
-        double m = 0.0, q = 0.0;
-        for (int64_t a = seg_off[s]; a < seg_off[s + 1]; ++a) {
-            m += atom_mass[a];
-            if (atom_q) q += atom_q[a];
-        }
-        msum_h[s] = m;
-        if (seg_mass) seg_mass[s] = m;
-        if (seg_q && atom_q) seg_q[s] = q;
-    }
+    const std::vector<double> sums = seg_sums(n_seg, seg_off, atom_mass, atom_q);
+    if (seg_mass) std::copy_n(sums.begin(), n_seg, seg_mass);
+    if (seg_q && atom_q) std::copy_n(sums.begin() + n_seg, n_seg, seg_q);
     if (n_frames == 0 || n_seg == 0 || n_attr == 0) return cs.end();
     MD_REQUIRE(attr && out, "NULL attr/out");
     MD_HIP(hipSetDevice(ctx->device));
@@ -446,93 +457,14 @@ int mdhip_segment_com(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, int n_a
         d_out = (double *)mdhip_ws(ctx, WS_OUT, out_b);
         if (!d_out) return MDHIP_ENOMEM;
     }
-    std::vector<SegBlock> blocks;
-    // default: four waves share a 1024-atom stage; seg_cap = 256 selects the wave-private form (one wave per block,
-    // 256-atom stage, no block barrier that costs anything) — measured 0.61 against 0.635 of HBM spec at C4 shape, so
-    // the two barriers per step are not what limits this kernel
-    int cap = ctx->opt_seg_cap == 512 ? 512 : ctx->opt_seg_cap == 256 ? 256 : SC_CAP_MAX;
-    bool staged;
-    if (ctx->opt_seg_cap == 0 && ctx->opt_seg_frame != 0) {  // (default: by the shape of the segment table, pick_seg_cap)
-        cap = pick_seg_cap(n_seg, seg_off, n_attr, blocks);
-        staged = !blocks.empty();
-    } else {
-        staged = build_seg_blocks(n_seg, seg_off, blocks, cap, cap == 256 ? 64 : 256);
-        if (!staged && cap != SC_CAP_MAX) {
-            cap = SC_CAP_MAX;
-            staged = build_seg_blocks(n_seg, seg_off, blocks, cap, 256);
-        }
-    }
-    SegBlock *d_blocks = nullptr;
-    const bool by_frame = staged && ctx->opt_seg_frame != 0 && (cap == SC_CAP_MAX || cap == 512);
-    std::vector<SegRun> runs;
-    SegRun *d_runs = nullptr;
-    double *d_msum = nullptr;
-    if (by_frame) {
-        runs.resize(blocks.size());
-        for (size_t i = 0; i < blocks.size(); ++i)
-            runs[i] = {blocks[i].s0, blocks[i].s1, (long long)seg_off[blocks[i].s0],
-                       (int)(seg_off[blocks[i].s1] - seg_off[blocks[i].s0]), 0};
-        const size_t rb = runs.size() * sizeof(SegRun);
-        unsigned char *d_tab = (unsigned char *)mdhip_ws(ctx, WS_AUX3, rb + (size_t)n_seg * 8);
-        if (!d_tab) return MDHIP_ENOMEM;
-        d_runs = reinterpret_cast<SegRun *>(d_tab);
-        d_msum = reinterpret_cast<double *>(d_tab + rb);
-        // (the tables are locals: through pinned staging of the call)
-        rc = mdhip_h2d_small(ctx, d_runs, runs.data(), rb);
-        if (rc) return rc;
-        rc = mdhip_h2d_small(ctx, d_msum, msum_h.data(), (size_t)n_seg * 8);
-        if (rc) return rc;
-    } else if (staged) {
-        d_blocks = (SegBlock *)mdhip_ws(ctx, WS_AUX3, blocks.size() * sizeof(SegBlock));
-        if (!d_blocks) return MDHIP_ENOMEM;
-        rc = mdhip_h2d_small(ctx, d_blocks, blocks.data(), blocks.size() * sizeof(SegBlock));
-        if (rc) return rc;
-    }
+    const SegPlan pl = seg_plan(seg_options(ctx), ctx->cu_count, n_seg, seg_off, n_attr, n_frames, false);
+    SegArgs a = {d_attr, d_mass, nullptr, d_off, d_out, n_attr, n_atoms, n_seg, n_frames, 1.0, 1.0};
+    rc = seg_stage_tables(ctx, WS_AUX3, pl, sums.data(), (size_t)n_seg, a);
+    if (rc) return rc;
     KernelTimer timer(ctx);
-    if (by_frame) {
-        const long long n_steps = (long long)n_frames * ((n_attr + SC_PLANES - 1) / SC_PLANES);
-        const unsigned gy = (unsigned)std::min<long long>(n_steps, 65535);
-        if (cap == 512) {
-            ctx->last_kernel = "segment_frame_kernel<false, 512>";
-            hipLaunchKernelGGL((segment_frame_kernel<false, 512>), dim3((unsigned)runs.size(), gy), dim3(256), 0,
-                               ctx->stream, d_attr, d_mass, d_msum, (const double *)nullptr, d_off, d_runs, d_out, n_attr,
-                               (long long)n_atoms, (long long)n_seg, n_steps, 1.0);
-        } else {
-        ctx->last_kernel = "segment_frame_kernel<false, 1024>";
-        hipLaunchKernelGGL((segment_frame_kernel<false, 1024>), dim3((unsigned)runs.size(), gy), dim3(256), 0,
-                           ctx->stream, d_attr, d_mass, d_msum, (const double *)nullptr, d_off, d_runs, d_out, n_attr,
-                           (long long)n_atoms, (long long)n_seg, n_steps, 1.0);
-        }
-    } else if (staged) {
-        // enough (block, frame slice) pairs to fill the chip several times over; a block loops over its frames
-        // frame slices: at least enough (block, slice) pairs to fill the chip several times over, and short runs of
-        // ~10 frames per block (measured at C4 shape: 82 slices 0.57 of HBM spec, 512 slices 0.63, 1250 slices 0.60)
-        int64_t want = ((int64_t)ctx->cu_count * 16 + (int64_t)blocks.size() - 1) / (int64_t)blocks.size();
-        want = std::max<int64_t>(want, n_frames / 10);
-        unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(n_frames, std::min<int64_t>(want, 65535)));
-        if (ctx->opt_seg_gy > 0) gy = (unsigned)std::min<int64_t>(std::min<int64_t>(n_frames, 65535), ctx->opt_seg_gy);
-        ctx->last_kernel = cap == 512 ? "segment_staged_kernel<false, 512, 256>" : "segment_staged_kernel<false, 1024, 256>";
-        if (cap == 256) {
-            ctx->last_kernel = "segment_staged_kernel<false, 256, 64>";
-            hipLaunchKernelGGL((segment_staged_kernel<false, 256, 64>), dim3((unsigned)blocks.size(), gy), dim3(64), 0,
-                               ctx->stream, d_attr, d_mass, (const double *)nullptr, d_off, d_blocks, d_out, n_attr,
-                               (long long)n_atoms, (long long)n_seg, (long long)n_frames, 1.0, 1.0, ctx->opt_seg_vec);
-        } else if (cap == 512)
-            hipLaunchKernelGGL((segment_staged_kernel<false, 512, 256>), dim3((unsigned)blocks.size(), gy), dim3(256), 0,
-                               ctx->stream, d_attr, d_mass, (const double *)nullptr, d_off, d_blocks, d_out, n_attr,
-                               (long long)n_atoms, (long long)n_seg, (long long)n_frames, 1.0, 1.0, ctx->opt_seg_vec);
-        else
-            hipLaunchKernelGGL((segment_staged_kernel<false, 1024, 256>), dim3((unsigned)blocks.size(), gy), dim3(256), 0,
-                               ctx->stream, d_attr, d_mass, (const double *)nullptr, d_off, d_blocks, d_out, n_attr,
-                               (long long)n_atoms, (long long)n_seg, (long long)n_frames, 1.0, 1.0, ctx->opt_seg_vec);
-    } else {
-        const unsigned gy = (unsigned)std::min<int64_t>(n_frames, 4096);
-        ctx->last_kernel = "segment_com_kernel";
-        hipLaunchKernelGGL(segment_com_kernel, dim3((unsigned)((n_seg + 255) / 256), gy), dim3(256), 0,
-                           ctx->stream, d_attr, d_mass, d_off, d_out, n_attr, (long long)n_atoms,
-                           (long long)n_seg, (long long)n_frames);
-    }
+    rc = seg_launch<false>(ctx, pl, a);
     timer.stop();
+    if (rc) return rc;
     MD_HIP(hipGetLastError());
     if (!out_on_device) {
         rc = mdhip_result(cs, out, d_out, out_b, 0);
@@ -596,97 +528,19 @@ static int charge_flux_impl(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, c
         d_flux = (double *)mdhip_ws(ctx, WS_OUT, flux_b);
         if (!d_flux) return MDHIP_ENOMEM;
     }
-    std::vector<SegBlock> blocks;
-    // default: four waves share a 1024-atom stage; seg_cap = 256 selects the wave-private form (one wave per block,
-    // 256-atom stage, no block barrier that costs anything) — measured 0.61 against 0.635 of HBM spec at C4 shape, so
-    // the two barriers per step are not what limits this kernel
-    int cap = ctx->opt_seg_cap == 512 ? 512 : ctx->opt_seg_cap == 256 ? 256 : SC_CAP_MAX;
-    bool staged;
-    if (ctx->opt_seg_cap == 0 && ctx->opt_seg_frame != 0) {  // (as mdhip_segment_com)
-        cap = pick_seg_cap(n_seg, seg_off, 3, blocks);
-        staged = !blocks.empty();
-    } else {
-        staged = build_seg_blocks(n_seg, seg_off, blocks, cap, cap == 256 ? 64 : 256);
-        if (!staged && cap != SC_CAP_MAX) {
-            cap = SC_CAP_MAX;
-            staged = build_seg_blocks(n_seg, seg_off, blocks, cap, 256);
-        }
+    const SegPlan pl = seg_plan(seg_options(ctx), ctx->cu_count, n_seg, seg_off, 3, n_frames, true);
+    std::vector<double> sums;  // by frame: per segment the mass sum, then (charge sum) x charge_conv
+    if (pl.form == SEG_FRAME) {
+        sums = seg_sums(n_seg, seg_off, atom_mass, atom_q);
+        for (int64_t sg = 0; sg < n_seg; ++sg) sums[(size_t)(n_seg + sg)] *= charge_conv;  // _conductivity.py:25
     }
-    SegBlock *d_blocks = nullptr;
-    if (staged) {
-        d_blocks = (SegBlock *)mdhip_ws(ctx, WS_PART, blocks.size() * sizeof(SegBlock) +
-                                                          (ctx->opt_seg_frame ? blocks.size() * sizeof(SegRun) + (size_t)n_seg * 16 : 0));
-        if (!d_blocks) return MDHIP_ENOMEM;
-        rc = mdhip_h2d_small(ctx, d_blocks, blocks.data(), blocks.size() * sizeof(SegBlock));
-        if (rc) return rc;
-    }
-    const bool by_frame = staged && ctx->opt_seg_frame != 0 && (cap == SC_CAP_MAX || cap == 512);
-    SegRun *d_runs = nullptr;
-    double *d_msq = nullptr;  // per segment: mass sum, then (charge sum) x charge_conv — the host's index-order sums
-    if (by_frame) {
-        std::vector<SegRun> runs(blocks.size());
-        for (size_t i = 0; i < blocks.size(); ++i)
-            runs[i] = {blocks[i].s0, blocks[i].s1, (long long)seg_off[blocks[i].s0],
-                       (int)(seg_off[blocks[i].s1] - seg_off[blocks[i].s0]), 0};
-        std::vector<double> msq((size_t)n_seg * 2);
-        for (int64_t sg = 0; sg < n_seg; ++sg) {
-            double m = 0.0, q = 0.0;
-            for (int64_t a = seg_off[sg]; a < seg_off[sg + 1]; ++a) {
-                m += atom_mass[a];
-                q += atom_q[a];
-            }
-            msq[sg] = m;
-            msq[n_seg + sg] = q * charge_conv;  // _conductivity.py:25
-        }
-        d_runs = reinterpret_cast<SegRun *>(d_blocks + blocks.size());
-        d_msq = reinterpret_cast<double *>(d_runs + runs.size());
-        rc = mdhip_h2d_small(ctx, d_runs, runs.data(), runs.size() * sizeof(SegRun));  // (the tables are locals)
-        if (rc) return rc;
-        rc = mdhip_h2d_small(ctx, d_msq, msq.data(), msq.size() * 8);
-        if (rc) return rc;
-    }
+    SegArgs a = {d_vel, d_mq, d_mq + n_atoms, d_off, d_tmp, 3, n_atoms, n_seg, n_frames, vel_conv, charge_conv};
+    rc = seg_stage_tables(ctx, WS_PART, pl, sums.data(), sums.size(), a);
+    if (rc) return rc;
     KernelTimer timer(ctx);
-    if (by_frame) {
-        const long long n_steps = (long long)n_frames;
-        const unsigned gy = (unsigned)std::min<long long>(n_steps, 65535);
-        if (cap == 512) {
-            ctx->last_kernel = "segment_frame_kernel<true, 512>";
-            hipLaunchKernelGGL((segment_frame_kernel<true, 512>), dim3((unsigned)blocks.size(), gy), dim3(256), 0,
-                               ctx->stream, d_vel, d_mq, d_msq, d_msq + n_seg, d_off, d_runs, d_tmp, 3, (long long)n_atoms,
-                               (long long)n_seg, n_steps, vel_conv);
-        } else {
-            ctx->last_kernel = "segment_frame_kernel<true, 1024>";
-            hipLaunchKernelGGL((segment_frame_kernel<true, 1024>), dim3((unsigned)blocks.size(), gy), dim3(256), 0,
-                               ctx->stream, d_vel, d_mq, d_msq, d_msq + n_seg, d_off, d_runs, d_tmp, 3, (long long)n_atoms,
-                               (long long)n_seg, n_steps, vel_conv);
-        }
-    } else if (staged) {
-        int64_t want = ((int64_t)ctx->cu_count * 16 + (int64_t)blocks.size() - 1) / (int64_t)blocks.size();
-        want = std::max<int64_t>(want, n_frames / 10);
-        unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(n_frames, std::min<int64_t>(want, 65535)));
-        if (ctx->opt_seg_gy > 0) gy = (unsigned)std::min<int64_t>(std::min<int64_t>(n_frames, 65535), ctx->opt_seg_gy);  // (as mdhip_segment_com)
-        ctx->last_kernel = cap == 512 ? "segment_staged_kernel<true, 512, 256>" : "segment_staged_kernel<true, 1024, 256>";
-        if (cap == 256) {
-            ctx->last_kernel = "segment_staged_kernel<true, 256, 64>";
-            hipLaunchKernelGGL((segment_staged_kernel<true, 256, 64>), dim3((unsigned)blocks.size(), gy), dim3(64), 0,
-                               ctx->stream, d_vel, d_mq, d_mq + n_atoms, d_off, d_blocks, d_tmp, 3, (long long)n_atoms,
-                               (long long)n_seg, (long long)n_frames, vel_conv, charge_conv, ctx->opt_seg_vec);
-        } else if (cap == 512)
-            hipLaunchKernelGGL((segment_staged_kernel<true, 512, 256>), dim3((unsigned)blocks.size(), gy), dim3(256), 0,
-                               ctx->stream, d_vel, d_mq, d_mq + n_atoms, d_off, d_blocks, d_tmp, 3, (long long)n_atoms,
-                               (long long)n_seg, (long long)n_frames, vel_conv, charge_conv, ctx->opt_seg_vec);
-        else
-            hipLaunchKernelGGL((segment_staged_kernel<true, 1024, 256>), dim3((unsigned)blocks.size(), gy), dim3(256), 0,
-                               ctx->stream, d_vel, d_mq, d_mq + n_atoms, d_off, d_blocks, d_tmp, 3, (long long)n_atoms,
-                               (long long)n_seg, (long long)n_frames, vel_conv, charge_conv, ctx->opt_seg_vec);
-    } else {
-        const unsigned gy = (unsigned)std::min<int64_t>(n_frames, 4096);
-        ctx->last_kernel = "mol_flux_kernel";
-        hipLaunchKernelGGL(mol_flux_kernel, dim3((unsigned)((n_seg + 255) / 256), gy), dim3(256), 0,
-                           ctx->stream, d_vel, d_mq, d_mq + n_atoms, d_off, d_tmp, (long long)n_atoms,
-                           (long long)n_seg, (long long)n_frames, vel_conv, charge_conv);
-    }
+    rc = seg_launch<true>(ctx, pl, a);
     timer.stop();
+    if (rc) return rc;
     MD_HIP(hipGetLastError());
     for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
         const unsigned nf = (unsigned)std::min<int64_t>(65535, n_frames - f0);

@@ -13,7 +13,8 @@ fuses a product into an addition):
 
 Every kernel variant of the dispatch (segment_frame_kernel, segment_staged_kernel in its three stage sizes,
 segment_com_kernel, mol_flux_kernel) does exactly these operations, so tests/test_gpu_segment_exact.py compares them
-with assert_array_equal. tests/test_segment_exact_cpu.py checks this file against Fraction arithmetic, against the
+with assert_array_equal; which of them the dispatch must pick (expected_kernel below) is held against csrc/seg_plan.h
+on the CPU (tests/test_seg_plan_native_cpu.py) and against the real call there. tests/test_segment_exact_cpu.py checks this file against Fraction arithmetic, against the
 oracle and the golden, and that the data below is data on which the order of the additions shows.
 """
 import numpy as np
@@ -112,7 +113,7 @@ def offsets(sizes):
 
 
 def segment_tables():
-    """name -> segment sizes. The shapes at which the dispatch changes form (csrc/segment_com.hip): pick_seg_cap takes
+    """name -> segment sizes. The shapes at which the dispatch changes form (csrc/seg_plan.h): pick_seg_cap takes
     512-atom stages for 3- and 10-atom molecules (the latter with three planes) and keeps 1024 for 4 and 16 (full runs
     of 256 and 64 molecules); one segment at each stage cap and one past it (the last two past every stage:
     segment_com_kernel / mol_flux_kernel); runs of one-atom segments at the 64 / 256 segments-per-block limits; ragged
@@ -184,6 +185,52 @@ def case_attr(name, off, F, K):
 def case_vel(name, off, F):
     """The velocities the GPU tests use for table `name` with F frames."""
     return gen_vel(_rng(name, 2, F), F, off)
+
+
+# ------------------------------------------------------------------------------------- what the dispatch must pick
+FALLBACK = {False: "segment_com_kernel", True: "mol_flux_kernel"}
+# (seg_frame, seg_cap, seg_vec, seg_gy): seg_frame 1 with seg_cap 0 lets pick_seg_cap choose; seg_cap 256 is the
+# wave-private staged form whatever seg_frame says; seg_vec and seg_gy act on the staged forms only
+CONFIGS = [
+    (1, 0, 1, 0),
+    (1, 512, 1, 0),
+    (1, 1024, 0, 3),
+    (1, 256, 1, 3),
+    (0, 0, 1, 0),
+    (0, 0, 0, 3),
+    (0, 512, 1, 1),
+    (0, 512, 0, 0),
+    (0, 1024, 1, 3),
+    (0, 256, 0, 1),
+    (0, 256, 1, 0),
+]
+
+
+def picked_cap(name, K):
+    """pick_seg_cap's stage for the uniform tables (csrc/seg_plan.h): 512 for 3-atom molecules (a 256-molecule run
+    fills 768 of 1024 atoms) and for 10-atom ones summed three planes at a time (306 sums take two rounds of 256 lanes);
+    1024 for 4- and 16-atom ones (full runs)."""
+    return {"water": 512, "ten": 512 if K >= 3 else 1024, "four": 1024, "sixteen": 1024}.get(name)
+
+
+def expected_kernel(flux, cfg, sizes, name, K):
+    """The kernel the dispatch must report (None: pick_seg_cap's choice on a table picked_cap does not list)."""
+    frame, cap, _, _ = cfg
+    mx = int(sizes.max())
+    if mx > 1024:
+        return FALLBACK[flux]
+    fl = "true" if flux else "false"
+    if cap == 0 and frame:
+        c = 1024 if mx > 512 else picked_cap(name, K)
+        if c is None:
+            return None
+    else:
+        c = cap if cap in (256, 512) and mx <= cap else 1024  # (a stage too small for a segment: 1024)
+    if c == 256:
+        return "segment_staged_kernel<%s, 256, 64>" % fl
+    if frame:
+        return "segment_frame_kernel<%s, %d>" % (fl, c)
+    return "segment_staged_kernel<%s, %d, 256>" % (fl, c)
 
 
 def edge_geometry(n_probe=40, n_mol=800, ddr=0.07, r_cut=7.0, cn_cut=(3.1, 4.7, 5.3)):

@@ -19,34 +19,13 @@ from oracle import cref as C
 
 pytestmark = pytest.mark.gpu
 
-FALLBACK = {False: "segment_com_kernel", True: "mol_flux_kernel"}
+FALLBACK = X.FALLBACK
 ALL_KERNELS = {FALLBACK[False], FALLBACK[True]} | {
     "segment_frame_kernel<%s, %d>" % (fl, cap) for fl in ("false", "true") for cap in (512, 1024)} | {
     "segment_staged_kernel<%s, %s>" % (fl, g) for fl in ("false", "true") for g in ("256, 64", "512, 256", "1024, 256")}
 DEFAULTS = dict(seg_frame=1, seg_cap=0, seg_vec=1, seg_gy=0)
-# (seg_frame, seg_cap, seg_vec, seg_gy): seg_frame 1 with seg_cap 0 lets pick_seg_cap choose; seg_cap 256 is the
-# wave-private staged form whatever seg_frame says; seg_vec and seg_gy act on the staged forms only
-CONFIGS = [
-    (1, 0, 1, 0),
-    (1, 512, 1, 0),
-    (1, 1024, 0, 3),
-    (1, 256, 1, 3),
-    (0, 0, 1, 0),
-    (0, 0, 0, 3),
-    (0, 512, 1, 1),
-    (0, 512, 0, 0),
-    (0, 1024, 1, 3),
-    (0, 256, 0, 1),
-    (0, 256, 1, 0),
-]
+CONFIGS = X.CONFIGS
 FORMS = ("host", "dev", "dev_odd")
-
-
-def _picked(name, K):
-    """pick_seg_cap's stage for the uniform tables (csrc/segment_com.hip): 512 for 3-atom molecules (a 256-molecule run
-    fills 768 of 1024 atoms) and for 10-atom ones summed three planes at a time (306 sums take two rounds of 256 lanes);
-    1024 for 4- and 16-atom ones (full runs)."""
-    return {"water": 512, "ten": 512 if K >= 3 else 1024, "four": 1024, "sixteen": 1024}.get(name)
 
 
 @pytest.fixture(scope="module")
@@ -75,26 +54,6 @@ def _on(x, form):
 
 def _host(r):
     return r.cpu().numpy() if hasattr(r, "cpu") else r
-
-
-def _expected(flux, cfg, sizes, name, K):
-    """The kernel the dispatch must report (None: pick_seg_cap's choice on a table _picked does not list)."""
-    frame, cap, _, _ = cfg
-    mx = int(sizes.max())
-    if mx > 1024:
-        return FALLBACK[flux]
-    fl = "true" if flux else "false"
-    if cap == 0 and frame:
-        c = 1024 if mx > 512 else _picked(name, K)
-        if c is None:
-            return None
-    else:
-        c = cap if cap in (256, 512) and mx <= cap else 1024  # (a stage too small for a segment: 1024)
-    if c == 256:
-        return "segment_staged_kernel<%s, 256, 64>" % fl
-    if frame:
-        return "segment_frame_kernel<%s, %d>" % (fl, c)
-    return "segment_staged_kernel<%s, %d, 256>" % (fl, c)
 
 
 def _loads16(kernel, n_atoms, form, seg_vec):
@@ -149,7 +108,7 @@ def test_segment_com_and_flux_bit_exact_on_every_variant(B):
                         form = FORMS[(ti + ci + ki) % 3]
                         out_dev = (ci + ki) % 2 == 1
                         what = "COM %s F=%d K=%d %s %s out=%s" % (name, F, K, cfg, form, "dev" if out_dev else "host")
-                        want_kernel = _expected(False, cfg, sizes, name, K)
+                        want_kernel = X.expected_kernel(False, cfg, sizes, name, K)
                         for async_ in (False, True):
                             out = torch.empty((F, K, M), dtype=torch.float64, device="cuda") if out_dev else None
                             r = B.segment_com(_on(com_cases[K], form), m, off, atom_q=q, out=out, ctx=ctx, async_=async_)
@@ -169,7 +128,7 @@ def test_segment_com_and_flux_bit_exact_on_every_variant(B):
                     form = FORMS[(ti + ci + 1) % 3]
                     out_dev = ci % 2 == 0
                     what = "flux %s F=%d %s %s out=%s" % (name, F, cfg, form, "dev" if out_dev else "host")
-                    want_kernel = _expected(True, cfg, sizes, name, 3)
+                    want_kernel = X.expected_kernel(True, cfg, sizes, name, 3)
                     for async_ in (False, True):
                         out = torch.empty((3, T, F), dtype=torch.float64, device="cuda") if out_dev else None
                         r = B.charge_flux(_on(vel, form), m, q, off, st, T, X.VEL_CONV, X.CHARGE_CONV, ctx=ctx, out=out,
