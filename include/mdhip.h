@@ -922,6 +922,63 @@ int mdhip_collective_displacement(mdhip_ctx *ctx, int64_t n_frames, int64_t n_en
 int mdhip_cross_msd(mdhip_ctx *ctx, int64_t n, int n_groups, const double *P, int P_on_device, int64_t max_lag,
                     double *out, double *abs_out, int out_on_device);
 
+/* ---- molecular reorientation (dynamical/reorientation.py, class Reorientation; no counterpart in the reference) ---- */
+/*
+ * Molecule-fixed unit vectors, time-major: the input of mdhip_orient_corr.
+ *   x          host|dev (x_on_device) [n_frames][3][n_atoms], atoms by id, molecules contiguous: the layout
+ *              mdhip_segment_com reads
+ *   box        host [n_frames][3] edge lengths, or NULL: x is unwrapped
+ *   jobs       job j covers job_mols[j] molecules of job_len[j] atoms each, the first one starting at atom job_atom0[j]
+ *              (host [n_jobs]); its terms are the pairs (k, w) = (term_atom[i], term_w[i]), term_off[j] <= i <
+ *              term_off[j+1] (host; term_off [n_jobs+1] starts at 0), with 1 <= k < job_len[j], k strictly ascending
+ *   U          host|dev (U_on_device) [n_series][3][n_frames], n_series = sum of job_mols: series are numbered job after
+ *              job, molecule after molecule
+ *   degenerate host uint64 [n_jobs]: the (molecule, frame) pairs of the job whose vector is exactly zero
+ * For a molecule whose first atom is a, per axis: d_k = x[a+k] - x[a]; with box, d_k is wrapped once as the reference's
+ * pair distances are (rdf_cn.py:44-57): d > L/2 -> d - L, d < -L/2 -> d + L, strict, a NaN shifts nothing;
+ * v = sum_k w_k * d_k in ascending k, one multiplication and one addition per term, unfused, starting from w_1 * d_1.
+ * Then n2 = (vx*vx + vy*vy) + vz*vz and u = v / sqrt(n2): three divisions by the correctly rounded root, so U is
+ * defined bit for bit. n2 == 0 gives u = (0, 0, 0) and +1 in degenerate[j], exactly counted; a non-finite n2 (NaN, or
+ * an overflow) gives three NaN components and is not counted. Atoms that no term names, the first atom apart, are
+ * never read: a NaN there does not leak.
+ * A bond or end-to-end vector tail -> head is the terms (tail, -1), (head, +1), the term of k = 0 dropped because it
+ * contributes zero; a dipole is (k, q_k) for every k >= 1. The dipole of a CHARGED molecule depends on the origin: here
+ * it is taken about the molecule's first atom. With box, the result is meaningful only when the named atoms lie within
+ * half a box edge of the molecule's first atom (one wrap per difference, no connectivity is followed).
+ * The trajectory is read frame-major and U written time-major through an LDS tile of 64 molecules x 64 frames, both
+ * sides coalesced; one read of the lines that hold named atoms: HBM-bound. Any number of frames, molecules and jobs:
+ * launch dimensions over 65535 are split inside the call.
+ * n_jobs < 1, a NULL array, a job that runs past n_atoms, a job without terms, k outside [1, job_len) or not strictly
+ * ascending: MDHIP_EINVAL before anything is written.
+ */
+int mdhip_axis_vectors(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *x, int x_on_device,
+                       const double *box, int n_jobs, const int64_t *job_atom0, const int64_t *job_mols,
+                       const int32_t *job_len, const int64_t *term_off, const int32_t *term_atom, const double *term_w,
+                       double *U, int U_on_device, uint64_t *degenerate);
+
+/*
+ * The sums behind the first- and second-rank orientational time-correlation functions, at every lag:
+ *   sums[k][g][0] = sum over the series m of group g and t = 0 .. n-1-k of c,   sums[k][g][1] = the same sum of c * c,
+ *   c = fma(uz, uz', fma(uy, uy', ux * ux')),  u = U[m][.][t], u' = U[m][.][t+k];  the second sum adds fma(c, c, S2).
+ *   U          host|dev (U_on_device) [n_series][3][n], 1 <= n < 2^29
+ *   group_off  host int64 [n_groups+1] contiguous series groups, 1 <= n_groups <= 16, ascending within [0, n_series];
+ *              an empty group gives zeros
+ *   max_lag    0 .. n-1
+ *   sums       host|dev (sums_on_device) [max_lag+1][n_groups][2]
+ * The caller forms C1 = S1 / W and C2 = 1.5 * S2 / W - 0.5 with W = (n - k) * (size of the group): P1 and P2 of the
+ * cosine, averaged over molecules and time origins. Composing C2 from autocorrelations of the nine products u_a u_b
+ * would take nine transforms per molecule and subtract large numbers; here every term is formed and squared directly.
+ * For any order of summation |S1 - exact| <= (W + 3) * 2^-53 * sum |c| and |S2 - exact| <= (W + 7) * 2^-53 * sum c * c
+ * over the given U. No floating-point atomics: the terms of a lag are added in an order fixed by n, max_lag, the
+ * groups and the device's compute-unit count; results are bit-identical from call to call. A NaN in a series of group g
+ * reaches group g only. n_series * (n * max_lag - max_lag^2 / 2) window positions of five FP64 operations: FP64-bound.
+ * Any n_series; launch dimensions stay below 65535 along the series and time slabs.
+ * n_groups outside 1..16, n outside 1..2^29-1, max_lag outside 0..n-1, n_series < 0, a group_off that does not ascend
+ * within [0, n_series] or a NULL array: MDHIP_EINVAL before anything is written.
+ */
+int mdhip_orient_corr(mdhip_ctx *ctx, int64_t n, int64_t n_series, const double *U, int U_on_device, int n_groups,
+                      const int64_t *group_off, int64_t max_lag, double *sums, int sums_on_device);
+
 /*
  * Replaces, for the inputs of the path, the un-vendored pymatgen `parse_lammps_dumps` + pandas
  * `read_csv` the reference uses (call sites structural/rdf_cn.py:176, dynamical/diffusion.py:172,

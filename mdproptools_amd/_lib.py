@@ -152,6 +152,9 @@ PROTOTYPES = {
     "mdhip_collective_displacement": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_double, C.c_int, c_lp,
                                                 vp, C.c_int, vp]),
     "mdhip_cross_msd": (C.c_int, [vp, C.c_int64, C.c_int, vp, C.c_int, C.c_int64, vp, vp, C.c_int]),
+    "mdhip_axis_vectors": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int, c_lp, c_lp, c_ip, c_lp, c_ip,
+                                     c_dp, vp, C.c_int, c_up]),
+    "mdhip_orient_corr": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, C.c_int, c_lp, C.c_int64, vp, C.c_int]),
     "mdhip_dump_open": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "mdhip_dump_close": (None, [vp]),
     "mdhip_dump_error": (C.c_char_p, [vp]),

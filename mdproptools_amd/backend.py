@@ -1027,3 +1027,74 @@ def cross_msd(P, max_lag, with_abs=False, out=None, abs_out=None, ctx=None):
     ctx.check(ctx.lib.mdhip_cross_msd(ctx.h, n, G, pp, p_dev, int(max_lag), C.c_void_p(res.ctypes.data),
                                       None if ab is None else C.c_void_p(ab.ctypes.data), 0))
     return (res, ab) if with_abs else res
+
+
+ORIENT_MAX_GROUPS = 16
+
+
+def axis_vectors(x, box, job_atom0, job_mols, job_len, terms, out=None, ctx=None):
+    """
+    Molecule-fixed unit vectors per frame (include/mdhip.h: mdhip_axis_vectors): x [F,3,A] coordinates, atoms by id and
+    molecules contiguous (host array or contiguous float64 device tensor); box [F,3] edge lengths, or None when x is
+    unwrapped. Job j covers job_mols[j] molecules of job_len[j] atoms from atom job_atom0[j] on and has the terms
+    terms[j] = [(k, w), ...], k the index of an atom inside the molecule (1 <= k < job_len[j], strictly ascending):
+    v = sum_k w (x[a + k] - x[a]), each difference wrapped once when there is a box, u = v / |v|.
+    Returns (U [S,3,F] with S = sum(job_mols), series job after job and molecule after molecule, degenerate uint64
+    [n_jobs] = the zero vectors of every job): U is a host array, or `out` (float64 CUDA tensor [S,3,F]) when given.
+    """
+    ctx = ctx or default_context()
+    F, _, A = _shape3(x, "x")
+    bx = None
+    if box is not None:
+        bx = _f64(box)
+        if bx.shape != (F, 3):
+            raise ValueError("box must have shape [n_frames, 3]")
+    a0, mols, length = _i64(job_atom0), _i64(job_mols), _i32(job_len)
+    J = len(terms)
+    if not (a0.shape == mols.shape == length.shape == (J,)):
+        raise ValueError("job_atom0, job_mols, job_len and terms must hold one entry per job")
+    t_off = np.zeros(J + 1, dtype=np.int64)
+    t_off[1:] = np.cumsum([len(t) for t in terms])
+    t_atom = _i32([k for t in terms for k, _ in t])
+    t_w = _f64([w for t in terms for _, w in t])
+    S = int(mols.sum()) if J and mols.min() >= 0 else 0
+    xp, x_dev, keep = as_input(x, ctx)
+    if out is None:
+        res = result_array((S, 3, F), device=ctx.device)
+        up, u_dev = C.c_void_p(res.ctypes.data), 0
+    else:
+        res, up, u_dev = out, _dev_out(out, (S, 3, F), ctx=ctx), 1
+    degenerate = np.zeros(max(J, 1), dtype=np.uint64)
+    ctx.check(ctx.lib.mdhip_axis_vectors(ctx.h, F, A, xp, x_dev, None if bx is None else ptr(bx), J,
+                                         ptr(a0, C.c_int64), ptr(mols, C.c_int64), ptr(length, C.c_int32),
+                                         ptr(t_off, C.c_int64), ptr(t_atom, C.c_int32), ptr(t_w), up, u_dev,
+                                         ptr(degenerate, C.c_uint64)))
+    return res, degenerate[:J]
+
+
+def orient_corr(U, group_off, max_lag, out=None, ctx=None):
+    """
+    Orientational correlation sums at every lag (include/mdhip.h: mdhip_orient_corr): U [S,3,n] unit vectors, time-major
+    (host array or contiguous float64 device tensor), group_off int64 [G+1] contiguous groups of series ->
+    sums [max_lag+1,G,2]: sums[k,g,0] = sum over the series m of g and t < n - k of c = u_m(t) . u_m(t+k),
+    sums[k,g,1] the same sum of c^2. C1 = S1 / W and C2 = 1.5 S2 / W - 0.5 with W = (n - k) * (size of g). A host array,
+    or `out` (float64 CUDA tensor of that shape) when given.
+    """
+    ctx = ctx or default_context()
+    shp = tuple(U.shape)
+    if len(shp) != 3 or shp[1] != 3:
+        raise ValueError("U must have shape [n_series, 3, n]")
+    S, _, n = shp
+    off = _i64(group_off)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError("group_off must be offsets [n_groups + 1]")
+    G = off.size - 1
+    L = int(max_lag) + 1
+    up, u_dev, keep = as_input(U, ctx)
+    if out is None:
+        res = np.empty((max(L, 0), G, 2))
+        op, o_dev = C.c_void_p(res.ctypes.data), 0
+    else:
+        res, op, o_dev = out, _dev_out(out, (L, G, 2), ctx=ctx), 1
+    ctx.check(ctx.lib.mdhip_orient_corr(ctx.h, n, S, up, u_dev, G, ptr(off, C.c_int64), int(max_lag), op, o_dev))
+    return res

@@ -135,7 +135,7 @@ def _keep_row(rows, row):
 
 
 def attribute_batches(pattern, leading, planes, n_atoms=None, files=None, stream=True, batch_bytes=None, missing=None,
-                      decide_on=UNWRAPPED, dumps=None):
+                      decide_on=UNWRAPPED, dumps=None, with_box=False):
     """The frames of `pattern` (or of `files`, a rank's share: native reader only) in parse_lammps_dumps order, atoms by
     id, reduced to two `leading` per-atom columns and three `planes` — `UNWRAPPED`, or any three columns such as vx vy
     vz. Returns (streamed, batches): `batches` yields host batches (timesteps [B], first [B,N], second [B,N], planes
@@ -152,6 +152,9 @@ def attribute_batches(pattern, leading, planes, n_atoms=None, files=None, stream
     columns in the order id, leading, planes. The caller raises there in its own words, or returns and leaves it to
     the reader. A per-atom row that every frame repeats is held once there: [B,N] is then a read-only view of it. A
     stream that produced no frame of a whole pattern hands out this route's batch instead.
+
+    `with_box`: every batch carries a fifth entry, the box edge lengths [B,3] (hi - lo of the bounds) of its frames —
+    what a caller that reads wrapped coordinates (planes x y z) needs beside them.
 
     Every frame is checked against `n_atoms` (check_atom_count; None: not checked)."""
     from .com_mols import check_atom_count
@@ -179,27 +182,31 @@ def attribute_batches(pattern, leading, planes, n_atoms=None, files=None, stream
             served = False
             for b in stream_reduced(pattern, mine, leading + planes, n_atoms, batch_bytes):
                 served = True
-                yield b.timesteps, b.ids, b.types, b.xyz
+                yield (b.timesteps, b.ids, b.types, b.xyz) + ((np.asarray(b.lengths, dtype=np.float64),) if with_box else ())
             if served or files is not None:
                 return
         frames = parsed()
         if mio.USE_NATIVE_READER:
             frames = ((ts, bounds, dict(zip(wanted(names), pl))) for ts, bounds, _l, names, pl in
                       mio.iter_native_frames(pattern, wanted, sort_by="id", files=files))
-        steps, xyz, rows = [], [], {c: [] for c in leading}
+        steps, xyz, boxes, rows = [], [], [], {c: [] for c in leading}
         for ts, bounds, cols in frames:
             if unwrapped:
                 unwrap(cols, bounds)
             if n_atoms is not None:
                 check_atom_count(n_atoms, len(cols[planes[0]]))
             steps.append(int(ts))
+            if with_box:
+                b = np.asarray(bounds, dtype=np.float64)
+                boxes.append(b[:, 1] - b[:, 0])
             xyz.append(np.stack([cols[c] for c in planes]))
             for c in rows:
                 _keep_row(rows[c], cols[c])
         if steps:
             held = {c: np.broadcast_to(r[0], (len(r), len(r[0]))) if all(x is r[0] for x in r) else np.stack(r)
                     for c, r in rows.items()}
-            yield np.array(steps, dtype=np.int64), held[leading[0]], held[leading[1]], np.stack(xyz)
+            yield (np.array(steps, dtype=np.int64), held[leading[0]], held[leading[1]], np.stack(xyz)) + (
+                (np.stack(boxes),) if with_box else ())
 
     return mine is not None, batches()
 

@@ -1,0 +1,468 @@
+// reorient.hip — molecular reorientation: molecule-fixed unit vectors and their first- and second-rank orientational
+// time-correlation sums at every lag (dynamical/reorientation.py, class Reorientation; the reference has no such module).
+//
+// mdhip_axis_vectors: U[s][x][t] = the unit vector of series s (one molecule of one job) at frame t, from a weighted sum
+//   of the differences between atoms of the molecule and its first atom (a bond: -1 / +1; a dipole: the charges). The
+//   trajectory is frame-major ([F][3][A]) and U is time-major ([S][3][F]): a workgroup owns a tile of AX_TM = 64
+//   molecules x AX_TF = 64 frames. Lane = molecule while reading (consecutive lanes read atoms one molecule apart, every
+//   fetched line is used by the neighbouring terms and lanes), the finished components go through an LDS tile
+//   ([3][64][64 + 1], conflict-free both ways), lane = frame while writing (512 contiguous bytes per wave and row).
+//   16 waves per workgroup keep four frames x three axes x the terms of loads in flight per lane. One read of the lines
+//   that hold named atoms, one write of U: HBM-bound.
+//
+// mdhip_orient_corr: sums[k][g] = sum over the series m of group g and the origins t of c and of c * c,
+//   c = u_m(t) . u_m(t + k). Organised as cross_msd_kernel (collective.hip): a workgroup owns a tile of OC_KT = 1024
+//   consecutive lags, OC_LPT = 4 per lane, and streams time in stages of OC_TT = 128 steps. A stage holds the window
+//   u[T0 + K0 ..] of the three components of ONE molecule in LDS, transposed ([i mod 4][i div 4]) so that the 64 lanes of
+//   a wave read consecutive doubles; a lane keeps a sliding window of 2 * 4 - 1 entries per component in registers, so
+//   that ONE LDS read per component and step feeds all four of its lags, and u(t) (the same for every lane) arrives
+//   through uniform loads. Unlike cross_msd_kernel the workgroup then goes on to the next molecule of its slab (OC_MS =
+//   8 molecules of one group) with the accumulators carried along: the eight sums of a lane stay in registers over
+//   slab x stage x step. Lag tiles are paired (j, nT - 1 - j) so that every workgroup has the same amount of work;
+//   time is split into slabs as well (about twelve rounds of the resident workgroups); the partial sums per (molecule
+//   slab, time slab) are added by a second kernel in a fixed order (no float atomics). A WAVE (256 lags) runs the steps
+//   up to the last origin of ITS smallest lag; those at which some of its lags have their partner sample beyond the
+//   series — the last 255 at most — run the same blocks of four steps with c selected to zero for such lags. Five FP64
+//   operations per lag and step against three LDS reads per four lags: FP64-VALU bound.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "ctx.h"
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------
+// axis vectors
+// ---------------------------------------------------------------------------------------------
+
+constexpr int AX_TM = 64;           // molecules per tile
+constexpr int AX_TF = 64;           // frames per tile
+constexpr int AX_WAVES = 16;
+constexpr int AX_THREADS = 64 * AX_WAVES;
+constexpr int AX_ROW = AX_TF + 1;   // doubles per (axis, molecule) row of the LDS tile
+constexpr size_t AX_LDS = (size_t)3 * AX_TM * AX_ROW * 8;
+constexpr long long AX_MAX_GRID = 65535;
+static_assert(AX_LDS <= 160 * 1024, "the tile must fit LDS");
+
+struct AxJob {
+    long long atom0, mols, series0, tile0;  // first atom, molecules, first series, first molecule tile of the job
+    int len, term0, n_terms, pad;
+};
+
+// Block (x, y): molecule tile tile_base + x (over all jobs), frame tile ftile_base + y.
+__global__ __launch_bounds__(AX_THREADS) void axis_vectors_kernel(const double *__restrict__ x,
+                                                                  const double *__restrict__ box, long long F,
+                                                                  long long A, const AxJob *__restrict__ jobs,
+                                                                  int n_jobs, const int *__restrict__ term_atom,
+                                                                  const double *__restrict__ term_w,
+                                                                  long long tile_base, long long ftile_base,
+                                                                  double *__restrict__ U,
+                                                                  unsigned long long *__restrict__ degenerate)
+{
+    extern __shared__ double s_u[];  // [3][AX_TM][AX_ROW]
+    const long long tile = tile_base + blockIdx.x;
+    int lo = 0, hi = n_jobs - 1;  // the last job whose first tile is not beyond this one (jobs without molecules have none)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (jobs[mid].tile0 <= tile) lo = mid;
+        else hi = mid - 1;
+    }
+    const AxJob job = jobs[lo];
+    const long long m0 = (tile - job.tile0) * AX_TM;
+    const int nm = (int)(job.mols - m0 < AX_TM ? job.mols - m0 : AX_TM);
+    const long long f0 = (ftile_base + blockIdx.y) * AX_TF;
+    const int nf = (int)(F - f0 < AX_TF ? F - f0 : AX_TF);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane < nm) {
+        const long long a = job.atom0 + (m0 + lane) * job.len;
+        unsigned long long zeros = 0;
+        for (int ff = wave; ff < nf; ff += AX_WAVES) {
+            const long long f = f0 + ff;
+            double v[3];
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                const double *__restrict__ plane = x + ((size_t)f * 3 + ax) * (size_t)A + a;
+                const double xa = plane[0];
+                const double L = box ? box[f * 3 + ax] : 0.0, half = L / 2;
+                double acc = 0.0;
+                for (int t = 0; t < job.n_terms; ++t) {
+                    double d = plane[term_atom[job.term0 + t]] - xa;
+                    if (box) {  // the single wrap of rdf_cn.py:50-55 (strict; a NaN shifts nothing)
+                        if (d > half) d -= L;
+                        else if (d < -half) d += L;
+                    }
+                    const double p = term_w[job.term0 + t] * d;
+                    acc = t == 0 ? p : acc + p;
+                }
+                v[ax] = acc;
+            }
+            const double n2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+            double u[3];
+            if (n2 == 0.0) {
+                u[0] = u[1] = u[2] = 0.0;
+                ++zeros;
+            } else if (!(__builtin_fabs(n2) < __builtin_inf())) {
+                u[0] = u[1] = u[2] = __builtin_nan("");
+            } else {
+                const double r = __builtin_sqrt(n2);
+                u[0] = v[0] / r, u[1] = v[1] / r, u[2] = v[2] / r;
+            }
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) s_u[(ax * AX_TM + lane) * AX_ROW + ff] = u[ax];
+        }
+        if (zeros) atomicAdd(degenerate + lo, zeros);
+    }
+    __syncthreads();
+    for (int row = wave; row < 3 * nm; row += AX_WAVES) {
+        const int mol = row / 3, ax = row - 3 * mol;
+        if (lane < nf)
+            U[((size_t)(job.series0 + m0 + mol) * 3 + ax) * (size_t)F + (size_t)(f0 + lane)] =
+                s_u[(ax * AX_TM + mol) * AX_ROW + lane];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// orientational correlation sums
+// ---------------------------------------------------------------------------------------------
+
+constexpr int OC_THREADS = 256;
+constexpr int OC_LPT = 4;                       // consecutive lags per lane
+constexpr int OC_KT = OC_THREADS * OC_LPT;      // lags per tile (1024)
+constexpr int OC_TT = 128;                      // time steps per LDS stage
+constexpr int OC_AW = OC_TT + OC_KT;            // window length per component and stage
+constexpr int OC_ROW = OC_AW / OC_LPT;          // OC_LPT transposed rows of OC_ROW doubles per component
+constexpr int OC_MS = 8;                        // molecules per slab
+constexpr int OC_MAX_GROUPS = 16;
+constexpr long long OC_MAX_MSLABS = 32768;      // beyond that the slabs grow (OC_MS, 2 OC_MS, ...)
+constexpr int OC_RESIDENT = 4;                  // workgroups per CU: at most 128 registers per lane (five would spill)
+constexpr int OC_ROUNDS = 12;                   // rounds of the resident workgroups the grid is cut into
+static_assert(OC_AW % OC_LPT == 0 && OC_TT % OC_LPT == 0, "stages are whole blocks of OC_LPT steps");
+static_assert((size_t)3 * OC_LPT * OC_ROW * 8 <= 160 * 1024, "the staged windows must fit LDS");
+
+struct OcGroups {
+    long long off[OC_MAX_GROUPS + 1];    // first series of every group
+    long long slab0[OC_MAX_GROUPS + 1];  // first molecule slab of every group
+};
+
+// c = u(t) . u(t + k) from the origin values p and the window entries w
+#define OC_DOT(PX, PY, PZ, WX, WY, WZ) __builtin_fma(PZ, WZ, __builtin_fma(PY, WY, (PX) * (WX)))
+
+// partial[mslab][tslab][q][2] = sum over the molecules of the slab and the slab's time range of c, c * c at lag lag0 + q
+__global__ __launch_bounds__(OC_THREADS, OC_RESIDENT) void orient_corr_kernel(const double *__restrict__ U, long long n,
+                                                                 OcGroups groups, int n_groups, int ms, long long lag0,
+                                                                 long long n_lags, int n_tiles, int n_tslabs,
+                                                                 double *__restrict__ partial)
+{
+    __shared__ double s_w[3 * OC_LPT * OC_ROW];  // [3][OC_LPT][OC_ROW]
+    const int tid = threadIdx.x;
+    const int pair_id = blockIdx.x;  // handles lag tiles pair_id and n_tiles-1-pair_id
+    const int tslab = blockIdx.y;
+    const long long mslab = blockIdx.z;
+    const int wave_lo = __builtin_amdgcn_readfirstlane(tid >> 6) * 64 * OC_LPT, wave_hi = wave_lo + 64 * OC_LPT;
+    int g = 0;  // the last group whose first slab is not beyond this one (empty groups have none)
+    while (g + 1 < n_groups && groups.slab0[g + 1] <= mslab) ++g;
+    const long long m_lo = groups.off[g] + (mslab - groups.slab0[g]) * ms;
+    const long long m_hi = m_lo + ms < groups.off[g + 1] ? m_lo + ms : groups.off[g + 1];
+
+    for (int half = 0; half < 2; ++half) {
+        const int tile = half == 0 ? pair_id : n_tiles - 1 - pair_id;
+        if (half == 1 && tile == pair_id) break;
+        const long long Q0 = (long long)tile * OC_KT;  // first lag of the tile, relative to lag0
+        if (Q0 >= n_lags) continue;
+        const long long K0 = lag0 + Q0;
+        // time range of this tile: t in [0, n-K0); split evenly into n_tslabs slabs
+        const long long t_total = n - K0;
+        const long long per = (t_total + n_tslabs - 1) / n_tslabs;
+        const long long t_lo = (long long)tslab * per;
+        const long long t_hi = t_lo + per < t_total ? t_lo + per : t_total;
+        double acc1[OC_LPT], acc2[OC_LPT];
+#pragma unroll
+        for (int j = 0; j < OC_LPT; ++j) acc1[j] = acc2[j] = 0.0;
+
+        for (long long m = m_lo; m < m_hi; ++m) {
+            const double *const Ux = U + (size_t)m * 3 * (size_t)n, *const Uy = Ux + n, *const Uz = Uy + n;
+            for (long long T0 = t_lo; T0 < t_hi; T0 += OC_TT) {
+                __syncthreads();
+                // stage u[x][T0+K0 .. T0+K0+AW), zero beyond the series (such entries are never used: see `fast` and `ok`)
+                for (int i = tid; i < OC_AW; i += OC_THREADS) {
+                    const long long at = T0 + K0 + i;
+                    const int slot = (i % OC_LPT) * OC_ROW + i / OC_LPT;
+                    const bool in = at < n;
+                    s_w[slot] = in ? Ux[at] : 0.0;
+                    s_w[OC_LPT * OC_ROW + slot] = in ? Uy[at] : 0.0;
+                    s_w[2 * OC_LPT * OC_ROW + slot] = in ? Uz[at] : 0.0;
+                }
+                __syncthreads();
+                const long long left = t_hi - T0;
+                // The steps of this WAVE (lags K0 + wave_lo .. K0 + wave_hi of the tile): those at which its smallest lag
+                // still has its partner inside the series, T0 + tt + K0 + wave_lo <= n - 1 — the tile's time range is
+                // that of ITS smallest lag — and none when all its lags lie beyond the requested ones (it only helps
+                // to stage then)
+                const long long some = Q0 + wave_lo >= n_lags ? 0 : n - K0 - wave_lo - T0;
+                const long long in_stage = left < OC_TT ? left : OC_TT;
+                const int tt_count = (int)(some <= 0 ? 0 : (some < in_stage ? some : in_stage));
+                // ... and those at which EVERY lag of the wave has: T0 + tt + K0 + wave_hi - 1 <= n - 1
+                const long long room = n - K0 - wave_hi - T0 + 1;
+                const int fast = (int)(room <= 0 ? 0 : (room < tt_count ? room : tt_count)) & ~(OC_LPT - 1);
+                const int blocks_end = tt_count & ~(OC_LPT - 1);
+                int tt = 0;
+                if (blocks_end > 0) {
+                    // Lane window: entries OC_LPT tid + tt + j. A block of OC_LPT steps uses the entries j = 0 ..
+                    // 2 OC_LPT - 2: the first OC_LPT - 1 are kept from the block before, the others are read here.
+                    double w[3][2 * OC_LPT - 1];
+#pragma unroll
+                    for (int x = 0; x < 3; ++x)
+#pragma unroll
+                        for (int j = 0; j < OC_LPT - 1; ++j) w[x][j] = s_w[(x * OC_LPT + j) * OC_ROW + tid];
+                    // GUARD: a lag whose partner sample does not exist adds c = 0 (selected, never multiplied: a NaN or an
+                    // infinity at the origin must not reach it); `valid` = the entries of the lane's window that exist
+#define OC_BLOCK(GUARD, VALID)                                                                                 \
+    _Pragma("unroll") for (int s = 0; s < OC_LPT; ++s)                                                         \
+    {                                                                                                          \
+        const double px = Ux[T0 + tt + s], py = Uy[T0 + tt + s], pz = Uz[T0 + tt + s];                         \
+        _Pragma("unroll") for (int j = 0; j < OC_LPT; ++j)                                                     \
+        {                                                                                                      \
+            double c = OC_DOT(px, py, pz, w[0][s + j], w[1][s + j], w[2][s + j]);                              \
+            if (GUARD) c = s + j < (VALID) ? c : 0.0;                                                          \
+            acc1[j] += c;                                                                                      \
+            acc2[j] = __builtin_fma(c, c, acc2[j]);                                                            \
+        }                                                                                                      \
+    }
+                    for (; tt < blocks_end; tt += OC_LPT) {
+                        const int col = tid + tt / OC_LPT;
+#pragma unroll
+                        for (int x = 0; x < 3; ++x)
+#pragma unroll
+                            for (int s = 0; s < OC_LPT; ++s) {
+                                const int e = OC_LPT - 1 + s;
+                                w[x][e] = s_w[(x * OC_LPT + e % OC_LPT) * OC_ROW + col + e / OC_LPT];
+                            }
+                        if (tt < fast) {
+                            OC_BLOCK(false, 0)
+                        } else {
+                            // the last steps of the wave's range, where only some of its lags still have a partner
+                            const long long rest = n - T0 - K0 - (long long)OC_LPT * tid - tt;
+                            const int valid = (int)(rest < 0 ? 0 : (rest < 2 * OC_LPT ? rest : 2 * OC_LPT));
+                            OC_BLOCK(true, valid)
+                        }
+#undef OC_BLOCK
+#pragma unroll
+                        for (int x = 0; x < 3; ++x)
+#pragma unroll
+                            for (int j = 0; j < OC_LPT - 1; ++j) w[x][j] = w[x][j + OC_LPT];
+                    }
+                }
+                // the up to OC_LPT - 1 steps behind the last whole block, one by one
+                for (; tt < tt_count; ++tt) {
+                    const double px = Ux[T0 + tt], py = Uy[T0 + tt], pz = Uz[T0 + tt];
+#pragma unroll
+                    for (int j = 0; j < OC_LPT; ++j) {
+                        const int i = OC_LPT * tid + tt + j;
+                        const int slot = (i % OC_LPT) * OC_ROW + i / OC_LPT;
+                        const double c = OC_DOT(px, py, pz, s_w[slot], s_w[OC_LPT * OC_ROW + slot],
+                                                s_w[2 * OC_LPT * OC_ROW + slot]);
+                        if (T0 + K0 + i < n) {
+                            acc1[j] += c;
+                            acc2[j] = __builtin_fma(c, c, acc2[j]);
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < OC_LPT; ++j) {
+            const long long q = Q0 + (long long)tid * OC_LPT + j;
+            if (q >= n_lags) continue;
+            const size_t at = (((size_t)mslab * (size_t)n_tslabs + (size_t)tslab) * (size_t)n_lags + (size_t)q) * 2;
+            partial[at] = acc1[j];
+            partial[at + 1] = acc2[j];
+        }
+    }
+}
+#undef OC_DOT
+
+// sums[lag0 + q][g][c] = the sum over the (molecule slab, time slab) partial sums of group g, in order
+__global__ void orient_corr_finish_kernel(const double *__restrict__ partial, double *__restrict__ sums,
+                                          OcGroups groups, int G, int n_tslabs, long long lag0, long long n_lags)
+{
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long row = n_lags * 2;
+    if (idx >= row * G) return;
+    const int g = (int)(idx / row);
+    const long long r = idx - (long long)g * row;  // 2 q + c
+    const long long s0 = groups.slab0[g] * n_tslabs, s1 = groups.slab0[g + 1] * n_tslabs;
+    double s = 0.0;
+    for (long long slab = s0; slab < s1; ++slab) s += partial[(size_t)slab * (size_t)row + (size_t)r];
+    sums[((size_t)(lag0 + (r >> 1)) * G + g) * 2 + (size_t)(r & 1)] = s;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mdhip_axis_vectors(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *x, int x_on_device,
+                       const double *box, int n_jobs, const int64_t *job_atom0, const int64_t *job_mols,
+                       const int32_t *job_len, const int64_t *term_off, const int32_t *term_atom, const double *term_w,
+                       double *U, int U_on_device, uint64_t *degenerate)
+{
+    if (!ctx) return MDHIP_EINVAL;
+    CallScope cs(ctx);
+    MD_REQUIRE(n_jobs >= 1 && n_jobs <= (1 << 20), "n_jobs must be in [1, 2^20]");
+    MD_REQUIRE(n_frames >= 1 && n_atoms >= 1, "n_frames and n_atoms must be positive");
+    MD_REQUIRE(n_atoms < (1ll << 40) && n_frames < (1ll << 31) && n_frames < (1ll << 40) / n_atoms, "trajectory too large");
+    MD_REQUIRE(x && job_atom0 && job_mols && job_len && term_off && term_atom && term_w && U && degenerate, "NULL array");
+    MD_REQUIRE(term_off[0] == 0, "term_off must start at 0");
+    std::vector<AxJob> jobs((size_t)n_jobs);
+    long long series = 0, tiles = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const long long len = job_len[j], mols = job_mols[j], a0 = job_atom0[j];
+        MD_REQUIRE(len >= 1 && mols >= 0 && a0 >= 0 && a0 <= n_atoms && mols <= (n_atoms - a0) / len,
+                   "job %d runs past the %lld atoms of a frame", j, (long long)n_atoms);
+        const long long t0 = term_off[j], t1 = term_off[j + 1];
+        MD_REQUIRE(t1 > t0 && t1 - t0 < len && t1 <= (1ll << 30), "job %d needs between 1 and job_len - 1 terms", j);
+        for (long long t = t0; t < t1; ++t)
+            MD_REQUIRE(term_atom[t] >= 1 && term_atom[t] < len && (t == t0 || term_atom[t] > term_atom[t - 1]),
+                       "job %d: the terms' atoms must ascend strictly within [1, job_len)", j);
+        jobs[(size_t)j] = {a0, mols, series, tiles, (int)len, (int)t0, (int)(t1 - t0), 0};
+        series += mols;
+        tiles += (mols + AX_TM - 1) / AX_TM;
+    }
+    MD_REQUIRE(series < (1ll << 40) / n_frames, "result too large");
+    MD_HIP(hipSetDevice(ctx->device));
+    int rc;
+    const size_t x_bytes = (size_t)n_frames * 3 * (size_t)n_atoms * 8;
+    const double *d_x = (const double *)mdhip_stage(ctx, WS_XYZ_I, x, x_bytes, x_on_device, &rc);
+    if (rc) return rc;
+    const double *d_box = nullptr;
+    if (box) {
+        MD_WS(d_b, double, WS_BOX, (size_t)n_frames * 3 * 8);
+        if ((rc = mdhip_h2d_small(ctx, d_b, box, (size_t)n_frames * 3 * 8))) return rc;
+        d_box = d_b;
+    }
+    // tables: jobs | term weights | term atoms | degenerate counters
+    const size_t n_terms = (size_t)term_off[n_jobs];
+    const size_t jobs_b = (size_t)n_jobs * sizeof(AxJob), w_b = n_terms * 8, a_b = (n_terms * 4 + 7) & ~(size_t)7;
+    const size_t deg_b = (size_t)n_jobs * 8;
+    MD_WS(d_tab, char, WS_TABLES, jobs_b + w_b + a_b + deg_b);
+    if ((rc = mdhip_h2d_small(ctx, d_tab, jobs.data(), jobs_b))) return rc;
+    if ((rc = mdhip_h2d_small(ctx, d_tab + jobs_b, term_w, w_b))) return rc;
+    if ((rc = mdhip_h2d_small(ctx, d_tab + jobs_b + w_b, term_atom, n_terms * 4))) return rc;
+    unsigned long long *d_deg = (unsigned long long *)(d_tab + jobs_b + w_b + a_b);
+    MD_HIP(hipMemsetAsync(d_deg, 0, deg_b, ctx->stream));
+    const size_t u_bytes = (size_t)series * 3 * (size_t)n_frames * 8;
+    double *d_U = U;
+    if (!U_on_device) {
+        d_U = (double *)mdhip_ws(ctx, WS_OUT, std::max<size_t>(u_bytes, 8));
+        if (!d_U) return MDHIP_ENOMEM;
+    }
+    MD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(axis_vectors_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)AX_LDS));
+    KernelTimer timer(ctx, 0);
+    int launches = 0;
+    const long long f_tiles = (n_frames + AX_TF - 1) / AX_TF;
+    // (launch dimensions stay within 65 535: more tiles go in several launches)
+    for (long long t0 = 0; t0 < tiles; t0 += AX_MAX_GRID)
+        for (long long ft0 = 0; ft0 < f_tiles; ft0 += AX_MAX_GRID, ++launches) {
+            const dim3 grid((unsigned)std::min(AX_MAX_GRID, tiles - t0), (unsigned)std::min(AX_MAX_GRID, f_tiles - ft0));
+            hipLaunchKernelGGL(axis_vectors_kernel, grid, dim3(AX_THREADS), AX_LDS, ctx->stream, d_x, d_box,
+                               (long long)n_frames, (long long)n_atoms, (const AxJob *)d_tab, n_jobs,
+                               (const int *)(d_tab + jobs_b + w_b), (const double *)(d_tab + jobs_b), t0, ft0, d_U, d_deg);
+            MD_HIP(hipGetLastError());
+        }
+    ctx->last_kernel = "axis_vectors_kernel";
+    ctx->last_launches = launches;
+    timer.stop();
+    if (!U_on_device && (rc = mdhip_result(cs, U, d_U, u_bytes, 0))) return rc;
+    if ((rc = mdhip_result(cs, degenerate, d_deg, deg_b, 0))) return rc;
+    cs.defer([timer]() {
+        timer.collect();
+        return MDHIP_OK;
+    });
+    return cs.end();
+}
+
+int mdhip_orient_corr(mdhip_ctx *ctx, int64_t n, int64_t n_series, const double *U, int U_on_device, int n_groups,
+                      const int64_t *group_off, int64_t max_lag, double *sums, int sums_on_device)
+{
+    if (!ctx) return MDHIP_EINVAL;
+    CallScope cs(ctx);
+    MD_REQUIRE(n_groups >= 1 && n_groups <= OC_MAX_GROUPS, "n_groups must be in [1, %d]", OC_MAX_GROUPS);
+    MD_REQUIRE(n >= 1 && n < (1LL << 29), "series of 1 .. 2^29 samples are supported");
+    MD_REQUIRE(max_lag >= 0 && max_lag <= n - 1, "max_lag must be in [0, n - 1]");
+    MD_REQUIRE(n_series >= 0 && n_series < (1LL << 40) / n, "n_series must not be negative (and n_series * n below 2^40)");
+    MD_REQUIRE(group_off && sums && (n_series == 0 || U), "NULL array");
+    for (int g = 0; g < n_groups; ++g)
+        MD_REQUIRE(group_off[g] >= 0 && group_off[g] <= group_off[g + 1] && group_off[g + 1] <= n_series,
+                   "group_off must ascend within [0, n_series] (group %d)", g);
+    MD_HIP(hipSetDevice(ctx->device));
+    int rc;
+    const int G = n_groups;
+    const long long n_lags_all = max_lag + 1;
+    const size_t u_bytes = (size_t)n_series * 3 * (size_t)n * 8;
+    const double *d_U = (const double *)mdhip_stage(ctx, WS_XYZ_I, U, u_bytes, U_on_device || u_bytes == 0, &rc);
+    if (rc) return rc;
+    const size_t out_b = (size_t)n_lags_all * G * 2 * 8;
+    double *d_out = sums;
+    if (!sums_on_device) {
+        d_out = (double *)mdhip_ws(ctx, WS_OUT, out_b);
+        if (!d_out) return MDHIP_ENOMEM;
+    }
+    // molecule slabs: OC_MS molecules of one group each; larger ones when there would be more than OC_MAX_MSLABS
+    OcGroups groups;
+    int ms = OC_MS;
+    long long n_mslabs;
+    for (;; ms *= 2) {
+        n_mslabs = 0;
+        for (int g = 0; g <= OC_MAX_GROUPS; ++g) {
+            const int gg = g < G ? g : G;
+            groups.off[g] = group_off[gg];
+            groups.slab0[g] = n_mslabs;
+            if (g < G) n_mslabs += (group_off[g + 1] - group_off[g] + ms - 1) / ms;
+        }
+        if (n_mslabs <= OC_MAX_MSLABS) break;
+    }
+    // Time slabs as in cross_msd, when the molecule slabs alone do not give about twelve rounds of the resident
+    // workgroups (OC_ROUNDS; a workgroup of a paired short tile is done long before one of a full tile, and the last
+    // round runs at the pace of the slowest); the lag range goes in chunks of whole tiles whose slab sums stay below
+    // ~1 GiB (each chunk pairs its own tiles)
+    const long long n_tiles_all = (n_lags_all + OC_KT - 1) / OC_KT;
+    const long long blocks_all = (n_tiles_all + 1) / 2 * std::max<long long>(n_mslabs, 1);
+    long long n_tslabs = ((long long)OC_ROUNDS * OC_RESIDENT * ctx->cu_count + blocks_all - 1) / blocks_all;
+    n_tslabs = std::max<long long>(
+        1, std::min<long long>({n_tslabs, (n + OC_TT - 1) / OC_TT, 65535, 65536 / std::max<long long>(n_mslabs, 1)}));
+    const size_t tile_b = (size_t)OC_KT * 2 * 8 * (size_t)(std::max<long long>(n_mslabs, 1) * n_tslabs);  // all slabs of one lag tile
+    const long long chunk_tiles =
+        std::max<long long>(1, std::min<long long>(n_tiles_all, (long long)(((size_t)1 << 30) / tile_b)));
+    const long long chunk_lags = std::min<long long>(chunk_tiles * OC_KT, n_lags_all);
+    const size_t part_b = (size_t)(std::max<long long>(n_mslabs, 1) * n_tslabs) * (size_t)chunk_lags * 2 * 8;
+    MD_WS(d_part, double, WS_PART, part_b);
+    KernelTimer timer(ctx, 0);
+    int launches = 0;
+    for (long long lag0 = 0; lag0 < n_lags_all; lag0 += chunk_lags) {
+        const long long n_lags = std::min(chunk_lags, n_lags_all - lag0);
+        const int n_tiles = (int)((n_lags + OC_KT - 1) / OC_KT);
+        if (n_mslabs > 0) {
+            const dim3 grid((unsigned)((n_tiles + 1) / 2), (unsigned)n_tslabs, (unsigned)n_mslabs);
+            hipLaunchKernelGGL(orient_corr_kernel, grid, dim3(OC_THREADS), 0, ctx->stream, d_U, (long long)n, groups, G, ms,
+                               lag0, n_lags, n_tiles, (int)n_tslabs, d_part);
+            MD_HIP(hipGetLastError());
+            ++launches;
+        }
+        const unsigned fin = (unsigned)((n_lags * 2 * G + 255) / 256);
+        hipLaunchKernelGGL(orient_corr_finish_kernel, dim3(fin), dim3(256), 0, ctx->stream, d_part, d_out, groups, G,
+                           (int)n_tslabs, lag0, n_lags);
+        MD_HIP(hipGetLastError());
+    }
+    ctx->last_kernel = "orient_corr_kernel";
+    ctx->last_launches = launches;
+    timer.stop();
+    if (!sums_on_device && (rc = mdhip_result(cs, sums, d_out, out_b, 0))) return rc;
+    cs.defer([timer]() {
+        timer.collect();
+        return MDHIP_OK;
+    });
+    return cs.end();
+}
+
+}  // extern "C"
