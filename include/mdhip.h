@@ -807,6 +807,64 @@ int mdhip_contact_components(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, 
                              const double *rsq_cut, int64_t n_nodes, const int32_t *node_of, int32_t *label,
                              int32_t *n_components, uint64_t *n_contacts);
 
+/* ---- hydrogen bonds (hydrogen_bonds.py calc_hydrogen_bonds, calc_hbond_lifetime; not in the reference) ---- */
+/*
+ * Which D-H...A bonds exist in a batch of frames: coordinates xyz [F][3][n_atoms] (host or device memory as
+ * xyz_on_device says), box [F][3], the donors donors[n_don] (heavy atoms) with their class don_class[n_don] in
+ * [0, n_dc), their hydrogens in CSR form (the hydrogens of donor d are the atoms h_atoms[h_off[d] .. h_off[d + 1]),
+ * h_off[0] == 0, h_off[n_don] == n_h), the acceptors acceptors[n_acc] with their class acc_class[n_acc] in [0, n_ac),
+ * mol_of[n_atoms] (NULL: no exclusion), the squared cutoffs r_da_sq and r_ha_sq (r_ha_sq <= 0: that test is off) and
+ * cos_cut = cos(angle_cut).
+ * In frame f, hydrogen h of donor d is bonded to acceptor a when
+ *   the atom of a is not the atom of d, and mol_of[a] != mol_of[d] under exclusion;
+ *   rsq(d, a) < r_da_sq (the reference's single-wrap rsq, rdf_cn.py:36-58, strict, unfused);
+ *   rsq(h, a) < r_ha_sq, when that test is on;
+ *   cos <= cos_cut, with u = x_d - x_h and v = x_a - x_h, each wrapped once per axis
+ *     (d > L/2 ? d - L : (d < -L/2 ? d + L : d)),
+ *     cos = ((ux vx + uy vy) + uz vz) / (sqrt((ux ux + uy uy) + uz uz) * sqrt((vx vx + vy vy) + vz vz)), unfused,
+ *     correctly rounded sqrt and division: the angle D-H...A is at least angle_cut.
+ * A NaN cosine (H on D or on A) is no bond; it counts in n_degenerate. A non-finite coordinate makes every comparison
+ * it enters false: that atom bonds to nothing, and no other atom's result changes (a non-finite hydrogen that is not
+ * stopped by the r_ha test has a NaN cosine and counts in n_degenerate).
+ *
+ * mdhip_hbond_counts (per frame, no capacity: nothing in it can overflow):
+ *   n_bonds [F][n_dc][n_ac] (int32): the bonds of every frame and class pair;
+ *   n_donated [n_don], n_accepted [n_acc] (uint64): the bonds each donor gives and each acceptor takes, summed over
+ *     the frames;
+ *   angle_hist [n_dc][n_ac][n_bins] (uint64, summed over the frames): every (h, a) that passes every test but the
+ *     angle test, binned by its cosine against cos_edges[n_bins] = cos(m * bin_size), strictly decreasing, with the
+ *     rule of mdhip_angle_hist: bin = the number of m in [1, n_bins) with cos <= cos_edges[m]. n_bins == 0: no
+ *     histogram (cos_edges and angle_hist may be NULL);
+ *   n_degenerate (uint64): the (h, a) with a NaN cosine among them.
+ *   1 <= n_dc * n_ac <= 64, n_dc * n_ac * n_bins <= 4096. Any number of frames.
+ *
+ * mdhip_hbond_lifetime (a whole trajectory, n_frames <= 65535, lags 0 .. max_lag, 0 <= max_lag < n_frames): with
+ * h(t) = 1 when the pair (position in h_atoms, position in acceptors) is bonded in frame t,
+ *   c_int [max_lag + 1] (uint64): c_int[k] = sum over pairs and t of h(t) h(t + k) (intermittent);
+ *   c_cont [max_lag + 1] (uint64): c_cont[k] = sum over pairs of the number of t with h(t) = ... = h(t + k) = 1
+ *     (continuous): every run of L consecutive ones adds max(0, L - k);
+ *   n_pairs: the distinct pairs that are ever bonded; n_records: the sum of all set bits (= c_int[0] = c_cont[0]).
+ *   The pairs' presence masks (one bit per frame) live in a hash table in device memory. table_slots == 0: the
+ *   library sizes it, and sweeps once more with a table sized from the bond count when it fills; table_slots > 0:
+ *   that many slots (rounded up to a power of two) for the first sweep. The table's byte limit is taken from the free
+ *   device memory; a table that cannot fit fails with MDHIP_ELIMIT and a text that names its size. More than 65535
+ *   frames: MDHIP_EINVAL before anything is launched. The call's aux time (mdhip_last_aux_ms) is that of the two lag
+ *   kernels; the rest of its kernel time is the gather and the sweep (or sweeps).
+ * Outputs are host memory.
+ */
+int mdhip_hbond_counts(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int xyz_on_device,
+                       const double *box, int32_t n_don, const int32_t *donors, const int32_t *don_class,
+                       const int32_t *h_off, int32_t n_h, const int32_t *h_atoms, int32_t n_acc,
+                       const int32_t *acceptors, const int32_t *acc_class, int32_t n_dc, int32_t n_ac,
+                       const int32_t *mol_of, double r_da_sq, double r_ha_sq, double cos_cut, int32_t n_bins,
+                       const double *cos_edges, int32_t *n_bonds, uint64_t *n_donated, uint64_t *n_accepted,
+                       uint64_t *angle_hist, uint64_t *n_degenerate);
+int mdhip_hbond_lifetime(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int xyz_on_device,
+                         const double *box, int32_t n_don, const int32_t *donors, const int32_t *h_off, int32_t n_h,
+                         const int32_t *h_atoms, int32_t n_acc, const int32_t *acceptors, const int32_t *mol_of,
+                         double r_da_sq, double r_ha_sq, double cos_cut, int32_t max_lag, int64_t table_slots,
+                         uint64_t *c_int, uint64_t *c_cont, uint64_t *n_pairs, uint64_t *n_records);
+
 /* ---- atom counts along the axis normal to a surface (number_density.py calc_number_density) ---- */
 /*
  * Replaces the per-type selections and the counting loop of calc_number_density   structural/number_density.py:76-105

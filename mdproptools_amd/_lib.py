@@ -144,6 +144,12 @@ PROTOTYPES = {
                                    c_ip, c_ip, C.c_int32, c_ip, c_dp, C.c_int32, c_dp, C.c_int32, c_up, c_up, c_ip]),
     "mdhip_contact_components": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int32, c_ip, c_ip, C.c_int32,
                                            c_ip, c_ip, C.c_int32, C.c_int32, c_dp, C.c_int64, c_ip, c_ip, c_ip, c_up]),
+    "mdhip_hbond_counts": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int32, c_ip, c_ip, c_ip, C.c_int32,
+                                     c_ip, C.c_int32, c_ip, c_ip, C.c_int32, C.c_int32, c_ip, C.c_double, C.c_double,
+                                     C.c_double, C.c_int32, c_dp, c_ip, c_up, c_up, c_up, c_up]),
+    "mdhip_hbond_lifetime": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int32, c_ip, c_ip, C.c_int32,
+                                       c_ip, C.c_int32, c_ip, c_ip, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                       C.c_int64, c_up, c_up, c_up, c_up]),
     "mdhip_axis_profile": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, C.POINTER(C.c_uint16), C.c_int, C.c_int32,
                                      C.c_int, C.c_double, C.c_double, C.c_int32, C.c_int, c_dp,
                                      C.POINTER(C.c_uint32), c_dp, C.POINTER(C.c_uint32)]),

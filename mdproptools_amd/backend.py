@@ -866,6 +866,99 @@ def contact_components(xyz, box, atoms_a, class_a, atoms_b, class_b, rsq_cut, no
     return label, n_comp, n_con
 
 
+HBOND_MAX_CLASSES = 64  # n_dc * n_ac of hbond_counts (include/mdhip.h: mdhip_hbond_counts)
+HBOND_MAX_CELLS = 4096  # n_dc * n_ac * n_bins
+HBOND_MAX_FRAMES = 65535  # frames of one hbond_lifetime call
+
+
+def _check_args(ctx, rc):
+    """ctx.check, with the library's argument errors (MDHIP_EINVAL) as ValueError carrying its text."""
+    try:
+        ctx.check(rc)
+    except _lib.MdhipError as e:
+        if e.code == -1:
+            raise ValueError(str(e)) from e
+        raise
+
+
+def _hbond_lists(N, donors, h_off, h_atoms, acceptors, mol_of):
+    don, off, hat, acc = (_i32(donors).ravel(), _i32(h_off).ravel(), _i32(h_atoms).ravel(), _i32(acceptors).ravel())
+    if len(off) != len(don) + 1:
+        raise ValueError("h_off must hold one offset per donor and the end")
+    mol = None
+    if mol_of is not None:
+        mol = _i32(mol_of).ravel()
+        if len(mol) != N:
+            raise ValueError("mol_of must hold one molecule index per atom")
+    return don, off, hat, acc, mol
+
+
+def hbond_counts(xyz, box, donors, don_class, h_off, h_atoms, acceptors, acc_class, r_da_sq, cos_cut, r_ha_sq=0.0,
+                 cos_edges=None, mol_of=None, n_dc=None, n_ac=None, ctx=None):
+    """
+    Hydrogen bonds per frame (include/mdhip.h: mdhip_hbond_counts): xyz [F,3,N] (numpy, or a torch device tensor), box
+    [F,3], the donor atoms [n_don] with their class [n_don], their hydrogens in CSR form (h_off [n_don+1], h_atoms
+    [n_h]), the acceptor atoms [n_acc] with their class [n_acc], the squared cutoffs (r_ha_sq <= 0: no H...A test),
+    cos_cut = cos(angle_cut), cos_edges [n_bins] from angle_cos_edges (None: no histogram), mol_of [N] (None: no
+    molecule exclusion), n_dc / n_ac (None: largest class + 1) -> (n_bonds int32 [F,n_dc,n_ac], n_donated uint64
+    [n_don], n_accepted uint64 [n_acc], angle_hist uint64 [n_dc,n_ac,n_bins], n_degenerate int). angle_hist counts
+    every (hydrogen, acceptor) that passes every test but the angle test. No capacity: nothing in this call can
+    overflow.
+    """
+    ctx = ctx or default_context()
+    F, _, N = _shape3(xyz, "xyz")
+    don, off, hat, acc, mol = _hbond_lists(N, donors, h_off, h_atoms, acceptors, mol_of)
+    dcl, acl = _i32(don_class).ravel(), _i32(acc_class).ravel()
+    if len(dcl) != len(don) or len(acl) != len(acc):
+        raise ValueError("one class per donor and per acceptor is required")
+    n_dc = int(n_dc) if n_dc is not None else (int(dcl.max()) + 1 if len(dcl) else 1)
+    n_ac = int(n_ac) if n_ac is not None else (int(acl.max()) + 1 if len(acl) else 1)
+    edges = np.zeros(0) if cos_edges is None else _f64(cos_edges).ravel()
+    n_bins = len(edges)
+    bx = _f64(box).reshape(F, 3)
+    xp, x_dev, keep = as_input(xyz, ctx)
+    n_bonds = np.zeros((F, max(n_dc, 0), max(n_ac, 0)), dtype=np.int32)
+    n_donated = np.zeros(len(don), dtype=np.uint64)
+    n_accepted = np.zeros(len(acc), dtype=np.uint64)
+    hist = np.zeros((max(n_dc, 0), max(n_ac, 0), n_bins), dtype=np.uint64)
+    degen = C.c_uint64(0)
+    _check_args(ctx, ctx.lib.mdhip_hbond_counts(
+        ctx.h, F, N, xp, x_dev, ptr(bx), len(don), ptr(don, C.c_int32), ptr(dcl, C.c_int32), ptr(off, C.c_int32),
+        len(hat), ptr(hat, C.c_int32), len(acc), ptr(acc, C.c_int32), ptr(acl, C.c_int32), n_dc, n_ac,
+        None if mol is None else ptr(mol, C.c_int32), float(r_da_sq), float(r_ha_sq), float(cos_cut), n_bins,
+        ptr(edges) if n_bins else None, ptr(n_bonds, C.c_int32), ptr(n_donated, C.c_uint64),
+        ptr(n_accepted, C.c_uint64), ptr(hist, C.c_uint64) if n_bins else None, C.byref(degen)))
+    return n_bonds, n_donated, n_accepted, hist, int(degen.value)
+
+
+def hbond_lifetime(xyz, box, donors, h_off, h_atoms, acceptors, r_da_sq, cos_cut, r_ha_sq=0.0, mol_of=None,
+                   max_lag=None, table_slots=0, ctx=None):
+    """
+    Hydrogen-bond time correlation numerators of a whole trajectory (include/mdhip.h: mdhip_hbond_lifetime): the
+    inputs of hbond_counts without the classes, at most 65 535 frames, max_lag (None: F - 1) -> (c_int uint64
+    [max_lag+1], c_cont uint64 [max_lag+1], n_pairs, n_records). With h(t) the bond indicator of a (hydrogen,
+    acceptor) pair, c_int[k] = sum h(t) h(t+k) and c_cont[k] = the number of (pair, t) with h(t) = ... = h(t+k) = 1.
+    table_slots > 0 forces the slot count of the first sweep's pair table (0: the library sizes it).
+    """
+    ctx = ctx or default_context()
+    F, _, N = _shape3(xyz, "xyz")
+    don, off, hat, acc, mol = _hbond_lists(N, donors, h_off, h_atoms, acceptors, mol_of)
+    max_lag = max(F - 1, 0) if max_lag is None else int(max_lag)
+    if max_lag < 0:
+        raise ValueError("max_lag must not be negative")
+    bx = _f64(box).reshape(F, 3)
+    xp, x_dev, keep = as_input(xyz, ctx)
+    c_int = np.zeros(max_lag + 1, dtype=np.uint64)
+    c_cont = np.zeros(max_lag + 1, dtype=np.uint64)
+    n_pairs, n_rec = C.c_uint64(0), C.c_uint64(0)
+    _check_args(ctx, ctx.lib.mdhip_hbond_lifetime(
+        ctx.h, F, N, xp, x_dev, ptr(bx), len(don), ptr(don, C.c_int32), ptr(off, C.c_int32), len(hat),
+        ptr(hat, C.c_int32), len(acc), ptr(acc, C.c_int32), None if mol is None else ptr(mol, C.c_int32),
+        float(r_da_sq), float(r_ha_sq), float(cos_cut), max_lag, int(table_slots), ptr(c_int, C.c_uint64),
+        ptr(c_cont, C.c_uint64), C.byref(n_pairs), C.byref(n_rec)))
+    return c_int, c_cont, int(n_pairs.value), int(n_rec.value)
+
+
 AP_REF_POS, AP_REF_NEG, AP_PROFILE = 0, 1, 2  # binning modes of axis_profile (include/mdhip.h: MDHIP_AP_*)
 AP_SURFACE = 0x4000  # code bit: the atom belongs to the surface
 AP_NONE = 0x3FFF     # row field of an atom that counts in no row
