@@ -780,6 +780,50 @@ int mdhip_angle_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const do
                      int32_t n_triplets, const int32_t *triplet_class, const double *triplet_rsq, int32_t n_bins,
                      const double *cos_edges, int32_t cap, uint64_t *hist, uint64_t *n_degenerate, int32_t *count);
 
+/* ---- spatial distribution functions (spatial_distribution.py calc_spatial_distribution; not in the reference) ---- */
+/*
+ * The three-dimensional histogram of observed atoms in the body-fixed frame of a reference molecule, for a batch of
+ * frames: coordinates xyz [F][3][n_atoms] (host or device memory as xyz_on_device says), box [F][3], per reference
+ * molecule its origin atom origin[n_centres], x-axis atom x_atom[n_centres] and xy-plane atom xy_atom[n_centres], the
+ * candidate atoms cand[n_cand] (every atom of an observed species) with their species cand_class[n_cand] in
+ * [0, n_species), mol_of[n_atoms] (NULL: no exclusion), r_cut, r_cut_sq = r_cut ** 2 as the caller squares it,
+ * bin_size and n_grid = G = ceil(2 * r_cut / bin_size). All arithmetic is unfused f64 with correctly rounded sqrt and
+ * division, in exactly this order; wrap(d, L) = d > L/2 ? d - L : (d < -L/2 ? d + L : d), per axis.
+ * The body frame of one frame and one molecule with origin atom o, x-axis atom p and xy-plane atom q:
+ *   a = wrap(x_p - x_o), b = wrap(x_q - x_o);
+ *   na2 = (ax ax + ay ay) + az az, e1 = a / sqrt(na2) component by component;
+ *   s = (bx e1x + by e1y) + bz e1z, c_k = b_k - s e1_k;
+ *   nc2 = (cx cx + cy cy) + cz cz, e2 = c / sqrt(nc2);
+ *   e3 = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x): right-handed;
+ *   the row (frame, molecule) is DEGENERATE when na2 or nc2 is zero or not finite (p on o, q on the line through o and
+ *   p, or a non-finite coordinate): it has no frame.
+ * A candidate j of species s is a hit for the origin atom o when j != o, mol_of[j] != mol_of[o] under exclusion, and
+ * rsq(o, j) < r_cut_sq (the reference's single-wrap rsq, rdf_cn.py:36-58, strict). For a hit, d = wrap(x_j - x_o),
+ *   p_k = (dx ekx + dy eky) + dz ekz for k = 1, 2, 3,
+ *   i_k = floor((p_k + r_cut) / bin_size) clamped to [0, G - 1] (the clamp is made on the double: NaN gives 0),
+ *   hist[s][i1][i2][i3] += 1; a hit of a degenerate row adds nothing to hist and counts in n_degenerate[s].
+ * hist [n_species][G][G][G] and n_degenerate [n_species] (uint64, summed over all frames and molecules, exact: the
+ * cells are 64-bit counters), n_hits [F][n_centres] (int32): the hits of the row over all species, n_degenerate_rows
+ * (uint64): the degenerate rows. There is no capacity: nothing in this call can overflow and nothing is run again.
+ * A non-finite coordinate makes every comparison it enters false: such a candidate is in no shell, an origin atom with
+ * one has no hits, a non-finite p or q makes the row degenerate, and no other atom's result changes.
+ * 1 <= n_species <= 8, 1 <= n_grid <= 256, n_species * n_grid ** 3 <= 2^25, r_cut and bin_size positive and finite.
+ * Outputs are host memory. The call's aux time (mdhip_last_aux_ms) is that of the frame pre-pass and the gather; the
+ * rest of its kernel time is the sweep.
+ * mdhip_body_frames is the frame pre-pass alone: frames [F][n_mols][10] (host memory), per row e1x e1y e1z e2x e2y e2z
+ * e3x e3y e3z and 1.0 for a row that has a frame, 0.0 for a degenerate one (whose nine components then mean nothing),
+ * and n_degenerate_rows.
+ */
+int mdhip_body_frames(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int xyz_on_device,
+                      const double *box, int32_t n_mols, const int32_t *origin, const int32_t *x_atom,
+                      const int32_t *xy_atom, double *frames, uint64_t *n_degenerate_rows);
+int mdhip_sdf_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int xyz_on_device,
+                   const double *box, int32_t n_centres, const int32_t *origin, const int32_t *x_atom,
+                   const int32_t *xy_atom, int32_t n_cand, const int32_t *cand, const int32_t *cand_class,
+                   int32_t n_species, const int32_t *mol_of, double r_cut, double r_cut_sq, double bin_size,
+                   int32_t n_grid, uint64_t *hist, uint64_t *n_degenerate, int32_t *n_hits,
+                   uint64_t *n_degenerate_rows);
+
 /* ---- connected components of a contact graph (aggregates.py calc_aggregates; not in the reference) ---- */
 /*
  * Which nodes (molecules, or atoms) hang together through contacts between listed atoms, for a batch of frames:

@@ -830,6 +830,79 @@ def angle_hist(xyz, box, types, triplets, r_cut_sq, cos_edges, mol_of=None, cap=
     return hist, degen, count, cen
 
 
+SDF_MAX_SPECIES = 8        # observed species per call of sdf_hist (include/mdhip.h: mdhip_sdf_hist)
+SDF_MAX_GRID = 256         # cells per axis
+SDF_MAX_CELLS = 1 << 25    # n_species * G**3
+
+
+def sdf_grid(r_cut, bin_size):
+    """G = ceil(2 * r_cut / bin_size): the cells per axis of sdf_hist's grid over [-r_cut, r_cut)."""
+    r_cut, bin_size = float(r_cut), float(bin_size)
+    if not (np.isfinite(r_cut) and np.isfinite(bin_size) and r_cut > 0.0 and bin_size > 0.0):
+        raise ValueError("r_cut and bin_size must be positive and finite")
+    return int(np.ceil(2.0 * r_cut / bin_size))
+
+
+def body_frames(xyz, box, origin, x_atom, xy_atom, ctx=None):
+    """
+    The body-fixed frames of sdf_hist alone (include/mdhip.h: mdhip_body_frames): xyz [F,3,N] (numpy, or a torch device
+    tensor), box [F,3], per molecule its origin, x-axis and xy-plane atom [M] each -> (e float64 [F,M,3,3] with rows
+    e1, e2, e3, valid bool [F,M], n_degenerate_rows int). The rows of e where valid is False mean nothing.
+    """
+    ctx = ctx or default_context()
+    F, _, N = _shape3(xyz, "xyz")
+    org, xa, xya = (_i32(v).ravel() for v in (origin, x_atom, xy_atom))
+    M = len(org)
+    if len(xa) != M or len(xya) != M:
+        raise ValueError("origin, x_atom and xy_atom must hold one atom per molecule")
+    bx = _f64(box).reshape(F, 3)
+    xp, x_dev, keep = as_input(xyz, ctx)
+    rows = np.zeros((F, M, 10), dtype=np.float64)
+    bad_rows = C.c_uint64(0)
+    ctx.check(ctx.lib.mdhip_body_frames(ctx.h, F, N, xp, x_dev, ptr(bx), M, ptr(org, C.c_int32), ptr(xa, C.c_int32),
+                                        ptr(xya, C.c_int32), ptr(rows), C.byref(bad_rows)))
+    return rows[:, :, :9].reshape(F, M, 3, 3), rows[:, :, 9] != 0.0, int(bad_rows.value)
+
+
+def sdf_hist(xyz, box, origin, x_atom, xy_atom, cand, cand_class, n_species, r_cut, bin_size, mol_of=None, ctx=None):
+    """
+    Spatial distribution histograms (include/mdhip.h: mdhip_sdf_hist): xyz [F,3,N] (numpy, or a torch device tensor),
+    box [F,3], per reference molecule its origin, x-axis and xy-plane atom [M] each, the observed atoms cand [n_cand]
+    with their species cand_class [n_cand] in [0, n_species), mol_of [N] (None: no molecule exclusion) -> (hist uint64
+    [S,G,G,G] in the body frame (e1, e2, e3) with G = sdf_grid(r_cut, bin_size), n_degenerate uint64 [S]: the hits of
+    rows without a frame, n_hits int32 [F,M], n_degenerate_rows int). No capacity limit.
+    """
+    ctx = ctx or default_context()
+    F, _, N = _shape3(xyz, "xyz")
+    org, xa, xya = (_i32(v).ravel() for v in (origin, x_atom, xy_atom))
+    M = len(org)
+    if len(xa) != M or len(xya) != M:
+        raise ValueError("origin, x_atom and xy_atom must hold one atom per reference molecule")
+    cnd, cls = _i32(cand).ravel(), _i32(cand_class).ravel()
+    if len(cls) != len(cnd):
+        raise ValueError("cand_class must hold one species per candidate")
+    S = int(n_species)
+    G = sdf_grid(r_cut, bin_size)
+    mol = None
+    if mol_of is not None:
+        mol = _i32(mol_of).ravel()
+        if len(mol) != N:
+            raise ValueError("mol_of must hold one molecule index per atom")
+    bx = _f64(box).reshape(F, 3)
+    xp, x_dev, keep = as_input(xyz, ctx)
+    ok = 1 <= S <= SDF_MAX_SPECIES and 1 <= G <= SDF_MAX_GRID and S * G ** 3 <= SDF_MAX_CELLS
+    hist = result_array((S, G, G, G), np.uint64, device=ctx.device, zero=True) if ok else np.zeros(1, dtype=np.uint64)
+    degen = np.zeros(max(S, 1), dtype=np.uint64)
+    n_hits = np.zeros((F, M), dtype=np.int32)
+    bad_rows = C.c_uint64(0)
+    ctx.check(ctx.lib.mdhip_sdf_hist(
+        ctx.h, F, N, xp, x_dev, ptr(bx), M, ptr(org, C.c_int32), ptr(xa, C.c_int32), ptr(xya, C.c_int32), len(cnd),
+        ptr(cnd, C.c_int32), ptr(cls, C.c_int32), S, None if mol is None else ptr(mol, C.c_int32), float(r_cut),
+        cutoff_sq(r_cut), float(bin_size), G, ptr(hist, C.c_uint64), ptr(degen, C.c_uint64), ptr(n_hits, C.c_int32),
+        C.byref(bad_rows)))
+    return hist, degen[:S], n_hits, int(bad_rows.value)
+
+
 CONTACT_MAX_CLASSES = 16  # classes per side of contact_components (include/mdhip.h: mdhip_contact_components)
 
 
