@@ -185,7 +185,7 @@ int mdhip_set_option(mdhip_ctx *ctx, const char *key, int value);
  * (tests/test_nonfinite_cpu.py, tests/test_gpu_nonfinite.py):
  *
  *   Pair counts — RDF, CN, RDF + CN in one sweep, atoms x sites, shell residence, shell members, shell coordination,
- *   contact components, angles, hydration. rdf_cn.py:36-69: a non-finite difference leaves rsq at NaN or +inf and
+ *   contact components, angles, hydration, distinct van Hove (its pairs land in `beyond`). rdf_cn.py:36-69: a non-finite difference leaves rsq at NaN or +inf and
  *   rsq < r_cut^2 false, so the pair is in no cutoff; every pair without such an atom counts as before. The integers of
  *   a frame with K poisoned atoms are those of the frame with the K atoms deleted. This holds on every route: the
  *   spatial sort clamps its keys in the integer domain (a non-finite atom lands in cell 0), bounding boxes leave NaN out
@@ -975,6 +975,40 @@ int mdhip_displacement_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, con
                             const int32_t *jobs, double bin_size, int32_t nbins, const double *edges,
                             uint64_t *hist, uint64_t *overflow, uint64_t *windows, double *moments,
                             uint64_t *crossings);
+
+/* ---- distinct part of the van Hove function (Displacement.calc_van_hove_distinct) ---- */
+/*
+ * G_d(r, t) before normalisation: per time origin, the histogram of the distances between where the entities of group a
+ * were at t0 and where the entities of group b are at t0 + lag. The reference has nothing like it; the conventions are
+ * those of mdhip_displacement_hist, whose self part this completes.
+ *   r          host|dev (r_on_device) [n_frames][3][n_ent], WRAPPED coordinates (no image counts are rebuilt)
+ *   box        host [n_frames][3] edge lengths; required
+ *   group_off  host int64 [n_groups+1] contiguous entity groups; empty groups are allowed
+ *   jobs       host int32 [n_jobs][4] = (group a, group b, lag, stride), 0 <= lag <= n_frames-1 (lag 0: the pair
+ *              counts of g(r)), stride >= 1
+ *   edges      host [nbins+1] from mdhip_bin_edges, or NULL to have it computed from bin_size; 1 <= nbins <= 2^20
+ * Anything else (NULL box, a group index out of range, a lag outside [0, n_frames-1], stride < 1, nbins out of range,
+ * a bin_size that is not positive and finite, a group_off that does not ascend within [0, n_ent]) is MDHIP_EINVAL
+ * before anything is written.
+ * Per job (a, b, k, s): origins t0 = 0, s, 2s, ... with t0 + k <= n_frames-1; for every origin, every i in a and every
+ * j in b with j != i as entity indices (which only bites when a == b): d = r[t0+k][x][j] - r[t0][x][i] per axis, one
+ * shift by L = box[t0][x] iff |d| > L/2 — strict, the reference's single-wrap convention (rdf_cn.py:44-57), i.e. the
+ * magnitude min(|d|, ||d| - L|) for L >= 0 — rsq = (dx*dx + dy*dy) + dz*dz unfused, bin = (int64)(sqrt(rsq) / bin_size)
+ * decided by comparing rsq with the edge table (never by device sqrt).
+ *   hist       host uint64 [n_jobs][nbins]: +1 in hist[job][bin] when rsq < edges[nbins]
+ *   beyond     host uint64 [n_jobs]: every other pair, a NaN or +inf rsq included
+ *   pairs      host uint64 [n_jobs] = origins * (N_a * N_b - (a == b ? N_a : 0)) = sum(hist[job]) + beyond[job]
+ * Pairs are ordered: for a == b every unordered pair is visited twice (at lag > 0 those are two different distances;
+ * at lag 0 the counts are those of mdhip_rdf_atomic, which adds 2 per pair for a == b); for a != b once.
+ * Non-finite input: a pair with a non-finite coordinate at either end lands in `beyond`, every other pair counts as
+ * before: hist is that of the trajectory without the entity.
+ * The outputs are integers, exact and independent of the launch geometry. Any number of frames, entities and jobs:
+ * launch dimensions over 65535 are split inside the call. Complete on return.
+ */
+int mdhip_van_hove_distinct(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const double *r, int r_on_device,
+                            const double *box, int n_groups, const int64_t *group_off, int n_jobs,
+                            const int32_t *jobs, double bin_size, int32_t nbins, const double *edges, uint64_t *hist,
+                            uint64_t *beyond, uint64_t *pairs);
 
 /* ---- Einstein-Helfand conductivity (Conductivity.einstein / nernst; `pass` in the reference,
  *      dynamical/conductivity.py:399-403) ---- */

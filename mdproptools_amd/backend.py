@@ -1134,6 +1134,51 @@ def displacement_hist(r, box, group_off, jobs, bin_size, n_bins, ctx=None):
     return hist, overflow, windows, moments, int(crossings.value)
 
 
+def van_hove_distinct(r, box, group_off, jobs, bin_size, n_bins, ctx=None):
+    """
+    Pair histograms across a time lag, the distinct part of the van Hove function before normalisation (include/mdhip.h:
+    mdhip_van_hove_distinct): r [F,3,E] WRAPPED coordinates (host array or contiguous float64 device tensor), box [F,3]
+    edge lengths, group_off int64 [G+1] contiguous entity groups, jobs int32 [J,4] rows (group a, group b, lag, stride),
+    lag 0 allowed -> (hist uint64 [J,n_bins], beyond uint64 [J], pairs uint64 [J]); hist.sum(1) + beyond == pairs.
+    """
+    F, _, E = _shape3(r, "r")
+    if box is None:
+        raise ValueError("box is required: the distinct van Hove function works on wrapped coordinates")
+    bx = _f64(box)
+    if bx.shape != (F, 3):
+        raise ValueError("box must have shape [n_frames, 3]")
+    off = _i64(group_off)
+    if off.ndim != 1 or off.size < 1 or off[0] < 0 or off[-1] > E or np.any(np.diff(off) < 0):
+        raise ValueError("group_off must be ascending offsets [n_groups + 1] within [0, n_ent]")
+    G = off.size - 1
+    jb = np.asarray(jobs)
+    if jb.size and (jb.ndim != 2 or jb.shape[1] != 4):
+        raise ValueError("jobs must have shape [n_jobs, 4]: (group a, group b, lag, stride)")
+    jb = _i32(jb).reshape(-1, 4)
+    if len(jb):
+        if jb[:, :2].min() < 0 or jb[:, :2].max() >= G:
+            raise ValueError("a job names a group outside [0, %d)" % G)
+        if jb[:, 2].min() < 0 or jb[:, 2].max() > F - 1:
+            raise ValueError("every lag must be in [0, n_frames - 1 = %d]" % (F - 1))
+        if jb[:, 3].min() < 1:
+            raise ValueError("every stride must be at least 1")
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= 1 << 20:
+        raise ValueError("n_bins must be in [1, 2^20]")
+    if not (float(bin_size) > 0.0 and np.isfinite(bin_size)):
+        raise ValueError("bin_size must be positive and finite")
+    ctx = ctx or default_context()
+    rp, r_dev, keep = as_input(r, ctx)
+    J = len(jb)
+    hist = result_array((J, n_bins), dtype=np.uint64, device=ctx.device)
+    beyond = np.empty(J, dtype=np.uint64)
+    pairs = np.empty(J, dtype=np.uint64)
+    ctx.check(ctx.lib.mdhip_van_hove_distinct(
+        ctx.h, F, E, rp, r_dev, ptr(bx), G, ptr(off, C.c_int64), J, ptr(jb, C.c_int32), float(bin_size), n_bins, None,
+        ptr(hist, C.c_uint64), ptr(beyond, C.c_uint64), ptr(pairs, C.c_uint64)))
+    return hist, beyond, pairs
+
+
 def collective_displacement(r, weight, group_off, scale=1.0, out=None, weighted=None, ctx=None):
     """
     Charge-weighted collective displacement of every group per frame (include/mdhip.h: mdhip_collective_displacement):

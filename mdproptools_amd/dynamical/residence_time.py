@@ -24,6 +24,10 @@ non-Gaussian parameter.
   GPU (`mdhip_displacement_hist`): image counts of the wrapped coordinates, the displacement of every (origin, atom)
       window, its histogram and the sums of r, r^2, r^4.
   Host: parsing, selection of the atoms by type, lag rounding, normalisation and the CSV files.
+`calc_van_hove_distinct` adds the other half of the van Hove function, G_d(r, t): the density of atoms of type b at
+time t0 + t at distance r from where an atom of type a was at t0, normalised like g(r) (at 0 ps it is g(r)).
+  GPU (`mdhip_van_hove_distinct`): the pair histograms across the lag, all (pair, lag) jobs in one launch.
+  Host: lag rounding, the ideal-gas normalisation and the CSV files.
 """
 
 import math
@@ -307,3 +311,65 @@ class Displacement:
                 df.to_csv(self.working_dir + "/van_hove_%s.csv" % t)
             alpha2.to_csv(self.working_dir + "/alpha2.csv")
         return gs, alpha2
+
+    def calc_van_hove_distinct(self, times, pairs=None, origin_stride=1):
+        """Distinct part of the van Hove function at the lags `times` (ps; rounded to frames, 0 ps is lag 0, duplicates
+        dropped), every `origin_stride`-th frame an origin: ({(type a, type b): DataFrame of r and G_d(r, t) per lag
+        time}, DataFrame of `pairs` and `beyond r_max` per (pair, lag)). G_d = hist / ((origins N_a) rho_b shell) with
+        rho_b = N_b / mean volume of the origin frames and shell = 4/3 pi bin_size^3 ((bin+1)^3 - bin^3): the g(r)
+        normalisation, so the 0 ps column is g_a-b(r). `pairs`: (type a, type b) tuples, both from atom_types; default
+        every unordered pair, same-type pairs included."""
+        if self.coords != "wrapped":
+            raise ValueError('calc_van_hove_distinct needs coords="wrapped": the single periodic wrap between two atoms '
+                             "is taken on the wrapped x y z")
+        if int(origin_stride) < 1:
+            raise ValueError("origin_stride must be at least 1")
+        stride = int(origin_stride)
+        r, box, group_off, delta = self._load()
+        n_frames = r.shape[0]
+        lags = []
+        for t in times:
+            k = int(math.floor(t / delta + 0.5))
+            if k < 0:
+                raise ValueError("the time %g ps is negative" % t)
+            if k > n_frames - 1:
+                raise ValueError("the time %g ps (%d frames) is longer than the trajectory (%d frames)"
+                                 % (t, k, n_frames))
+            if k not in lags:
+                lags.append(k)
+        types = list(self.atom_types)
+        if pairs is None:
+            pairs = [(a, b) for i, a in enumerate(types) for b in types[i:]]
+        pairs = [tuple(p) for p in pairs]
+        for a, b in pairs:
+            if a not in types or b not in types:
+                raise ValueError("pair (%s, %s): both types must be in atom_types" % (a, b))
+        jobs = [(types.index(a), types.index(b), k, stride) for a, b in pairs for k in lags]
+        n_bins = self._bins(box)
+        hist, beyond, n_pairs = backend.van_hove_distinct(r, box, group_off, jobs, self.bin_size, n_bins)
+        k_bin = np.arange(n_bins, dtype=np.float64)
+        shell = 4.0 / 3.0 * math.pi * self.bin_size ** 3 * ((k_bin + 1.0) ** 3 - k_bin ** 3)
+        volume = box[:, 0] * box[:, 1] * box[:, 2]
+        sizes = np.diff(group_off)
+        gd, summary = {}, {"pair": [], "Time (ps)": [], "origins": [], "pairs": [], "beyond r_max": []}
+        for p, (a, b) in enumerate(pairs):
+            n_a, n_b = float(sizes[types.index(a)]), float(sizes[types.index(b)])
+            cols = {"r": (k_bin + 0.5) * self.bin_size}
+            for i, k in enumerate(lags):
+                j = p * len(lags) + i
+                origins = np.arange(0, n_frames - k, stride)
+                rho_b = n_b / np.mean(volume[origins])
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    cols[k * delta] = hist[j] / ((len(origins) * n_a) * rho_b * shell)
+                summary["pair"].append("%s-%s" % (a, b))
+                summary["Time (ps)"].append(k * delta)
+                summary["origins"].append(len(origins))
+                summary["pairs"].append(int(n_pairs[j]))
+                summary["beyond r_max"].append(int(beyond[j]))
+            gd[(a, b)] = pd.DataFrame(cols)
+        summary = pd.DataFrame(summary)
+        if self.save_mode and is_writer():
+            for (a, b), df in gd.items():
+                df.to_csv(self.working_dir + "/van_hove_distinct_%s-%s.csv" % (a, b))
+            summary.to_csv(self.working_dir + "/van_hove_distinct_pairs.csv")
+        return gd, summary
