@@ -427,10 +427,18 @@ __device__ __forceinline__ RelQ load_relq(const float *__restrict__ p)
 //     sqrt, fma, fract, cvt, lshl_add                               (bin guess + LDS address)
 //     v_cmpx_ge  d = exec = lanes whose guess is safe               (was v_cmp + s_andn2 amb + s_and exec)
 //     ds_add_u32
-//     s_andn2    amb = c & ~d  (c = 0 on the skipped path)          (the lanes inside the error band of an edge)
+//     s_andn2    amb = c & ~d                                       (the lanes inside the error band of an edge)
+//   skipped path joins here: its v_cmpx found no lane and left c = 0, which IS amb = 0, so it lands behind the s_andn2
 //     s_mov      exec = full
-// = 8 VALU + 2 SALU + 1 branch per slot (round 1: 7 VALU + 5 SALU + 1 branch, and a compare + branch on amb per slot
-// behind it; the caller now tests amb0 | amb1 once). `full` is the exec mask of the sweep (read once per item).
+//   (slot 1, forms without RET: its v_cmp stands ahead of slot 0 and it starts with s_mov exec, c1 — BP_PRE1 below —
+//   so slot 0 ends without an exec restore; `full` comes back once, behind slot 1)
+// = 8 VALU + 2 SALU + 1 branch per live slot (CUTG: one v_cmpx more; round 1: 7 VALU + 5 SALU + 1 branch, and a compare
+// + branch on amb per slot behind it; the caller now tests amb0 | amb1 once). A skipped slot, per form:
+//   without RET, slot 0: its v_cmpx, the taken branch, the s_mov that starts slot 1   = 1 VALU + 1 SALU + 1 branch
+//   without RET, slot 1: the hoisted v_cmp, s_mov exec, c1, the taken branch, s_mov exec, full
+//                                                                                    = 1 VALU + 2 SALU + 1 branch
+//   with RET, either slot: v_cmpx, the taken branch, s_and, s_andn2, s_mov exec, full = 1 VALU + 3 SALU + 1 branch
+// `full` is the exec mask of the sweep (read once per item).
 // INVARIANT (also pk_push): these blocks rewrite exec and put `full` back, and the compiler does not know — every call
 // must sit in wave-uniform control flow with exactly the lanes of `full` live (sj_item_pk reads it at its top; every
 // branch between there and the sweeps is on a wave-uniform value: ballots, scalar masks, readfirstlane'd indices).
@@ -450,6 +458,18 @@ __device__ __forceinline__ RelQ load_relq(const float *__restrict__ p)
     "s_cbranch_execz " L "f\n\t"                                     \
     "v_sqrt_f32 %[t" K "], %[rsq" K "]\n\t"                           \
     "s_nop 0\n\t"
+// Slot 1 of the forms without RET: its cutoff compare is a plain v_cmp into c1 under the full mask, AHEAD of slot 0
+// (BP_PRE1), and the slot starts with s_mov exec, c1 where it had "s_mov exec, full; v_cmpx". The same instructions in
+// number on the live path, but the compare no longer waits behind a write of exec: measured alone on the sources
+// before, C2 -2.4 %, C3 RDF -2.6 % (profiles/halves_ab.txt). A skipped slot 1 left exec = c1 = 0, which is amb = 0.
+#define BP_PRE1 "v_cmp_gt_f32_e64 %[c1], %[rc2], %[rsq1]\n\t"
+#define BP_SLOT1(L)                                                  \
+    "s_mov_b64 exec, %[c1]\n\t"                                      \
+    "s_cbranch_execz " L "f\n\t"                                     \
+    "v_sqrt_f32 %[t1], %[rsq1]\n\t"                                  \
+    "s_nop 0\n\t"
+// slot 0's end in front of BP_SLOT1: no exec restore, the next instruction sets exec
+#define BP_SLOT0_END(L) "s_andn2_b64 %[c0], %[c0], %[d0]\n\t" L ":\n\t"
 #define BP_SLOT_CUT(K) "v_cmpx_lt_f32_e64 %[d" K "], %[t" K "], %[cl]\n\t"
 #define BP_SLOT_MID(K)                                               \
     "v_fma_f32 %[t" K "], %[t" K "], %[gs], %[no" K "]\n\t"           \
@@ -459,16 +479,22 @@ __device__ __forceinline__ RelQ load_relq(const float *__restrict__ p)
     "v_cmpx_ge_f32_e64 %[d" K "], %[fr], %[n2]\n\t"                  \
     "ds_add_u32 %[t" K "], %[one]\n\t"
 #define BP_SLOT_END(K, L)                                            \
-    L ":\n\t"                                                       \
     "s_andn2_b64 %[c" K "], %[c" K "], %[d" K "]\n\t"                 \
+    L ":\n\t"                                                       \
     "s_mov_b64 exec, %[full]\n\t"
-// RET: the lanes that added = c & d (c = 0 when the slot was skipped), before c becomes amb
+// RET: the lanes that added = c & d (c = 0 when the slot was skipped: that path joins in front of the s_and, which makes
+// done = 0 of whatever d holds, and runs the s_andn2 as well), before c becomes amb
 #define BP_SLOT_DONE(K, L) L ":\n\t" "s_and_b64 %[dn" K "], %[c" K "], %[d" K "]\n\t"
 struct PairOut {
     unsigned long long amb0, amb1;    // lanes whose pair lies inside the error band (to be queued for the exact chain)
     unsigned long long done0, done1;  // RET: lanes that added to the histogram
     unsigned addr0, addr1;            // RET: the LDS address every lane computed
 };
+// `hold` is not read: as an operand it keeps a value of the caller (the next two slots' squared distances) computed
+// ahead of this block, where the compiler would otherwise sink its chain behind the block. This rests on how this
+// compiler schedules, not on anything the language promises, and nothing asserts it: after a compiler update the
+// chain may sink again (the result stays right; the s_nops and ~0.7 % of the C2 step come back). Compare the hot
+// loop's s_nop count in the compiler's assembly, tools/disasm_pair_loop.py, when the toolchain changes.
 // Returns whether any lane of either slot is ambiguous (one test for both slots; leaving the asm through an
 // `asm goto` exit on the s_or's scc would save the compare, but callbr with outputs crashes this compiler's ISel).
 // (Round 3 measured the queue push of the ambiguous lanes inside the block, branching on the s_andn2's SCC, build
@@ -478,14 +504,14 @@ struct PairOut {
 template <bool CUTG, bool RET>
 __device__ __forceinline__ bool bin_pair2(float rsq0, float rsq1, float rc2hi, float gscale, float nearoff0, float nearoff1,
                                           float near2, unsigned rowbase0, unsigned rowbase1, float cut_lo,
-                                          unsigned long long full, PairOut &o)
+                                          unsigned long long full, f32x2 hold, PairOut &o)
 {
     unsigned long long c0, c1, d0, d1;
     float t0, t1, fr;
 #define BP_OUT [c0] "=&s"(c0), [c1] "=&s"(c1), [d0] "=&s"(d0), [d1] "=&s"(d1), [t0] "=&v"(t0), [t1] "=&v"(t1), [fr] "=&v"(fr)
 #define BP_IN                                                                                                          \
     [rc2] "s"(rc2hi), [rsq0] "v"(rsq0), [rsq1] "v"(rsq1), [gs] "v"(gscale), [no0] "s"(nearoff0), [no1] "s"(nearoff1),   \
-        [n2] "v"(near2), [rb0] "v"(rowbase0), [rb1] "v"(rowbase1), [one] "v"(1u), [full] "s"(full)
+        [n2] "v"(near2), [rb0] "v"(rowbase0), [rb1] "v"(rowbase1), [one] "v"(1u), [full] "s"(full), [hold] "v"(hold)
     if (RET) {
         unsigned long long dn0, dn1;
         if (CUTG)
@@ -513,14 +539,14 @@ __device__ __forceinline__ bool bin_pair2(float rsq0, float rsq1, float rc2hi, f
         return (c0 | c1) != 0;
     }
     if (CUTG) {
-        asm volatile(BP_SLOT("0", "1") BP_SLOT_CUT("0") BP_SLOT_MID("0") BP_SLOT_END("0", "1")
-                     BP_SLOT("1", "2") BP_SLOT_CUT("1") BP_SLOT_MID("1") BP_SLOT_END("1", "2")
+        asm volatile(BP_PRE1 BP_SLOT("0", "1") BP_SLOT_CUT("0") BP_SLOT_MID("0") BP_SLOT0_END("1")
+                     BP_SLOT1("2") BP_SLOT_CUT("1") BP_SLOT_MID("1") BP_SLOT_END("1", "2")
                      : BP_OUT
                      : BP_IN, [cl] "v"(cut_lo)
                      : "vcc", "scc", "memory");
     } else {
-        asm volatile(BP_SLOT("0", "1") BP_SLOT_MID("0") BP_SLOT_END("0", "1")
-                     BP_SLOT("1", "2") BP_SLOT_MID("1") BP_SLOT_END("1", "2")
+        asm volatile(BP_PRE1 BP_SLOT("0", "1") BP_SLOT_MID("0") BP_SLOT0_END("1")
+                     BP_SLOT1("2") BP_SLOT_MID("1") BP_SLOT_END("1", "2")
                      : BP_OUT
                      : BP_IN
                      : "vcc", "scc", "memory");
@@ -532,6 +558,9 @@ __device__ __forceinline__ bool bin_pair2(float rsq0, float rsq1, float rc2hi, f
 #undef BP_IN
 }
 #undef BP_SLOT
+#undef BP_PRE1
+#undef BP_SLOT1
+#undef BP_SLOT0_END
 #undef BP_SLOT_CUT
 #undef BP_SLOT_MID
 #undef BP_SLOT_END
@@ -585,13 +614,19 @@ __device__ __forceinline__ void pk_push(PkCtx &p, unsigned long long mask, unsig
 // itself prefetched during the previous sweep.
 // CNG: the group is near enough to the wave to hold pairs of a CN split bin: every pair the sweep bins is looked up in
 // the flag bits, and the ones in a flagged word are queued as PK_CN_ONLY entries.
-template <bool DIAG, int VAR, bool PF, bool CUTG, bool ROWS, bool CNG>
+template <bool DIAG, int VAR, bool PF, bool CUTG, bool ROWS, bool CNG, bool HOLD>
 __device__ __forceinline__ void sweep_group_pk(const RelQ &rq, GroupIdx jidx0, int local0, PkCtx &p, const FastCtx &c,
                                                int lane_in_tile, int lane, const float *next_p, RelQ &next)
 {
     unsigned row[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    // The squared distances of all four slots first, the two pair blocks behind them: a packed f32 result needs a wait
+    // state before a dependent instruction reads it, and with the two halves' chains in one basic block the scheduler
+    // fills those with the other half's operations, where a chain on its own between two pair blocks got an s_nop
+    // behind each of its last three links (HOLD; bin_pair2's `hold` operand keeps the second chain up there). Not in the
+    // kernels that also count coordination numbers, which have no registers left for it: they keep chain, blocks, chain,
+    // blocks, and their spills (tests/test_codegen_cpu.py holds both to their budgets).
+    f32x2 rsq2[2];
+    auto chain = [&](int h) {
         const f32x4 ra = h ? rq.c : rq.a, rb = h ? rq.d : rq.b;
         const f32x2 xj = {ra[0], ra[1]};
         const f32x2 yj = {ra[2], ra[3]};
@@ -618,7 +653,11 @@ __device__ __forceinline__ void sweep_group_pk(const RelQ &rq, GroupIdx jidx0, i
         if (VAR & 4) dz = wrap_pk(dz, p.Lz2, p.iLz2);
         f32x2 rsq = dx * dx;
         rsq = __builtin_elementwise_fma(dy, dy, rsq);
-        rsq = __builtin_elementwise_fma(dz, dz, rsq);
+        rsq2[h] = __builtin_elementwise_fma(dz, dz, rsq);
+    };
+    auto blocks = [&](int h) {
+        const f32x4 rb = h ? rq.d : rq.b;
+        const f32x2 rsq = rsq2[h];
         // ordered rows: w = the bin-guess addend near + tj * row_len; class rows: w = the table offset of tj
         const float nearoff0 = ROWS ? c.near : rb[2], nearoff1 = ROWS ? c.near : rb[3];
         const unsigned rowbase0 = ROWS ? row[2 * h] : c.rowbase_me, rowbase1 = ROWS ? row[2 * h + 1] : c.rowbase_me;
@@ -638,7 +677,7 @@ __device__ __forceinline__ void sweep_group_pk(const RelQ &rq, GroupIdx jidx0, i
         }
         PairOut o;
         const bool any_amb = bin_pair2<CUTG, CNG>(r2a, r2b, p.rc2hi, c.gscale, nearoff0, nearoff1, c.near2, rowbase0,
-                                                  rowbase1, p.cut_lo, p.full, o);
+                                                  rowbase1, p.cut_lo, p.full, HOLD ? rsq2[1] : rsq, o);
         if (CNG && (o.done0 | o.done1)) {  // wave-uniform
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
@@ -647,7 +686,8 @@ __device__ __forceinline__ void sweep_group_pk(const RelQ &rq, GroupIdx jidx0, i
                 if (hm) pk_push(p, hm, PK_CN_ONLY | ((unsigned)(jidx_here(jidx0) + 2 * h + u) << 6), lane);
             }
         }
-        if (any_amb) {  // wave-uniform, rare: some lane's pair is inside the error band -> the exact chain, later
+        // wave-uniform, rare: some lane's pair is inside the error band -> the exact chain, later
+        if (__builtin_expect(any_amb, 0)) {
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 // (the copy through a volatile asm keeps the per-lane test inside this branch: the compiler would
@@ -657,6 +697,17 @@ __device__ __forceinline__ void sweep_group_pk(const RelQ &rq, GroupIdx jidx0, i
                 if (amb_in) pk_push(p, amb_in, (unsigned)(jidx_here(jidx0) + 2 * h + u) << 6, lane);
             }
         }
+    };
+    if (HOLD) {
+        chain(0);
+        chain(1);
+        blocks(0);
+        blocks(1);
+    } else {
+        chain(0);
+        blocks(0);
+        chain(1);
+        blocks(1);
     }
 }
 
@@ -873,7 +924,7 @@ __device__ __forceinline__ int sj_item_pk(const PairArgs &a, FastCtx &c, const u
             }
             const int jbase = J * TILE;
 #define PK_DRAIN_CHECK() \
-    if (p.qn > 64) pk_drain<CNG>(p, c, lane)
+    if (__builtin_expect(p.qn > 64, 0)) pk_drain<CNG>(p, c, lane)
             // the common variant (no per-pair wrap), software-pipelined: the records of the next group are loaded
             // while the current group is swept; two buffers, loop unrolled by two (no register copies). With CNG the
             // groups near the wave run the same pipeline in its split-bin-checking form (an unpipelined near loop
@@ -899,13 +950,13 @@ __device__ __forceinline__ int sj_item_pk(const PairArgs &a, FastCtx &c, const u
                 PK_DRAIN_CHECK();                                                                                       \
                 const bool moreB = mk != 0;                                                                             \
                 PK_NEXT(gB)                                                                                             \
-                sweep_group_pk<DG, VAR, true, CUTG, ROWS, CN>(qA, GroupIdx{jbase, gA}, gA * SJ_GROUP, p, c,             \
+                sweep_group_pk<DG, VAR, true, CUTG, ROWS, CN, !CNG>(qA, GroupIdx{jbase, gA}, gA * SJ_GROUP, p, c,             \
                                                                  lane_in_tile, lane, PK_REC(gB), qB);                   \
                 if (!moreB) break;                                                                                      \
                 PK_DRAIN_CHECK();                                                                                       \
                 const bool moreA = mk != 0;                                                                             \
                 PK_NEXT(gA)                                                                                             \
-                sweep_group_pk<DG, VAR, true, CUTG, ROWS, CN>(qB, GroupIdx{jbase, gB}, gB * SJ_GROUP, p, c,             \
+                sweep_group_pk<DG, VAR, true, CUTG, ROWS, CN, !CNG>(qB, GroupIdx{jbase, gB}, gB * SJ_GROUP, p, c,             \
                                                                  lane_in_tile, lane, PK_REC(gA), qA);                   \
                 if (!moreA) break;                                                                                      \
             }                                                                                                           \
@@ -938,15 +989,15 @@ __device__ __forceinline__ int sj_item_pk(const PairArgs &a, FastCtx &c, const u
             // what is left — the diagonal tile, and wrapping groups the CN check walks —: not pipelined
 #define PK_SWEEP_CASES(CN)                                                                                             \
     switch (A) {                                                                                                       \
-    case 1: sweep_group_pk<false, 1, false, CUTG, ROWS, CN>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break; \
-    case 2: sweep_group_pk<false, 2, false, CUTG, ROWS, CN>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break; \
-    case 3: sweep_group_pk<false, 3, false, CUTG, ROWS, CN>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break; \
-    case 4: sweep_group_pk<false, 4, false, CUTG, ROWS, CN>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break; \
-    case 5: sweep_group_pk<false, 5, false, CUTG, ROWS, CN>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break; \
-    case 6: sweep_group_pk<false, 6, false, CUTG, ROWS, CN>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break; \
-    case 7: sweep_group_pk<false, 7, false, CUTG, ROWS, CN>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break; \
-    case 9: sweep_group_pk<true, 0, false, CUTG, ROWS, CN>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break;  \
-    case 8: sweep_group_pk<true, 7, false, CUTG, ROWS, CN>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break;  \
+    case 1: sweep_group_pk<false, 1, false, CUTG, ROWS, CN, !CNG>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break; \
+    case 2: sweep_group_pk<false, 2, false, CUTG, ROWS, CN, !CNG>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break; \
+    case 3: sweep_group_pk<false, 3, false, CUTG, ROWS, CN, !CNG>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break; \
+    case 4: sweep_group_pk<false, 4, false, CUTG, ROWS, CN, !CNG>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break; \
+    case 5: sweep_group_pk<false, 5, false, CUTG, ROWS, CN, !CNG>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break; \
+    case 6: sweep_group_pk<false, 6, false, CUTG, ROWS, CN, !CNG>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break; \
+    case 7: sweep_group_pk<false, 7, false, CUTG, ROWS, CN, !CNG>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break; \
+    case 9: sweep_group_pk<true, 0, false, CUTG, ROWS, CN, !CNG>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break;  \
+    case 8: sweep_group_pk<true, 7, false, CUTG, ROWS, CN, !CNG>(q, j0, l0, p, c, lane_in_tile, lane, nullptr, qnone); break;  \
     default: break;                                                                                                    \
     }
             // (the diagonal tile, i < j inside the tile: 9 = plain where every axis qualifies, 8 = the wrap on all axes)
