@@ -780,6 +780,45 @@ int mdhip_angle_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const do
                      int32_t n_triplets, const int32_t *triplet_class, const double *triplet_rsq, int32_t n_bins,
                      const double *cos_edges, int32_t cap, uint64_t *hist, uint64_t *n_degenerate, int32_t *count);
 
+/* ---- order parameters (order_parameters.py calc_order_parameters; not in the reference) ---- */
+/*
+ * Per centre and frame the Steinhardt bond-orientational order parameters q_l, the Lechner-Dellago averaged qbar_l and
+ * the tetrahedral pair (q_tet, s_k), for a batch of frames: coordinates xyz [F][3][n_atoms] (host or device memory as
+ * xyz_on_device says), box [F][3], the centre atoms centres[n_centres], the candidate atoms cand[n_cand] (every atom
+ * that can be a neighbour, distinct), mol_of[n_atoms] (NULL: no exclusion), the squared cutoff, the degrees
+ * degrees[n_degrees] (distinct, 1 <= l <= 12, at most 4) and n_nearest (0: every neighbour).
+ * For one frame and one centre c:
+ *   neighbour j of c: a candidate, j != c, rsq(c, j) < r_cut_sq (the reference's single-wrap rsq, rdf_cn.py:36-58,
+ *     strict), and mol_of[j] != mol_of[c] under exclusion; with n_nearest = k > 0 the k neighbours smallest by
+ *     (rsq, atom index) are selected, else all; a row of fewer than k neighbours (k = 0: of none) is short;
+ *   d_j = x_j - x_c wrapped once per axis (d > L/2 ? d - L : (d < -L/2 ? d + L : d)), n_j = sqrt((dx dx + dy dy) + dz dz),
+ *     u_j = d_j / n_j; a selected neighbour with n_j == 0 or not finite makes the row degenerate (a short row is short
+ *     only);
+ *   q_lm = (1 / N) sum_j Y_lm(u_j) over the N selected neighbours in ascending atom index, real spherical harmonics
+ *     from the recurrence of the normalised associated Legendre functions in u_z and the powers of rho = sqrt(ux ux +
+ *     uy uy) and (ux + i uy) / rho (rho == 0: only m = 0 is not zero); q_l = sqrt(4 pi / (2l + 1) sum_m q_lm q_lm);
+ *   qbar_lm(c) = (q_lm(c) + sum_j q_lm(j)) / (N + 1) over the same N neighbours in ascending atom index (averaged:
+ *     cand must equal centres, so that a neighbour is a row of its own), qbar_l from qbar_lm as q_l from q_lm; NaN of
+ *     any member (the row itself or a neighbour, short or degenerate) propagates, and the row counts as short;
+ *   q_tet = 1 - 3/8 sum_{j<k} (cos_jk + 1/3)^2, cos_jk = ((dxj dxk + dyj dyk) + dzj dzk) / (n_j n_k), and
+ *     s_k = 1 - 1/3 sum_k ((n_k - rbar)^2 / (4 rbar rbar)), rbar = (((n_0 + n_1) + n_2) + n_3) / 4, over the 4 neighbours
+ *     smallest by (rsq, atom index), taken in ascending atom index (pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3));
+ *     fewer than 4 neighbours: short; one of the 4 with n == 0 or not finite: degenerate.
+ *   q [F][n_centres][n_degrees], qbar the same (averaged != 0, else NULL), tet [F][n_centres][2] = (q_tet, s_k)
+ *     (tetrahedral != 0, else NULL): NaN for a short or degenerate row;
+ *   flags [F][n_centres]: bit 0 q short, 1 q degenerate, 2 tetrahedral short, 3 tetrahedral degenerate, 4 qbar short;
+ *   count [F][n_centres]: the neighbours of the row, exact even when it exceeds cap. A row with count > cap gives NaN
+ *     and no flag: call again with cap >= the largest count.
+ * The values do not depend on cap, on the order in which the search found the neighbours, or on the launch. 1 <= cap
+ * <= 512, 0 <= n_nearest <= 512; at least one degree or tetrahedral. Outputs are host memory. The call's aux time
+ * (mdhip_last_aux_ms) is that of the gather and the search; the rest of its kernel time is the row passes.
+ */
+int mdhip_bond_order(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int xyz_on_device,
+                     const double *box, int32_t n_centres, const int32_t *centres, int32_t n_cand, const int32_t *cand,
+                     const int32_t *mol_of, double r_cut_sq, int32_t n_degrees, const int32_t *degrees,
+                     int32_t n_nearest, int32_t averaged, int32_t tetrahedral, int32_t cap, double *q, double *qbar,
+                     double *tet, int32_t *flags, int32_t *count);
+
 /* ---- spatial distribution functions (spatial_distribution.py calc_spatial_distribution; not in the reference) ---- */
 /*
  * The three-dimensional histogram of observed atoms in the body-fixed frame of a reference molecule, for a batch of

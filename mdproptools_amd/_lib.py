@@ -142,6 +142,9 @@ PROTOTYPES = {
                                          c_ip, C.c_double, C.c_double, C.c_double, C.c_int32, c_ip, c_ip, c_up]),
     "mdhip_angle_hist": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int32, c_ip, c_ip, C.c_int32, c_ip,
                                    c_ip, c_ip, C.c_int32, c_ip, c_dp, C.c_int32, c_dp, C.c_int32, c_up, c_up, c_ip]),
+    "mdhip_bond_order": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int32, c_ip, C.c_int32, c_ip, c_ip,
+                                   C.c_double, C.c_int32, c_ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_dp, c_dp,
+                                   c_dp, c_ip, c_ip]),
     "mdhip_body_frames": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int32, c_ip, c_ip, c_ip, c_dp, c_up]),
     "mdhip_sdf_hist": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int32, c_ip, c_ip, c_ip, C.c_int32, c_ip,
                                  c_ip, C.c_int32, c_ip, C.c_double, C.c_double, C.c_double, C.c_int32, c_up, c_up, c_ip,

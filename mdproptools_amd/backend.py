@@ -830,6 +830,73 @@ def angle_hist(xyz, box, types, triplets, r_cut_sq, cos_edges, mol_of=None, cap=
     return hist, degen, count, cen
 
 
+BOND_CAP = 64  # first-try neighbours per (frame, centre) row of bond_order; a batch with a larger row is run again
+BOND_MAX_CAP = 512  # what the row kernel stages (include/mdhip.h: mdhip_bond_order)
+BOND_MAX_DEGREES = 4
+BOND_MAX_L = 12
+# the bits of bond_order's flags
+BOND_Q_SHORT, BOND_Q_DEGENERATE, BOND_TET_SHORT, BOND_TET_DEGENERATE, BOND_QBAR_SHORT = 1, 2, 4, 8, 16
+
+
+def bond_order(xyz, box, types, centre_type, neighbour_types, r_cut_sq, degrees=(4, 6), n_nearest=None, averaged=False,
+               tetrahedral=False, mol_of=None, cap=BOND_CAP, ctx=None):
+    """
+    Per-centre order parameters (include/mdhip.h: mdhip_bond_order): xyz [F,3,N], box [F,3], types [N] (the same in
+    every frame), the centres the atoms of `centre_type`, the candidates those whose type is in `neighbour_types` (both
+    ascending), degrees the l of q_l (distinct, 1..12, at most 4; may be empty with tetrahedral), n_nearest (None:
+    every neighbour within the cutoff), mol_of [N] (None: no molecule exclusion) -> a dict:
+      q float64 [F,C,D]; qbar float64 [F,C,D] (averaged, else None); tet float64 [F,C,2] = (q_tet, s_k) (tetrahedral,
+      else None); flags int32 [F,C] (the BOND_* bits); count int32 [F,C]; centres int32 [C].
+    NaN where a row is short or degenerate. A batch with a row of more than `cap` neighbours is run once more with a cap
+    of the largest count; more than 512 is a ValueError.
+    """
+    ctx = ctx or default_context()
+    F, _, N = _shape3(xyz, "xyz")
+    typ = _i32(types).ravel()
+    if len(typ) != N:
+        raise ValueError("types must hold one type per atom")
+    deg = _i32(list(degrees)).ravel()
+    D = len(deg)
+    mol = None
+    if mol_of is not None:
+        mol = _i32(mol_of).ravel()
+        if len(mol) != N:
+            raise ValueError("mol_of must hold one molecule index per atom")
+    cen = np.flatnonzero(typ == int(centre_type)).astype(np.int32)
+    cand = np.flatnonzero(np.isin(typ, _i32(list(neighbour_types)).ravel())).astype(np.int32)
+    C_ = len(cen)
+    bx = _f64(box).reshape(F, 3)
+    xp, x_dev, keep = as_input(xyz, ctx)
+
+    def run(k):
+        q = np.full((F, C_, D), np.nan)
+        qbar = np.full((F, C_, D), np.nan) if averaged else None
+        tet = np.full((F, C_, 2), np.nan) if tetrahedral else None
+        flags = np.zeros((F, C_), dtype=np.int32)
+        count = np.zeros((F, C_), dtype=np.int32)
+        ctx.check(ctx.lib.mdhip_bond_order(
+            ctx.h, F, N, xp, x_dev, ptr(bx), C_, ptr(cen, C.c_int32), len(cand), ptr(cand, C.c_int32),
+            None if mol is None else ptr(mol, C.c_int32), float(r_cut_sq), D, ptr(deg, C.c_int32),
+            int(n_nearest or 0), int(bool(averaged)), int(bool(tetrahedral)), int(k), ptr(q),
+            None if qbar is None else ptr(qbar), None if tet is None else ptr(tet), ptr(flags, C.c_int32),
+            ptr(count, C.c_int32)))
+        return {"q": q, "qbar": qbar, "tet": tet, "flags": flags, "count": count, "centres": cen}
+
+    cap = int(cap)
+    out = run(cap)
+    count = out["count"]
+    big = int(count.max()) if count.size else 0
+    if big > cap:
+        if big > BOND_MAX_CAP:
+            f, c = np.unravel_index(int(count.argmax()), count.shape)
+            raise ValueError("bond_order: frame %d, centre atom %d has %d neighbours; at most %d are supported "
+                             "(a smaller cutoff?)" % (f, int(cen[c]), big, BOND_MAX_CAP))
+        out = run(big)  # (the first call's values are discarded)
+        if not np.array_equal(out["count"], count):
+            raise RuntimeError("bond_order: the re-run found other row sizes than the first sweep")
+    return out
+
+
 SDF_MAX_SPECIES = 8        # observed species per call of sdf_hist (include/mdhip.h: mdhip_sdf_hist)
 SDF_MAX_GRID = 256         # cells per axis
 SDF_MAX_CELLS = 1 << 25    # n_species * G**3

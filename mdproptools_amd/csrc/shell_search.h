@@ -1,6 +1,6 @@
-// shell_search.h — the per-centre shell search and what its four consumers do around it. For each centre atom of each
+// shell_search.h — the per-centre shell search and what its five consumers do around it. For each centre atom of each
 // frame, the sweep hands every candidate point within r_cut under the reference's single-wrap rsq (rdf_cn.py:44-57) to
-// a functor. All four run the sweep, append hits to capped rows (append; on the host RowSet) and begin and end their
+// a functor. All five run the sweep, append hits to capped rows (append; on the host RowSet) and begin and end their
 // entry points with stage and finish. Beyond that:
 //   clusters.hip        every atom a candidate, rows of molecules; rank_row puts them in order
 //   configurations.hip  every atom a candidate, rows of (molecule, word) records; row_of in its hit, rank_row_keyed
@@ -8,6 +8,8 @@
 //                       in its row pass; its counts mode keeps no rows (plain counters)
 //   angles.hip          gathered candidates (check_indices); wrap_signed; row_of in its pair pass; finish with the
 //                       search's aux timer
+//   bond_order.hip      gathered candidates (check_indices); row_of, wrap_signed and rsq again in its row pass, which
+//                       ranks a row by (rsq, atom) itself; finish with the search's aux timer
 // The reference's arithmetic is unfused: an including .hip puts `#pragma clang fp contract(off)` AHEAD of this include
 // (it has to be in force where wrap_abs / wrap_signed / rsq are instantiated). residence.hip (rt_wrap_abs) and
 // pair_common.h (wrap_abs) keep copies of the wrap: the committed counter runs are tied to those files byte for byte.
