@@ -1154,6 +1154,63 @@ int mdhip_axis_vectors(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const 
 int mdhip_orient_corr(mdhip_ctx *ctx, int64_t n, int64_t n_series, const double *U, int U_on_device, int n_groups,
                       const int64_t *group_off, int64_t max_lag, double *sums, int sums_on_device);
 
+/* ---- dihedral angles (structural/dihedral_distribution.py; no counterpart in the reference) ---- */
+/*
+ * Intramolecular torsions i-j-k-l: their histograms per row and / or their series (cos phi, sin phi, 0), time-major —
+ * the input of mdhip_orient_corr, whose S1 then is the sum of cos(phi(t+k) - phi(t)): the torsional autocorrelation.
+ *   x          host|dev (x_on_device) [n_frames][3][n_atoms], atoms by id, molecules contiguous (as mdhip_axis_vectors)
+ *   box        host [n_frames][3] edge lengths, or NULL: x is unwrapped
+ *   jobs       job j covers job_mols[j] molecules of job_len[j] atoms each, the first one starting at atom job_atom0[j]
+ *              (host [n_jobs]); job_quad host [n_jobs][4]: the atoms i j k l, 0-based inside the molecule, within
+ *              [0, job_len) and pairwise different; job_row host [n_jobs]: the histogram row the job adds to, within
+ *              [0, n_rows), 1 <= n_rows <= 16 (several jobs may share a row: pooled torsions)
+ *   n_bins     even, 2 .. 1440: bins of D = 360 / n_bins degrees over [-180, 180)
+ *   cos_edges  host [n_bins / 2]: cos(m * D) as the host evaluates it, strictly decreasing (entry 0 is not read)
+ *   hist       host uint64 [n_rows][n_bins], or NULL: no histogram (cos_edges may be NULL then)
+ *   U          host|dev (U_on_device) [n_series][3][n_frames], n_series = sum of job_mols, series numbered job after
+ *              job, molecule after molecule; or NULL: no series
+ *   degenerate host uint64 [n_jobs]
+ * hist and degenerate hold THIS call's counts (they are not accumulated into: the host adds batches).
+ * Per (job, molecule, frame), a the molecule's first atom, every operation an IEEE double operation, nothing fused,
+ * sqrt and division correctly rounded:
+ *   per axis  b1 = w(x[a+j] - x[a+i]),  b2 = w(x[a+k] - x[a+j]),  b3 = w(x[a+l] - x[a+k]);  w is the single strict wrap
+ *             of the siblings, w(d) = d > L/2 ? d - L : (d < -L/2 ? d + L : d) (a NaN shifts nothing), the identity when
+ *             box == NULL. Each bond difference is wrapped on its own: correct whenever consecutive named atoms lie
+ *             within half a box edge of each other, as bonded atoms do; the molecule's first atom is not involved
+ *             unless it is named;
+ *   n1 = b1 x b2, n2 = b2 x b3, every component p*q - r*s as two products and one subtraction:
+ *             (u x v)_x = uy*vz - uz*vy, (u x v)_y = uz*vx - ux*vz, (u x v)_z = ux*vy - uy*vx;
+ *   dot(u, v) = (ux*vx + uy*vy) + uz*vz;
+ *   l1 = sqrt(dot(n1, n1)), l2 = sqrt(dot(n2, n2)), lb = sqrt(dot(b2, b2)), den = l1 * l2;
+ *   c = dot(n1, n2) / den                                                         (cos phi)
+ *   s = dot(b1, n2)                  (the sign of sin phi; IUPAC: cis = 0, trans = 180, right-hand rule about j -> k)
+ *   sn = (s * lb) / den                                                           (sin phi)
+ *   den == 0 (three of the four atoms collinear or coincident): degenerate[job] += 1, no bin, U = (0, 0, 0);
+ *   else c or s NaN (non-finite input): no bin, nothing counted, U = (NaN, NaN, 0);
+ *   else m = the number of q in [1, n_bins/2) with c <= cos_edges[q] — no acos, no atan2, no clamp: a cosine an ulp
+ *             outside +-1 lands in the first or last half-bin —, bin = s >= 0 ? n_bins/2 + m : n_bins/2 - 1 - m,
+ *             hist[job_row][bin] += 1 and U = (c, sn, 0).
+ * The bins mirror each other about 0: |phi| in [m D, (m+1) D) on either side. The positive half is left-closed as usual,
+ * the NEGATIVE HALF IS RIGHT-CLOSED: bin n_bins/2 - 1 - m holds -(m+1) D < phi <= -m D, except that s == +-0 counts as
+ * the positive side, so exactly 0 falls in bin n_bins/2 and exactly 180 in the last bin.
+ * Atoms that no quadruple names are never read: a NaN there does not leak.
+ * A workgroup owns 64 molecules x 64 frames (the tile of mdhip_axis_vectors: lane = molecule while reading, the two
+ * components through a padded LDS tile, lane = frame while writing); counts go to an LDS histogram of the workgroup
+ * and from there once into 64-bit device bins, with integer atomics only: exact, and independent of the order. Jobs
+ * with the same (job_atom0, job_mols, job_len) are worked by the same workgroup one after the other, so their lines
+ * come from HBM once (and from the caches for the further jobs). One read of the lines that hold named atoms, one
+ * write of U when asked: a single job per molecule type runs at the HBM rate (DESIGN 4.13c has the measured cost of
+ * pooled ones). Any number of frames and molecules, up to 2^20 jobs: launch dimensions over 65535 are split inside
+ * the call.
+ * n_jobs < 1 (or > 2^20), n_rows outside 1..16, a job_row outside [0, n_rows), n_bins odd or outside 2..1440, a
+ * quadruple entry outside [0, job_len) or repeated, a job that runs past n_atoms, hist and U both NULL, cos_edges NULL
+ * (or not strictly decreasing) while hist is not, any other NULL array: MDHIP_EINVAL before anything is written.
+ */
+int mdhip_dihedral_angles(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *x, int x_on_device,
+                          const double *box, int n_jobs, const int64_t *job_atom0, const int64_t *job_mols,
+                          const int32_t *job_len, const int32_t *job_quad, const int32_t *job_row, int n_rows, int n_bins,
+                          const double *cos_edges, uint64_t *hist, double *U, int U_on_device, uint64_t *degenerate);
+
 /*
  * Replaces, for the inputs of the path, the un-vendored pymatgen `parse_lammps_dumps` + pandas
  * `read_csv` the reference uses (call sites structural/rdf_cn.py:176, dynamical/diffusion.py:172,

@@ -1376,3 +1376,70 @@ def orient_corr(U, group_off, max_lag, out=None, ctx=None):
         res, op, o_dev = out, _dev_out(out, (L, G, 2), ctx=ctx), 1
     ctx.check(ctx.lib.mdhip_orient_corr(ctx.h, n, S, up, u_dev, G, ptr(off, C.c_int64), int(max_lag), op, o_dev))
     return res
+
+
+DIHEDRAL_MAX_ROWS = 16    # histogram rows per call of dihedral_angles (include/mdhip.h: mdhip_dihedral_angles)
+DIHEDRAL_MAX_BINS = 1440  # bins over [-180, 180): 0.25 degrees
+
+
+def dihedral_cos_edges(n_bins):
+    """cos(m * D), m = 0 .. n_bins/2 - 1, D = 360 / n_bins degrees: the bin table of dihedral_angles."""
+    return np.cos(np.radians(np.arange(n_bins // 2) * (360.0 / n_bins)))
+
+
+def dihedral_angles(x, box, job_atom0, job_mols, job_len, quads, job_row=None, n_bins=None, want_series=False, out=None,
+                    ctx=None):
+    """
+    Dihedral angles i-j-k-l inside molecules (include/mdhip.h: mdhip_dihedral_angles): x [F,3,A] coordinates, atoms by id
+    and molecules contiguous (host array or contiguous float64 device tensor); box [F,3] edge lengths, or None when x is
+    unwrapped. Job j covers job_mols[j] molecules of job_len[j] atoms from atom job_atom0[j] on; quads[j] = (i, j, k, l),
+    0-based atoms inside the molecule, all different; job_row[j] the histogram row it adds to (default: row j).
+    n_bins (even, 2 .. 1440): histograms over [-180, 180) in bins of 360 / n_bins degrees, mirrored about 0 (the
+    negative half is right-closed); None: no histogram. want_series (or `out`): the series U [S,3,F] = (cos phi,
+    sin phi, 0), S = sum(job_mols), series job after job and molecule after molecule.
+    Returns (hist uint64 [n_rows, n_bins] or None, U or None, degenerate uint64 [n_jobs] = the (molecule, frame) pairs
+    of every job with three collinear atoms): U is a host array, or `out` (float64 CUDA tensor [S,3,F]) when given.
+    """
+    ctx = ctx or default_context()
+    F, _, A = _shape3(x, "x")
+    bx = None
+    if box is not None:
+        bx = _f64(box)
+        if bx.shape != (F, 3):
+            raise ValueError("box must have shape [n_frames, 3]")
+    a0, mols, length = _i64(job_atom0), _i64(job_mols), _i32(job_len)
+    quad = _i32(quads)
+    J = len(quad)
+    if not (a0.shape == mols.shape == length.shape == (J,)) or quad.shape != (J, 4):
+        raise ValueError("job_atom0, job_mols and job_len must hold one entry, quads one (i, j, k, l), per job")
+    want_series = bool(want_series) or out is not None
+    if n_bins is None and not want_series:
+        raise ValueError("nothing asked for: give n_bins for histograms, want_series or out for the series")
+    if n_bins is None:
+        rows, n_rows = np.zeros(J, dtype=np.int32), 1
+    else:
+        rows = _i32(np.arange(J) if job_row is None else job_row)
+        if rows.shape != (J,):
+            raise ValueError("job_row must hold one row per job")
+        n_rows = int(rows.max()) + 1 if J else 1
+    nb = 2 if n_bins is None else int(n_bins)
+    edges = hist = None
+    if n_bins is not None:
+        edges = _f64(dihedral_cos_edges(nb))
+        hist = np.zeros((max(n_rows, 0), max(nb, 0)), dtype=np.uint64)
+    S = int(mols.sum()) if J and mols.min() >= 0 else 0
+    xp, x_dev, keep = as_input(x, ctx)
+    res, up, u_dev = None, None, 0
+    if out is not None:
+        res, up, u_dev = out, _dev_out(out, (S, 3, F), ctx=ctx), 1
+    elif want_series:
+        res = result_array((S, 3, F), device=ctx.device)
+        up = C.c_void_p(res.ctypes.data)
+    degenerate = np.zeros(max(J, 1), dtype=np.uint64)
+    ctx.check(ctx.lib.mdhip_dihedral_angles(ctx.h, F, A, xp, x_dev, None if bx is None else ptr(bx), J,
+                                            ptr(a0, C.c_int64), ptr(mols, C.c_int64), ptr(length, C.c_int32),
+                                            ptr(quad, C.c_int32), ptr(rows, C.c_int32), n_rows, nb,
+                                            None if edges is None else ptr(edges),
+                                            None if hist is None else ptr(hist, C.c_uint64), up, u_dev,
+                                            ptr(degenerate, C.c_uint64)))
+    return hist, res, degenerate[:J]

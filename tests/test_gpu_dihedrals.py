@@ -1,0 +1,379 @@
+"""
+mdhip_dihedral_angles (csrc/dihedrals.hip) and structural/dihedral_distribution.py on the GPU, against the numpy
+restatement (tests/dihedral_ref.py).
+
+The header states every operation, so histograms and degenerate counts are compared with `==` and the series U bit for
+bit (reorientation_ref.same_bits). Shapes are the smallest at which the kernel can go wrong: either side of its
+64 x 64 tile, bond differences at the half edge, every n_bins from 2 to 1440, 16 rows, pooled jobs over one molecule
+type (one class, worked by one workgroup) beside a second type, and the launch dimension beyond 65 535.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import dihedral_ref as R
+import reorientation_ref as RR
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def B():
+    from mdproptools_amd import backend
+
+    return backend
+
+
+def _check(B, x, box, a0, mols, length, quads, rows=None, n_bins=360, want_deg=None):
+    """hist, U and degenerate of one call asking for both, against the restatement."""
+    w_hist, w_U, w_deg = R.dihedral_angles(x, box, a0, mols, length, quads, job_row=rows, n_bins=n_bins)
+    hist, U, deg = B.dihedral_angles(x, box, a0, mols, length, quads, job_row=rows, n_bins=n_bins, want_series=True)
+    assert hist.shape == w_hist.shape and hist.dtype == np.uint64 and U.shape == w_U.shape
+    bad = np.argwhere(~((U == w_U) | (np.isnan(U) & np.isnan(w_U))))
+    print("series", U.shape[0], "frames", U.shape[2], "bins", n_bins, "U mismatches", len(bad), bad[:5].tolist(),
+          "hist mismatches", int((hist != w_hist).sum()))
+    assert np.array_equal(hist, w_hist)
+    assert RR.same_bits(U, w_U)
+    assert deg.tolist() == w_deg.tolist()
+    if want_deg is not None:
+        assert deg.tolist() == list(want_deg)
+    return hist, U, deg
+
+
+def _molecules(rng, F, mols, per, L):
+    """Wrapped coordinates [F,3,mols*per] of chains with bonds about 1 long placed anywhere in boxes L [F,3]."""
+    centre = rng.random((F, 3, mols, 1)) * L[:, :, None, None]
+    x = centre + np.cumsum(rng.normal(0.0, 0.6, size=(F, 3, mols, per)), axis=3)
+    return np.ascontiguousarray(np.mod(x, L[:, :, None, None]).reshape(F, 3, mols * per))
+
+
+@pytest.mark.parametrize("mols", [1, 63, 64, 65])
+@pytest.mark.parametrize("F", [1, 63, 65, 130])
+def test_either_side_of_the_tile(B, mols, F):
+    rng = np.random.default_rng(1000 * mols + F)
+    L = 9.0 + rng.random((F, 3))                                    # the box varies per frame and axis
+    x = _molecules(rng, F, mols, 5, L)
+    hist, U, _ = _check(B, x, L, [0], [mols], [5], [(0, 1, 3, 4)], want_deg=[0])
+    assert hist.sum() == mols * F and np.abs(U[:, 0] ** 2 + U[:, 1] ** 2 - 1.0).max() < 1e-14 and not U[:, 2].any()
+    if mols == 65 and F == 130:   # some bond difference must have been wrapped
+        d = x[:, :, 1::5] - x[:, :, 0::5]
+        assert (np.abs(d) > L[:, :, None] / 2).any()
+
+
+def test_bond_differences_at_the_half_edge(B):
+    """Each of the three bond differences just above, exactly at and just below +-L/2 on every axis: the wrap is strict."""
+    F = 5
+    L = np.array([[8.0, 10.0, 12.0]] * F) + np.arange(F)[:, None] * 0.5
+    half = L / 2
+    base = np.array([[1.0, 0.25, 0.0], [0.5, 1.0, 0.25], [0.25, -0.5, 1.0]])     # b1, b2, b3 of a bent chain
+    cases = []
+    for bond in range(3):
+        for ax in range(3):
+            for sign in (1.0, -1.0):
+                for pick in (lambda h: h, lambda h: np.nextafter(h, np.inf), lambda h: np.nextafter(h, 0.0)):
+                    v = sign * pick(half[:, ax])
+                    pts = np.concatenate([np.zeros((F, 1, 3)), np.cumsum(np.tile(base[None], (F, 1, 1)), axis=1)], axis=1)
+                    # along `ax`: the atom before the bond at 0, the one behind it at v, the others a step of 1 away, so
+                    # that every difference the kernel forms is exact
+                    col = np.zeros((F, 4))
+                    col[:, bond + 1] = v
+                    for k in range(bond - 1, -1, -1):
+                        col[:, k] = col[:, k + 1] - 1.0
+                    for k in range(bond + 2, 4):
+                        col[:, k] = col[:, k - 1] - sign
+                    pts[:, :, ax] = col
+                    assert np.array_equal(col[:, bond + 1] - col[:, bond], v)
+                    assert np.all(np.abs(np.delete(np.diff(col, axis=1), bond, axis=1)) == 1.0)
+                    cases.append(pts)                                  # [F,4,3]
+    pts = np.stack(cases, axis=1)                                      # [F,M,4,3]
+    M = pts.shape[1]
+    x = np.ascontiguousarray(pts.transpose(0, 3, 1, 2).reshape(F, 3, 4 * M))
+    _, U, _ = _check(B, x, L, [0], [M], [4], [(0, 1, 2, 3)], want_deg=[0])
+    _, U_open, _ = _check(B, x, None, [0], [M], [4], [(0, 1, 2, 3)], want_deg=[0])
+    assert not RR.same_bits(U, U_open)                                 # some difference was shifted
+
+
+@pytest.mark.parametrize("n_bins", [2, 4, 360, 1440])
+def test_rows_pooled_jobs_and_a_second_type(B, n_bins):
+    """Three jobs over one molecule type pooled into one row (one class: the same workgroup works them one after the
+    other), a job over a second type, a quadruple and its reverse in rows of their own, and 16 rows with 16 jobs."""
+    rng = np.random.default_rng(n_bins)
+    F, m1, m2 = 70, 67, 5
+    L = 14.0 + rng.random((F, 3))
+    x = np.concatenate([_molecules(rng, F, m1, 7, L), _molecules(rng, F, m2, 4, L)], axis=2)
+    a0 = [0, 0, 7 * m1, 0, 0, 0]
+    quads = [(0, 1, 2, 3), (1, 2, 3, 4), (0, 1, 2, 3), (2, 3, 4, 5), (6, 5, 3, 1), (1, 3, 5, 6)]
+    rows = [0, 0, 1, 0, 2, 3]
+    hist, U, _ = _check(B, x, L, a0, [m1, m1, m2, m1, m1, m1], [7, 7, 4, 7, 7, 7], quads, rows, n_bins,
+                        want_deg=[0] * 6)
+    assert hist.sum(axis=1).tolist() == [3 * m1 * F, m2 * F, m1 * F, m1 * F]
+    assert np.array_equal(hist[2], hist[3])                           # (l, k, j, i) sees the same angle as (i, j, k, l)
+    quads16 = [tuple(rng.permutation(7)[:4]) for _ in range(16)]
+    hist, _, _ = _check(B, x, L, [0] * 16, [m1] * 16, [7] * 16, quads16, list(range(16))[::-1], n_bins)
+    assert hist.shape == (16, n_bins) and (hist.sum(axis=1) == m1 * F).all()
+
+
+def test_the_lattice_on_the_device(B):
+    """b1 = e_x, b2 = e_y, b3 in {-e_x, +e_x, +e_z, -e_z}: phi = 0, 180, +90, -90 exactly; n_bins = 4 puts them in bins
+    2, 3, 3 and 0 (the mirrored edge rule); a chain at prescribed torsions lands in the bins they name at D = 1."""
+    ex, ey, ez = np.eye(3)
+    pts = np.stack([np.cumsum([np.zeros(3), ex, ey, b3], axis=0) for b3 in (-ex, ex, ez, -ez)])       # [4,4,3]
+    x = np.ascontiguousarray(pts.transpose(2, 0, 1).reshape(1, 3, 16))
+    hist, U, _ = _check(B, x, None, [0, 4, 8, 12], [1] * 4, [4] * 4, [(0, 1, 2, 3)] * 4, [0, 1, 2, 3], 4, want_deg=[0] * 4)
+    assert hist.tolist() == [[0, 0, 1, 0], [0, 0, 0, 1], [0, 0, 0, 1], [1, 0, 0, 0]]
+    assert U[:, :, 0].tolist() == [[1.0, 0.0, 0.0], [-1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, -1.0, 0.0]]
+    phis = (60.5, -60.5, 179.5, -179.5, 0.5)
+    x = np.ascontiguousarray(np.stack([R.chain(p) for p in phis]).transpose(2, 0, 1).reshape(1, 3, 20))
+    hist, _, _ = _check(B, x, None, [0], [5], [4], [(0, 1, 2, 3)], n_bins=360, want_deg=[0])
+    assert np.flatnonzero(hist[0]).tolist() == sorted(int(np.floor(p + 180.0)) for p in phis)
+
+
+def test_unwrapped_far_from_the_origin_device_tensors_and_single_outputs(B):
+    rng = np.random.default_rng(7)
+    F, mols = 70, 37
+    x = np.cumsum(rng.normal(0.0, 0.4, size=(F, 3, 5 * mols + 4 * 11)), axis=0) + rng.normal(0, 3000, (1, 3, 1))
+    a0, m, length = np.array([0, 0, 5 * mols], dtype=np.int64), [mols, mols, 11], [5, 5, 4]
+    quads, rows = [(0, 1, 2, 3), (4, 2, 1, 0), (3, 1, 0, 2)], [1, 1, 0]
+    hist, U, deg = _check(B, x, None, a0, m, length, quads, rows, 72, want_deg=[0, 0, 0])
+    assert U.shape == (2 * mols + 11, 3, F)
+    # only the histogram, only the series
+    h_only, none, d1 = B.dihedral_angles(x, None, a0, m, length, quads, job_row=rows, n_bins=72)
+    assert none is None and h_only.tobytes() == hist.tobytes() and d1.tolist() == deg.tolist()
+    none, u_only, d2 = B.dihedral_angles(x, None, a0, m, length, quads, want_series=True)
+    assert none is None and u_only.tobytes() == U.tobytes() and d2.tolist() == deg.tolist()
+    # a device tensor in and `out=` give the same bytes
+    import torch
+
+    dev = torch.device("cuda", B.default_context().device)
+    out = torch.full((2 * mols + 11, 3, F), 7.0, dtype=torch.float64, device=dev)
+    h_dev, got, d3 = B.dihedral_angles(torch.as_tensor(x, device=dev), None, a0, m, length, quads, job_row=rows, n_bins=72,
+                                       out=out)
+    assert got is out and out.cpu().numpy().tobytes() == U.tobytes() and h_dev.tobytes() == hist.tobytes()
+    assert d3.tolist() == deg.tolist()
+
+
+def test_degenerate_and_non_finite_input(B):
+    rng = np.random.default_rng(8)
+    F, mols = 66, 70
+    L = np.full((F, 3), 11.0)
+    x = _molecules(rng, F, mols, 5, L)
+    a0, m, length = [0, 0], [mols, mols], [5, 5]
+    quads, rows = [(0, 1, 3, 4), (1, 3, 4, 0)], [0, 1]
+    base_h, base_U, _ = _check(B, x, L, a0, m, length, quads, rows, 360, want_deg=[0, 0])
+    # collinear quadruples: counted, not binned, zero series
+    z = x.copy()
+    z[5, :, 5 * 9 + 3] = z[5, :, 5 * 9 + 1]                            # atoms 1 and 3 of molecule 9 coincide: both jobs
+    z[65, :, 5 * 69 + 4] = 0.5 * (z[65, :, 5 * 69 + 3] + z[65, :, 5 * 69 + 3])   # ... 3 and 4 of molecule 69
+    hist, U, _ = _check(B, z, L, a0, m, length, quads, rows, 360, want_deg=[2, 2])
+    assert hist.sum(axis=1).tolist() == [mols * F - 2] * 2
+    assert not U[9, :, 5].any() and not U[69, :, 65].any() and not U[mols + 9, :, 5].any()
+    # a NaN in an atom no quadruple names: no bit changes
+    y = x.copy()
+    y[:, :, 2::5] = np.nan
+    hist, U, _ = _check(B, y, L, a0, m, length, quads, rows, 360, want_deg=[0, 0])
+    assert hist.tobytes() == base_h.tobytes() and U.tobytes() == base_U.tobytes()
+    # a NaN in a named atom: NaN in that (series, frame) only, that count missing, everything else unchanged
+    y = x.copy()
+    y[40, 1, 5 * 64 + 4] = np.nan
+    hist, U, _ = _check(B, y, L, a0, m, length, quads, rows, 360, want_deg=[0, 0])
+    hit = np.zeros(U.shape, dtype=bool)
+    hit[64, :2, 40] = hit[mols + 64, :2, 40] = True
+    assert np.isnan(U[hit]).all() and np.array_equal(U[~hit], base_U[~hit]) and not U[:, 2].any()
+    assert (base_h.astype(np.int64) - hist.astype(np.int64)).sum(axis=1).tolist() == [1, 1]
+    assert (base_h >= hist).all()
+    # coordinates of 1e300: products overflow; whatever the restatement makes of them
+    y = x.copy()
+    y[3, 0, 4] = 1e300
+    y[4, :, 5 * 2 + 1] = 1e300
+    _check(B, y, None, a0, m, length, quads, rows, 360)
+
+
+def test_invalid_arguments_leave_the_outputs_untouched(B):
+    """Straight to the C entry point: MDHIP_EINVAL before anything is written."""
+    from mdproptools_amd._lib import MdhipError, default_context, ptr
+
+    ctx = default_context()
+    vp = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+    x = np.random.default_rng(0).normal(size=(4, 3, 12))
+    good = dict(n_jobs=2, a0=[0, 6], mols=[2, 2], length=[3, 3], F=4, A=12, quad=[[0, 1, 2, 3]] * 2, row=[0, 1], n_rows=2,
+                n_bins=8)
+    good.update(a0=[0, 4], mols=[1, 2], length=[4, 4])
+    bad = [dict(n_jobs=0), dict(n_jobs=-1), dict(n_rows=0), dict(n_rows=17), dict(row=[0, 2]), dict(row=[-1, 0]),
+           dict(n_bins=0), dict(n_bins=7), dict(n_bins=1442), dict(n_bins=-2), dict(quad=[[0, 1, 2, 4]] * 2),
+           dict(quad=[[0, 1, 2, 3], [-1, 1, 2, 3]]), dict(quad=[[0, 1, 2, 3], [0, 1, 2, 0]]),
+           dict(quad=[[0, 1, 1, 3], [0, 1, 2, 3]]), dict(a0=[0, 5]), dict(mols=[1, 3]), dict(mols=[-1, 2]),
+           dict(a0=[-1, 4]), dict(length=[4, 0]), dict(A=11), dict(F=0), dict(A=0),
+           dict(null=("hist", "U")), dict(null=("edges",)), dict(null=("x",)), dict(null=("degenerate",)),
+           dict(null=("a0",)), dict(null=("mols",)), dict(null=("length",)), dict(null=("quad",)), dict(null=("row",))]
+    for change in bad:
+        c = dict(good, **{k: v for k, v in change.items() if k != "null"})
+        a0, mols = np.array(c["a0"], dtype=np.int64), np.array(c["mols"], dtype=np.int64)
+        length, quad = np.array(c["length"], dtype=np.int32), np.array(c["quad"], dtype=np.int32)
+        row = np.array(c["row"], dtype=np.int32)
+        edges = R.cos_edges(8)
+        hist = np.full((17, 1442), 77, dtype=np.uint64)
+        U = np.full((4, 3, 4), 77.0)
+        deg = np.full(2, 77, dtype=np.uint64)
+        args = {"x": vp(x), "a0": ptr(a0, C.c_int64), "mols": ptr(mols, C.c_int64), "length": ptr(length, C.c_int32),
+                "quad": ptr(quad, C.c_int32), "row": ptr(row, C.c_int32), "edges": ptr(edges),
+                "hist": ptr(hist, C.c_uint64), "U": vp(U), "degenerate": ptr(deg, C.c_uint64)}
+        for name in change.get("null", ()):
+            args[name] = None
+        with pytest.raises(MdhipError) as err:
+            ctx.check(ctx.lib.mdhip_dihedral_angles(ctx.h, c["F"], c["A"], args["x"], 0, None, c["n_jobs"], args["a0"],
+                                                    args["mols"], args["length"], args["quad"], args["row"], c["n_rows"],
+                                                    c["n_bins"], args["edges"], args["hist"], args["U"], 0,
+                                                    args["degenerate"]))
+        assert err.value.code == -1, change
+        assert (hist == 77).all() and (U == 77.0).all() and (deg == 77).all(), change
+    # ... and the arguments these were derived from are fine
+    hist, U, deg = B.dihedral_angles(x, None, good["a0"], good["mols"], good["length"], good["quad"], job_row=good["row"],
+                                     n_bins=8, want_series=True)
+    assert hist.shape == (2, 8) and hist.sum() == 12 and U.shape == (3, 3, 4) and not deg.any()
+
+
+def test_beyond_the_launch_limits(B):
+    """The implementation splits its grid along both launch dimensions with the same two loops as mdhip_axis_vectors:
+    65 535 x 64 + 1 four-site molecules in one frame are one molecule tile more than a launch holds (two launches; the
+    last molecule, alone in the second one, is the only degenerate one), and 70 001 frames of two molecules cross
+    65 535 along the frame-tile dimension only at 4.2 million frames: the same loop, out of a test's reach, so that
+    shape checks the frame tiles of a long trajectory instead."""
+    rng = np.random.default_rng(3)
+    x = rng.normal(size=(70001, 3, 8))
+    hist, _, _ = _check(B, x, None, [0], [2], [4], [(0, 1, 2, 3)], n_bins=72, want_deg=[0])
+    assert hist.sum() == 2 * 70001
+    mols = 65535 * R.TM + 1
+    x = rng.random(size=(1, 3, 4 * mols)) + 0.5
+    x[0, :, 4 * (mols - 1) + 2] = x[0, :, 4 * (mols - 1) + 1]
+    hist, U, _ = _check(B, x, None, [0], [mols], [4], [(0, 1, 2, 3)], n_bins=72, want_deg=[1])
+    assert hist.sum() == mols - 1 and not U[-1].any() and U[-2].any()
+    assert B.default_context().last_kernel_ms()[1] == 2
+
+
+def test_call_order(B):
+    """One context: dihedral_angles between an axis_vectors call and an orient_corr call, then the opposite order on a
+    caller's stream; every result has the bytes of the call made alone on a fresh context."""
+    import torch
+
+    from mdproptools_amd._lib import Context
+
+    rng = np.random.default_rng(12)
+    F, mols = 130, 90
+    L = 10.0 + rng.random((F, 3))
+    x = _molecules(rng, F, mols, 5, L)
+    jobs = ([0, 0], [mols, mols], [5, 5])
+    quads, terms = [(0, 1, 2, 3), (1, 2, 3, 4)], [[(1, -1.0), (4, 1.0)], [(2, 1.0)]]
+    series = RR.axis_series(rng, 12, 300)
+    off = np.array([0, 5, 12], dtype=np.int64)
+
+    def dihedral(ctx):
+        h, U, d = B.dihedral_angles(x, L, *jobs, quads, job_row=[0, 0], n_bins=360, want_series=True, ctx=ctx)
+        return h.tobytes(), np.array(U).tobytes(), d.tobytes()
+
+    def axis(ctx):
+        U, d = B.axis_vectors(x, L, *jobs, terms, ctx=ctx)
+        return np.array(U).tobytes(), d.tobytes()
+
+    def corr(ctx):
+        return (B.orient_corr(series, off, 299, ctx=ctx).tobytes(),)
+
+    alone = []
+    for call in (axis, dihedral, corr):
+        ctx = Context(0)
+        try:
+            alone.append(call(ctx))
+        finally:
+            ctx.close()
+    ctx = Context(0)
+    try:
+        assert [axis(ctx), dihedral(ctx), corr(ctx)] == alone
+        S = torch.cuda.Stream(device=torch.device("cuda", ctx.device))
+        ctx.set_stream(S.cuda_stream)
+        with torch.cuda.stream(S):
+            assert [corr(ctx), dihedral(ctx), axis(ctx)] == alone[::-1]
+        ctx.set_stream(None)
+        assert dihedral(ctx) == alone[1]
+    finally:
+        ctx.close()
+
+
+# ---- end to end ------------------------------------------------------------------------------------------------------------
+
+ENTRIES = [(1, 1, 2, 3, 4), (2, [(1, 2, 3, 4), (2, 3, 4, 5), (6, 5, 4, 3)], "backbone"), (1, 2, 1, 3, 4)]
+LABELS = ["1:1-2-3-4", "backbone", "1:2-1-3-4"]
+FILE_ORDER = [7, 3] + [f for f in range(40) if f not in (3, 7)]       # the timestep column is out of order
+
+
+@pytest.fixture(scope="module")
+def dumps(tmp_path_factory):
+    d = tmp_path_factory.mktemp("dihedrals")
+    traj = R.synthetic_trajectory()
+    a0, mols, length, quads, rows, off = R.entry_jobs([(1, [(1, 2, 3, 4)]), (2, ENTRIES[1][1]), (1, [(2, 1, 3, 4)])])
+    hist, U, deg = R.dihedral_angles(traj["x"], traj["L"], a0, mols, length, quads, job_row=rows, n_bins=360)
+    assert not deg.any()
+    S1, _, A1, _ = RR.orient_truth(U, off, 39)
+    return {"dir": d, "pattern": R.write_dumps(d, traj, file_order=FILE_ORDER), "traj": traj, "hist": hist, "U": U,
+            "off": off, "S1": S1, "A1": A1}
+
+
+@pytest.mark.parametrize("stream", [True, False])
+def test_end_to_end(B, dumps, stream, monkeypatch):
+    from mdproptools_amd.structural import dihedral_distribution as M
+
+    traj = dumps["traj"]
+    # molecules are cut by faces: the wrapped coordinates of some bond differ by more than half an edge
+    assert (np.abs(traj["x"][:, :, 1:280:4] - traj["x"][:, :, 0:280:4]) > traj["L"][:, :, None] / 2).any()
+    monkeypatch.setattr(M, "STREAM", stream)
+    monkeypatch.setattr(M, "BATCH_BYTES", 7 * 334 * 24)             # seven frames per streamed batch: six batches
+    where = str(dumps["dir"])
+    dist, pop = M.calc_dihedral_distribution(ENTRIES, dumps["pattern"], R.NUM_MOLS, R.ATOMS_PER_MOL, working_dir=where)
+    hist = dumps["hist"]
+    assert pop["n"].tolist() == hist.sum(axis=1).tolist() == [70 * 40, 3 * 9 * 40, 70 * 40]
+    assert not pop["n_degenerate"].any() and pop["dihedral"].tolist() == LABELS
+    for e, lab in enumerate(LABELS):
+        assert np.array_equal(dist["p_" + lab], R.density(hist[e], 360))       # the histograms are exact
+        for name, (lo, hi) in M.DEFAULT_STATES.items():
+            assert pop[name][e] == R.population(hist[e], lo, hi, 360)
+    du, pu = M.calc_dihedral_distribution(ENTRIES, dumps["pattern"], R.NUM_MOLS, R.ATOMS_PER_MOL, coords="unwrapped",
+                                          save_mode=False)
+    assert np.array_equal(du.to_numpy(), dist.to_numpy()) and np.array_equal(pu["n"], pop["n"])
+    # the correlation functions: the frames back in time order, C within the bound mdhip_orient_corr documents for S1
+    df = M.calc_dihedral_correlation(ENTRIES, dumps["pattern"], R.NUM_MOLS, R.ATOMS_PER_MOL, dt=2, max_lag=39,
+                                     working_dir=where)
+    assert len(df) == 40 and np.array_equal(df["Time (ps)"], (250 * np.arange(40)).astype(np.float64) * 2e-3)
+    W = RR.windows(40, dumps["off"], 39)
+    worst = 0.0
+    for g, lab in enumerate(LABELS):
+        bound = (W[:, g] + 3.0) * RR.EPS * dumps["A1"][:, g] / W[:, g]
+        err = np.abs(df["C_" + lab].to_numpy() - dumps["S1"][:, g] / W[:, g])
+        worst = max(worst, (err / bound).max())
+        assert np.all(err <= bound), lab
+        grp = dumps["U"][dumps["off"][g]:dumps["off"][g + 1]]
+        p = grp[:, 0].mean() ** 2 + grp[:, 1].mean() ** 2
+        C = df["C_" + lab].to_numpy()
+        assert np.abs(df["Cn_" + lab].to_numpy() - (C - p) / (1.0 - p)).max() < 1e-12
+    print("worst share of the bound", worst)
+    assert len(M.calc_dihedral_correlation(ENTRIES, dumps["pattern"], R.NUM_MOLS, R.ATOMS_PER_MOL, save_mode=False)) == 20
+    # the series themselves, in time order, bit for bit
+    entries, num_mols, per = M._prepare(ENTRIES, dumps["pattern"], R.NUM_MOLS, R.ATOMS_PER_MOL, "wrapped")
+    U, times, off, deg = M._load_series(entries, dumps["pattern"], num_mols, per, 2, "wrapped")
+    assert RR.same_bits(U.cpu().numpy(), dumps["U"]) and off.tolist() == dumps["off"].tolist() and not deg.any()
+
+
+def test_a_collinear_quadruple_end_to_end(B, dumps, tmp_path):
+    from mdproptools_amd.structural import dihedral_distribution as M
+
+    traj = dict(dumps["traj"])
+    xu = traj["xu"].copy()
+    xu[4, :, 4 * 7 + 2] = xu[4, :, 4 * 7 + 1]        # atoms 2 and 3 of chain 8 of type 1 coincide in frame 4
+    traj["xu"] = xu
+    traj["x"] = xu - traj["img"] * traj["L"][:, :, None]
+    traj["x"][4, :, 4 * 7 + 2] = traj["x"][4, :, 4 * 7 + 1]
+    traj["img"] = traj["img"].copy()
+    traj["img"][4, :, 4 * 7 + 2] = traj["img"][4, :, 4 * 7 + 1]
+    pattern = R.write_dumps(tmp_path, traj, file_order=range(8))
+    _, pop = M.calc_dihedral_distribution(ENTRIES, pattern, R.NUM_MOLS, R.ATOMS_PER_MOL, bin_size=5, save_mode=False)
+    assert pop["n_degenerate"].tolist() == [1, 0, 1] and pop["n"].tolist() == [70 * 8 - 1, 3 * 9 * 8, 70 * 8 - 1]
+    with pytest.raises(ValueError, match=r"1:1-2-3-4 \(1\), 1:2-1-3-4 \(1\)"):
+        M.calc_dihedral_correlation(ENTRIES, pattern, R.NUM_MOLS, R.ATOMS_PER_MOL, save_mode=False)
