@@ -1310,6 +1310,19 @@ def cross_msd(P, max_lag, with_abs=False, out=None, abs_out=None, ctx=None):
 ORIENT_MAX_GROUPS = 16
 
 
+def _mol_jobs(x, box, job_atom0, job_mols, job_len, J, mismatch):
+    """What the per-molecule series calls marshal alike: (F, A, box [F,3] or None, job_atom0 int64, job_mols int64,
+    job_len int32, S = sum(job_mols)); `mismatch`: the ValueError text when the job arrays do not hold J entries."""
+    F, _, A = _shape3(x, "x")
+    bx = None if box is None else _f64(box)
+    if bx is not None and bx.shape != (F, 3):
+        raise ValueError("box must have shape [n_frames, 3]")
+    a0, mols, length = _i64(job_atom0), _i64(job_mols), _i32(job_len)
+    if not (a0.shape == mols.shape == length.shape == (J,)):
+        raise ValueError(mismatch)
+    return F, A, bx, a0, mols, length, int(mols.sum()) if J and mols.min() >= 0 else 0
+
+
 def axis_vectors(x, box, job_atom0, job_mols, job_len, terms, out=None, ctx=None):
     """
     Molecule-fixed unit vectors per frame (include/mdhip.h: mdhip_axis_vectors): x [F,3,A] coordinates, atoms by id and
@@ -1321,27 +1334,15 @@ def axis_vectors(x, box, job_atom0, job_mols, job_len, terms, out=None, ctx=None
     [n_jobs] = the zero vectors of every job): U is a host array, or `out` (float64 CUDA tensor [S,3,F]) when given.
     """
     ctx = ctx or default_context()
-    F, _, A = _shape3(x, "x")
-    bx = None
-    if box is not None:
-        bx = _f64(box)
-        if bx.shape != (F, 3):
-            raise ValueError("box must have shape [n_frames, 3]")
-    a0, mols, length = _i64(job_atom0), _i64(job_mols), _i32(job_len)
     J = len(terms)
-    if not (a0.shape == mols.shape == length.shape == (J,)):
-        raise ValueError("job_atom0, job_mols, job_len and terms must hold one entry per job")
+    F, A, bx, a0, mols, length, S = _mol_jobs(x, box, job_atom0, job_mols, job_len, J,
+                                              "job_atom0, job_mols, job_len and terms must hold one entry per job")
     t_off = np.zeros(J + 1, dtype=np.int64)
     t_off[1:] = np.cumsum([len(t) for t in terms])
     t_atom = _i32([k for t in terms for k, _ in t])
     t_w = _f64([w for t in terms for _, w in t])
-    S = int(mols.sum()) if J and mols.min() >= 0 else 0
     xp, x_dev, keep = as_input(x, ctx)
-    if out is None:
-        res = result_array((S, 3, F), device=ctx.device)
-        up, u_dev = C.c_void_p(res.ctypes.data), 0
-    else:
-        res, up, u_dev = out, _dev_out(out, (S, 3, F), ctx=ctx), 1
+    res, up, u_dev = _dest(out, (S, 3, F), ctx, pinned=True)
     degenerate = np.zeros(max(J, 1), dtype=np.uint64)
     ctx.check(ctx.lib.mdhip_axis_vectors(ctx.h, F, A, xp, x_dev, None if bx is None else ptr(bx), J,
                                          ptr(a0, C.c_int64), ptr(mols, C.c_int64), ptr(length, C.c_int32),
@@ -1401,17 +1402,12 @@ def dihedral_angles(x, box, job_atom0, job_mols, job_len, quads, job_row=None, n
     of every job with three collinear atoms): U is a host array, or `out` (float64 CUDA tensor [S,3,F]) when given.
     """
     ctx = ctx or default_context()
-    F, _, A = _shape3(x, "x")
-    bx = None
-    if box is not None:
-        bx = _f64(box)
-        if bx.shape != (F, 3):
-            raise ValueError("box must have shape [n_frames, 3]")
-    a0, mols, length = _i64(job_atom0), _i64(job_mols), _i32(job_len)
     quad = _i32(quads)
     J = len(quad)
-    if not (a0.shape == mols.shape == length.shape == (J,)) or quad.shape != (J, 4):
-        raise ValueError("job_atom0, job_mols and job_len must hold one entry, quads one (i, j, k, l), per job")
+    mismatch = "job_atom0, job_mols and job_len must hold one entry, quads one (i, j, k, l), per job"
+    F, A, bx, a0, mols, length, S = _mol_jobs(x, box, job_atom0, job_mols, job_len, J, mismatch)
+    if quad.shape != (J, 4):
+        raise ValueError(mismatch)
     want_series = bool(want_series) or out is not None
     if n_bins is None and not want_series:
         raise ValueError("nothing asked for: give n_bins for histograms, want_series or out for the series")
@@ -1427,14 +1423,8 @@ def dihedral_angles(x, box, job_atom0, job_mols, job_len, quads, job_row=None, n
     if n_bins is not None:
         edges = _f64(dihedral_cos_edges(nb))
         hist = np.zeros((max(n_rows, 0), max(nb, 0)), dtype=np.uint64)
-    S = int(mols.sum()) if J and mols.min() >= 0 else 0
     xp, x_dev, keep = as_input(x, ctx)
-    res, up, u_dev = None, None, 0
-    if out is not None:
-        res, up, u_dev = out, _dev_out(out, (S, 3, F), ctx=ctx), 1
-    elif want_series:
-        res = result_array((S, 3, F), device=ctx.device)
-        up = C.c_void_p(res.ctypes.data)
+    res, up, u_dev = _dest(out, (S, 3, F), ctx, pinned=True) if want_series else (None, None, 0)
     degenerate = np.zeros(max(J, 1), dtype=np.uint64)
     ctx.check(ctx.lib.mdhip_dihedral_angles(ctx.h, F, A, xp, x_dev, None if bx is None else ptr(bx), J,
                                             ptr(a0, C.c_int64), ptr(mols, C.c_int64), ptr(length, C.c_int32),

@@ -337,11 +337,7 @@ int mdhip_collective_displacement(mdhip_ctx *ctx, int64_t n_frames, int64_t n_en
     ctx->last_kernel = "collective_kernel";
     timer.stop();
     if (!P_on_device && (rc = mdhip_result(cs, P, d_P, p_bytes, 0))) return rc;
-    cs.defer([timer]() {
-        timer.collect();
-        return MDHIP_OK;
-    });
-    return cs.end();
+    return mdhip_end_timed(cs, timer);
 }
 
 int mdhip_cross_msd(mdhip_ctx *ctx, int64_t n, int n_groups, const double *P, int P_on_device, int64_t max_lag,
@@ -420,11 +416,7 @@ int mdhip_cross_msd(mdhip_ctx *ctx, int64_t n, int n_groups, const double *P, in
         if ((rc = mdhip_result(cs, out, d_out, out_b, 0))) return rc;
         if (want_abs && (rc = mdhip_result(cs, abs_out, d_abs, out_b, 0))) return rc;
     }
-    cs.defer([timer]() {
-        timer.collect();
-        return MDHIP_OK;
-    });
-    return cs.end();
+    return mdhip_end_timed(cs, timer);
 }
 
 }  // extern "C"

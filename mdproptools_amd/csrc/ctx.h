@@ -549,3 +549,10 @@ struct KernelTimer {
         return ms;
     }
 };
+
+// The end of an entry point whose launches ran under `timer`: its time is read when the call completes.
+static inline int mdhip_end_timed(CallScope &cs, const KernelTimer &timer)
+{
+    cs.defer([timer]() { return timer.collect(), MDHIP_OK; });
+    return cs.end();
+}

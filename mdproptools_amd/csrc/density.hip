@@ -431,11 +431,7 @@ int mdhip_axis_profile(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const 
     if ((rc = mdhip_result(cs, counts, d_counts, (size_t)n_frames * words * 4, 0))) return rc;
     if ((rc = mdhip_result(cs, extent, d_extent, (size_t)n_frames * 16, 0))) return rc;
     if ((rc = mdhip_result(cs, outside, d_outside, (size_t)n_frames * 4, 0))) return rc;
-    cs.defer([timer]() {
-        timer.collect();
-        return MDHIP_OK;
-    });
-    return cs.end();
+    return mdhip_end_timed(cs, timer);
 }
 
 }  // extern "C"

@@ -398,11 +398,7 @@ int mdhip_displacement_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, con
         if ((rc = mdhip_result(cs, moments, d_mom, (size_t)n_jobs * 24, 0))) return rc;
     }
     if (crossings && (rc = mdhip_result(cs, crossings, d_cross, 8, 0))) return rc;
-    cs.defer([timer]() {
-        timer.collect();
-        return MDHIP_OK;
-    });
-    return cs.end();
+    return mdhip_end_timed(cs, timer);
 }
 
 }  // extern "C"

@@ -670,11 +670,7 @@ int msd_pairs_impl(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const double
                                       (size_t)col_len * 8, hipMemcpyDeviceToHost, ctx->stream));
         }
     }
-    cs.defer([timer]() {
-        timer.collect();
-        return MDHIP_OK;
-    });
-    return cs.end();
+    return mdhip_end_timed(cs, timer);
 }
 
 }  // namespace
@@ -744,11 +740,7 @@ static int msd_windows_impl(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, con
         rc = mdhip_result(cs, win_sums, d_out, (size_t)n_ent * 4 * 8, 0);
         if (rc) return rc;
     }
-    cs.defer([timer]() {
-        timer.collect();
-        return MDHIP_OK;
-    });
-    return cs.end();
+    return mdhip_end_timed(cs, timer);
 }
 
 int mdhip_msd_windows(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const double *r,
@@ -947,11 +939,7 @@ static int lag_exact_ends(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const
         rc = mdhip_result(cs, out + (size_t)k_hi * G * 4, d_rows + (size_t)kl * G * 4, n_hi * row_b, out_on_device);
         if (rc) return rc;
     }
-    cs.defer([timer]() {
-        timer.collect();
-        return MDHIP_OK;
-    });
-    return cs.end();
+    return mdhip_end_timed(cs, timer);
 }
 
 // force_variant >= 0: that lag_variant instead of the context's option (the fallback of the spectral path)
@@ -1119,11 +1107,7 @@ static int lag_msd_impl(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const d
         rc = mdhip_result(cs, out, d_out, out_b, 0);
         if (rc) return rc;
     }
-    cs.defer([timer]() {
-        timer.collect();
-        return MDHIP_OK;
-    });
-    return cs.end();
+    return mdhip_end_timed(cs, timer);
 }
 
 int mdhip_lag_msd(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const double *r, int on_device,

@@ -2,13 +2,9 @@
 // time-correlation sums at every lag (dynamical/reorientation.py, class Reorientation; the reference has no such module).
 //
 // mdhip_axis_vectors: U[s][x][t] = the unit vector of series s (one molecule of one job) at frame t, from a weighted sum
-//   of the differences between atoms of the molecule and its first atom (a bond: -1 / +1; a dipole: the charges). The
-//   trajectory is frame-major ([F][3][A]) and U is time-major ([S][3][F]): a workgroup owns a tile of AX_TM = 64
-//   molecules x AX_TF = 64 frames. Lane = molecule while reading (consecutive lanes read atoms one molecule apart, every
-//   fetched line is used by the neighbouring terms and lanes), the finished components go through an LDS tile
-//   ([3][64][64 + 1], conflict-free both ways), lane = frame while writing (512 contiguous bytes per wave and row).
-//   16 waves per workgroup keep four frames x three axes x the terms of loads in flight per lane. One read of the lines
-//   that hold named atoms, one write of U: HBM-bound.
+//   of the differences between atoms of the molecule and its first atom (a bond: -1 / +1; a dipole: the charges). Tile,
+//   job plan and launch are those of mol_tile.h, every job a class of its own; here: what a lane computes per
+//   (molecule, frame).
 //
 // mdhip_orient_corr: sums[k][g] = sum over the series m of group g and the origins t of c and of c * c,
 //   c = u_m(t) . u_m(t + k). Organised as cross_msd_kernel (collective.hip): a workgroup owns a tile of OC_KT = 1024
@@ -29,6 +25,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "mol_tile.h"
 
 namespace {
 
@@ -36,90 +33,55 @@ namespace {
 // axis vectors
 // ---------------------------------------------------------------------------------------------
 
-constexpr int AX_TM = 64;           // molecules per tile
-constexpr int AX_TF = 64;           // frames per tile
-constexpr int AX_WAVES = 16;
-constexpr int AX_THREADS = 64 * AX_WAVES;
-constexpr int AX_ROW = AX_TF + 1;   // doubles per (axis, molecule) row of the LDS tile
-constexpr size_t AX_LDS = (size_t)3 * AX_TM * AX_ROW * 8;
-constexpr long long AX_MAX_GRID = 65535;
+constexpr size_t AX_LDS = mt_tile_lds(3);
 static_assert(AX_LDS <= 160 * 1024, "the tile must fit LDS");
 
-struct AxJob {
-    long long atom0, mols, series0, tile0;  // first atom, molecules, first series, first molecule tile of the job
-    int len, term0, n_terms, pad;
+struct AxJob {  // by position in the plan (= the job's number: nothing is pooled)
+    long long series0;  // first series of the job
+    int term0, n_terms;
 };
 
-// Block (x, y): molecule tile tile_base + x (over all jobs), frame tile ftile_base + y.
-__global__ __launch_bounds__(AX_THREADS) void axis_vectors_kernel(const double *__restrict__ x,
-                                                                  const double *__restrict__ box, long long F,
-                                                                  long long A, const AxJob *__restrict__ jobs,
-                                                                  int n_jobs, const int *__restrict__ term_atom,
-                                                                  const double *__restrict__ term_w,
-                                                                  long long tile_base, long long ftile_base,
-                                                                  double *__restrict__ U,
-                                                                  unsigned long long *__restrict__ degenerate)
+__global__ __launch_bounds__(MT_THREADS) void axis_vectors_kernel(
+    const double *__restrict__ x, const double *__restrict__ box, long long F, long long A,
+    const MolClass *__restrict__ classes, int n_classes, const AxJob *__restrict__ jobs, const int *__restrict__ term_atom,
+    const double *__restrict__ term_w, long long tile_base, long long ftile_base, double *__restrict__ U,
+    unsigned long long *__restrict__ degenerate)
 {
-    extern __shared__ double s_u[];  // [3][AX_TM][AX_ROW]
-    const long long tile = tile_base + blockIdx.x;
-    int lo = 0, hi = n_jobs - 1;  // the last job whose first tile is not beyond this one (jobs without molecules have none)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].tile0 <= tile) lo = mid;
-        else hi = mid - 1;
-    }
-    const AxJob job = jobs[lo];
-    const long long m0 = (tile - job.tile0) * AX_TM;
-    const int nm = (int)(job.mols - m0 < AX_TM ? job.mols - m0 : AX_TM);
-    const long long f0 = (ftile_base + blockIdx.y) * AX_TF;
-    const int nf = (int)(F - f0 < AX_TF ? F - f0 : AX_TF);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane < nm) {
-        const long long a = job.atom0 + (m0 + lane) * job.len;
-        unsigned long long zeros = 0;
-        for (int ff = wave; ff < nf; ff += AX_WAVES) {
-            const long long f = f0 + ff;
-            double v[3];
+    extern __shared__ double s_u[];  // [3][MT_TM][MT_ROW]
+    const MolTile t = mt_locate(classes, n_classes, tile_base, ftile_base, F);
+    const AxJob job = jobs[t.cls.job0];
+    mt_walk(t, degenerate + t.cls.job0, [&](long long a, long long f, int ff, unsigned long long &zeros) {
+        double v[3];
 #pragma unroll
-            for (int ax = 0; ax < 3; ++ax) {
-                const double *__restrict__ plane = x + ((size_t)f * 3 + ax) * (size_t)A + a;
-                const double xa = plane[0];
-                const double L = box ? box[f * 3 + ax] : 0.0, half = L / 2;
-                double acc = 0.0;
-                for (int t = 0; t < job.n_terms; ++t) {
-                    double d = plane[term_atom[job.term0 + t]] - xa;
-                    if (box) {  // the single wrap of rdf_cn.py:50-55 (strict; a NaN shifts nothing)
-                        if (d > half) d -= L;
-                        else if (d < -half) d += L;
-                    }
-                    const double p = term_w[job.term0 + t] * d;
-                    acc = t == 0 ? p : acc + p;
-                }
-                v[ax] = acc;
+        for (int ax = 0; ax < 3; ++ax) {
+            const double *__restrict__ plane = x + ((size_t)f * 3 + ax) * (size_t)A + a;
+            const double xa = plane[0];
+            const double L = box ? box[f * 3 + ax] : 0.0, half = L / 2;
+            double acc = 0.0;
+            for (int k = 0; k < job.n_terms; ++k) {
+                double d = plane[term_atom[job.term0 + k]] - xa;
+                if (box) d = mt_wrap(d, L, half);
+                const double p = term_w[job.term0 + k] * d;
+                acc = k == 0 ? p : acc + p;
             }
-            const double n2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
-            double u[3];
-            if (n2 == 0.0) {
-                u[0] = u[1] = u[2] = 0.0;
-                ++zeros;
-            } else if (!(__builtin_fabs(n2) < __builtin_inf())) {
-                u[0] = u[1] = u[2] = __builtin_nan("");
-            } else {
-                const double r = __builtin_sqrt(n2);
-                u[0] = v[0] / r, u[1] = v[1] / r, u[2] = v[2] / r;
-            }
-#pragma unroll
-            for (int ax = 0; ax < 3; ++ax) s_u[(ax * AX_TM + lane) * AX_ROW + ff] = u[ax];
+            v[ax] = acc;
         }
-        if (zeros) atomicAdd(degenerate + lo, zeros);
-    }
+        const double n2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+        double u[3];
+        if (n2 == 0.0) {
+            u[0] = u[1] = u[2] = 0.0;
+            ++zeros;
+        } else if (!(__builtin_fabs(n2) < __builtin_inf())) {
+            u[0] = u[1] = u[2] = __builtin_nan("");
+        } else {
+            const double r = __builtin_sqrt(n2);
+            u[0] = v[0] / r, u[1] = v[1] / r, u[2] = v[2] / r;
+        }
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) s_u[mt_at(ax, t.lane, ff)] = u[ax];
+    });
     __syncthreads();
-    for (int row = wave; row < 3 * nm; row += AX_WAVES) {
-        const int mol = row / 3, ax = row - 3 * mol;
-        if (lane < nf)
-            U[((size_t)(job.series0 + m0 + mol) * 3 + ax) * (size_t)F + (size_t)(f0 + lane)] =
-                s_u[(ax * AX_TM + mol) * AX_ROW + lane];
-    }
+    mt_store<3>(t, s_u, job.series0, F, U);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -313,73 +275,44 @@ int mdhip_axis_vectors(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const 
     MD_REQUIRE(n_atoms < (1ll << 40) && n_frames < (1ll << 31) && n_frames < (1ll << 40) / n_atoms, "trajectory too large");
     MD_REQUIRE(x && job_atom0 && job_mols && job_len && term_off && term_atom && term_w && U && degenerate, "NULL array");
     MD_REQUIRE(term_off[0] == 0, "term_off must start at 0");
+    const MolPlan plan = mol_plan(n_jobs, job_atom0, job_mols, job_len, n_atoms, n_frames, false, 1);
     std::vector<AxJob> jobs((size_t)n_jobs);
-    long long series = 0, tiles = 0;
-    for (int j = 0; j < n_jobs; ++j) {
-        const long long len = job_len[j], mols = job_mols[j], a0 = job_atom0[j];
-        MD_REQUIRE(len >= 1 && mols >= 0 && a0 >= 0 && a0 <= n_atoms && mols <= (n_atoms - a0) / len,
-                   "job %d runs past the %lld atoms of a frame", j, (long long)n_atoms);
-        const long long t0 = term_off[j], t1 = term_off[j + 1];
+    for (int j = 0; j < plan.checked_jobs(); ++j) {
+        const long long len = job_len[j], t0 = term_off[j], t1 = term_off[j + 1];
         MD_REQUIRE(t1 > t0 && t1 - t0 < len && t1 <= (1ll << 30), "job %d needs between 1 and job_len - 1 terms", j);
-        for (long long t = t0; t < t1; ++t)
-            MD_REQUIRE(term_atom[t] >= 1 && term_atom[t] < len && (t == t0 || term_atom[t] > term_atom[t - 1]),
+        for (long long k = t0; k < t1; ++k)
+            MD_REQUIRE(term_atom[k] >= 1 && term_atom[k] < len && (k == t0 || term_atom[k] > term_atom[k - 1]),
                        "job %d: the terms' atoms must ascend strictly within [1, job_len)", j);
-        jobs[(size_t)j] = {a0, mols, series, tiles, (int)len, (int)t0, (int)(t1 - t0), 0};
-        series += mols;
-        tiles += (mols + AX_TM - 1) / AX_TM;
+        jobs[(size_t)j] = {plan.series0[(size_t)j], (int)t0, (int)(t1 - t0)};
     }
-    MD_REQUIRE(series < (1ll << 40) / n_frames, "result too large");
-    MD_HIP(hipSetDevice(ctx->device));
     int rc;
-    const size_t x_bytes = (size_t)n_frames * 3 * (size_t)n_atoms * 8;
-    const double *d_x = (const double *)mdhip_stage(ctx, WS_XYZ_I, x, x_bytes, x_on_device, &rc);
-    if (rc) return rc;
-    const double *d_box = nullptr;
-    if (box) {
-        MD_WS(d_b, double, WS_BOX, (size_t)n_frames * 3 * 8);
-        if ((rc = mdhip_h2d_small(ctx, d_b, box, (size_t)n_frames * 3 * 8))) return rc;
-        d_box = d_b;
-    }
-    // tables: jobs | term weights | term atoms | degenerate counters
+    if ((rc = mt_plan_error(ctx, plan, n_atoms))) return rc;
+    MolIo io;
+    if ((rc = io.open(ctx, n_frames, n_atoms, x, x_on_device, box, U, U_on_device, plan.series))) return rc;
+    // tables: classes | jobs | term weights | term atoms | degenerate counters
     const size_t n_terms = (size_t)term_off[n_jobs];
-    const size_t jobs_b = (size_t)n_jobs * sizeof(AxJob), w_b = n_terms * 8, a_b = (n_terms * 4 + 7) & ~(size_t)7;
-    const size_t deg_b = (size_t)n_jobs * 8;
-    MD_WS(d_tab, char, WS_TABLES, jobs_b + w_b + a_b + deg_b);
-    if ((rc = mdhip_h2d_small(ctx, d_tab, jobs.data(), jobs_b))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + jobs_b, term_w, w_b))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + jobs_b + w_b, term_atom, n_terms * 4))) return rc;
-    unsigned long long *d_deg = (unsigned long long *)(d_tab + jobs_b + w_b + a_b);
+    const size_t cls_b = (size_t)n_jobs * sizeof(MolClass), jobs_b = (size_t)n_jobs * sizeof(AxJob), w_b = n_terms * 8;
+    const size_t a_b = (n_terms * 4 + 7) & ~(size_t)7, deg_b = (size_t)n_jobs * 8;
+    MD_WS(d_tab, char, WS_TABLES, cls_b + jobs_b + w_b + a_b + deg_b);
+    if ((rc = mdhip_h2d_small(ctx, d_tab, plan.classes.data(), cls_b))) return rc;
+    if ((rc = mdhip_h2d_small(ctx, d_tab + cls_b, jobs.data(), jobs_b))) return rc;
+    if ((rc = mdhip_h2d_small(ctx, d_tab + cls_b + jobs_b, term_w, w_b))) return rc;
+    if ((rc = mdhip_h2d_small(ctx, d_tab + cls_b + jobs_b + w_b, term_atom, n_terms * 4))) return rc;
+    unsigned long long *d_deg = (unsigned long long *)(d_tab + cls_b + jobs_b + w_b + a_b);
     MD_HIP(hipMemsetAsync(d_deg, 0, deg_b, ctx->stream));
-    const size_t u_bytes = (size_t)series * 3 * (size_t)n_frames * 8;
-    double *d_U = U;
-    if (!U_on_device) {
-        d_U = (double *)mdhip_ws(ctx, WS_OUT, std::max<size_t>(u_bytes, 8));
-        if (!d_U) return MDHIP_ENOMEM;
-    }
     MD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(axis_vectors_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)AX_LDS));
     KernelTimer timer(ctx, 0);
-    int launches = 0;
-    const long long f_tiles = (n_frames + AX_TF - 1) / AX_TF;
-    // (launch dimensions stay within 65 535: more tiles go in several launches)
-    for (long long t0 = 0; t0 < tiles; t0 += AX_MAX_GRID)
-        for (long long ft0 = 0; ft0 < f_tiles; ft0 += AX_MAX_GRID, ++launches) {
-            const dim3 grid((unsigned)std::min(AX_MAX_GRID, tiles - t0), (unsigned)std::min(AX_MAX_GRID, f_tiles - ft0));
-            hipLaunchKernelGGL(axis_vectors_kernel, grid, dim3(AX_THREADS), AX_LDS, ctx->stream, d_x, d_box,
-                               (long long)n_frames, (long long)n_atoms, (const AxJob *)d_tab, n_jobs,
-                               (const int *)(d_tab + jobs_b + w_b), (const double *)(d_tab + jobs_b), t0, ft0, d_U, d_deg);
-            MD_HIP(hipGetLastError());
-        }
-    ctx->last_kernel = "axis_vectors_kernel";
-    ctx->last_launches = launches;
-    timer.stop();
-    if (!U_on_device && (rc = mdhip_result(cs, U, d_U, u_bytes, 0))) return rc;
-    if ((rc = mdhip_result(cs, degenerate, d_deg, deg_b, 0))) return rc;
-    cs.defer([timer]() {
-        timer.collect();
-        return MDHIP_OK;
+    rc = mt_launch(ctx, "axis_vectors_kernel", timer, plan.tiles, n_frames, [&](dim3 grid, long long t0, long long ft0) {
+        hipLaunchKernelGGL(axis_vectors_kernel, grid, dim3(MT_THREADS), AX_LDS, ctx->stream, io.x, io.box,
+                           (long long)n_frames, (long long)n_atoms, (const MolClass *)d_tab, n_jobs,
+                           (const AxJob *)(d_tab + cls_b), (const int *)(d_tab + cls_b + jobs_b + w_b),
+                           (const double *)(d_tab + cls_b + jobs_b), t0, ft0, io.U, d_deg);
     });
-    return cs.end();
+    if (rc) return rc;
+    if (U && !U_on_device && (rc = mdhip_result(cs, U, io.U, io.u_bytes, 0))) return rc;
+    if ((rc = mdhip_result(cs, degenerate, d_deg, deg_b, 0))) return rc;
+    return mdhip_end_timed(cs, timer);
 }
 
 int mdhip_orient_corr(mdhip_ctx *ctx, int64_t n, int64_t n_series, const double *U, int U_on_device, int n_groups,
@@ -458,11 +391,7 @@ int mdhip_orient_corr(mdhip_ctx *ctx, int64_t n, int64_t n_series, const double 
     ctx->last_launches = launches;
     timer.stop();
     if (!sums_on_device && (rc = mdhip_result(cs, sums, d_out, out_b, 0))) return rc;
-    cs.defer([timer]() {
-        timer.collect();
-        return MDHIP_OK;
-    });
-    return cs.end();
+    return mdhip_end_timed(cs, timer);
 }
 
 }  // extern "C"

@@ -268,11 +268,7 @@ static int cumtrapz_impl(mdhip_ctx *ctx, int64_t n, int n_series, const double *
         rc = mdhip_result(cs, out, d_out, out_b, 0);
         if (rc) return rc;
     }
-    cs.defer([timer]() {
-        timer.collect();
-        return MDHIP_OK;
-    });
-    return cs.end();
+    return mdhip_end_timed(cs, timer);
 }
 
 extern "C" {

@@ -270,12 +270,8 @@ inline int row_results(CallScope &cs, const RowSet &rs, int32_t *idx, int32_t *c
 // call's aux time): the times are read when the call completes.
 inline int finish(CallScope &cs, const KernelTimer &timer, const KernelTimer *aux = nullptr)
 {
-    cs.defer([timer, has_aux = aux != nullptr, a = aux ? *aux : timer]() {
-        if (has_aux) timer.ctx->last_aux_ms = a.collect();
-        timer.collect();
-        return MDHIP_OK;
-    });
-    return cs.end();
+    if (aux) cs.defer([a = *aux]() { return a.ctx->last_aux_ms = a.collect(), MDHIP_OK; });
+    return mdhip_end_timed(cs, timer);
 }
 
 }  // namespace shell

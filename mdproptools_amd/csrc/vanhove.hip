@@ -286,11 +286,7 @@ int mdhip_van_hove_distinct(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, con
     timer.stop();
     if ((rc = mdhip_result(cs, hist, d_hist, hist_bytes, 0))) return rc;
     if ((rc = mdhip_result(cs, beyond, d_bey, (size_t)n_jobs * 8, 0))) return rc;
-    cs.defer([timer]() {
-        timer.collect();
-        return MDHIP_OK;
-    });
-    return cs.end();
+    return mdhip_end_timed(cs, timer);
 }
 
 }  // extern "C"

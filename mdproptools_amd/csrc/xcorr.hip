@@ -329,11 +329,7 @@ int xcorr_lags_impl(mdhip_ctx *ctx, int64_t n, int n_pairs, const double *a, con
         rc = mdhip_result(cs, out, d_out, out_b, 0);
         if (rc) return rc;
     }
-    cs.defer([timer]() {
-        timer.collect();
-        return MDHIP_OK;
-    });
-    return cs.end();
+    return mdhip_end_timed(cs, timer);
 }
 
 }  // namespace
@@ -429,11 +425,7 @@ int mdhip_green_kubo(mdhip_ctx *ctx, int64_t n, int n_series, const double *a, c
         rc = mdhip_result(cs, integral_mean, d_mean, (size_t)m * 8, 0);
         if (rc) return rc;
     }
-    cs.defer([timer]() {
-        timer.collect();
-        return MDHIP_OK;
-    });
-    return cs.end();
+    return mdhip_end_timed(cs, timer);
 }
 
 int mdhip_green_kubo_async(mdhip_ctx *ctx, int64_t n, int n_series, const double *a, const double *b, int on_device,

@@ -24,9 +24,8 @@ import numpy as np
 import pandas as pd
 
 from .. import backend
-from ..common import trajectory as T
+from ..common import mol_series
 from ..dist import is_writer
-from .conductivity import Conductivity
 
 # True: the dumps are parsed into page-locked staging batches and each is reduced on the GPU while the next one is
 # being parsed (mdproptools_amd/stream.py). False: every frame is parsed first and reduced in one call.
@@ -57,10 +56,7 @@ class Reorientation:
         """
         if coords not in ("wrapped", "unwrapped"):
             raise ValueError('coords must be "wrapped" or "unwrapped"')
-        self.num_mols = [int(v) for v in num_mols]
-        self.num_atoms_per_mol = [int(v) for v in num_atoms_per_mol]
-        if len(self.num_mols) != len(self.num_atoms_per_mol):
-            raise ValueError("num_mols and num_atoms_per_mol must hold one entry per molecule type")
+        self.num_mols, self.num_atoms_per_mol = mol_series.layout(num_mols, num_atoms_per_mol)
         self.vectors = self._checked(vectors, self.num_atoms_per_mol)
         self.labels = [_label(v) for v in self.vectors]
         self.filename = filename
@@ -108,10 +104,7 @@ class Reorientation:
 
     def _jobs(self):
         """(job_atom0, job_mols, job_len) of the vectors: one job per vector, over all molecules of its type."""
-        first = np.concatenate(([0], np.cumsum(np.multiply(self.num_mols, self.num_atoms_per_mol)))).astype(np.int64)
-        types = [v[0] - 1 for v in self.vectors]
-        return (first[types], np.asarray([self.num_mols[t] for t in types], dtype=np.int64),
-                np.asarray([self.num_atoms_per_mol[t] for t in types], dtype=np.int32))
+        return mol_series.type_jobs([v[0] - 1 for v in self.vectors], self.num_mols, self.num_atoms_per_mol)
 
     def _terms(self, q):
         """Per vector the terms [(k, w)], k ascending from 1: (tail, -1), (head, +1) without the first atom's, or the
@@ -133,55 +126,36 @@ class Reorientation:
     def _refuse_degenerate(self, degenerate):
         """Keeps the zero-vector counts of the vectors; a direction that does not exist has no correlation function."""
         self.degenerate = np.asarray(degenerate, dtype=np.uint64)
-        if self.degenerate.any():
-            bad = ", ".join("%s (%d)" % (lab, n) for lab, n in zip(self.labels, self.degenerate) if n)
-            raise ValueError("zero-length vectors (in brackets: molecule-frame pairs): %s. Tail and head coincide "
-                             "there, or the dipole vanishes" % bad)
+        mol_series.refuse_degenerate(self.labels, self.degenerate, "zero-length vectors",
+                                     "Tail and head coincide there, or the dipole vanishes")
 
     def _load(self):
         """(U [S,3,F] float64 CUDA tensor, frames in time order; times [F] in ps; group_off [V+1]): read once."""
         if self._traj is not None:
             return self._traj
-        import torch
-
         from ..structural.angular_distribution import _refuse_triclinic
 
         _refuse_triclinic(self.filename)
-        wrapped = self.coords == "wrapped"
         dipole = any(v[1] == "dipole" for v in self.vectors)
-        n_atoms = int(np.dot(self.num_mols, self.num_atoms_per_mol))
         a0, mols, length = self._jobs()
-        S = int(mols.sum())
 
         def missing(lacking, _names):
             what = " (a dipole needs the charges)" if lacking[0] == "q" else ""
             raise ValueError(f"Missing column '{lacking[0]}' in dump file{what}.")
 
-        _, batches = T.attribute_batches(self.filename, ("q" if dipole else "id", "type"),
-                                         ["x", "y", "z"] if wrapped else T.UNWRAPPED, n_atoms=n_atoms, stream=STREAM,
-                                         batch_bytes=BATCH_BYTES, missing=missing, with_box=True)
-        terms = ctx = None
-        parts, steps = [], []
-        degenerate = np.zeros(len(self.vectors), dtype=np.uint64)
-        # whatever the route, each batch is reduced to unit vectors [S,3,B] that stay on the device
-        for ts, first, _types, xyz, box in batches:
-            if terms is None:
-                terms = self._terms(first[0] if dipole else None)
-                ctx = backend.default_context()
-            out = torch.empty((S, 3, len(ts)), dtype=torch.float64, device=torch.device("cuda", ctx.device))
-            _, deg = backend.axis_vectors(xyz, box if wrapped else None, a0, mols, length, terms, out=out, ctx=ctx)
-            degenerate += deg
-            parts.append(out)
-            steps.extend(np.asarray(ts).tolist())
-        if not parts:
-            raise ValueError(f"no frames match {self.filename}")
+        terms = []  # of every vector, once the first batch has shown the charges
+
+        def compute(xyz, box, out, ctx, first):
+            if not terms:
+                terms.extend(self._terms(first[0] if dipole else None))
+            return backend.axis_vectors(xyz, box, a0, mols, length, terms, out=out, ctx=ctx)[1]
+
+        V = len(self.vectors)
+        U, times, group_off, degenerate = mol_series.load_series(
+            self.filename, self.coords, int(np.dot(self.num_mols, self.num_atoms_per_mol)), compute, mols, np.arange(V), V,
+            self.dt, lead="q" if dipole else "id", stream=STREAM, batch_bytes=BATCH_BYTES, missing=missing)
         self._refuse_degenerate(degenerate)
-        order, times = Conductivity.frame_times(steps, self.dt)
-        U = parts[0] if len(parts) == 1 else torch.cat(parts, dim=2)
-        if np.any(order != np.arange(len(order))):
-            U = U.index_select(2, torch.as_tensor(order, device=U.device))
-        group_off = np.concatenate(([0], np.cumsum(mols))).astype(np.int64)
-        self._traj = (U.contiguous(), times, group_off)
+        self._traj = (U, times, group_off)
         return self._traj
 
     # ---- correlation functions ----------------------------------------------------------------------------------------
@@ -191,13 +165,9 @@ class Reorientation:
         `C1_<label>`, `C2_<label>` per vector, label = `type:tail-head` or `type:dipole`; kept in `self.corr_df` and,
         with save_mode, written to reorientation.csv (plot: reorientation.png) in working_dir."""
         U, times, group_off = self._load()
-        F = len(times)
-        max_lag = (F - 1) // 2 if max_lag is None else int(max_lag)
-        if not 0 <= max_lag <= F - 1:
-            raise ValueError("max_lag must be in [0, n_frames - 1 = %d]" % (F - 1))
-        sums = backend.orient_corr(U, group_off, max_lag)
+        max_lag, sums = mol_series.orient_corr(U, group_off, max_lag)
         cols = {"Time (ps)": times[: max_lag + 1] - times[0]}
-        origins = (F - np.arange(max_lag + 1)).astype(np.float64)
+        origins = (len(times) - np.arange(max_lag + 1)).astype(np.float64)
         for g, lab in enumerate(self.labels):
             w = origins * float(group_off[g + 1] - group_off[g])
             with np.errstate(invalid="ignore", divide="ignore"):

@@ -25,7 +25,7 @@ import numpy as np
 import pandas as pd
 
 from .. import backend
-from ..common import trajectory as T
+from ..common import mol_series
 from ..dist import is_writer
 from .angular_distribution import _refuse_triclinic
 
@@ -86,23 +86,13 @@ def _checked(dihedrals, atoms_per_mol):
     return out
 
 
-def _layout(num_mols, num_atoms_per_mol):
-    num_mols, per = [int(v) for v in num_mols], [int(v) for v in num_atoms_per_mol]
-    if len(num_mols) != len(per):
-        raise ValueError("num_mols and num_atoms_per_mol must hold one entry per molecule type")
-    return num_mols, per
-
-
 def _jobs(entries, num_mols, num_atoms_per_mol):
     """(job_atom0, job_mols, job_len, quads [J,4] 0-based, job_row) of the entries: one job per quadruple over all
     molecules of its type, the jobs of an entry in a row and adding to the entry's histogram row."""
-    first = np.concatenate(([0], np.cumsum(np.multiply(num_mols, num_atoms_per_mol)))).astype(np.int64)
-    types = [t - 1 for e, (t, quads, _) in enumerate(entries) for _ in quads]
     rows = [e for e, (_, quads, _) in enumerate(entries) for _ in quads]
     quads = [[v - 1 for v in q] for _, qs, _ in entries for q in qs]
-    return (first[types], np.asarray([num_mols[t] for t in types], dtype=np.int64),
-            np.asarray([num_atoms_per_mol[t] for t in types], dtype=np.int32), np.asarray(quads, dtype=np.int32),
-            np.asarray(rows, dtype=np.int32))
+    return mol_series.type_jobs([entries[e][0] - 1 for e in rows], num_mols, num_atoms_per_mol) + (
+        np.asarray(quads, dtype=np.int32), np.asarray(rows, dtype=np.int32))
 
 
 def _n_bins(bin_size):
@@ -133,19 +123,10 @@ def _state_bins(states, n_bins):
     return out
 
 
-def _batches(filename, coords, n_atoms):
-    """Host batches (timesteps [B], coordinates [B,3,N] by id, box [B,3] or None when unwrapped)."""
-    wrapped = coords == "wrapped"
-    _, batches = T.attribute_batches(filename, ("id", "type"), ["x", "y", "z"] if wrapped else T.UNWRAPPED,
-                                     n_atoms=n_atoms, stream=STREAM, batch_bytes=BATCH_BYTES, with_box=True)
-    for ts, _ids, _types, xyz, box in batches:
-        yield ts, xyz, (box if wrapped else None)
-
-
 def _prepare(dihedrals, filename, num_mols, num_atoms_per_mol, coords):
     if coords not in ("wrapped", "unwrapped"):
         raise ValueError('coords must be "wrapped" or "unwrapped"')
-    num_mols, per = _layout(num_mols, num_atoms_per_mol)
+    num_mols, per = mol_series.layout(num_mols, num_atoms_per_mol)
     entries = _checked(dihedrals, per)
     return entries, num_mols, per
 
@@ -180,15 +161,14 @@ def calc_dihedral_distribution(dihedrals, filename, num_mols, num_atoms_per_mol,
     a0, mols, length, quads, rows = _jobs(entries, num_mols, per)
     E = len(entries)
     hist = np.zeros((E, n_bins), dtype=np.uint64)
-    degenerate = np.zeros(E, dtype=np.uint64)
-    n_frames = 0
-    for ts, xyz, box in _batches(filename, coords, int(np.dot(num_mols, per))):
+
+    def compute(xyz, box, _out, _ctx, _ids):
         h, _, deg = backend.dihedral_angles(xyz, box, a0, mols, length, quads, job_row=rows, n_bins=n_bins)
-        hist += h
-        np.add.at(degenerate, rows, np.asarray(deg, dtype=np.uint64))
-        n_frames += len(ts)
-    if not n_frames:
-        raise ValueError(f"no frames match {filename}")
+        np.add(hist, h, out=hist)
+        return deg
+
+    degenerate = mol_series.load_series(filename, coords, int(np.dot(num_mols, per)), compute, mols, rows, E,
+                                        stream=STREAM, batch_bytes=BATCH_BYTES)[3]
 
     dist = {"phi (deg)": -180.0 + D / 2 + D * np.arange(n_bins)}
     pops = []
@@ -212,43 +192,20 @@ def calc_dihedral_distribution(dihedrals, filename, num_mols, num_atoms_per_mol,
 
 def _refuse_degenerate(entries, degenerate):
     """A torsion that does not exist has no correlation function."""
-    if np.any(degenerate):
-        bad = ", ".join("%s (%d)" % (e[2], n) for e, n in zip(entries, degenerate) if n)
-        raise ValueError("degenerate dihedrals (in brackets: molecule-frame pairs): %s. Three of the four atoms are "
-                         "collinear or coincide there" % bad)
+    mol_series.refuse_degenerate([e[2] for e in entries], degenerate, "degenerate dihedrals",
+                                 "Three of the four atoms are collinear or coincide there")
 
 
 def _load_series(entries, filename, num_mols, per, dt, coords):
     """(U [S,3,F] float64 CUDA tensor = (cos phi, sin phi, 0), frames in time order; times [F] in ps; group_off [E+1];
     degenerate uint64 [E])."""
-    import torch
-
-    from ..dynamical.conductivity import Conductivity
-
     a0, mols, length, quads, rows = _jobs(entries, num_mols, per)
-    S = int(mols.sum())
-    ctx = None
-    parts, steps = [], []
-    degenerate = np.zeros(len(entries), dtype=np.uint64)
-    # whatever the route, each batch is reduced to series [S,3,B] that stay on the device
-    for ts, xyz, box in _batches(filename, coords, int(np.dot(num_mols, per))):
-        if ctx is None:
-            ctx = backend.default_context()
-        out = torch.empty((S, 3, len(ts)), dtype=torch.float64, device=torch.device("cuda", ctx.device))
-        _, _, deg = backend.dihedral_angles(xyz, box, a0, mols, length, quads, out=out, ctx=ctx)
-        np.add.at(degenerate, rows, np.asarray(deg, dtype=np.uint64))
-        parts.append(out)
-        steps.extend(np.asarray(ts).tolist())
-    if not parts:
-        raise ValueError(f"no frames match {filename}")
-    order, times = Conductivity.frame_times(steps, dt * 10 ** -3)  # dt in fs, as Reorientation
-    U = parts[0] if len(parts) == 1 else torch.cat(parts, dim=2)
-    if np.any(order != np.arange(len(order))):
-        U = U.index_select(2, torch.as_tensor(order, device=U.device))
-    sizes = np.zeros(len(entries), dtype=np.int64)
-    np.add.at(sizes, rows, mols)
-    group_off = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
-    return U.contiguous(), times, group_off, degenerate
+
+    def compute(xyz, box, out, ctx, _ids):
+        return backend.dihedral_angles(xyz, box, a0, mols, length, quads, out=out, ctx=ctx)[2]
+
+    return mol_series.load_series(filename, coords, int(np.dot(num_mols, per)), compute, mols, rows, len(entries),
+                                  dt * 10 ** -3, stream=STREAM, batch_bytes=BATCH_BYTES)  # dt in fs, as Reorientation
 
 
 def calc_dihedral_correlation(dihedrals, filename, num_mols, num_atoms_per_mol, dt=1, max_lag=None, coords="wrapped",
@@ -267,13 +224,9 @@ def calc_dihedral_correlation(dihedrals, filename, num_mols, num_atoms_per_mol, 
     _refuse_triclinic(filename)
     U, times, group_off, degenerate = _load_series(entries, filename, num_mols, per, dt, coords)
     _refuse_degenerate(entries, degenerate)
-    F = len(times)
-    max_lag = (F - 1) // 2 if max_lag is None else int(max_lag)
-    if not 0 <= max_lag <= F - 1:
-        raise ValueError("max_lag must be in [0, n_frames - 1 = %d]" % (F - 1))
-    sums = backend.orient_corr(U, group_off, max_lag)
+    max_lag, sums = mol_series.orient_corr(U, group_off, max_lag)
     cols = {"Time (ps)": times[: max_lag + 1] - times[0]}
-    origins = (F - np.arange(max_lag + 1)).astype(np.float64)
+    origins = (len(times) - np.arange(max_lag + 1)).astype(np.float64)
     for g, (_, _, label) in enumerate(entries):
         lo, hi = int(group_off[g]), int(group_off[g + 1])
         w = origins * float(hi - lo)

@@ -61,6 +61,17 @@ def test_either_side_of_the_tile(B, mols, F):
         assert (np.abs(d) > L[:, :, None] / 2).any()
 
 
+def test_a_job_without_molecules_between_two_others(B):
+    """job_mols = (65, 0, 1): the empty job's class has no tile, and the tiles behind it still find their own class."""
+    rng = np.random.default_rng(6501)
+    F = 65
+    L = 9.0 + rng.random((F, 3))
+    x = _molecules(rng, F, 66, 4, L)
+    hist, U, _ = _check(B, x, L, [0, 260, 260], [65, 0, 1], [4, 4, 4], [(0, 1, 2, 3), (3, 2, 1, 0), (0, 2, 1, 3)], [0, 1, 2],
+                        n_bins=4, want_deg=[0, 0, 0])
+    assert hist.sum(axis=1).tolist() == [65 * F, 0, F] and U.shape == (66, 3, F)
+
+
 def test_bond_differences_at_the_half_edge(B):
     """Each of the three bond differences just above, exactly at and just below +-L/2 on every axis: the wrap is strict."""
     F = 5

@@ -65,6 +65,17 @@ def test_axis_vectors_either_side_of_the_tile(B, mols, F):
         assert (np.abs(d) > L[:, :, None] / 2).any()
 
 
+def test_axis_vectors_a_job_without_molecules_between_two_others(B):
+    """job_mols = (65, 0, 1): the empty job has no tile, and the tiles behind it still find their own job."""
+    rng = np.random.default_rng(6501)
+    F = 65
+    L = 9.0 + rng.random((F, 3))
+    x = _molecules(rng, F, 66, 4, L)
+    U = _check_axis(B, x, L, [0, 260, 260], [65, 0, 1], [4, 4, 4], [[(1, -1.0), (3, 1.0)], [(2, 1.0)], [(1, 1.0)]],
+                    want_deg=[0, 0, 0])
+    assert U.shape == (66, 3, F) and np.abs(np.sum(U * U, axis=1) - 1.0).max() < 1e-15
+
+
 def test_axis_vectors_at_the_faces(B):
     """d just above, exactly at and just below +-L/2 on every axis: the wrap is strict."""
     F = 7
