@@ -1211,6 +1211,106 @@ int mdhip_dihedral_angles(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, con
                           const int32_t *job_len, const int32_t *job_quad, const int32_t *job_row, int n_rows, int n_bins,
                           const double *cos_edges, uint64_t *hist, double *U, int U_on_device, uint64_t *degenerate);
 
+/* ---- orientational pair correlations and the dielectric constant (structural/orientational_correlation.py,
+ *      structural/dielectric.py; no counterpart in the reference) ---- */
+/*
+ * Per-molecule sites and vectors, FRAME-major — the input of mdhip_vector_pair_hist — and the per-frame totals of the
+ * vectors (the total dipole M of a molecule type).
+ *   x          host|dev (x_on_device) [n_frames][3][n_atoms], atoms by id, molecules contiguous (as mdhip_axis_vectors)
+ *   box        host [n_frames][3] edge lengths, or NULL: x is unwrapped
+ *   jobs       job j covers job_mols[j] molecules of job_len[j] atoms each, the first one starting at atom job_atom0[j]
+ *              (host [n_jobs]). It has two term lists in the form of mdhip_axis_vectors, the SITE terms (site_off
+ *              [n_jobs+1] starting at 0, site_atom, site_w) and the VECTOR terms (vec_off, vec_atom, vec_w): pairs (k, w)
+ *              with 1 <= k < job_len[j], k strictly ascending within a list. Either list may be empty.
+ *   job_unit   host int32 [n_jobs], 0 or 1: 1 normalises the job's vectors
+ *   site, vec  host|dev (out_on_device, one flag for both) [n_frames][3][n_series], n_series = sum of job_mols, series
+ *              numbered job after job, molecule after molecule; either may be NULL: not written
+ *   total      host [n_jobs][3][n_frames], or NULL: the sum of the job's vectors AS WRITTEN, per frame and axis
+ *   sq_total   host [n_jobs][n_frames], or NULL: the sum over the job's molecules of (vx*vx + vy*vy) + vz*vz of the
+ *              vectors as written
+ *   degenerate host uint64 [n_jobs]: the (molecule, frame) pairs of a job with job_unit set whose vector is exactly zero
+ * For a molecule whose first atom is a, per axis, every operation an IEEE double operation, nothing fused:
+ *   d_k = w(x[a+k] - x[a]); w is the single strict wrap of the siblings, w(d) = d > L/2 ? d - L : (d < -L/2 ? d + L : d)
+ *         with L/2 formed as L / 2 (a NaN shifts nothing), the identity when box == NULL;
+ *   o = sum_k w_k * d_k over the site terms in ascending k, one multiplication and one addition per term, starting from
+ *         w_1 * d_1;  site = x[a] + o — with no site terms site = x[a] itself, untouched. The site is NOT folded into the
+ *         box (mdhip_vector_pair_hist takes the nearest image from any image);
+ *   v = the same sum over the vector terms; with no vector terms v = (0, 0, 0), which is never counted as degenerate;
+ *   job_unit (and at least one vector term): n2 = (vx*vx + vy*vy) + vz*vz, v = v / sqrt(n2), three divisions by the
+ *         correctly rounded root. n2 == 0 gives (0, 0, 0) and +1 in degenerate[j]; a non-finite n2 gives three NaN
+ *         components and is not counted: the rules of mdhip_axis_vectors.
+ * Atoms that no term names, the first atom apart, are never read: a NaN there does not leak.
+ * A centre of mass is the site terms (k, m_k / M), a named atom k is the term (k, 1); a raw dipole about the first atom
+ * is the vector terms (k, q_k) with job_unit 0, a unit bond vector (tail, -1), (head, +1) with job_unit 1.
+ * Totals: per (job, frame) 256 partial sums per quantity, partial i adding the molecules i, i + 256, ... of the job in
+ * order, and a fixed tree over them (red[i] += red[i + w], w = 128 .. 1), as mdhip_collective_displacement: the order
+ * depends on the job's size alone, no floating-point atomics, every call gives the same bits. A NaN stays in its own
+ * job, frame and axis (and in that job's and frame's sq_total).
+ * Lane = molecule on both sides (reads one molecule apart, writes consecutive): one read of the lines that hold named
+ * atoms, one write of the two outputs: HBM-bound. Any number of frames, molecules and jobs (up to 2^20): launch
+ * dimensions over 65535 are split inside the call.
+ * n_jobs < 1, a NULL array among x, the job arrays, the offsets, job_unit and degenerate (a term array may be NULL when
+ * its list is empty for every job), a job that runs past n_atoms, a list of job_len terms or more, k outside
+ * [1, job_len) or not strictly ascending, a job_unit other than 0 or 1: MDHIP_EINVAL before anything is written.
+ */
+int mdhip_mol_moments(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *x, int x_on_device,
+                      const double *box, int n_jobs, const int64_t *job_atom0, const int64_t *job_mols,
+                      const int32_t *job_len, const int64_t *site_off, const int32_t *site_atom, const double *site_w,
+                      const int64_t *vec_off, const int32_t *vec_atom, const double *vec_w, const int32_t *job_unit,
+                      double *site, double *vec, int out_on_device, double *total, double *sq_total,
+                      uint64_t *degenerate);
+
+/*
+ * Distance-resolved orientational pair sums: per bin of the site-site distance the number of pairs and the exact sums
+ * of cos(theta), cos^2(theta) between the two vectors and of the cosine of vector j against the direction i -> j.
+ *   site, vec  host|dev (in_on_device, one flag for both) [n_frames][3][n_ent], as mdhip_mol_moments writes them
+ *   box        host [n_frames][3] edge lengths; required
+ *   group_off  host int64 [n_groups+1] contiguous entity groups; empty groups are allowed
+ *   jobs       host int32 [n_jobs][2] = (group a, group b)
+ *   edges      host [nbins+1] from mdhip_bin_edges, or NULL to have it computed from bin_size; 1 <= nbins <= 4096
+ * Per frame f, for every i in a and every j in b with j != i as entity indices; every operation an IEEE double
+ * operation, nothing fused, sqrt and division correctly rounded:
+ *   per axis  inv = 1.0 / L with L = box[f][axis];  d = site_j - site_i;  d = d - L * rint(d * inv), rint rounding half
+ *             to even: the nearest image from ANY image of either site (sites outside the box are fine); at an exact
+ *             tie (d * inv = +-0.5) nothing shifts;
+ *   rsq = (dx*dx + dy*dy) + dz*dz;
+ *   rsq < edges[nbins]: bin = (int64)(sqrt(rsq) / bin_size), decided by comparing rsq with the edge table (never by a
+ *             device sqrt), hist[job][bin] += 1; every other pair — a NaN or infinite rsq, hence a NaN site or a box
+ *             edge of 0, included — counts in beyond[job] and nowhere else.
+ * For a binned pair:
+ *   c  = (vxi*vxj + vyi*vyj) + vzi*vzj
+ *   c2 = c * c
+ *   e  = ((dx*vxj + dy*vyj) + dz*vzj) / sqrt(rsq)          (the vector of j against the direction i -> j)
+ * If all three are finite and each has magnitude < 2, the pair adds (int64) rint(value * 4294967296.0) to each of its
+ * three sums (fixed point, 32 fractional bits: the product is exact, rint rounds half to even, |addend| < 2^33).
+ * Otherwise it adds to none of them and counts in unsummed[job]: coincident sites (rsq == 0, e = 0/0), a NaN vector, a
+ * vector far from unit length.
+ *   hist       host uint64 [n_jobs][nbins]
+ *   sums       host uint64 [n_jobs][3][nbins][2]: (c, c2, e) x bin x (low word, high word) of the exact 128-bit
+ *              two's-complement integer sum of the addends; no precondition on sizes is needed
+ *   beyond, unsummed, pairs  host uint64 [n_jobs]; pairs = n_frames * (N_a * N_b - (a == b ? N_a : 0))
+ *              = sum(hist[job]) + beyond[job]; an unsummed pair is inside hist
+ * Pairs are ordered as in mdhip_van_hove_distinct: for a == b every unordered pair is visited twice, and e differs
+ * between the two visits (c and c2 do not); for a != b once.
+ * Why fixed point: the project adds nothing with floating-point atomics, and a floating-point sum would depend on the
+ * order in which workgroups finish. Integer addition is associative: all outputs are integers, exact, and independent
+ * of the launch geometry; the caller divides once, on the host.
+ * The group that fills its tiles of 64 better lies along the lanes (six values in registers), the other comes through
+ * uniform addresses (scalar loads); which is which changes nothing in the results: d, and with it e, change sign
+ * exactly. The cutoff compare comes first; the payload, the sqrt and the division run only for pairs inside it. A
+ * workgroup holds its job's row in LDS (a uint32 count and three int64 sums per bin, 28 bytes: 112 KiB at 4096 bins),
+ * added with LDS integer atomics and flushed with 64-bit integer atomics: low word, carry when the add wrapped, sign
+ * extension. At most 2^29 pairs per workgroup between zeroing and flushing: 2^29 * 2^33 < 2^63. Any number of frames,
+ * entities and jobs: launch dimensions over 65535 are split inside the call. Complete on return.
+ * NULL box, a group index out of range, nbins outside [1, 4096], a bin_size that is not positive and finite, edges that
+ * do not start at 0 and ascend, a group_off that does not ascend within [0, n_ent], a NULL array: MDHIP_EINVAL before
+ * anything is written.
+ */
+int mdhip_vector_pair_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const double *site, const double *vec,
+                           int in_on_device, const double *box, int n_groups, const int64_t *group_off, int n_jobs,
+                           const int32_t *jobs, double bin_size, int32_t nbins, const double *edges, uint64_t *hist,
+                           uint64_t *sums, uint64_t *beyond, uint64_t *unsummed, uint64_t *pairs);
+
 /*
  * Replaces, for the inputs of the path, the un-vendored pymatgen `parse_lammps_dumps` + pandas
  * `read_csv` the reference uses (call sites structural/rdf_cn.py:176, dynamical/diffusion.py:172,

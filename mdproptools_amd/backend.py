@@ -1379,6 +1379,124 @@ def orient_corr(U, group_off, max_lag, out=None, ctx=None):
     return res
 
 
+def _term_lists(terms, J, what):
+    """(offsets int64 [J+1], atoms int32, weights float64) of J lists [(k, w), ...]."""
+    if len(terms) != J:
+        raise ValueError("%s must hold one list of (k, w) per job" % what)
+    off = np.zeros(J + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(t) for t in terms])
+    return off, _i32([k for t in terms for k, _ in t]), _f64([w for t in terms for _, w in t])
+
+
+def mol_moments(x, box, job_atom0, job_mols, job_len, site_terms, vec_terms, job_unit, site_out=None, vec_out=None,
+                want_site=True, want_vec=True, totals=False, ctx=None):
+    """
+    Per-molecule sites and vectors, frame-major, and the per-frame totals of the vectors (include/mdhip.h:
+    mdhip_mol_moments): x [F,3,A] coordinates, atoms by id and molecules contiguous (host array or contiguous float64
+    device tensor); box [F,3] edge lengths, or None when x is unwrapped. Job j covers job_mols[j] molecules of
+    job_len[j] atoms from atom job_atom0[j] on; site_terms[j] and vec_terms[j] are lists [(k, w), ...] (1 <= k <
+    job_len[j], strictly ascending, possibly empty): site = x[a] + sum_k w (x[a + k] - x[a]), v = sum_k w (x[a + k] -
+    x[a]), each difference wrapped once when there is a box; job_unit[j] = 1 normalises v.
+    Returns a dict: "site", "vec" [F,3,S] with S = sum(job_mols) — host arrays, or `site_out` / `vec_out` (float64 CUDA
+    tensors [F,3,S]; give both or neither), or None where want_site / want_vec is False —, "degenerate" uint64 [J], and
+    with `totals` "total" [J,3,F] (the sum of the job's vectors per frame and axis) and "sq_total" [J,F] (the sum of
+    their squared lengths).
+    """
+    ctx = ctx or default_context()
+    J = len(job_unit)
+    F, A, bx, a0, mols, length, S = _mol_jobs(x, box, job_atom0, job_mols, job_len, J,
+                                              "job_atom0, job_mols, job_len and job_unit must hold one entry per job")
+    s_off, s_atom, s_w = _term_lists(site_terms, J, "site_terms")
+    v_off, v_atom, v_w = _term_lists(vec_terms, J, "vec_terms")
+    unit = _i32(job_unit)
+    given = [o is not None for o, want in ((site_out, want_site), (vec_out, want_vec)) if want]
+    if any(given) and not all(given):
+        raise ValueError("site_out and vec_out go together: both device tensors, or neither")
+    on_dev = int(any(given))
+    xp, x_dev, keep = as_input(x, ctx)
+    site = vec = sp = vp_ = None
+    if want_site:
+        site, sp, _ = _dest(site_out, (F, 3, S), ctx, pinned=True)
+    if want_vec:
+        vec, vp_, _ = _dest(vec_out, (F, 3, S), ctx, pinned=True)
+    total = np.empty((J, 3, F)) if totals else None
+    sq_total = np.empty((J, F)) if totals else None
+    degenerate = np.zeros(max(J, 1), dtype=np.uint64)
+    ctx.check(ctx.lib.mdhip_mol_moments(
+        ctx.h, F, A, xp, x_dev, None if bx is None else ptr(bx), J, ptr(a0, C.c_int64), ptr(mols, C.c_int64),
+        ptr(length, C.c_int32), ptr(s_off, C.c_int64), ptr(s_atom, C.c_int32), ptr(s_w), ptr(v_off, C.c_int64),
+        ptr(v_atom, C.c_int32), ptr(v_w), ptr(unit, C.c_int32), sp, vp_, on_dev,
+        None if total is None else ptr(total), None if sq_total is None else ptr(sq_total), ptr(degenerate, C.c_uint64)))
+    return {"site": site, "vec": vec, "degenerate": degenerate[:J], "total": total, "sq_total": sq_total}
+
+
+VECTOR_PAIR_MAX_BINS = 4096  # bins per call of vector_pair_hist (include/mdhip.h: mdhip_vector_pair_hist)
+VECTOR_PAIR_ONE = 1 << 32    # the fixed-point unit of its sums
+
+
+def combine_words(words):
+    """The signed Python integers behind 128-bit two's-complement words: uint64 [..., 2] (low, high) -> object array
+    [...] of int."""
+    w = np.asarray(words, dtype=np.uint64)
+    if w.shape[-1:] != (2,):
+        raise ValueError("words must have shape [..., 2]: (low, high)")
+    flat = w.reshape(-1, 2)
+    out = np.empty(len(flat), dtype=object)
+    for n, (lo, hi) in enumerate(flat.tolist()):
+        v = (hi << 64) | lo
+        out[n] = v - (1 << 128) if hi >> 63 else v
+    return out.reshape(w.shape[:-1])
+
+
+def vector_pair_hist(site, vec, box, group_off, jobs, bin_size, n_bins, ctx=None):
+    """
+    Distance-resolved orientational pair sums (include/mdhip.h: mdhip_vector_pair_hist): site, vec [F,3,E] (both host
+    arrays or both contiguous float64 device tensors, as mol_moments returns them), box [F,3] edge lengths, group_off
+    int64 [G+1] contiguous entity groups, jobs int32 [J,2] rows (group a, group b) ->
+    (hist uint64 [J,n_bins], sums object [J,3,n_bins] of Python int, beyond, unsummed, pairs uint64 [J]).
+    sums[j, 0], [j, 1], [j, 2] are the exact sums of rint(2^32 c), rint(2^32 c^2), rint(2^32 e) over the pairs of a bin, c
+    the cosine between the two vectors and e the cosine of vector j against the direction i -> j: divide by
+    VECTOR_PAIR_ONE * hist. hist.sum(1) + beyond == pairs; unsummed pairs are inside hist and in no sum.
+    """
+    F, _, E = _shape3(site, "site")
+    if tuple(vec.shape) != (F, 3, E):
+        raise ValueError("vec must have the shape of site")
+    if box is None:
+        raise ValueError("box is required: the pair sums take the nearest image")
+    bx = _f64(box)
+    if bx.shape != (F, 3):
+        raise ValueError("box must have shape [n_frames, 3]")
+    off = _i64(group_off)
+    if off.ndim != 1 or off.size < 1 or off[0] < 0 or off[-1] > E or np.any(np.diff(off) < 0):
+        raise ValueError("group_off must be ascending offsets [n_groups + 1] within [0, n_ent]")
+    G = off.size - 1
+    jb = np.asarray(jobs)
+    if jb.size and (jb.ndim != 2 or jb.shape[1] != 2):
+        raise ValueError("jobs must have shape [n_jobs, 2]: (group a, group b)")
+    jb = _i32(jb).reshape(-1, 2)
+    if len(jb) and (jb.min() < 0 or jb.max() >= G):
+        raise ValueError("a job names a group outside [0, %d)" % G)
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= VECTOR_PAIR_MAX_BINS:
+        raise ValueError("n_bins must be in [1, %d]" % VECTOR_PAIR_MAX_BINS)
+    if not (float(bin_size) > 0.0 and np.isfinite(bin_size)):
+        raise ValueError("bin_size must be positive and finite")
+    ctx = ctx or default_context()
+    sp, s_dev, keep_s = as_input(site, ctx)
+    vp_, v_dev, keep_v = as_input(vec, ctx)
+    if s_dev != v_dev:
+        raise ValueError("site and vec must both be host arrays or both be device tensors")
+    J = len(jb)
+    hist = np.empty((J, n_bins), dtype=np.uint64)
+    words = np.empty((J, 3, n_bins, 2), dtype=np.uint64)
+    beyond, unsummed, pairs = (np.empty(J, dtype=np.uint64) for _ in range(3))
+    ctx.check(ctx.lib.mdhip_vector_pair_hist(
+        ctx.h, F, E, sp, vp_, s_dev, ptr(bx), G, ptr(off, C.c_int64), J, ptr(jb, C.c_int32), float(bin_size), n_bins,
+        None, ptr(hist, C.c_uint64), ptr(words, C.c_uint64), ptr(beyond, C.c_uint64), ptr(unsummed, C.c_uint64),
+        ptr(pairs, C.c_uint64)))
+    return hist, combine_words(words), beyond, unsummed, pairs
+
+
 DIHEDRAL_MAX_ROWS = 16    # histogram rows per call of dihedral_angles (include/mdhip.h: mdhip_dihedral_angles)
 DIHEDRAL_MAX_BINS = 1440  # bins over [-180, 180): 0.25 degrees
 

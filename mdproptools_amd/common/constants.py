@@ -16,6 +16,7 @@ LIGHT_SPEED = 299792458  # m/s
 BOHR_RADIUS = 5.29177210903 * 10 ** -11  # m
 CAL_TO_J = 4.184
 HA_TO_J = 4.3597447222071 * 10 ** -18
+VACUUM_PERMITTIVITY = 8.8541878128 * 10 ** -12  # F/m
 
 SUPPORTED_UNITS = ["real", "metal", "si", "cgs", "electron", "micro", "nano"]
 
