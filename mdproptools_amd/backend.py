@@ -86,6 +86,34 @@ def _dest(out, shape, ctx, dtype=np.float64, dev_dtype="torch.float64", pinned=F
     return res, ptr(res, np.ctypeslib.as_ctypes_type(dtype)), 0
 
 
+def _group_jobs(F, E, box, group_off, jobs, cols, group_cols, bin_size, n_bins, max_bins, max_text):
+    """What the histogram calls over jobs on contiguous entity groups check first: -> (box float64 [F,3] or None,
+    group_off int64 [G+1], G, jobs int32 [J, width], n_bins). `cols` names a job's columns, the first `group_cols` of
+    which are groups."""
+    bx = None
+    if box is not None:
+        bx = _f64(box)
+        if bx.shape != (F, 3):
+            raise ValueError("box must have shape [n_frames, 3]")
+    off = _i64(group_off)
+    if off.ndim != 1 or off.size < 1 or off[0] < 0 or off[-1] > E or np.any(np.diff(off) < 0):
+        raise ValueError("group_off must be ascending offsets [n_groups + 1] within [0, n_ent]")
+    G = off.size - 1
+    width = cols.count(",") + 1
+    jb = np.asarray(jobs)
+    if jb.size and (jb.ndim != 2 or jb.shape[1] != width):
+        raise ValueError("jobs must have shape [n_jobs, %d]: %s" % (width, cols))
+    jb = _i32(jb).reshape(-1, width)
+    if len(jb) and (jb[:, :group_cols].min() < 0 or jb[:, :group_cols].max() >= G):
+        raise ValueError("a job names a group outside [0, %d)" % G)
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= max_bins:
+        raise ValueError("n_bins must be in [1, %s]" % max_text)
+    if not (float(bin_size) > 0.0 and np.isfinite(bin_size)):
+        raise ValueError("bin_size must be positive and finite")
+    return bx, off, G, jb, n_bins
+
+
 def _check_cols(cols, n, what):
     """A host destination of per-entity columns: float64 [4, n] whose rows are contiguous (they may be rows of a larger
     C-ordered block). Returns (its address, the row stride in doubles)."""
@@ -1161,31 +1189,13 @@ def displacement_hist(r, box, group_off, jobs, bin_size, n_bins, ctx=None):
     moments float64 [J,3] = sums of r, r^2, r^4 over the job's windows, crossings int: the image shifts found).
     """
     F, _, E = _shape3(r, "r")
-    bx = None
-    if box is not None:
-        bx = _f64(box)
-        if bx.shape != (F, 3):
-            raise ValueError("box must have shape [n_frames, 3]")
-    off = _i64(group_off)
-    if off.ndim != 1 or off.size < 1 or off[0] < 0 or off[-1] > E or np.any(np.diff(off) < 0):
-        raise ValueError("group_off must be ascending offsets [n_groups + 1] within [0, n_ent]")
-    G = off.size - 1
-    jb = np.asarray(jobs)
-    if jb.size and (jb.ndim != 2 or jb.shape[1] != 3):
-        raise ValueError("jobs must have shape [n_jobs, 3]: (group, lag, stride)")
-    jb = _i32(jb).reshape(-1, 3)
+    bx, off, G, jb, n_bins = _group_jobs(F, E, box, group_off, jobs, "(group, lag, stride)", 1, bin_size, n_bins,
+                                         1 << 20, "2^20")
     if len(jb):
-        if jb[:, 0].min() < 0 or jb[:, 0].max() >= G:
-            raise ValueError("a job names a group outside [0, %d)" % G)
         if jb[:, 1].min() < 1 or jb[:, 1].max() > F - 1:
             raise ValueError("every lag must be in [1, n_frames - 1 = %d]" % (F - 1))
         if jb[:, 2].min() < 1:
             raise ValueError("every stride must be at least 1")
-    n_bins = int(n_bins)
-    if not 1 <= n_bins <= 1 << 20:
-        raise ValueError("n_bins must be in [1, 2^20]")
-    if not (float(bin_size) > 0.0 and np.isfinite(bin_size)):
-        raise ValueError("bin_size must be positive and finite")
     ctx = ctx or default_context()
     rp, r_dev, keep = as_input(r, ctx)
     J = len(jb)
@@ -1211,29 +1221,13 @@ def van_hove_distinct(r, box, group_off, jobs, bin_size, n_bins, ctx=None):
     F, _, E = _shape3(r, "r")
     if box is None:
         raise ValueError("box is required: the distinct van Hove function works on wrapped coordinates")
-    bx = _f64(box)
-    if bx.shape != (F, 3):
-        raise ValueError("box must have shape [n_frames, 3]")
-    off = _i64(group_off)
-    if off.ndim != 1 or off.size < 1 or off[0] < 0 or off[-1] > E or np.any(np.diff(off) < 0):
-        raise ValueError("group_off must be ascending offsets [n_groups + 1] within [0, n_ent]")
-    G = off.size - 1
-    jb = np.asarray(jobs)
-    if jb.size and (jb.ndim != 2 or jb.shape[1] != 4):
-        raise ValueError("jobs must have shape [n_jobs, 4]: (group a, group b, lag, stride)")
-    jb = _i32(jb).reshape(-1, 4)
+    bx, off, G, jb, n_bins = _group_jobs(F, E, box, group_off, jobs, "(group a, group b, lag, stride)", 2, bin_size,
+                                         n_bins, 1 << 20, "2^20")
     if len(jb):
-        if jb[:, :2].min() < 0 or jb[:, :2].max() >= G:
-            raise ValueError("a job names a group outside [0, %d)" % G)
         if jb[:, 2].min() < 0 or jb[:, 2].max() > F - 1:
             raise ValueError("every lag must be in [0, n_frames - 1 = %d]" % (F - 1))
         if jb[:, 3].min() < 1:
             raise ValueError("every stride must be at least 1")
-    n_bins = int(n_bins)
-    if not 1 <= n_bins <= 1 << 20:
-        raise ValueError("n_bins must be in [1, 2^20]")
-    if not (float(bin_size) > 0.0 and np.isfinite(bin_size)):
-        raise ValueError("bin_size must be positive and finite")
     ctx = ctx or default_context()
     rp, r_dev, keep = as_input(r, ctx)
     J = len(jb)
@@ -1463,24 +1457,8 @@ def vector_pair_hist(site, vec, box, group_off, jobs, bin_size, n_bins, ctx=None
         raise ValueError("vec must have the shape of site")
     if box is None:
         raise ValueError("box is required: the pair sums take the nearest image")
-    bx = _f64(box)
-    if bx.shape != (F, 3):
-        raise ValueError("box must have shape [n_frames, 3]")
-    off = _i64(group_off)
-    if off.ndim != 1 or off.size < 1 or off[0] < 0 or off[-1] > E or np.any(np.diff(off) < 0):
-        raise ValueError("group_off must be ascending offsets [n_groups + 1] within [0, n_ent]")
-    G = off.size - 1
-    jb = np.asarray(jobs)
-    if jb.size and (jb.ndim != 2 or jb.shape[1] != 2):
-        raise ValueError("jobs must have shape [n_jobs, 2]: (group a, group b)")
-    jb = _i32(jb).reshape(-1, 2)
-    if len(jb) and (jb.min() < 0 or jb.max() >= G):
-        raise ValueError("a job names a group outside [0, %d)" % G)
-    n_bins = int(n_bins)
-    if not 1 <= n_bins <= VECTOR_PAIR_MAX_BINS:
-        raise ValueError("n_bins must be in [1, %d]" % VECTOR_PAIR_MAX_BINS)
-    if not (float(bin_size) > 0.0 and np.isfinite(bin_size)):
-        raise ValueError("bin_size must be positive and finite")
+    bx, off, G, jb, n_bins = _group_jobs(F, E, box, group_off, jobs, "(group a, group b)", 2, bin_size, n_bins,
+                                         VECTOR_PAIR_MAX_BINS, VECTOR_PAIR_MAX_BINS)
     ctx = ctx or default_context()
     sp, s_dev, keep_s = as_input(site, ctx)
     vp_, v_dev, keep_v = as_input(vec, ctx)

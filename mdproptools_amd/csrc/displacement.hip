@@ -27,10 +27,7 @@
 // dp_moment_kernel adds a job's partials in a fixed order. No float atomics: integers are exact and independent of
 // the launch geometry, moments are reproducible for a given geometry. Measured: DESIGN.md 4.12.
 
-#include <algorithm>
-#include <vector>
-
-#include "ctx.h"
+#include "group_pairs.h"  // (its three argument checks; the kernels and the plan here are this file's own)
 
 #pragma clang fp contract(off)
 
@@ -257,10 +254,8 @@ int mdhip_displacement_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, con
                "trajectory too large");
     MD_REQUIRE(nbins >= 1 && nbins <= (1 << 20), "nbins must be in [1, 2^20]");
     MD_REQUIRE(bin_size > 0.0 && bin_size < __builtin_inf(), "bin_size must be positive and finite");
-    MD_REQUIRE(n_groups == 0 || group_off, "NULL group_off");
-    for (int g = 0; g < n_groups; ++g)
-        MD_REQUIRE(group_off[g] >= 0 && group_off[g] <= group_off[g + 1] && group_off[g + 1] <= n_ent,
-                   "group_off must ascend within [0, n_ent] (group %d)", g);
+    int rc;
+    if ((rc = gp_check_groups(ctx, n_groups, group_off, n_ent))) return rc;
     MD_REQUIRE(n_jobs == 0 || (jobs && hist && overflow && windows && moments), "NULL array");
     for (int j = 0; j < n_jobs; ++j) {
         const int32_t *q = jobs + 3 * (size_t)j;
@@ -269,10 +264,7 @@ int mdhip_displacement_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, con
         MD_REQUIRE(q[2] >= 1, "job %d: stride %d must be positive", j, q[2]);
     }
     MD_REQUIRE((size_t)n_jobs * (size_t)nbins < ((size_t)1 << 34), "result too large");
-    if (edges && n_jobs) {  // (the kernel walks the table: it has to start at 0 and ascend)
-        MD_REQUIRE(edges[0] == 0.0, "edges[0] must be 0");
-        for (int k = 0; k < nbins; ++k) MD_REQUIRE(edges[k] <= edges[k + 1], "edges must ascend (bin %d)", k);
-    }
+    if ((rc = gp_check_edges(ctx, edges, nbins, n_jobs))) return rc;
     const bool wrap = box != nullptr && n_ent > 0 && n_frames >= 2;
     if (crossings) *crossings = 0;
     if (n_jobs == 0 && !(wrap && crossings)) return cs.end();
@@ -300,15 +292,9 @@ int mdhip_displacement_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, con
         windows[j] = (uint64_t)J.n_win;
     }
     std::vector<double> own;
-    if (n_jobs && !edges) {
-        own.resize((size_t)nbins + 1);
-        if (mdhip_bin_edges(bin_size, nbins, own.data()) != MDHIP_OK)
-            return mdhip_fail(ctx, MDHIP_EINVAL, "no bin edges for bin_size %g", bin_size);
-        edges = own.data();
-    }
+    if (n_jobs && (rc = gp_edges(ctx, edges, own, bin_size, nbins))) return rc;
 
     MD_HIP(hipSetDevice(ctx->device));
-    int rc;
     const size_t r_bytes = (size_t)n_frames * 3 * (size_t)n_ent * 8;
     const double *d_r = (const double *)mdhip_stage(ctx, WS_XYZ_I, r, r_bytes, r_on_device || r_bytes == 0, &rc);
     if (rc) return rc;

@@ -1,7 +1,8 @@
 """mdhip_mol_moments, mdhip_vector_pair_hist and the two drop-ins on top of them against tests/dipole_ref.py, which
 restates include/mdhip.h operation by operation: every output is compared with == or bit for bit. The shapes are the
 smallest at which the kernels can go wrong: either side of the 64-molecule and 64-frame tile, of the 64-lane tile of the
-pair sweep with either group on the lanes, more than one workgroup, more than 65 535 jobs."""
+pair sweep with either group on the lanes, more than one workgroup, more than 65 535 jobs, more uniform entities than
+one chunk of 2^20."""
 import ctypes as C
 import math
 
@@ -332,6 +333,67 @@ def test_pairs_more_jobs_than_a_launch_holds(B):
     for name, g, w in zip(("hist", "sums", "beyond", "unsummed", "pairs"), got, want):
         assert np.array_equal(g, w[pick]), name
     assert got[0].sum() > 0
+
+
+def test_pairs_and_van_hove_on_one_walker(B):
+    """vp_pair_kernel and vh_pair_kernel step through the same units (csrc/group_pairs.h): on sites that are multiples of
+    1/8 in a cubic box of edge 16 every difference, wrap and square is exact, the single wrap and the nearest image are
+    the same number, and hist, beyond and pairs of the vector sweep equal those of the distinct van Hove function at
+    lag 0, stride 1 — for every ordered pair of groups of 5, 64, 65 and 130 entities, a with a included."""
+    import vanhove_ref as R
+
+    from mdproptools_amd._lib import bin_edges
+
+    rng = np.random.default_rng(35)
+    sizes = [5, 64, 65, 130]
+    F, E = 3, sum(sizes)
+    site = rng.integers(0, 16 * 8, size=(F, 3, E)) / 8.0
+    vec, box = _unit_vectors(rng, (F, 3, E)), np.full((F, 3), 16.0)
+    off = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+    jobs = [(a, b) for a in range(4) for b in range(4)]
+    lagged = [(a, b, 0, 1) for a, b in jobs]
+    # the premise, on the CPU: the two restatements agree on these inputs
+    want_vh = R.van_hove_distinct(site, box, off, lagged, 0.25, 32)
+    want_vp = D.vector_pair_hist(site, vec, box, off, jobs, 0.25, 32, bin_edges(0.25, 32))
+    for w_vh, w_vp in zip(want_vh, (want_vp[0], want_vp[2], want_vp[4])):
+        assert np.array_equal(w_vh, w_vp)
+    assert want_vh[0].sum() > 10000 and want_vh[1].sum() > 10000
+    hist, _, beyond, _, pairs = B.vector_pair_hist(site, vec, box, off, jobs, 0.25, 32)
+    got_vh = B.van_hove_distinct(site, box, off, lagged, 0.25, 32)
+    for name, g_vp, g_vh, w in zip(("hist", "beyond", "pairs"), (hist, beyond, pairs), got_vh, want_vh):
+        assert g_vp.tolist() == g_vh.tolist(), name
+        assert g_vp.tolist() == w.tolist(), name
+
+
+def _long_group(rng):
+    """One frame in a box of edge 64: group a of 64 entities, then 2^20 + 65 more, the last 65 of them within 2 of
+    entity 0 -> (sites [1,3,E], box, group_off of (a, b), group_off of (a, b1, b2) with b split at 2^20 - 7)."""
+    n_b = (1 << 20) + 65
+    E = 64 + n_b
+    site = rng.random((1, 3, E)) * 64.0
+    site[0, :, -65:] = np.mod(site[0, :, :1] + rng.uniform(-1.0, 1.0, size=(3, 65)), 64.0)
+    whole = np.array([0, 64, E], dtype=np.int64)
+    return site, np.full((1, 3), 64.0), whole, np.array([0, 64, 64 + (1 << 20) - 7, E], dtype=np.int64)
+
+
+def test_pairs_past_one_chunk_of_uniform_entities(B):
+    """2^20 + 65 entities on the uniform side, the lanes holding a (job (a, b)) and holding b (job (b, a)): two chunks
+    per tile. Every output equals the sum over the two parts of the long group, each of which is one chunk."""
+    rng = np.random.default_rng(36)
+    site, box, whole, split = _long_group(rng)
+    vec = _unit_vectors(rng, site.shape)
+    got = B.vector_pair_hist(site, vec, box, whole, [(0, 1), (1, 0)], 0.25, 16)
+    part = B.vector_pair_hist(site, vec, box, split, [(0, 1), (0, 2), (1, 0), (2, 0)], 0.25, 16)
+    for name, g, p in zip(("hist", "sums", "beyond", "unsummed", "pairs"), got, part):
+        assert (p[0] + p[1]).tolist() == g[0].tolist(), name
+        assert (p[2] + p[3]).tolist() == g[1].tolist(), name
+    hist, sums, beyond, _, pairs = got
+    assert pairs.tolist() == [64 * ((1 << 20) + 65)] * 2 and (hist.sum(axis=1) + beyond).tolist() == pairs.tolist()
+    # the last 65 entities are all within reach of entity 0, and they are counted
+    assert part[0][1].sum() >= 65 and part[0][0].sum() > 1000 and hist[0].sum() == part[0][0].sum() + part[0][1].sum()
+    # the same pairs and cosines either way round, another direction cosine
+    assert hist[0].tolist() == hist[1].tolist() and sums[0, 0].tolist() == sums[1, 0].tolist()
+    assert sums[0, 2].tolist() != sums[1, 2].tolist()
 
 
 def test_pairs_invalid_arguments(B):

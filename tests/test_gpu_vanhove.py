@@ -6,7 +6,7 @@ part, mdhip_displacement_hist, through the doubled-trajectory identity hist(A, B
 hist.sum(1) + beyond == pairs is asserted in every case. Shapes are the smallest at which the kernel can go wrong: group
 sizes either side of a wave and a block, an empty group, rows that fit LDS and that do not, a distance on a bin edge
 and the double below, |d| of exactly half a box edge and one ulp more, a bin that receives more than 2^32 pairs, more
-jobs than one launch dimension, 70 001 frames, NaN and +inf.
+jobs than one launch dimension, 70 001 frames, more uniform entities than one chunk of 2^20, NaN and +inf.
 """
 import numpy as np
 import pytest
@@ -173,6 +173,27 @@ def test_70001_frames_of_3_entities(B):
     got = B.van_hove_distinct(x, box, off, jobs, 0.5, 16)
     _same(got, R.van_hove_distinct(x, box, off, jobs, 0.5, 16))
     assert got[2].tolist() == [140000, 140000, 2, 2, 4, 2 * 17499]
+
+
+def test_past_one_chunk_of_uniform_entities(B):
+    """One frame in a box of edge 64, group a of 64 entities and group b of 2^20 + 65, the last 65 of them within 2 of
+    entity 0: the long group is the uniform side of both jobs, the lanes holding a (job (a, b)) and holding b (job
+    (b, a)), two chunks per tile. Every output equals the sum over b1 | b2 = b split at 2^20 - 7, one chunk each."""
+    rng = np.random.default_rng(41)
+    n_b = (1 << 20) + 65
+    E = 64 + n_b
+    x = rng.random((1, 3, E)) * 64.0
+    x[0, :, -65:] = np.mod(x[0, :, :1] + rng.uniform(-1.0, 1.0, size=(3, 65)), 64.0)
+    box = np.full((1, 3), 64.0)
+    got = _check(B.van_hove_distinct(x, box, np.array([0, 64, E]), [(0, 1, 0, 1), (1, 0, 0, 1)], 0.25, 16))
+    part = _check(B.van_hove_distinct(x, box, np.array([0, 64, 64 + (1 << 20) - 7, E]),
+                                      [(0, 1, 0, 1), (0, 2, 0, 1), (1, 0, 0, 1), (2, 0, 0, 1)], 0.25, 16))
+    for g, p in zip(got, part):
+        assert np.array_equal(p[0] + p[1], g[0]) and np.array_equal(p[2] + p[3], g[1])
+    hist, beyond, pairs = got
+    assert pairs.tolist() == [64 * n_b] * 2 and np.array_equal(hist[0], hist[1])
+    # the last 65 entities are all within reach of entity 0, and they are counted
+    assert part[0][1].sum() >= 65 and part[0][0].sum() > 1000 and hist[0].sum() == part[0][0].sum() + part[0][1].sum()
 
 
 def test_nan_and_inf_leave_with_their_atoms(B):
