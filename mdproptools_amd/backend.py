@@ -65,6 +65,22 @@ def _shape3(x, name):
     return shp
 
 
+def _xyz_box(xyz, box, ctx):
+    """What the calls on xyz [F,3,N] and box [F,3] open with: -> (the context, F, N, box float64 [F,3], coordinate
+    pointer, on_device, keepalive)."""
+    ctx = ctx or default_context()
+    F, _, N = _shape3(xyz, "xyz")
+    return (ctx, F, N, _f64(box).reshape(F, 3)) + as_input(xyz, ctx)
+
+
+def _mol_of(mol_of, N):
+    """mol_of [N] as the library reads it."""
+    mol = _i32(mol_of).ravel()
+    if len(mol) != N:
+        raise ValueError("mol_of must hold one molecule index per atom")
+    return mol
+
+
 def _pair_inputs(xyz, types, box, relation_matrix, ctx, check_types=True):
     """What every atom-atom pair call marshals: (F, N, coordinate pointer, on_device, keepalive, types int32, their
     frame stride (0: one [N] row shared by the frames), box [F,3], relations int32 [R,2])."""
@@ -616,6 +632,29 @@ def _with_overflow_rerun(run, xyz, inp, bx, cap, pads, what, ctx, per_frame=None
     return (*outs, count)
 
 
+def _with_larger_cap(run, count_of, cap, max_cap, cen, name, hint):
+    """
+    The capped whole-call search behind angle_hist and bond_order. run(cap) -> the call's result, count_of(result) its
+    count [n_frames, C] (exact even past cap); cen [C] the centres' atoms. A call with a row of more than `cap`
+    neighbours is run once more, whole, with a cap of the largest count (the first call's values are discarded); more
+    than `max_cap`, what the row kernel stages, is a ValueError that names the frame and the centre atom. `name` and
+    `hint` are the function's, for the error texts.
+    """
+    cap = int(cap)
+    out = run(cap)
+    count = count_of(out)
+    big = int(count.max()) if count.size else 0
+    if big > cap:
+        if big > max_cap:
+            f, c = np.unravel_index(int(count.argmax()), count.shape)
+            raise ValueError("%s: frame %d, centre atom %d has %d neighbours; at most %d are supported (%s)"
+                             % (name, f, int(cen[c]), big, max_cap, hint))
+        out = run(big)
+        if not np.array_equal(count_of(out), count):
+            raise RuntimeError("%s: the re-run found other row sizes than the first sweep" % name)
+    return out
+
+
 SHELL_CAP = 32  # first-try molecules per (frame, centre) row of shell_members; rows that hold more are re-run
 
 
@@ -627,14 +666,10 @@ def shell_members(xyz, box, centres, mol_of, r_cut_sq, cap=SHELL_CAP, ctx=None):
     -1 up to K = max(cap, largest count). Frames whose shells overflow `cap` are run again with a cap of their
     largest count (include/mdhip.h: mdhip_shell_members).
     """
-    ctx = ctx or default_context()
-    F, _, N = _shape3(xyz, "xyz")
+    ctx, F, N, bx, *inp = _xyz_box(xyz, box, ctx)
     cen = _i32(centres).ravel()
-    mol = _i32(mol_of).ravel()
-    if len(mol) != N:
-        raise ValueError("mol_of must hold one molecule index per atom")
+    mol = _mol_of(mol_of, N)
     C_ = len(cen)
-    bx = _f64(box).reshape(F, 3)
 
     def run(n_f, p, dev, b, k):
         mols = np.empty((n_f, C_, k), dtype=np.int32)
@@ -644,7 +679,7 @@ def shell_members(xyz, box, centres, mol_of, r_cut_sq, cap=SHELL_CAP, ctx=None):
             ptr(mols, C.c_int32), ptr(count, C.c_int32)))
         return mols, count
 
-    return _with_overflow_rerun(run, xyz, as_input(xyz, ctx), bx, cap, (-1,), ("shell_members", "shell"), ctx)
+    return _with_overflow_rerun(run, xyz, inp, bx, cap, (-1,), ("shell_members", "shell"), ctx)
 
 
 COORD_CLASSES = 8  # 8-bit counters in the 64-bit word of shell_coordination
@@ -665,8 +700,7 @@ def shell_coordination(xyz, box, centres, mol_of, seg_off, mol_type, cls, r_shel
     (type, word) sequences. Frames whose rows overflow `cap` are run again with a cap of their largest count
     (include/mdhip.h: mdhip_shell_coordination).
     """
-    ctx = ctx or default_context()
-    F, _, N = _shape3(xyz, "xyz")
+    ctx, F, N, bx, *inp = _xyz_box(xyz, box, ctx)
     cen = _i32(centres).ravel()
     mol = _i32(mol_of).ravel()
     off = _i64(seg_off).ravel()
@@ -683,7 +717,6 @@ def shell_coordination(xyz, box, centres, mol_of, seg_off, mol_type, cls, r_shel
     if M and int(np.diff(off).max()) > COORD_MOL_ATOMS:
         raise ValueError("a molecule of more than %d atoms: a coordination counter could wrap" % COORD_MOL_ATOMS)
     C_ = len(cen)
-    bx = _f64(box).reshape(F, 3)
     mask = None
     if passes is not None:
         mask = np.ascontiguousarray(np.asarray(passes).reshape(F, M) != 0, dtype=np.uint8)
@@ -699,7 +732,7 @@ def shell_coordination(xyz, box, centres, mol_of, seg_off, mol_type, cls, r_shel
             ptr(count, C.c_int32)))
         return mols, words, count
 
-    return _with_overflow_rerun(run, xyz, as_input(xyz, ctx), bx, cap, (-1, np.uint64(0xFFFFFFFFFFFFFFFF)),
+    return _with_overflow_rerun(run, xyz, inp, bx, cap, (-1, np.uint64(0xFFFFFFFFFFFFFFFF)),
                                 ("shell_coordination", "shell"), ctx, per_frame=mask)
 
 
@@ -732,12 +765,10 @@ def hydration_cosines(xyz, box, cations, waters, r_cut_sq, cap=HYDRATION_CAP, ct
     Frames whose rows overflow `cap` are run again with a cap of their largest count (include/mdhip.h:
     mdhip_hydration_cosines).
     """
-    ctx = ctx or default_context()
-    F, _, N = _shape3(xyz, "xyz")
+    ctx, F, N, bx, *inp = _xyz_box(xyz, box, ctx)
     cat = _i32(cations).ravel()
     wat = _i32(waters).ravel()
     C_, W = len(cat), len(wat)
-    bx = _f64(box).reshape(F, 3)
 
     def run(n_f, p, dev, b, k):
         idx = np.empty((n_f, C_, k), dtype=np.int32)
@@ -748,8 +779,7 @@ def hydration_cosines(xyz, box, cations, waters, r_cut_sq, cap=HYDRATION_CAP, ct
             ptr(idx, C.c_int32), ptr(cos), ptr(count, C.c_int32)))
         return idx, cos, count
 
-    return _with_overflow_rerun(run, xyz, as_input(xyz, ctx), bx, cap, (-1, np.nan), ("hydration_cosines", "row"),
-                                ctx)
+    return _with_overflow_rerun(run, xyz, inp, bx, cap, (-1, np.nan), ("hydration_cosines", "row"), ctx)
 
 
 def hydration_counts(xyz, box, cations, waters, r_cut_sq, cos_cut, bin_width, n_bins, ctx=None):
@@ -758,13 +788,10 @@ def hydration_counts(xyz, box, cations, waters, r_cut_sq, cos_cut, bin_width, n_
     counts cos < cos_cut, hist bins trunc((cos + 1) / bin_width) clamped to n_bins - 1 over all rows, NaN in no bin
     (include/mdhip.h: mdhip_hydration_counts). No capacity limit.
     """
-    ctx = ctx or default_context()
-    F, _, N = _shape3(xyz, "xyz")
+    ctx, F, N, bx, xp, x_dev, keep = _xyz_box(xyz, box, ctx)
     cat = _i32(cations).ravel()
     wat = _i32(waters).ravel()
     C_, W = len(cat), len(wat)
-    bx = _f64(box).reshape(F, 3)
-    xp, x_dev, keep = as_input(xyz, ctx)
     n_water = np.zeros((F, C_), dtype=np.int32)
     n_away = np.zeros((F, C_), dtype=np.int32)
     hist = np.zeros(int(n_bins), dtype=np.uint64)
@@ -808,8 +835,7 @@ def angle_hist(xyz, box, types, triplets, r_cut_sq, cos_edges, mol_of=None, cap=
     cutoff of the centre's triplets. A batch with a row of more than `cap` neighbours is run once more with a cap of
     the largest count; more than 512 is a ValueError.
     """
-    ctx = ctx or default_context()
-    F, _, N = _shape3(xyz, "xyz")
+    ctx, F, N, bx, xp, x_dev, keep = _xyz_box(xyz, box, ctx)
     typ = _i32(types).ravel()
     if len(typ) != N:
         raise ValueError("types must hold one type per atom")
@@ -822,16 +848,10 @@ def angle_hist(xyz, box, types, triplets, r_cut_sq, cos_edges, mol_of=None, cap=
     n_bins = len(edges)
     if n_bins < 1 or not np.all(np.diff(edges) < 0):
         raise ValueError("cos_edges must be strictly decreasing")
-    mol = None
-    if mol_of is not None:
-        mol = _i32(mol_of).ravel()
-        if len(mol) != N:
-            raise ValueError("mol_of must hold one molecule index per atom")
+    mol = None if mol_of is None else _mol_of(mol_of, N)
     cen = np.flatnonzero(np.isin(typ, trip[:, 1])).astype(np.int32)
     cand = np.flatnonzero(np.isin(typ, np.concatenate([trip[:, 0], trip[:, 2]]))).astype(np.int32)
     cen_cls, cand_cls = np.ascontiguousarray(typ[cen]), np.ascontiguousarray(typ[cand])
-    bx = _f64(box).reshape(F, 3)
-    xp, x_dev, keep = as_input(xyz, ctx)
 
     def run(k):
         hist = np.zeros((T, n_bins), dtype=np.uint64)
@@ -844,18 +864,7 @@ def angle_hist(xyz, box, types, triplets, r_cut_sq, cos_edges, mol_of=None, cap=
             ptr(degen, C.c_uint64), ptr(count, C.c_int32)))
         return hist, degen, count
 
-    cap = int(cap)
-    hist, degen, count = run(cap)
-    big = int(count.max()) if count.size else 0
-    if big > cap:
-        if big > ANGLE_MAX_CAP:
-            f, c = np.unravel_index(int(count.argmax()), count.shape)
-            raise ValueError("angle_hist: frame %d, centre atom %d has %d neighbours; at most %d are supported "
-                             "(smaller cutoffs?)" % (f, int(cen[c]), big, ANGLE_MAX_CAP))
-        hist, degen, again = run(big)  # (the first call's histograms are discarded)
-        if not np.array_equal(again, count):
-            raise RuntimeError("angle_hist: the re-run found other row sizes than the first sweep")
-    return hist, degen, count, cen
+    return (*_with_larger_cap(run, lambda out: out[2], cap, ANGLE_MAX_CAP, cen, "angle_hist", "smaller cutoffs?"), cen)
 
 
 BOND_CAP = 64  # first-try neighbours per (frame, centre) row of bond_order; a batch with a larger row is run again
@@ -878,23 +887,16 @@ def bond_order(xyz, box, types, centre_type, neighbour_types, r_cut_sq, degrees=
     NaN where a row is short or degenerate. A batch with a row of more than `cap` neighbours is run once more with a cap
     of the largest count; more than 512 is a ValueError.
     """
-    ctx = ctx or default_context()
-    F, _, N = _shape3(xyz, "xyz")
+    ctx, F, N, bx, xp, x_dev, keep = _xyz_box(xyz, box, ctx)
     typ = _i32(types).ravel()
     if len(typ) != N:
         raise ValueError("types must hold one type per atom")
     deg = _i32(list(degrees)).ravel()
     D = len(deg)
-    mol = None
-    if mol_of is not None:
-        mol = _i32(mol_of).ravel()
-        if len(mol) != N:
-            raise ValueError("mol_of must hold one molecule index per atom")
+    mol = None if mol_of is None else _mol_of(mol_of, N)
     cen = np.flatnonzero(typ == int(centre_type)).astype(np.int32)
     cand = np.flatnonzero(np.isin(typ, _i32(list(neighbour_types)).ravel())).astype(np.int32)
     C_ = len(cen)
-    bx = _f64(box).reshape(F, 3)
-    xp, x_dev, keep = as_input(xyz, ctx)
 
     def run(k):
         q = np.full((F, C_, D), np.nan)
@@ -910,19 +912,7 @@ def bond_order(xyz, box, types, centre_type, neighbour_types, r_cut_sq, degrees=
             ptr(count, C.c_int32)))
         return {"q": q, "qbar": qbar, "tet": tet, "flags": flags, "count": count, "centres": cen}
 
-    cap = int(cap)
-    out = run(cap)
-    count = out["count"]
-    big = int(count.max()) if count.size else 0
-    if big > cap:
-        if big > BOND_MAX_CAP:
-            f, c = np.unravel_index(int(count.argmax()), count.shape)
-            raise ValueError("bond_order: frame %d, centre atom %d has %d neighbours; at most %d are supported "
-                             "(a smaller cutoff?)" % (f, int(cen[c]), big, BOND_MAX_CAP))
-        out = run(big)  # (the first call's values are discarded)
-        if not np.array_equal(out["count"], count):
-            raise RuntimeError("bond_order: the re-run found other row sizes than the first sweep")
-    return out
+    return _with_larger_cap(run, lambda out: out["count"], cap, BOND_MAX_CAP, cen, "bond_order", "a smaller cutoff?")
 
 
 SDF_MAX_SPECIES = 8        # observed species per call of sdf_hist (include/mdhip.h: mdhip_sdf_hist)
@@ -944,14 +934,11 @@ def body_frames(xyz, box, origin, x_atom, xy_atom, ctx=None):
     tensor), box [F,3], per molecule its origin, x-axis and xy-plane atom [M] each -> (e float64 [F,M,3,3] with rows
     e1, e2, e3, valid bool [F,M], n_degenerate_rows int). The rows of e where valid is False mean nothing.
     """
-    ctx = ctx or default_context()
-    F, _, N = _shape3(xyz, "xyz")
+    ctx, F, N, bx, xp, x_dev, keep = _xyz_box(xyz, box, ctx)
     org, xa, xya = (_i32(v).ravel() for v in (origin, x_atom, xy_atom))
     M = len(org)
     if len(xa) != M or len(xya) != M:
         raise ValueError("origin, x_atom and xy_atom must hold one atom per molecule")
-    bx = _f64(box).reshape(F, 3)
-    xp, x_dev, keep = as_input(xyz, ctx)
     rows = np.zeros((F, M, 10), dtype=np.float64)
     bad_rows = C.c_uint64(0)
     ctx.check(ctx.lib.mdhip_body_frames(ctx.h, F, N, xp, x_dev, ptr(bx), M, ptr(org, C.c_int32), ptr(xa, C.c_int32),
@@ -967,8 +954,7 @@ def sdf_hist(xyz, box, origin, x_atom, xy_atom, cand, cand_class, n_species, r_c
     [S,G,G,G] in the body frame (e1, e2, e3) with G = sdf_grid(r_cut, bin_size), n_degenerate uint64 [S]: the hits of
     rows without a frame, n_hits int32 [F,M], n_degenerate_rows int). No capacity limit.
     """
-    ctx = ctx or default_context()
-    F, _, N = _shape3(xyz, "xyz")
+    ctx, F, N, bx, xp, x_dev, keep = _xyz_box(xyz, box, ctx)
     org, xa, xya = (_i32(v).ravel() for v in (origin, x_atom, xy_atom))
     M = len(org)
     if len(xa) != M or len(xya) != M:
@@ -978,13 +964,7 @@ def sdf_hist(xyz, box, origin, x_atom, xy_atom, cand, cand_class, n_species, r_c
         raise ValueError("cand_class must hold one species per candidate")
     S = int(n_species)
     G = sdf_grid(r_cut, bin_size)
-    mol = None
-    if mol_of is not None:
-        mol = _i32(mol_of).ravel()
-        if len(mol) != N:
-            raise ValueError("mol_of must hold one molecule index per atom")
-    bx = _f64(box).reshape(F, 3)
-    xp, x_dev, keep = as_input(xyz, ctx)
+    mol = None if mol_of is None else _mol_of(mol_of, N)
     ok = 1 <= S <= SDF_MAX_SPECIES and 1 <= G <= SDF_MAX_GRID and S * G ** 3 <= SDF_MAX_CELLS
     hist = result_array((S, G, G, G), np.uint64, device=ctx.device, zero=True) if ok else np.zeros(1, dtype=np.uint64)
     degen = np.zeros(max(S, 1), dtype=np.uint64)
@@ -1009,8 +989,7 @@ def contact_components(xyz, box, atoms_a, class_a, atoms_b, class_b, rsq_cut, no
     -> (label int32 [F,n_nodes], n_components int32 [F], n_contacts uint64 [F]). label[f, m] is the smallest node of
     the component of m in frame f. No capacity: nothing in this call can overflow.
     """
-    ctx = ctx or default_context()
-    F, _, N = _shape3(xyz, "xyz")
+    ctx, F, N, bx, xp, x_dev, keep = _xyz_box(xyz, box, ctx)
     aa, ca = _i32(atoms_a).ravel(), _i32(class_a).ravel()
     ab, cb = _i32(atoms_b).ravel(), _i32(class_b).ravel()
     if len(aa) != len(ca) or len(ab) != len(cb):
@@ -1022,8 +1001,6 @@ def contact_components(xyz, box, atoms_a, class_a, atoms_b, class_b, rsq_cut, no
     if len(node) != N:
         raise ValueError("node_of must hold one node index per atom")
     n_nodes = int(n_nodes)
-    bx = _f64(box).reshape(F, 3)
-    xp, x_dev, keep = as_input(xyz, ctx)
     label = result_array((F, max(n_nodes, 0)), np.int32)
     n_comp = np.zeros(F, dtype=np.int32)
     n_con = np.zeros(F, dtype=np.uint64)
@@ -1053,12 +1030,7 @@ def _hbond_lists(N, donors, h_off, h_atoms, acceptors, mol_of):
     don, off, hat, acc = (_i32(donors).ravel(), _i32(h_off).ravel(), _i32(h_atoms).ravel(), _i32(acceptors).ravel())
     if len(off) != len(don) + 1:
         raise ValueError("h_off must hold one offset per donor and the end")
-    mol = None
-    if mol_of is not None:
-        mol = _i32(mol_of).ravel()
-        if len(mol) != N:
-            raise ValueError("mol_of must hold one molecule index per atom")
-    return don, off, hat, acc, mol
+    return don, off, hat, acc, None if mol_of is None else _mol_of(mol_of, N)
 
 
 def hbond_counts(xyz, box, donors, don_class, h_off, h_atoms, acceptors, acc_class, r_da_sq, cos_cut, r_ha_sq=0.0,
@@ -1073,8 +1045,7 @@ def hbond_counts(xyz, box, donors, don_class, h_off, h_atoms, acceptors, acc_cla
     every (hydrogen, acceptor) that passes every test but the angle test. No capacity: nothing in this call can
     overflow.
     """
-    ctx = ctx or default_context()
-    F, _, N = _shape3(xyz, "xyz")
+    ctx, F, N, bx, xp, x_dev, keep = _xyz_box(xyz, box, ctx)
     don, off, hat, acc, mol = _hbond_lists(N, donors, h_off, h_atoms, acceptors, mol_of)
     dcl, acl = _i32(don_class).ravel(), _i32(acc_class).ravel()
     if len(dcl) != len(don) or len(acl) != len(acc):
@@ -1083,8 +1054,6 @@ def hbond_counts(xyz, box, donors, don_class, h_off, h_atoms, acceptors, acc_cla
     n_ac = int(n_ac) if n_ac is not None else (int(acl.max()) + 1 if len(acl) else 1)
     edges = np.zeros(0) if cos_edges is None else _f64(cos_edges).ravel()
     n_bins = len(edges)
-    bx = _f64(box).reshape(F, 3)
-    xp, x_dev, keep = as_input(xyz, ctx)
     n_bonds = np.zeros((F, max(n_dc, 0), max(n_ac, 0)), dtype=np.int32)
     n_donated = np.zeros(len(don), dtype=np.uint64)
     n_accepted = np.zeros(len(acc), dtype=np.uint64)
@@ -1108,14 +1077,11 @@ def hbond_lifetime(xyz, box, donors, h_off, h_atoms, acceptors, r_da_sq, cos_cut
     acceptor) pair, c_int[k] = sum h(t) h(t+k) and c_cont[k] = the number of (pair, t) with h(t) = ... = h(t+k) = 1.
     table_slots > 0 forces the slot count of the first sweep's pair table (0: the library sizes it).
     """
-    ctx = ctx or default_context()
-    F, _, N = _shape3(xyz, "xyz")
+    ctx, F, N, bx, xp, x_dev, keep = _xyz_box(xyz, box, ctx)
     don, off, hat, acc, mol = _hbond_lists(N, donors, h_off, h_atoms, acceptors, mol_of)
     max_lag = max(F - 1, 0) if max_lag is None else int(max_lag)
     if max_lag < 0:
         raise ValueError("max_lag must not be negative")
-    bx = _f64(box).reshape(F, 3)
-    xp, x_dev, keep = as_input(xyz, ctx)
     c_int = np.zeros(max_lag + 1, dtype=np.uint64)
     c_cont = np.zeros(max_lag + 1, dtype=np.uint64)
     n_pairs, n_rec = C.c_uint64(0), C.c_uint64(0)

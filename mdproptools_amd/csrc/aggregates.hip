@@ -8,7 +8,8 @@
 // connected component. Contraction is off in this file.
 //
 //  1. agg_init_kernel: parent[f][m] = m, one lane per (frame, node).
-//  2. agg_gather_kernel: the planes [F][3][n_b] of the B atoms, so that the sweep reads coalesced planes.
+//  2. shell::gather_kernel (shell_gather.h): the planes [F][3][n_b] of the B atoms, so that the sweep reads coalesced
+//     planes.
 //  3. agg_union_kernel: the sweep of shell_search.h, A as centres against the B planes, with the largest table entry.
 //     A hit (rare) is tested again against the cutoff of its class pair, skipped when both atoms are of one node,
 //     counted (one 64-bit add to the frame's counter) and its two nodes united in the frame's parent row (agg_unite).
@@ -22,7 +23,7 @@
 
 #pragma clang fp contract(off)
 
-#include "shell_search.h"
+#include "shell_gather.h"
 
 namespace {
 
@@ -33,20 +34,6 @@ __global__ __launch_bounds__(256) void agg_init_kernel(int *__restrict__ parent,
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (long long)gridDim.x * blockDim.x)
         parent[i] = (int)(i % n_nodes);
-}
-
-__global__ __launch_bounds__(256) void agg_gather_kernel(const double *__restrict__ xyz, long long n,
-                                                         const int *__restrict__ cand, long long n_cand,
-                                                         long long total, double *__restrict__ planes)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const long long w = i % n_cand, f = i / n_cand;
-        const long long a = cand[w];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            planes[((size_t)f * 3 + k) * (size_t)n_cand + w] = xyz[((size_t)f * 3 + k) * (size_t)n + a];
-    }
 }
 
 // parent[x] as the memory side holds it (a relaxed agent-scope load goes past this CU's L1). A plain load would do:
@@ -107,8 +94,8 @@ __global__ __launch_bounds__(shell::THREADS) void agg_union_kernel(
         const int na = t.node_a[r.c], nb = t.node_b[b];
         if (na == nb) return;
         const double cut = t.rsq_cut[t.class_a[r.c] * t.n_cb + t.class_b[b]];
-        const double *q = planes + (size_t)r.f * 3 * (size_t)n_b;
-        if (!(shell::rsq(r.cx, r.cy, r.cz, q[b], q[n_b + b], q[2 * n_b + b], r.Lx, r.Ly, r.Lz) < cut)) return;
+        const shell::Xyz p = shell::cand_xyz(planes, n_b, r.f, b);
+        if (!(shell::rsq(r.cx, r.cy, r.cz, p.x, p.y, p.z, r.Lx, r.Ly, r.Lz) < cut)) return;
         atomicAdd(&contacts[r.f], 1ull);
         agg_unite(parent + (size_t)r.f * (size_t)n_nodes, na, nb);
     });
@@ -211,24 +198,16 @@ int mdhip_contact_components(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, 
     if (pairs) {
         if ((rc = shell::stage(ctx, "A atom", n_frames, n_atoms, xyz, xyz_on_device, box, n_a, atoms_a, in)))
             return rc;
-        const size_t n_int = 2 * (size_t)n_a + 3 * (size_t)n_b;
-        std::vector<int> h_int(n_int);
-        int *h = h_int.data();
-        std::copy(class_a, class_a + n_a, h);
-        for (int32_t k = 0; k < n_a; ++k) h[(size_t)n_a + k] = node_of[atoms_a[k]];
-        h += 2 * (size_t)n_a;
-        std::copy(atoms_b, atoms_b + n_b, h);
-        std::copy(class_b, class_b + n_b, h + n_b);
-        for (int32_t k = 0; k < n_b; ++k) h[2 * (size_t)n_b + k] = node_of[atoms_b[k]];
-        MD_WS(d_int, int, WS_TYPE_J, n_int * 4);
-        if ((rc = mdhip_h2d_small(ctx, d_int, h_int.data(), n_int * 4))) return rc;
+        shell::IntTable ints;
+        ints.add(class_a, n_a, &t.class_a);
+        ints.add_generated(n_a, [&](size_t k) { return node_of[atoms_a[k]]; }, &t.node_a);
+        ints.add(atoms_b, n_b, &d_atoms_b);
+        ints.add(class_b, n_b, &t.class_b);
+        ints.add_generated(n_b, [&](size_t k) { return node_of[atoms_b[k]]; }, &t.node_b);
+        if ((rc = shell::upload_ints(ctx, ints, WS_TYPE_J))) return rc;
         MD_WS(d_cut, double, WS_TABLES, (size_t)n_ca * n_cb * 8);
         if ((rc = mdhip_h2d_small(ctx, d_cut, rsq_cut, (size_t)n_ca * n_cb * 8))) return rc;
-        MD_WS(d_pl, double, WS_AUX1, (size_t)n_frames * 3 * (size_t)n_b * 8);
-        d_planes = d_pl;
-        t.class_a = d_int, t.node_a = d_int + n_a;
-        d_atoms_b = d_int + 2 * (size_t)n_a;
-        t.class_b = d_atoms_b + n_b, t.node_b = d_atoms_b + 2 * (size_t)n_b;
+        if ((rc = shell::planes_room(ctx, n_frames, n_b, d_planes))) return rc;
         t.rsq_cut = d_cut, t.n_cb = (int)n_cb;
     }
 
@@ -240,11 +219,7 @@ int mdhip_contact_components(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, 
     MD_HIP(hipGetLastError());
     KernelTimer search(ctx, 2, true);  // the gather and the union sweep: the call's aux time
     if (pairs) {
-        const size_t total = (size_t)n_frames * (size_t)n_b;
-        const unsigned ggrid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)ctx->cu_count * 32);
-        hipLaunchKernelGGL(agg_gather_kernel, dim3(ggrid), dim3(256), 0, ctx->stream, in.xyz, (long long)n_atoms,
-                           d_atoms_b, (long long)n_b, (long long)total, d_planes);
-        MD_HIP(hipGetLastError());
+        if ((rc = shell::gather(ctx, in.xyz, n_frames, n_atoms, d_atoms_b, n_b, d_planes))) return rc;
         const shell::Grid g = shell::sweep_grid(ctx, n_frames, n_a, n_b);
         hipLaunchKernelGGL(agg_union_kernel, dim3(g.grid), dim3(shell::THREADS), 0, ctx->stream, in.xyz,
                            (long long)n_atoms, d_planes, (long long)n_b, in.box, in.centres, (int)n_a, t, rc2, g,

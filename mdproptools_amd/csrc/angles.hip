@@ -14,8 +14,8 @@
 //     once, an asymmetric one every ordered (j, k), j != k, j in role A and k in role B.
 // Contraction is off in this file.
 //
-//  1. ang_gather_kernel: one lane per (frame, candidate): the candidate planes [F][3][n_cand], so that the sweep
-//     reads coalesced planes of only the atoms that can be a neighbour.
+//  1. shell::gather_kernel (shell_gather.h): one lane per (frame, candidate): the candidate planes [F][3][n_cand], so
+//     that the sweep reads coalesced planes of only the atoms that can be a neighbour.
 //  2. ang_search_kernel: the sweep of shell_search.h with the largest cutoff of all. A hit (rare) that is not the
 //     centre itself, not of its molecule under exclusion, and within the largest cutoff of the centre's class is
 //     appended to the row (frame, centre) (shell::append). Which of those tests a call needs at all is decided on
@@ -32,7 +32,7 @@
 
 #pragma clang fp contract(off)
 
-#include "shell_search.h"
+#include "shell_gather.h"
 
 namespace {
 
@@ -49,20 +49,6 @@ struct AngTriplets {
     double ra2[ANG_MAX_TRIPLETS], rb2[ANG_MAX_TRIPLETS];
 };
 
-__global__ __launch_bounds__(256) void ang_gather_kernel(const double *__restrict__ xyz, long long n,
-                                                         const int *__restrict__ cand, long long n_cand,
-                                                         long long total, double *__restrict__ planes)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const long long w = i % n_cand, f = i / n_cand;
-        const long long a = cand[w];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            planes[((size_t)f * 3 + k) * (size_t)n_cand + w] = xyz[((size_t)f * 3 + k) * (size_t)n + a];
-    }
-}
-
 // What the search tests at a hit beyond the sweep's own cutoff, decided per call on the host (wave-uniform): most calls
 // (one centre type, no atom both centre and candidate, no exclusion) test nothing more and a hit is an append.
 constexpr int ANG_TEST_ATOM = 1;    // the candidate's atom is looked up: it may be the centre, or of its molecule
@@ -77,15 +63,11 @@ __global__ __launch_bounds__(shell::THREADS) void ang_search_kernel(
     shell::Grid g, int *__restrict__ idx, int *__restrict__ count)
 {
     shell::sweep(xyz, n, centres, n_c, planes, 3, n_cand, box, rc2, g, [=](const shell::Row &r, size_t row, long long a) {
-        if (tests & ANG_TEST_ATOM) {
-            const int aj = cand[a];
-            if (aj == r.ci) return;
-            if (mol_of && mol_of[aj] == mol_of[r.ci]) return;
+        if ((tests & ANG_TEST_ATOM) && shell::excluded(cand[a], r.ci, mol_of)) return;
+        if (tests & ANG_TEST_RADIUS) {
+            const shell::Xyz p = shell::cand_xyz(planes, n_cand, r.f, a);
+            if (!(shell::rsq(r.cx, r.cy, r.cz, p.x, p.y, p.z, r.Lx, r.Ly, r.Lz) < cen_rmax2[r.c])) return;
         }
-        const double *q = planes + (size_t)r.f * 3 * (size_t)n_cand;
-        if ((tests & ANG_TEST_RADIUS) &&
-            !(shell::rsq(r.cx, r.cy, r.cz, q[a], q[n_cand + a], q[2 * n_cand + a], r.Lx, r.Ly, r.Lz) < cen_rmax2[r.c]))
-            return;
         shell::append(count, idx, row, cap, (int)a);
     });
 }
@@ -104,7 +86,7 @@ __device__ __forceinline__ void ang_stage(const AngTile &s, int lane, int m, con
 {
     if (lane < m) {
         const long long a = r[lane];
-        const double x = q[a], y = q[n_cand + a], z = q[2 * n_cand + a];
+        const double x = q[a], y = q[n_cand + a], z = q[2 * n_cand + a];  // (q: the frame's planes, found once per row)
         const double dx = shell::wrap_signed(x - c.cx, c.Lx), dy = shell::wrap_signed(y - c.cy, c.Ly),
                      dz = shell::wrap_signed(z - c.cz, c.Lz);
         const double rsq = shell::rsq(c.cx, c.cy, c.cz, x, y, z, c.Lx, c.Ly, c.Lz);
@@ -280,7 +262,6 @@ int mdhip_angle_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const do
     // the tables: doubles E [n_bins] | largest squared cutoff of every centre's class [n_centres]; ints the centres'
     // classes | the candidates' atoms | their classes | mol_of [n_atoms] (under exclusion)
     const size_t n_dbl = (size_t)n_bins + (size_t)n_centres;
-    const size_t n_int = (size_t)n_centres + 2 * (size_t)n_cand + (mol_of ? (size_t)n_atoms : 0);
     std::vector<double> h_dbl(n_dbl);
     std::copy(cos_edges, cos_edges + n_bins, h_dbl.begin());
     for (int32_t c = 0; c < n_centres; ++c) {
@@ -292,38 +273,28 @@ int mdhip_angle_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const do
     int tests = mol_of ? ANG_TEST_ATOM : 0;
     for (int32_t c = 0; c < n_centres; ++c)
         if (h_dbl[(size_t)n_bins + c] != rc2) tests |= ANG_TEST_RADIUS;
-    if (!(tests & ANG_TEST_ATOM)) {  // is an atom both a centre and a candidate?
-        std::vector<char> is_cand((size_t)n_atoms, 0);
-        for (int32_t w = 0; w < n_cand; ++w) is_cand[cand[w]] = 1;
-        for (int32_t c = 0; c < n_centres; ++c)
-            if (is_cand[centres[c]]) tests |= ANG_TEST_ATOM;
-    }
+    if (!mol_of && shell::shares_an_atom(n_atoms, centres, n_centres, cand, n_cand)) tests |= ANG_TEST_ATOM;
     MD_WS(d_dbl, double, WS_TABLES, n_dbl * 8);
     if ((rc = mdhip_h2d_small(ctx, d_dbl, h_dbl.data(), n_dbl * 8))) return rc;
-    std::vector<int> h_int(n_int);
-    std::copy(centre_class, centre_class + n_centres, h_int.begin());
-    std::copy(cand, cand + n_cand, h_int.begin() + n_centres);
-    std::copy(cand_class, cand_class + n_cand, h_int.begin() + n_centres + n_cand);
-    if (mol_of) std::copy(mol_of, mol_of + n_atoms, h_int.begin() + n_centres + 2 * (size_t)n_cand);
-    MD_WS(d_int, int, WS_TYPE_J, n_int * 4);
-    if ((rc = mdhip_h2d_small(ctx, d_int, h_int.data(), n_int * 4))) return rc;
-    const int *d_cen_class = d_int, *d_cand = d_int + n_centres, *d_cand_class = d_cand + n_cand;
-    const int *d_mol = mol_of ? d_cand_class + n_cand : nullptr;
+    const int *d_cen_class, *d_cand, *d_cand_class, *d_mol;
+    shell::IntTable ints;
+    ints.add(centre_class, n_centres, &d_cen_class);
+    ints.add(cand, n_cand, &d_cand);
+    ints.add(cand_class, n_cand, &d_cand_class);
+    ints.add_optional(mol_of, n_atoms, &d_mol);
+    if ((rc = shell::upload_ints(ctx, ints, WS_TYPE_J))) return rc;
     const double *d_edges = d_dbl, *d_rmax2 = d_dbl + n_bins;
 
     const size_t n_cells = (size_t)n_triplets * (size_t)n_bins + (size_t)n_triplets;
-    MD_WS(d_planes, double, WS_AUX1, (size_t)n_frames * 3 * (size_t)n_cand * 8);
+    double *d_planes;
+    if ((rc = shell::planes_room(ctx, n_frames, n_cand, d_planes))) return rc;
     MD_WS(d_hist, unsigned long long, WS_HIST, n_cells * 8);
     MD_HIP(hipMemsetAsync(d_hist, 0, n_cells * 8, ctx->stream));
 
     KernelTimer timer(ctx, 3);
     KernelTimer search(ctx, 2, true);  // the gather and the search: the call's aux time; the rest is the angle pass
     ctx->last_kernel = "ang_search_kernel";
-    const size_t total = (size_t)n_frames * (size_t)n_cand;
-    const unsigned ggrid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)ctx->cu_count * 32);
-    hipLaunchKernelGGL(ang_gather_kernel, dim3(ggrid), dim3(256), 0, ctx->stream, in.xyz, (long long)n_atoms, d_cand,
-                       (long long)n_cand, (long long)total, d_planes);
-    MD_HIP(hipGetLastError());
+    if ((rc = shell::gather(ctx, in.xyz, n_frames, n_atoms, d_cand, n_cand, d_planes))) return rc;
     const shell::Grid g = shell::sweep_grid(ctx, n_frames, n_centres, n_cand);
     hipLaunchKernelGGL(ang_search_kernel, dim3(g.grid), dim3(shell::THREADS), 0, ctx->stream, in.xyz,
                        (long long)n_atoms, d_planes, (long long)n_cand, in.box, in.centres, (int)n_centres, d_cand, d_mol,

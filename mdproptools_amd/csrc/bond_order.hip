@@ -15,7 +15,7 @@
 //     by (rsq, atom index), taken in ascending atom index.
 // Contraction is off in this file.
 //
-//  1. bo_gather_kernel: one lane per (frame, candidate): the candidate planes [F][3][n_cand].
+//  1. shell::gather_kernel (shell_gather.h): one lane per (frame, candidate): the candidate planes [F][3][n_cand].
 //  2. bo_search_kernel: the sweep of shell_search.h; a hit that is not the centre itself and not of its molecule under
 //     exclusion is appended to the row (frame, centre) (shell::append).
 //  3. bo_row_kernel: one wave per row. The row is staged in LDS (d, rsq, atom, candidate position), ranked by
@@ -35,7 +35,7 @@
 
 #pragma clang fp contract(off)
 
-#include "shell_search.h"
+#include "shell_gather.h"
 
 namespace {
 
@@ -60,20 +60,6 @@ struct BoDegrees {
     int l[BO_MAX_DEG], off[BO_MAX_DEG];
 };
 
-__global__ __launch_bounds__(256) void bo_gather_kernel(const double *__restrict__ xyz, long long n,
-                                                        const int *__restrict__ cand, long long n_cand,
-                                                        long long total, double *__restrict__ planes)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const long long w = i % n_cand, f = i / n_cand;
-        const long long a = cand[w];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            planes[((size_t)f * 3 + k) * (size_t)n_cand + w] = xyz[((size_t)f * 3 + k) * (size_t)n + a];
-    }
-}
-
 // A candidate within the cutoff of a row's centre is appended unless it is the centre or of the centre's molecule
 // (mol_of != nullptr). test_atom (wave-uniform, decided on the host): some atom is both centre and candidate, or there
 // is an exclusion; most calls of distinct types test nothing more and a hit is an append.
@@ -84,11 +70,7 @@ __global__ __launch_bounds__(shell::THREADS) void bo_search_kernel(
     int *__restrict__ count)
 {
     shell::sweep(xyz, n, centres, n_c, planes, 3, n_cand, box, rc2, g, [=](const shell::Row &r, size_t row, long long a) {
-        if (test_atom) {
-            const int aj = cand[a];
-            if (aj == r.ci) return;
-            if (mol_of && mol_of[aj] == mol_of[r.ci]) return;
-        }
+        if (test_atom && shell::excluded(cand[a], r.ci, mol_of)) return;
         shell::append(count, idx, row, cap, (int)a);
     });
 }
@@ -169,11 +151,10 @@ __global__ __launch_bounds__(64) void bo_row_kernel(const double *__restrict__ x
         const bool q_short = k == 0 || k < k_nearest, t_short = k < 4;
         if (!over && k > 0) {
             const shell::Row c = shell::row_of(xyz, n, box, centres, row / n_c, (int)(row % n_c));
-            const double *pl = planes + (size_t)c.f * 3 * (size_t)n_cand;
             const int *r = idx + (size_t)row * (size_t)cap;
             for (int i = lane; i < k; i += 64) {
                 const long long a = r[i];
-                const double x = pl[a], y = pl[n_cand + a], z = pl[2 * n_cand + a];
+                const auto [x, y, z] = shell::cand_xyz(planes, n_cand, c.f, a);
                 r_dx[i] = shell::wrap_signed(x - c.cx, c.Lx);
                 r_dy[i] = shell::wrap_signed(y - c.cy, c.Ly);
                 r_dz[i] = shell::wrap_signed(z - c.cz, c.Lz);
@@ -420,23 +401,16 @@ int mdhip_bond_order(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const do
     bo_tables(dg, h_tab);
     MD_WS(d_tab, double, WS_TABLES, sizeof h_tab);
     if ((rc = mdhip_h2d_small(ctx, d_tab, h_tab, sizeof h_tab))) return rc;
-    const size_t n_int = (size_t)n_cand + (mol_of ? (size_t)n_atoms : 0);
-    std::vector<int> h_int(n_int);
-    std::copy(cand, cand + n_cand, h_int.begin());
-    if (mol_of) std::copy(mol_of, mol_of + n_atoms, h_int.begin() + n_cand);
-    MD_WS(d_int, int, WS_TYPE_J, n_int * 4);
-    if ((rc = mdhip_h2d_small(ctx, d_int, h_int.data(), n_int * 4))) return rc;
-    const int *d_cand = d_int, *d_mol = mol_of ? d_int + n_cand : nullptr;
-    int test_atom = mol_of ? 1 : 0;
-    if (!test_atom) {  // is an atom both a centre and a candidate?
-        std::vector<char> is_cand((size_t)n_atoms, 0);
-        for (int32_t w = 0; w < n_cand; ++w) is_cand[cand[w]] = 1;
-        for (int32_t c = 0; c < n_centres; ++c)
-            if (is_cand[centres[c]]) test_atom = 1;
-    }
+    const int *d_cand, *d_mol;
+    shell::IntTable ints;
+    ints.add(cand, n_cand, &d_cand);
+    ints.add_optional(mol_of, n_atoms, &d_mol);
+    if ((rc = shell::upload_ints(ctx, ints, WS_TYPE_J))) return rc;
+    const int test_atom = mol_of || shell::shares_an_atom(n_atoms, centres, n_centres, cand, n_cand);
 
     const size_t nq = rs.n_rows * (size_t)std::max(n_degrees, 1);
-    MD_WS(d_planes, double, WS_AUX1, (size_t)n_frames * 3 * (size_t)n_cand * 8);
+    double *d_planes;
+    if ((rc = shell::planes_room(ctx, n_frames, n_cand, d_planes))) return rc;
     MD_WS(d_q, double, WS_HIST, nq * 8);
     MD_WS(d_qbar, double, WS_OUT2, averaged ? nq * 8 : 8);
     MD_WS(d_tet, double, WS_OUT3, rs.n_rows * 16);
@@ -447,11 +421,7 @@ int mdhip_bond_order(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const do
     KernelTimer timer(ctx, averaged ? 4 : 3);
     KernelTimer search(ctx, 2, true);  // the gather and the search: the call's aux time; the rest is the row passes
     ctx->last_kernel = "bo_search_kernel";
-    const size_t total = (size_t)n_frames * (size_t)n_cand;
-    const unsigned ggrid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)ctx->cu_count * 32);
-    hipLaunchKernelGGL(bo_gather_kernel, dim3(ggrid), dim3(256), 0, ctx->stream, in.xyz, (long long)n_atoms, d_cand,
-                       (long long)n_cand, (long long)total, d_planes);
-    MD_HIP(hipGetLastError());
+    if ((rc = shell::gather(ctx, in.xyz, n_frames, n_atoms, d_cand, n_cand, d_planes))) return rc;
     const shell::Grid g = shell::sweep_grid(ctx, n_frames, n_centres, n_cand);
     hipLaunchKernelGGL(bo_search_kernel, dim3(g.grid), dim3(shell::THREADS), 0, ctx->stream, in.xyz,
                        (long long)n_atoms, d_planes, (long long)n_cand, in.box, in.centres, (int)n_centres, d_cand, d_mol,

@@ -13,8 +13,8 @@
 //   bonded when cos <= cos_cut (the angle D-H...A is at least angle_cut).
 // Contraction is off in this file.
 //
-//  1. hb_gather_kernel: one lane per (frame, acceptor): the acceptor planes [F][3][n_acc], so that the sweep reads
-//     coalesced planes of only the atoms that can accept.
+//  1. shell::gather_kernel (shell_gather.h): one lane per (frame, acceptor): the acceptor planes [F][3][n_acc], so that
+//     the sweep reads coalesced planes of only the atoms that can accept.
 //  2. hb_search_kernel<LIFE>: the sweep of shell_search.h, the donors as centres against the acceptor planes with
 //     r_da_sq. A hit (rare) walks the donor's hydrogens through the tests above (hb_walk).
 //       counts (LIFE = false): every (h, a) that reaches the angle test is binned by its cosine into the block's LDS
@@ -41,7 +41,7 @@
 
 #pragma clang fp contract(off)
 
-#include "shell_search.h"
+#include "shell_gather.h"
 
 #include "presence_table.h"
 
@@ -51,20 +51,6 @@ constexpr int HB_MAX_CELLS = 4096;  // n_dc * n_ac * n_bins: the counts sweep ke
                                     // (n_bins <= n_cells: 32 KB) in LDS
 constexpr int HB_MAX_CLASSES = 64;  // n_dc * n_ac
 constexpr int HB_RUNS_LDS = 4096;   // run lengths below this are counted in LDS (32 KB)
-
-__global__ __launch_bounds__(256) void hb_gather_kernel(const double *__restrict__ xyz, long long n,
-                                                        const int *__restrict__ acc, long long n_acc,
-                                                        long long total, double *__restrict__ planes)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const long long w = i % n_acc, f = i / n_acc;
-        const long long a = acc[w];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            planes[((size_t)f * 3 + k) * (size_t)n_acc + w] = xyz[((size_t)f * 3 + k) * (size_t)n + a];
-    }
-}
 
 // what both searches read (device pointers; by value: wave-uniform loads)
 struct HbGeom {
@@ -81,11 +67,8 @@ template <class Degenerate, class Angle, class Bond>
 __device__ __forceinline__ void hb_walk(const HbGeom &g, const shell::Row &r, long long a, Degenerate degenerate,
                                         Angle angle, Bond bond)
 {
-    const int aj = g.acc[a];
-    if (aj == r.ci) return;
-    if (g.mol_of && g.mol_of[aj] == g.mol_of[r.ci]) return;
-    const double *q = g.planes + (size_t)r.f * 3 * (size_t)g.n_acc;
-    const double ax = q[a], ay = q[g.n_acc + a], az = q[2 * g.n_acc + a];
+    if (shell::excluded(g.acc[a], r.ci, g.mol_of)) return;
+    const auto [ax, ay, az] = shell::cand_xyz(g.planes, g.n_acc, r.f, a);
     for (int k = g.h_off[r.c]; k < g.h_off[r.c + 1]; ++k) {
         const int hi = g.h_atoms[k];
         const double hx = r.px[hi], hy = r.py[hi], hz = r.pz[hi];
@@ -231,6 +214,7 @@ __global__ __launch_bounds__(64) void hb_runs_kernel(presence::Table tb, unsigne
 
 struct HbInputs : shell::Inputs {
     HbGeom g;
+    double *planes = nullptr;  // (g.planes, to write)
     shell::Grid grid;
     int n_h = 0;
 };
@@ -259,40 +243,21 @@ int hb_stage(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xy
     if ((rc = shell::check_indices(ctx, "acceptor", n_acc, acceptors, 1, n_atoms))) return rc;
 
     // ints: the donors' classes | h_off | h_atoms | the acceptors' atoms | their classes | mol_of (under exclusion)
-    const size_t n_int = 2 * (size_t)n_don + 1 + (size_t)n_h + 2 * (size_t)n_acc + (mol_of ? (size_t)n_atoms : 0);
-    std::vector<int> h_int(n_int);
-    auto at = h_int.begin();
-    at = std::copy(don_class, don_class + n_don, at);
-    at = std::copy(h_off, h_off + n_don + 1, at);
-    at = std::copy(h_atoms, h_atoms + n_h, at);
-    at = std::copy(acceptors, acceptors + n_acc, at);
-    at = std::copy(acc_class, acc_class + n_acc, at);
-    if (mol_of) std::copy(mol_of, mol_of + n_atoms, at);
-    MD_WS(d_int, int, WS_TYPE_J, n_int * 4);
-    if ((rc = mdhip_h2d_small(ctx, d_int, h_int.data(), n_int * 4))) return rc;
-    MD_WS(d_planes, double, WS_AUX1, (size_t)n_frames * 3 * (size_t)n_acc * 8);
-    in.g.planes = d_planes;
+    shell::IntTable ints;
+    ints.add(don_class, n_don, &in.g.don_class);
+    ints.add(h_off, (size_t)n_don + 1, &in.g.h_off);
+    ints.add(h_atoms, n_h, &in.g.h_atoms);
+    ints.add(acceptors, n_acc, &in.g.acc);
+    ints.add(acc_class, n_acc, &in.g.acc_class);
+    ints.add_optional(mol_of, n_atoms, &in.g.mol_of);
+    if ((rc = shell::upload_ints(ctx, ints, WS_TYPE_J))) return rc;
+    if ((rc = shell::planes_room(ctx, n_frames, n_acc, in.planes))) return rc;
+    in.g.planes = in.planes;
     in.g.n_acc = n_acc;
-    in.g.don_class = d_int;
-    in.g.h_off = in.g.don_class + n_don;
-    in.g.h_atoms = in.g.h_off + n_don + 1;
-    in.g.acc = in.g.h_atoms + n_h;
-    in.g.acc_class = in.g.acc + n_acc;
-    in.g.mol_of = mol_of ? in.g.acc_class + n_acc : nullptr;
     in.g.r_ha_sq = r_ha_sq;
     in.g.cos_cut = cos_cut;
     in.grid = shell::sweep_grid(ctx, n_frames, n_don, n_acc);
     in.n_h = n_h;
-    return MDHIP_OK;
-}
-
-int hb_gather(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const HbInputs &in)
-{
-    const size_t total = (size_t)n_frames * (size_t)in.g.n_acc;
-    const unsigned ggrid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)ctx->cu_count * 32);
-    hipLaunchKernelGGL(hb_gather_kernel, dim3(ggrid), dim3(256), 0, ctx->stream, in.xyz, (long long)n_atoms, in.g.acc,
-                       in.g.n_acc, (long long)total, const_cast<double *>(in.g.planes));
-    MD_HIP(hipGetLastError());
     return MDHIP_OK;
 }
 
@@ -343,7 +308,7 @@ int mdhip_hbond_counts(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const 
 
     KernelTimer timer(ctx, 2);
     ctx->last_kernel = "hb_search_kernel<false>";
-    if ((rc = hb_gather(ctx, n_frames, n_atoms, in))) return rc;
+    if ((rc = shell::gather(ctx, in.xyz, n_frames, n_atoms, in.g.acc, n_acc, in.planes))) return rc;
     hipLaunchKernelGGL(hb_search_kernel<false>, dim3(in.grid.grid), dim3(shell::THREADS),
                        (n_cells + (size_t)n_bins) * 8, ctx->stream, in.xyz, (long long)n_atoms, in.box, in.centres, (int)n_don, r_da_sq, in.grid, in.g,
                        HbCounts{(int)n_dc, (int)n_ac, (int)n_bins, d_edges, d_bonds, d_atoms, d_atoms + n_don, d_hist});
@@ -399,7 +364,7 @@ int mdhip_hbond_lifetime(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, cons
 
     KernelTimer timer(ctx);
     ctx->last_kernel = "hb_search_kernel<true>";
-    if ((rc = hb_gather(ctx, n_frames, n_atoms, in))) return rc;
+    if ((rc = shell::gather(ctx, in.xyz, n_frames, n_atoms, in.g.acc, n_acc, in.planes))) return rc;
     // The table: one slot per (hydrogen, acceptor) pair that is ever bonded, at most half full. The first sweep's
     // comes from the acceptors expected within r_da of a donor in ONE frame, times its hydrogens, times 8: far more
     // than pass the angle test, and a pair that is bonded in one frame is mostly the same pair in the next. A call

@@ -13,7 +13,7 @@
 //   (as doubles: NaN -> 0), hist[s][i1][i2][i3] += 1; a hit of a degenerate row counts in n_degenerate[s] instead.
 // Contraction is off in this file.
 //
-//  1. sdf_gather_kernel: one lane per (frame, candidate): the candidate planes [F][3][n_cand].
+//  1. shell::gather_kernel (shell_gather.h): one lane per (frame, candidate): the candidate planes [F][3][n_cand].
 //  2. sdf_frames_kernel: one lane per (frame, molecule): rows of SDF_FRAME doubles, e1 e2 e3 and a valid flag, so that a
 //     tile of 16 molecules is one contiguous run of 160 doubles; counts the degenerate rows.
 //  3. sdf_sweep_kernel: the tile and chunk decomposition of shell::sweep (16 centres per block step with wave-uniform
@@ -37,7 +37,7 @@
 
 #pragma clang fp contract(off)
 
-#include "shell_search.h"
+#include "shell_gather.h"
 
 namespace {
 
@@ -51,20 +51,6 @@ constexpr int SDF_QUEUE = 64 * (SDF_PASS + 1);  // records per wave (see above);
 constexpr int SDF_TEST_ATOM = 1;  // the candidate's atom is looked up: it may be the origin atom, or of its molecule
 
 static_assert(shell::CHUNK <= 4096 && shell::TC <= 16 && shell::TC % SDF_PASS == 0, "a queue record is 4 + 12 bits");
-
-__global__ __launch_bounds__(256) void sdf_gather_kernel(const double *__restrict__ xyz, long long n,
-                                                         const int *__restrict__ cand, long long n_cand,
-                                                         long long total, double *__restrict__ planes)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        const long long w = i % n_cand, f = i / n_cand;
-        const long long a = cand[w];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            planes[((size_t)f * 3 + k) * (size_t)n_cand + w] = xyz[((size_t)f * 3 + k) * (size_t)n + a];
-    }
-}
 
 __global__ __launch_bounds__(256) void sdf_frames_kernel(const double *__restrict__ xyz, long long n,
                                                          const double *__restrict__ box,
@@ -262,11 +248,11 @@ int mdhip_body_frames(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const d
     if ((rc = shell::stage(ctx, "origin", n_frames, n_atoms, xyz, xyz_on_device, box, n_mols, origin, in))) return rc;
     if ((rc = shell::check_indices(ctx, "x-axis atom", n_mols, x_atom, 1, n_atoms))) return rc;
     if ((rc = shell::check_indices(ctx, "xy-plane atom", n_mols, xy_atom, 1, n_atoms))) return rc;
-    std::vector<int> h_int(2 * (size_t)n_mols);
-    std::copy(x_atom, x_atom + n_mols, h_int.begin());
-    std::copy(xy_atom, xy_atom + n_mols, h_int.begin() + n_mols);
-    MD_WS(d_int, int, WS_TYPE_J, h_int.size() * 4);
-    if ((rc = mdhip_h2d_small(ctx, d_int, h_int.data(), h_int.size() * 4))) return rc;
+    const int *d_xa, *d_xya;
+    shell::IntTable ints;
+    ints.add(x_atom, n_mols, &d_xa);
+    ints.add(xy_atom, n_mols, &d_xya);
+    if ((rc = shell::upload_ints(ctx, ints, WS_TYPE_J))) return rc;
     MD_WS(d_frames, double, WS_AUX2, n_rows * SDF_FRAME * 8);
     MD_WS(d_cnt, unsigned long long, WS_MISC, 8);
     MD_HIP(hipMemsetAsync(d_cnt, 0, 8, ctx->stream));
@@ -274,7 +260,7 @@ int mdhip_body_frames(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const d
     ctx->last_kernel = "sdf_frames_kernel";
     const unsigned fgrid = (unsigned)std::min<size_t>((n_rows + 255) / 256, (size_t)ctx->cu_count * 32);
     hipLaunchKernelGGL(sdf_frames_kernel, dim3(fgrid), dim3(256), 0, ctx->stream, in.xyz, (long long)n_atoms, in.box,
-                       in.centres, d_int, d_int + n_mols, (long long)n_mols, (long long)n_rows, d_frames, d_cnt);
+                       in.centres, d_xa, d_xya, (long long)n_mols, (long long)n_rows, d_frames, d_cnt);
     MD_HIP(hipGetLastError());
     timer.stop();
     if ((rc = mdhip_result(cs, frames, d_frames, n_rows * SDF_FRAME * 8, 0))) return rc;
@@ -320,28 +306,18 @@ int mdhip_sdf_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const doub
         MD_REQUIRE(cand_class[w] >= 0 && cand_class[w] < n_species, "candidate %d: class %d out of range", (int)w,
                    (int)cand_class[w]);
 
-    int tests = mol_of ? SDF_TEST_ATOM : 0;
-    if (!tests && n_cand) {  // is an origin atom a candidate?
-        std::vector<char> is_cand((size_t)n_atoms, 0);
-        for (int32_t w = 0; w < n_cand; ++w) is_cand[cand[w]] = 1;
-        for (int32_t c = 0; c < n_centres; ++c)
-            if (is_cand[origin[c]]) tests |= SDF_TEST_ATOM;
-    }
+    // is an origin atom a candidate?
+    const int tests = (mol_of || shell::shares_an_atom(n_atoms, origin, n_centres, cand, n_cand)) ? SDF_TEST_ATOM : 0;
     // the tables: ints the x-axis atoms | the xy-plane atoms | the candidates' atoms | their classes | mol_of [n_atoms]
     // (under exclusion)
-    const size_t n_int = 2 * (size_t)n_centres + 2 * (size_t)n_cand + (mol_of ? (size_t)n_atoms : 0);
-    std::vector<int> h_int(n_int);
-    std::copy(x_atom, x_atom + n_centres, h_int.begin());
-    std::copy(xy_atom, xy_atom + n_centres, h_int.begin() + n_centres);
-    if (n_cand) {
-        std::copy(cand, cand + n_cand, h_int.begin() + 2 * (size_t)n_centres);
-        std::copy(cand_class, cand_class + n_cand, h_int.begin() + 2 * (size_t)n_centres + n_cand);
-    }
-    if (mol_of) std::copy(mol_of, mol_of + n_atoms, h_int.begin() + 2 * (size_t)n_centres + 2 * (size_t)n_cand);
-    MD_WS(d_int, int, WS_TYPE_J, n_int * 4);
-    if ((rc = mdhip_h2d_small(ctx, d_int, h_int.data(), n_int * 4))) return rc;
-    const int *d_xa = d_int, *d_xya = d_xa + n_centres, *d_cand = d_xya + n_centres, *d_cls = d_cand + n_cand;
-    const int *d_mol = mol_of ? d_cls + n_cand : nullptr;
+    const int *d_xa, *d_xya, *d_cand, *d_cls, *d_mol;
+    shell::IntTable ints;
+    ints.add(x_atom, n_centres, &d_xa);
+    ints.add(xy_atom, n_centres, &d_xya);
+    ints.add(cand, n_cand, &d_cand);
+    ints.add(cand_class, n_cand, &d_cls);
+    ints.add_optional(mol_of, n_atoms, &d_mol);
+    if ((rc = shell::upload_ints(ctx, ints, WS_TYPE_J))) return rc;
 
     MD_WS(d_frames, double, WS_AUX2, n_rows * SDF_FRAME * 8);
     MD_WS(d_hits, int, WS_AUX0, n_rows * 4);
@@ -360,12 +336,9 @@ int mdhip_sdf_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const doub
                        d_cnt + SDF_MAX_SPECIES);
     MD_HIP(hipGetLastError());
     if (n_cand) {
-        MD_WS(d_planes, double, WS_AUX1, (size_t)n_frames * 3 * (size_t)n_cand * 8);
-        const size_t total = (size_t)n_frames * (size_t)n_cand;
-        const unsigned ggrid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)ctx->cu_count * 32);
-        hipLaunchKernelGGL(sdf_gather_kernel, dim3(ggrid), dim3(256), 0, ctx->stream, in.xyz, (long long)n_atoms,
-                           d_cand, (long long)n_cand, (long long)total, d_planes);
-        MD_HIP(hipGetLastError());
+        double *d_planes;
+        if ((rc = shell::planes_room(ctx, n_frames, n_cand, d_planes))) return rc;
+        if ((rc = shell::gather(ctx, in.xyz, n_frames, n_atoms, d_cand, n_cand, d_planes))) return rc;
         pre.stop();
         const shell::Grid g = shell::sweep_grid(ctx, n_frames, n_centres, n_cand);
         hipLaunchKernelGGL(sdf_sweep_kernel, dim3(g.grid), dim3(shell::THREADS), 0, ctx->stream, in.xyz,

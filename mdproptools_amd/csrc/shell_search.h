@@ -1,15 +1,26 @@
-// shell_search.h — the per-centre shell search and what its five consumers do around it. For each centre atom of each
+// shell_search.h — the per-centre shell search and what its eight consumers do around it. For each centre atom of each
 // frame, the sweep hands every candidate point within r_cut under the reference's single-wrap rsq (rdf_cn.py:44-57) to
-// a functor. All five run the sweep, append hits to capped rows (append; on the host RowSet) and begin and end their
-// entry points with stage and finish. Beyond that:
-//   clusters.hip        every atom a candidate, rows of molecules; rank_row puts them in order
-//   configurations.hip  every atom a candidate, rows of (molecule, word) records; row_of in its hit, rank_row_keyed
-//   hydration.hip       the water O (check_indices) as candidates; wrap_signed for the cosines; row_of and rank_row
-//                       in its row pass; its counts mode keeps no rows (plain counters)
-//   angles.hip          gathered candidates (check_indices); wrap_signed; row_of in its pair pass; finish with the
-//                       search's aux timer
-//   bond_order.hip      gathered candidates (check_indices); row_of, wrap_signed and rsq again in its row pass, which
-//                       ranks a row by (rsq, atom) itself; finish with the search's aux timer
+// a functor. All eight check and stage their inputs with stage and end their entry points with finish; all but sdf.hip
+// run the sweep itself. The first three include this header alone; the other five, whose candidates are a list of the
+// caller's, include shell_gather.h (which includes this one) and take from it the packed integer tables (IntTable,
+// upload_ints), the candidate planes (planes_room, gather) and, where named below, shares_an_atom, excluded, cand_xyz:
+//   clusters.hip        every atom a candidate; capped rows of molecules (append, RowSet); rank_row puts them in order
+//   configurations.hip  every atom a candidate; capped rows of (molecule, word) records; row_of in its hit,
+//                       rank_row_keyed
+//   hydration.hip       the water O (check_indices) as candidates, gathered by its own hy_water_kernel (six planes,
+//                       with a derived vector); wrap_signed for the cosines; capped rows, row_of and rank_row in its
+//                       row pass; its counts mode keeps no rows (plain counters)
+//   angles.hip          capped rows; wrap_signed; row_of in its pair pass; shares_an_atom, excluded and cand_xyz in
+//                       the search, cand_xyz in the pair pass; finish with the search's aux timer
+//   bond_order.hip      capped rows; row_of, wrap_signed and rsq again in its row pass, which ranks a row by
+//                       (rsq, atom) itself; shares_an_atom and excluded in the search, cand_xyz in the row pass; finish
+//                       with the search's aux timer
+//   sdf.hip             a sweep of its own on this header's tile and chunk decomposition (Grid, sweep_grid, rsq,
+//                       wrap_signed): hits go through a queue in LDS, and the self / same-molecule test reads the
+//                       centres' molecules from LDS, so it keeps its own form of `excluded`; shares_an_atom; no rows
+//   aggregates.hip      no rows (a union-find per frame); the hit is tested by node, not by atom or molecule; cand_xyz
+//                       for the class pair's own cutoff; its node tables are generated segments of the IntTable
+//   hbonds.hip          no rows (counters, or presence_table.h); excluded and cand_xyz in hb_walk
 // The reference's arithmetic is unfused: an including .hip puts `#pragma clang fp contract(off)` AHEAD of this include
 // (it has to be in force where wrap_abs / wrap_signed / rsq are instantiated). residence.hip (rt_wrap_abs) and
 // pair_common.h (wrap_abs) keep copies of the wrap: the committed counter runs are tied to those files byte for byte.
