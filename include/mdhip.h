@@ -1311,6 +1311,90 @@ int mdhip_vector_pair_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, cons
                            const int32_t *jobs, double bin_size, int32_t nbins, const double *edges, uint64_t *hist,
                            uint64_t *sums, uint64_t *beyond, uint64_t *unsummed, uint64_t *pairs);
 
+/* ---- molecular shape (structural/molecular_shape.py; no counterpart in the reference) ---- */
+/*
+ * The shape of flexible molecules: per (job, molecule, frame) the mass-weighted gyration tensor about the centre of mass,
+ * the radius of gyration squared Rg2, the end-to-end distance squared Ree2, the second invariant I2, the relative shape
+ * anisotropy k2 (kappa^2) and the principal moments l1 >= l2 >= l3; their histograms, per-frame totals and, when asked,
+ * the values themselves.
+ *   x          host|dev (x_on_device) [n_frames][3][n_atoms], atoms by id, molecules contiguous (as mdhip_axis_vectors)
+ *   box        host [n_frames][3] edge lengths, or NULL: x is unwrapped
+ *   jobs       job j covers job_mols[j] molecules of job_len[j] >= 1 atoms each, the first one starting at atom
+ *              job_atom0[j] (host [n_jobs]): one molecule type
+ *   w_off, w   host int64 [n_jobs+1], host double: the weight row of job j — the masses of one molecule's atoms — is
+ *              w[w_off[j] .. w_off[j+1]); w_off[0] = 0 and w_off[j+1] - w_off[j] = job_len[j]
+ *   job_ends   host int32 [n_jobs][2]: the end atoms (e0, e1), 0-based inside the molecule, within [0, job_len)
+ *   unwrap     1: positions follow the chain; 0: every atom against the molecule's first atom (see below)
+ *   nbins, bin_size, edges   the histograms of Rg and Ree: 1 <= nbins <= 4096 bins of bin_size; edges host [nbins+1] from
+ *              mdhip_bin_edges, or NULL to have it computed from bin_size
+ *   n_kbins    1 .. 1024 bins of k2 over [0, 1]
+ * Outputs — THIS call's values (nothing is accumulated into: the host adds batches); any may be NULL, not all:
+ *   hist_rg, hist_ee  host uint64 [n_jobs][nbins]
+ *   hist_k     host uint64 [n_jobs][n_kbins]
+ *   beyond     host uint64 [n_jobs][2]: the (molecule, frame) pairs whose Rg2 ([0]) or Ree2 ([1]) has no bin
+ *   degenerate host uint64 [n_jobs]: those with Rg2 == 0
+ *   totals     host double [n_jobs][9][n_frames]: per frame the sums over the job's molecules of Rg2, sqrt(Rg2), Ree2,
+ *              l1, l2, l3, k2, I2 and Rg2 * Rg2
+ *   per_mol    host|dev (per_mol_on_device) [n_frames][6][n_series]: Rg2, Ree2, k2, l1, l2, l3; n_series = sum of
+ *              job_mols, series numbered job after job, molecule after molecule
+ * Per (job, molecule, frame), a the molecule's first atom, w_k its weights, every operation an IEEE double operation,
+ * nothing fused, sqrt and division correctly rounded; per axis unless said otherwise:
+ *   positions  p_0 = 0.0. unwrap = 1: p_k = p_(k-1) + w(x[a+k] - x[a+k-1]), k = 1, 2, ...: the chain is followed, right
+ *              whenever CONSECUTIVE atoms lie within half a box edge of each other, however long the molecule is.
+ *              unwrap = 0: p_k = w(x[a+k] - x[a]), the rule of mdhip_axis_vectors: right only while every atom lies
+ *              within half an edge of the first. w is the single strict wrap of the siblings, w(d) = d > L/2 ? d - L :
+ *              (d < -L/2 ? d + L : d) with L/2 formed as L / 2 (a NaN shifts nothing), the identity when box == NULL;
+ *   mass       M = the sum of w_k in ascending k from 0.0, formed on the host;
+ *   centre     s = 0.0; s = s + w_k * p_k in ascending k from k = 0;  c = s / M;
+ *   tensor     q_k = p_k - c (the p_k formed again by the same operations); with t_a = w_k * q_ka, from 0.0 in ascending
+ *              k: Gxx += t_x * q_kx, Gyy += t_y * q_ky, Gzz += t_z * q_kz, Gxy += t_x * q_ky, Gyz += t_y * q_kz,
+ *              Gzx += t_z * q_kx; then each of the six is divided by M once;
+ *   Rg2 = (Gxx + Gyy) + Gzz  (with weights >= 0 a sum of non-negative terms: never negative, 0 or more unless it is NaN);
+ *   I2  = ((Gxx*Gyy + Gyy*Gzz) + Gzz*Gxx) - ((Gxy*Gxy + Gyz*Gyz) + Gzx*Gzx);
+ *   k2  = 1.0 - (3.0 * I2) / (Rg2 * Rg2); with Rg2 == 0 (one atom, or all atoms with weight coincide): k2 = 0.0;
+ *   Ree2 = (rx*rx + ry*ry) + rz*rz,  r = p_e1 - p_e0;
+ *   principal moments: 5 sweeps of cyclic Jacobi over the pairs (x,y), (x,z), (y,z) in that order — +, -, *, / and sqrt
+ *     only, no acos or cos. For the pair (p, q), r the third axis: skipped when G_pq == 0.0 exactly; otherwise
+ *       theta = (G_qq - G_pp) / (2.0 * G_pq);   root = sqrt(theta * theta + 1.0);
+ *       t = theta >= 0.0 ? 1.0 / (theta + root) : -1.0 / (-theta + root);
+ *       c = 1.0 / sqrt(t * t + 1.0);  s = t * c;  u = t * G_pq;
+ *       G_pp = G_pp - u;  G_qq = G_qq + u;  G_pq = 0.0;
+ *       (G_rp, G_rq) = (c * G_rp - s * G_rq,  s * G_rp + c * G_rq), both from the values before the rotation;
+ *     then (a, b, d) = (Gxx, Gyy, Gzz) go through `if (a < b) swap(a, b); if (b < d) swap(b, d); if (a < b) swap(a, b)`:
+ *     l1 = a, l2 = b, l3 = d. 5 sweeps: four bring every tensor of tests/test_shape_cpu.py — nearly equal moments,
+ *     planar and collinear molecules among them — to within 17 * 2^-53 * |G|_F of numpy.linalg.eigvalsh of the tensor
+ *     accumulated in extended precision, where further sweeps change nothing; one more is kept in hand.
+ *     When neither per_mol nor totals is asked for, the moments are not formed.
+ * Counting:
+ *   v = Rg2 into hist_rg[job], v = Ree2 into hist_ee[job]: when 0 <= v < edges[nbins] the bin (int)(sqrt(v) / bin_size),
+ *     decided by comparing v with the edge table (never by a device sqrt); every other v — NaN and infinities included —
+ *     counts in beyond[job][0 | 1] and nowhere else;
+ *   Rg2 == 0: degenerate[job] += 1, k2 is not binned; else when k2 is finite: hist_k[job][b] += 1 with
+ *     b = (int)(k2 * n_kbins) clamped to [0, n_kbins - 1]; else (NaN, infinite) nothing.
+ *   So sum(hist_rg[j]) + beyond[j][0] = sum(hist_ee[j]) + beyond[j][1] = job_mols[j] * n_frames, and sum(hist_k[j]) +
+ *   degenerate[j] + (the non-finite k2) the same.
+ * per_mol holds the values as computed — a NaN or an infinity where the input gave one.
+ * Totals: per (job, frame) 256 partial sums per quantity, partial i adding the values of the molecules i, i + 256, ...
+ * of the job in order (sqrt(Rg2) and Rg2 * Rg2 formed from the Rg2 as written), and a fixed tree over them
+ * (red[i] += red[i + w], w = 128 .. 1), as mdhip_mol_moments: no floating-point atomics, the same bits from call to call.
+ * A NaN stays in its own job and frame.
+ * A workgroup owns a run of whole molecules of one job that fits its LDS stage — at most 256 molecules and 1024 atoms —
+ * and strides over the frames; per frame the run's three planes come in with coalesced loads into padded LDS, then one
+ * lane per molecule walks its atoms there in index order. Molecules of more than 1024 atoms take one lane per
+ * (molecule, frame) in global memory: the same operations in the same order, the same bits. Counts go through LDS bins
+ * into 64-bit device bins with integer atomics only. Any number of frames (gridDim.y is capped at 65535, frames stride).
+ * n_jobs < 1 (or > 2^20), a NULL input array, every output NULL, a job that runs past n_atoms, a weight row that does
+ * not hold job_len weights or whose sum is not positive and finite, an end atom outside [0, job_len), nbins outside
+ * 1..4096, n_kbins outside 1..1024, unwrap other than 0 or 1, a bin_size that is not positive and finite, edges that do
+ * not start at 0 and ascend: MDHIP_EINVAL before anything is written.
+ */
+int mdhip_mol_shape(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *x, int x_on_device, const double *box,
+                    int n_jobs, const int64_t *job_atom0, const int64_t *job_mols, const int32_t *job_len,
+                    const int64_t *w_off, const double *w, const int32_t *job_ends, int unwrap, double bin_size,
+                    int32_t nbins, const double *edges, int32_t n_kbins, uint64_t *hist_rg, uint64_t *hist_ee,
+                    uint64_t *hist_k, uint64_t *beyond, uint64_t *degenerate, double *totals, double *per_mol,
+                    int per_mol_on_device);
+
 /*
  * Replaces, for the inputs of the path, the un-vendored pymatgen `parse_lammps_dumps` + pandas
  * `read_csv` the reference uses (call sites structural/rdf_cn.py:176, dynamical/diffusion.py:172,

@@ -1495,3 +1495,52 @@ def dihedral_angles(x, box, job_atom0, job_mols, job_len, quads, job_row=None, n
                                             None if hist is None else ptr(hist, C.c_uint64), up, u_dev,
                                             ptr(degenerate, C.c_uint64)))
     return hist, res, degenerate[:J]
+
+
+SHAPE_MAX_BINS = 4096    # bins of Rg and Ree per call of mol_shape (include/mdhip.h: mdhip_mol_shape)
+SHAPE_MAX_KBINS = 1024   # bins of kappa^2 over [0, 1]
+SHAPE_TOTALS = ("Rg2", "Rg", "Ree2", "l1", "l2", "l3", "k2", "I2", "Rg4")  # the rows of its totals
+SHAPE_VALUES = ("Rg2", "Ree2", "k2", "l1", "l2", "l3")                    # the rows of its per-molecule values
+
+
+def mol_shape(x, box, job_atom0, job_mols, job_len, weights, ends=None, unwrap=1, bin_size=0.05, n_bins=200, n_kbins=50,
+              per_mol=False, out=None, totals=True, ctx=None):
+    """
+    Gyration tensors and chain size of molecules (include/mdhip.h: mdhip_mol_shape): x [F,3,A] coordinates, atoms by id
+    and molecules contiguous (host array or contiguous float64 device tensor); box [F,3] edge lengths, or None when x is
+    unwrapped. Job j covers job_mols[j] molecules of job_len[j] atoms from atom job_atom0[j] on; weights[j] the masses of
+    one molecule's atoms [job_len[j]]; ends[j] = (e0, e1) the end atoms, 0-based inside the molecule (default: first and
+    last). unwrap 1: positions follow the chain, every bond difference wrapped once; 0: every atom against the first.
+    Histograms of Rg and Ree in n_bins bins of bin_size, of kappa^2 in n_kbins bins over [0, 1].
+    Returns a dict: "hist_rg", "hist_ee" uint64 [J,n_bins], "hist_k" uint64 [J,n_kbins], "beyond" uint64 [J,2] (Rg, Ree
+    without a bin), "degenerate" uint64 [J] (Rg == 0), "totals" [J,9,F] (rows SHAPE_TOTALS; None without `totals`) and
+    "per_mol" [F,6,S] (rows SHAPE_VALUES, S = sum(job_mols)): a host array with `per_mol`, `out` (float64 CUDA tensor of
+    that shape) when given, else None.
+    """
+    ctx = ctx or default_context()
+    J = len(weights)
+    F, A, bx, a0, mols, length, S = _mol_jobs(x, box, job_atom0, job_mols, job_len, J,
+                                              "job_atom0, job_mols, job_len and weights must hold one entry per job")
+    rows = [_f64(w).ravel() for w in weights]
+    w_off = np.zeros(J + 1, dtype=np.int64)
+    w_off[1:] = np.cumsum([len(r) for r in rows])
+    w = _f64(np.concatenate(rows)) if rows else np.zeros(0)
+    if ends is None:
+        ends = [(0, max(int(n) - 1, 0)) for n in length]
+    e = _i32(ends)
+    if e.shape != (J, 2):
+        raise ValueError("ends must hold one (e0, e1) per job")
+    nb, nk = int(n_bins), int(n_kbins)
+    hist_rg, hist_ee = (np.zeros((J, max(nb, 0)), dtype=np.uint64) for _ in range(2))
+    hist_k = np.zeros((J, max(nk, 0)), dtype=np.uint64)
+    beyond, degenerate = np.zeros((J, 2), dtype=np.uint64), np.zeros(max(J, 1), dtype=np.uint64)
+    tot = np.empty((J, len(SHAPE_TOTALS), F)) if totals else None
+    xp, x_dev, keep = as_input(x, ctx)
+    res, pp, p_dev = _dest(out, (F, len(SHAPE_VALUES), S), ctx, pinned=True) if per_mol or out is not None else (None, None, 0)
+    ctx.check(ctx.lib.mdhip_mol_shape(
+        ctx.h, F, A, xp, x_dev, None if bx is None else ptr(bx), J, ptr(a0, C.c_int64), ptr(mols, C.c_int64),
+        ptr(length, C.c_int32), ptr(w_off, C.c_int64), ptr(w), ptr(e, C.c_int32), int(unwrap), float(bin_size), nb, None, nk,
+        ptr(hist_rg, C.c_uint64), ptr(hist_ee, C.c_uint64), ptr(hist_k, C.c_uint64), ptr(beyond, C.c_uint64),
+        ptr(degenerate, C.c_uint64), None if tot is None else ptr(tot), pp, p_dev))
+    return {"hist_rg": hist_rg, "hist_ee": hist_ee, "hist_k": hist_k, "beyond": beyond, "degenerate": degenerate[:J],
+            "totals": tot, "per_mol": res}
