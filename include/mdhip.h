@@ -213,6 +213,9 @@ int mdhip_set_option(mdhip_ctx *ctx, const char *key, int value);
  *       cumsum of the increments gives (a finite series whose running sum overflows included); the integrals before it,
  *       and the series after it in the batch, are untouched. green_kubo is the chain of the separate calls, masks
  *       included.
+ *     velocity_spectrum: as xcorr through the FFT — a non-finite sample of an entity of group g on axis a makes
+ *       sums[.][g][a], power[g][a][.], a0[g][a] and that group's totals non-finite THROUGHOUT; every other output is
+ *       bit-identical to the call on clean data. An entity of group -1 is never read into a sum, whatever it holds.
  *
  * Not covered: NaN in box lengths, types or masses.
  */
@@ -1394,6 +1397,46 @@ int mdhip_mol_shape(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const dou
                     int32_t nbins, const double *edges, int32_t n_kbins, uint64_t *hist_rg, uint64_t *hist_ee,
                     uint64_t *hist_k, uint64_t *beyond, uint64_t *degenerate, double *totals, double *per_mol,
                     int per_mol_on_device);
+
+/* ---- velocity autocorrelation and power spectrum (dynamical/velocity_correlation.py, class VelocityCorrelation; no
+ *      counterpart in the reference) ---- */
+/*
+ * Per-group lag sums and power spectra of the series s_e,a(t) = coef[e] * v[t][a][e], a = x, y, z:
+ *   sums[k][g][a]  = sum over the entities e of group g and t = 0 .. n_frames-1-k of s_e,a(t) * s_e,a(t+k)
+ *   power[g][a][j] = sum over the entities e of group g of |sum_t s_e,a(t) e^{-2 pi i j t / L}|^2, unnormalised
+ *   a0[g][a]       = sum over the entities e of group g and all t of s_e,a(t)^2
+ * Column 3 of each is the total, (x + y) + z of the finished values.
+ *   v          host|dev (v_on_device) [n_frames][3][n_ent], frames in time order: the layout every trajectory call reads
+ *   coef       host [n_ent], or NULL: 1. One multiplication per sample; the results are those of the rounded products
+ *              (sqrt(mass) gives the mass-weighted spectrum)
+ *   ent_group  host int32 [n_ent], values -1 .. n_groups-1; -1: the entity is in no group and enters no sum. Groups need
+ *              not be contiguous (atom types inside molecules); 1 <= n_groups <= 16; an empty group gives zeros
+ *   L          the padded transform length: a power of two, 4 <= L < 2^30, L >= n_frames + max_lag (at equality the
+ *              circular correlation is still the linear one); 0 <= max_lag <= n_frames-1
+ *   sums       host|dev (out_on_device) [max_lag+1][n_groups][4]
+ *   power      NULL, or host|dev (out_on_device) [n_groups][4][L/2+1]
+ *   a0         host [n_groups][4]: formed directly, without a transform — the scale of the error bounds; always returned
+ * The work goes in batches bounded by the context option lag_batch_mb: a batch is one axis of a range of consecutive
+ * entities with ALL their groups, so that every line of the trajectory is read once however the groups are interleaved.
+ * The batch is read through 64 x 64 tiles, entities along the lanes, and written as whole time-major rows in the order
+ * (group, entity ascending) inside the batch's buffer, every group a contiguous range of rows there. The rows go through
+ * the shared FP64 transforms (two passes, the second fused with the column sums of |X|^2 over a group's rows, where the
+ * length allows; else the packed transform and its column sums); the partial spectra of splits and batches are added in
+ * a fixed order, one inverse transform over the 3 * n_groups summed spectra gives the lag sums. The launches that
+ * mdhip_last_kernel_ms reports for this call are its batches (each: one gather, one forward transform, its column sums).
+ * Error: |sums[k][g][a] - exact| <= 4 * 2^-52 * log2(L) * a0[g][a] at every lag (|S(k)| <= S(0) = a0: unlike the MSD, the
+ * autocorrelation has no conditioning problem and needs no exact fallback); for series without a dominant line
+ * |power - exact| <= 4 * 2^-52 * log2(L) * sqrt(n_frames) * a0.
+ * No floating-point atomics: the order of every sum is fixed by the shape, the options and the device's compute-unit
+ * count; results are bit-identical from call to call. Non-finite samples: see "Non-finite input" above.
+ * Any n_frames and n_ent (n_frames * n_ent below 2^40); launch dimensions over 65535 are split inside the call.
+ * n_groups outside 1..16, n_frames < 1, n_ent < 0, an ent_group value outside -1..n_groups-1, L no power of two, outside
+ * [4, 2^30) or below n_frames + max_lag, max_lag outside 0..n_frames-1, a NULL v, ent_group, sums or a0: MDHIP_EINVAL before
+ * anything is written. n_ent == 0 gives zeros.
+ */
+int mdhip_velocity_spectrum(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const double *v, int v_on_device,
+                            const double *coef, int n_groups, const int32_t *ent_group, int64_t L, int64_t max_lag,
+                            double *sums, double *power, int out_on_device, double *a0);
 
 /*
  * Replaces, for the inputs of the path, the un-vendored pymatgen `parse_lammps_dumps` + pandas

@@ -1544,3 +1544,55 @@ def mol_shape(x, box, job_atom0, job_mols, job_len, weights, ends=None, unwrap=1
         ptr(degenerate, C.c_uint64), None if tot is None else ptr(tot), pp, p_dev))
     return {"hist_rg": hist_rg, "hist_ee": hist_ee, "hist_k": hist_k, "beyond": beyond, "degenerate": degenerate[:J],
             "totals": tot, "per_mol": res}
+
+
+VELOCITY_MAX_GROUPS = 16
+
+
+def spectrum_length(n_frames):
+    """The default padded transform length of velocity_spectrum: the smallest power of two >= 2 * n_frames (at least 4)."""
+    L = 4
+    while L < 2 * int(n_frames):
+        L *= 2
+    return L
+
+
+def velocity_spectrum(v, ent_group, max_lag, L=None, coef=None, want_power=False, out=None, ctx=None):
+    """
+    Per-group lag sums and power spectra of velocity series (include/mdhip.h: mdhip_velocity_spectrum): v [F,3,E], frames
+    in time order (host array or contiguous float64 device tensor); ent_group int32 [E], the group of every entity in
+    -1 .. G-1 (-1: in no group; G = max + 1, at least 1; groups may be interleaved); coef [E] or None: the series are
+    coef[e] * v[t,a,e]. L: the padded transform length, a power of two >= F + max_lag (default: the smallest >= 2 F).
+    Returns (sums [max_lag+1,G,4], power [G,4,L/2+1] or None without `want_power`, a0 [G,4]): sums[k,g,a] = sum over the
+    entities of g and t < F - k of s(t) s(t+k), power the unnormalised |DFT_L|^2 summed over the entities, a0 the sum of
+    the squares (the scale of the documented error bounds); column 3 is the total over the axes. sums and power are host
+    arrays, or `out` = (sums, power or None), float64 CUDA tensors of those shapes, when given; a0 is a host array.
+    """
+    ctx = ctx or default_context()
+    F, _, E = _shape3(v, "v")
+    grp = _i32(ent_group).ravel()
+    if len(grp) != E:
+        raise ValueError("ent_group must hold one group per entity")
+    G = max(int(grp.max()) + 1, 1) if E else 1
+    c = None
+    if coef is not None:
+        c = _f64(coef).ravel()
+        if len(c) != E:
+            raise ValueError("coef must hold one factor per entity")
+    L = spectrum_length(F) if L is None else int(L)
+    n_lags = max(int(max_lag) + 1, 0)
+    vp, v_dev, keep = as_input(v, ctx)
+    a0 = np.zeros((G, 4))
+    if out is None:
+        sums = np.empty((n_lags, G, 4))
+        power = np.empty((G, 4, L // 2 + 1)) if want_power else None
+        sp, pp, o_dev = C.c_void_p(sums.ctypes.data), None if power is None else C.c_void_p(power.ctypes.data), 0
+    else:
+        sums, power = out if isinstance(out, (tuple, list)) else (out, None)
+        if want_power and power is None:
+            raise ValueError("want_power with device results needs out = (sums, power)")
+        sp, o_dev = _dev_out(sums, (n_lags, G, 4), ctx=ctx), 1
+        pp = None if power is None else _dev_out(power, (G, 4, L // 2 + 1), ctx=ctx)
+    ctx.check(ctx.lib.mdhip_velocity_spectrum(ctx.h, F, E, vp, v_dev, None if c is None else ptr(c), G, ptr(grp, C.c_int32),
+                                              L, int(max_lag), sp, pp, o_dev, ptr(a0)))
+    return sums, power, a0
