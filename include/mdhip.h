@@ -174,6 +174,7 @@ int mdhip_device_name(mdhip_ctx *ctx, char *buf, int buflen);
  *   "lag_direct"   fused full-lag MSD path: -1 default (= 2), 0 transposed copy made by a pass of its own, 1 the kernel reads
  *                  the trajectory in place, 2 clusters of 16 workgroups transpose their tiles inside the kernel (results of
  *                  the three agree within the reported bound)
+ *   "free_volume_batch"  mdhip_free_volume: frames per batch; 0 (default) what its workspace budget holds
  *   "sync_spin"    waiting for device work: 1 (default) poll the completion event (no interrupt wake-up latency; turns
  *                  into a blocking wait after 100 ms), 0 block at once */
 int mdhip_set_option(mdhip_ctx *ctx, const char *key, int value);
@@ -1397,6 +1398,66 @@ int mdhip_mol_shape(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const dou
                     int32_t nbins, const double *edges, int32_t n_kbins, uint64_t *hist_rg, uint64_t *hist_ee,
                     uint64_t *hist_k, uint64_t *beyond, uint64_t *degenerate, double *totals, double *per_mol,
                     int per_mol_on_device);
+
+/* ---- free volume and cavity sizes (structural/free_volume.py, calc_free_volume; no counterpart in the reference) ---- */
+/*
+ * For every point of a regular grid laid over the periodic cell of every frame: the distance s to the nearest atom
+ * SURFACE (atoms are spheres of their class's radius), which atom that is, and counts of these over all points and frames.
+ *   xyz        host|dev (xyz_on_device) [n_frames][3][n_atoms]; wrapped, unwrapped, negative or many boxes away
+ *   box        host [n_frames][3]: the orthorhombic edge lengths of every frame, each positive and finite
+ *   atom_class host int32 [n_atoms], each in [0, n_classes), or -1: the atom is ignored
+ *   radius     host [n_classes], finite and >= 0;  1 <= n_classes <= 16
+ *   grid       host int32 [3] = (gx, gy, gz), each >= 1, G = gx * gy * gz <= 2^27; the same for every frame
+ *   r_search, r_search_sq   the search radius and its square AS THE CALLER FORMS THEM: r_search positive and finite,
+ *              r_search_sq == r_search * r_search as doubles
+ *   edges      host [nbins + 1], edges[0] == 0, strictly ascending, finite; 1 <= nbins <= 4096
+ *   probe      host [n_probes], each finite, 0 <= probe[k] <= edges[nbins]; 1 <= n_probes <= 8
+ * Outputs — THIS call's values; any may be NULL, not all:
+ *   hist       host uint64 [n_classes][nbins]
+ *   occupied   host uint64 [n_classes]
+ *   beyond     host uint64 [1]
+ *   n_free     host int64 [n_frames][n_probes]
+ *   free_map   host uint32 [G], point (i, j, k) at (i * gy + j) * gz + k
+ *   s_out      host|dev (field_on_device) double [n_frames][G];  nearest_out  host|dev (the same flag) int32 [n_frames][G]
+ * Every operation is an IEEE double operation, nothing fused, division and sqrt correctly rounded; per frame f with the
+ * edges L_a = box[f][a]:
+ *   atom       an atom whose class is -1, or with a coordinate that is NaN or infinite, is seen by no point. Every other
+ *              atom j is brought into the cell once per axis:  s = x / L;  f = s - floor(s);  f = f < 1 ? f : 0;
+ *              xw = f * L  (the wrapped fraction of the spatial sort of the pair path);
+ *   point      (i, j, k), 0 <= i_a < g_a, lies at p_a = ((i_a + 0.5) / g_a) * L_a: the grid is fractional and anchored
+ *              at coordinate 0 (only edge lengths are known; a rigid shift of the grid changes no statistic);
+ *   distance   per axis a = |p - xw|, d = min(a, |a - L|) (the single wrap of the shell searches: for two positions in
+ *              [0, L] the exact minimum image at any search radius);  rsq = (dx*dx + dy*dy) + dz*dz.
+ *              Atom j is a CANDIDATE of the point iff rsq < r_search_sq, strictly; then s_j = sqrt(rsq) - radius[class_j];
+ *   value      s = the minimum of s_j over the candidates, nearest = the LOWEST atom index among those that attain it
+ *              (a minimum over the pairs (s_j, j): independent of the order in which atoms are met);
+ *              lining = atom_class[nearest]. Without a candidate s = +inf and nearest = -1.
+ * Counting over all frames and points, each point in exactly one place:
+ *   s < 0:                           occupied[lining] += 1
+ *   edges[b] <= s < edges[b + 1]:    hist[lining][b] += 1   (by comparison with the edge table, never by a division)
+ *   otherwise (no candidate, or s >= edges[nbins]):  beyond[0] += 1
+ * so sum(hist) + sum(occupied) + beyond[0] == n_frames * G.
+ *   n_free[f][k] = the points of frame f without a candidate or with s >= probe[k] (probe 0: the geometric free volume;
+ *   a point exactly on a sphere's surface is free);  free_map[point] = the frames in which it is free for probe[0].
+ * How it runs (csrc/cell_plan.h, csrc/free_volume.hip): per frame the atoms are counting-sorted into a grid of
+ * nc_x * nc_y * nc_z cells, nc_a the largest count in [1, 64] whose cell edge L_a / nc_a is at least
+ * r_search * (1 + 2^-20) — so nc differs from frame to frame when the box does —; a workgroup takes the grid points that
+ * lie in one cell (in bricks of 1024), stages the atoms of the up to 27 DISTINCT neighbouring cells in LDS in chunks of
+ * 1024 and every lane carries the running (s, index) minimum of its four points. Counts go through 32-bit LDS bins (when
+ * n_classes * nbins + n_classes + 1 <= 6144, else straight) into 64-bit device cells with integer atomics only: the
+ * results do not depend on the cells, the bricks or the order of arrival. Frames are worked in batches bounded by the
+ * workspace (about 1 GiB, or the option "free_volume_batch"; host-resident xyz is copied batch by batch); no launch dimension grows with n_frames or G.
+ * n_frames < 1, n_atoms outside [1, 2^31), n_classes outside 1..16, nbins outside 1..4096, n_probes outside 1..8, a
+ * g_a < 1 or G > 2^27, a probe that is negative, not finite or above edges[nbins], a radius that is negative or not
+ * finite, a class outside [-1, n_classes), a box edge that is not positive and finite, r_search not positive and finite
+ * or r_search_sq not its square, edges that do not start at 0 and ascend, a NULL input array, every output NULL:
+ * MDHIP_EINVAL before anything is written.
+ */
+int mdhip_free_volume(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *xyz, int xyz_on_device,
+                      const double *box, const int32_t *atom_class, int32_t n_classes, const double *radius,
+                      const int32_t *grid, double r_search, double r_search_sq, int32_t nbins, const double *edges,
+                      int32_t n_probes, const double *probe, uint64_t *hist, uint64_t *occupied, uint64_t *beyond,
+                      int64_t *n_free, uint32_t *free_map, double *s_out, int32_t *nearest_out, int field_on_device);
 
 /* ---- velocity autocorrelation and power spectrum (dynamical/velocity_correlation.py, class VelocityCorrelation; no
  *      counterpart in the reference) ---- */

@@ -179,6 +179,9 @@ PROTOTYPES = {
     "mdhip_mol_shape": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int, c_lp, c_lp, c_ip, c_lp, c_dp, c_ip,
                                   C.c_int, C.c_double, C.c_int32, c_dp, C.c_int32, c_up, c_up, c_up, c_up, c_up, c_dp, vp,
                                   C.c_int]),
+    "mdhip_free_volume": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, c_ip, C.c_int32, c_dp, c_ip, C.c_double,
+                                    C.c_double, C.c_int32, c_dp, C.c_int32, c_dp, c_up, c_up, c_up, c_lp,
+                                    C.POINTER(C.c_uint32), vp, vp, C.c_int]),
     "mdhip_velocity_spectrum": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int, c_ip, C.c_int64, C.c_int64,
                                           vp, vp, C.c_int, c_dp]),
     "mdhip_dump_open": (C.c_int, [C.c_char_p, C.POINTER(vp)]),

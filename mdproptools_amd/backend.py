@@ -1596,3 +1596,58 @@ def velocity_spectrum(v, ent_group, max_lag, L=None, coef=None, want_power=False
     ctx.check(ctx.lib.mdhip_velocity_spectrum(ctx.h, F, E, vp, v_dev, None if c is None else ptr(c), G, ptr(grp, C.c_int32),
                                               L, int(max_lag), sp, pp, o_dev, ptr(a0)))
     return sums, power, a0
+
+
+FREE_VOLUME_MAX_CLASSES = 16   # atom classes per call of free_volume (include/mdhip.h: mdhip_free_volume)
+FREE_VOLUME_MAX_BINS = 4096
+FREE_VOLUME_MAX_PROBES = 8
+FREE_VOLUME_MAX_POINTS = 1 << 27
+
+
+def free_volume(xyz, box, atom_class, radius, grid, r_search, edges, probe=(0.0,), want_map=False, field=False,
+                out=None, counts=True, ctx=None):
+    """
+    Free volume and cavity sizes on a grid (include/mdhip.h: mdhip_free_volume): xyz [F,3,N] (host array or contiguous
+    float64 device tensor), box [F,3] edge lengths, atom_class int32 [N] in -1 .. C-1 (-1: the atom is ignored), radius
+    [C], grid = (gx, gy, gz), r_search the search radius (its square is formed here, r_search * r_search), edges
+    [nbins+1] from 0 ascending, probe [P] radii. Per grid point s = the distance to the nearest atom surface within
+    r_search and `nearest`, the lowest atom index that attains it.
+    Returns a dict: "hist" uint64 [C,nbins], "occupied" uint64 [C], "beyond" uint64 (a number) — None without `counts` —,
+    "n_free" int64 [F,P], "free_map" uint32 [gx,gy,gz] with `want_map` (else None), and with `field` "s" float64
+    [F,gx,gy,gz] and "nearest" int32 [F,gx,gy,gz] as host arrays, or `out` = (s, nearest), CUDA tensors of those shapes
+    and dtypes float64 and int32, when given.
+    """
+    ctx, F, N, bx, xp, x_dev, keep = _xyz_box(xyz, box, ctx)
+    cls = _i32(atom_class).ravel()
+    if len(cls) != N:
+        raise ValueError("atom_class must hold one class per atom")
+    rad, ed, pr, g = _f64(radius).ravel(), _f64(edges).ravel(), _f64(probe).ravel(), _i32(grid).ravel()
+    if len(g) != 3:
+        raise ValueError("grid must hold (gx, gy, gz)")
+    n_cls, nb, n_pr = len(rad), len(ed) - 1, len(pr)
+    shape = tuple(max(int(v), 0) for v in g)
+    G = shape[0] * shape[1] * shape[2]
+    if G > FREE_VOLUME_MAX_POINTS:
+        raise ValueError("the grid holds %d points; at most 2^27" % G)
+    hist = np.zeros((max(n_cls, 0), max(nb, 0)), dtype=np.uint64) if counts else None
+    occupied = np.zeros(max(n_cls, 1), dtype=np.uint64) if counts else None
+    beyond = np.zeros(1, dtype=np.uint64) if counts else None
+    n_free = np.zeros((F, max(n_pr, 1)), dtype=np.int64)
+    fmap = np.zeros(shape, dtype=np.uint32) if want_map else None
+    s = near = sp = npn = None
+    f_dev = 0
+    if out is not None:
+        s, near = out
+        sp, npn, f_dev = _dev_out(s, (F,) + shape, ctx=ctx), _dev_out(near, (F,) + shape, "torch.int32", ctx), 1
+    elif field:
+        s, near = np.empty((F,) + shape), np.empty((F,) + shape, dtype=np.int32)
+        sp, npn = C.c_void_p(s.ctypes.data), C.c_void_p(near.ctypes.data)
+    r = float(r_search)
+    ctx.check(ctx.lib.mdhip_free_volume(
+        ctx.h, F, N, xp, x_dev, ptr(bx), ptr(cls, C.c_int32), n_cls, ptr(rad), ptr(g, C.c_int32), r, r * r, nb, ptr(ed), n_pr,
+        ptr(pr), None if hist is None else ptr(hist, C.c_uint64), None if hist is None else ptr(occupied, C.c_uint64),
+        None if hist is None else ptr(beyond, C.c_uint64), ptr(n_free, C.c_int64),
+        None if fmap is None else ptr(fmap, C.c_uint32), sp, npn, f_dev))
+    return {"hist": hist, "occupied": None if occupied is None else occupied[:n_cls],
+            "beyond": None if beyond is None else int(beyond[0]), "n_free": n_free[:, :n_pr], "free_map": fmap, "s": s,
+            "nearest": near}

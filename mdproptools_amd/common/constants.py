@@ -89,3 +89,10 @@ DENSITY_3D_CONVERSION = {
     "micro": MASS_CONVERSION["micro"] / DISTANCE_CONVERSION["micro"] ** 3,
     "nano": MASS_CONVERSION["nano"] / DISTANCE_CONVERSION["nano"] ** 3,
 }
+
+# van der Waals radii in Angstrom by element symbol (A. Bondi, J. Phys. Chem. 68 (1964) 441), for building the `radii`
+# argument of structural.free_volume.calc_free_volume: {atom_type: BONDI_RADII[element_of[atom_type]]}
+BONDI_RADII = {
+    "H": 1.20, "He": 1.40, "Li": 1.82, "C": 1.70, "N": 1.55, "O": 1.52, "F": 1.47, "Ne": 1.54, "Na": 2.27, "Mg": 1.73,
+    "Si": 2.10, "P": 1.80, "S": 1.80, "Cl": 1.75, "Ar": 1.88, "K": 2.75, "Br": 1.85, "I": 1.98,
+}

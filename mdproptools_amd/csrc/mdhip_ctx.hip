@@ -802,6 +802,8 @@ int mdhip_set_option(mdhip_ctx *ctx, const char *key, int value)
         ctx->opt_rdf_pk_passes = value < 0 ? 1 : value;
     else if (!strcmp(key, "residence_cap"))
         ctx->opt_residence_cap = value;
+    else if (!strcmp(key, "free_volume_batch"))
+        ctx->opt_fv_batch = value < 0 ? 0 : value;
     else if (!strcmp(key, "rdf_disp"))
         ctx->opt_rdf_disp = value;
     else if (!strcmp(key, "rdf_sort"))

@@ -56,22 +56,29 @@ def _reference_atoms(reference, num_mols, num_atoms_per_mol):
     return tuple((first + a - 1).astype(np.int32) for a in atoms)
 
 
-def write_cube(path, grid, r_cut, bin_size, title):
+def write_cube(path, grid, r_cut, bin_size, title, voxel=None, comment=None):
     """`grid` [G,G,G] (body-frame axes e1, e2, e3) as a Gaussian cube file: lengths in Bohr, the first voxel centred at
-    -r_cut + bin_size / 2 on every axis, one dummy atom at the origin of the body frame."""
-    G = grid.shape[0]
-    o = (-float(r_cut) + 0.5 * float(bin_size)) / _ANGSTROM_PER_BOHR
-    v = float(bin_size) / _ANGSTROM_PER_BOHR
+    -r_cut + bin_size / 2 on every axis, one dummy atom at the origin of the body frame.
+    With `voxel` = (vx, vy, vz) in Angstrom instead (r_cut and bin_size are then not read): a grid [Gx,Gy,Gz] over a
+    cell whose lower corner is the origin, voxel (i, j, k) centred at ((i + 1/2) vx, (j + 1/2) vy, (k + 1/2) vz);
+    `comment` replaces the second line."""
+    shape = tuple(grid.shape)
+    if voxel is None:
+        o = (-float(r_cut) + 0.5 * float(bin_size)) / _ANGSTROM_PER_BOHR
+        origin, v = (o, o, o), (float(bin_size) / _ANGSTROM_PER_BOHR,) * 3
+    else:
+        v = tuple(float(x) / _ANGSTROM_PER_BOHR for x in voxel)
+        origin = tuple(0.5 * x for x in v)
     with open(path, "w") as fh:
         fh.write("%s\n" % title)
-        fh.write("body-frame axes e1 e2 e3; outer loop e1, inner loop e3\n")
-        fh.write("%5d %12.6f %12.6f %12.6f\n" % (1, o, o, o))
+        fh.write("%s\n" % (comment or "body-frame axes e1 e2 e3; outer loop e1, inner loop e3"))
+        fh.write("%5d %12.6f %12.6f %12.6f\n" % ((1,) + origin))
         for k in range(3):
-            fh.write("%5d %12.6f %12.6f %12.6f\n" % ((G,) + tuple(v if j == k else 0.0 for j in range(3))))
+            fh.write("%5d %12.6f %12.6f %12.6f\n" % ((shape[k],) + tuple(v[k] if j == k else 0.0 for j in range(3))))
         fh.write("%5d %12.6f %12.6f %12.6f %12.6f\n" % (0, 0.0, 0.0, 0.0, 0.0))
-        flat = np.nan_to_num(np.asarray(grid, dtype=np.float64)).reshape(G * G, G)
+        flat = np.nan_to_num(np.asarray(grid, dtype=np.float64)).reshape(shape[0] * shape[1], shape[2])
         for row in flat:  # (a new line after every run along e3, six values to a line)
-            for i in range(0, G, 6):
+            for i in range(0, shape[2], 6):
                 fh.write(" ".join("%13.5E" % x for x in row[i:i + 6]) + "\n")
 
 
