@@ -8,22 +8,19 @@
 //
 // mdhip_cross_msd: out[k][a][b] = sum_t sum_x (P[a][x][t+k] - P[a][x][t]) * (P[b][x][t+k] - P[b][x][t]) / (n - k).
 //   Difference form throughout (subtract, then multiply): FP64-VALU bound, n * max_lag / 2 window positions with
-//   3 G subtractions and 3 G (G + 1) / 2 fused multiply-adds each. Organised as xcorr_direct_kernel (xcorr.hip):
-//   a workgroup owns a tile of CM_KT = 512 consecutive lags, CM_LPT = 2 per lane, and streams time in stages of
-//   CM_TT = 128 steps. A stage holds, for every series of the workgroup's groups, the window P[T0 + K0 ..] in LDS,
-//   transposed ([i mod 2][i div 2]) so that the 64 lanes of a wave read consecutive doubles; a lane keeps a sliding
-//   window of two entries per series in registers, so that one LDS read per series and step feeds both of its lags,
-//   and P[.][t] (the same for every lane) arrives through uniform loads. ALL pair accumulators of a lane's lags
-//   stay in registers: one staged window feeds every group pair. Groups go in tiles of four: up to four groups are one
-//   launch (10 pairs x 2 lags, twice that with the |term| sums); more groups take one launch per pair of tiles
-//   (A <= B: the diagonal ones as above, the others all 16 pairs of 4 x 4 groups). Lag tiles are paired
-//   (j, nT - 1 - j) so that every workgroup has the same amount of work; time is split into slabs whose partial sums a
-//   second kernel adds in a fixed order, divides and mirrors (no float atomics). The steps at which some lag of a WAVE
-//   (128 lags) has its partner sample beyond the series — the last 127 time origins of its lags at most — run in a
-//   predicated loop.
+//   3 G subtractions and 3 G (G + 1) / 2 fused multiply-adds each, with the geometry helpers of lag_tiles.h (tiles of 512
+//   lags, 2 per lane; time slabs; stages of 128 steps with the windows of every series of the workgroup's groups in
+//   LDS). The inner loop: a lane keeps a sliding window of two entries per series in registers, so that one LDS read
+//   per series and step feeds both of its lags, and P[.][t] (the same for every lane) arrives through uniform loads.
+//   ALL pair accumulators of a lane's lags stay in registers: one staged window feeds every group pair. Groups go in
+//   tiles of four: up to four groups are one launch (10 pairs x 2 lags, twice that with the |term| sums); more groups
+//   take one launch per pair of tiles (A <= B: the diagonal ones as above, the others all 16 pairs of 4 x 4 groups).
+//   The finish kernel divides and mirrors. The steps at which some lag of a WAVE (128 lags) has its partner sample
+//   beyond the series — the last 127 time origins of its lags at most — run in a predicated loop.
 #include <algorithm>
 
 #include "ctx.h"
+#include "lag_tiles.h"
 
 namespace {
 
@@ -72,12 +69,8 @@ __global__ __launch_bounds__(CD_THREADS) void collective_kernel(const double *__
 // cross-displacement correlation
 // ---------------------------------------------------------------------------------------------
 
-constexpr int CM_THREADS = 256;
-constexpr int CM_LPT = 2;                        // consecutive lags per lane
-constexpr int CM_KT = CM_THREADS * CM_LPT;       // lags per tile (512)
-constexpr int CM_TT = 128;                       // time steps per LDS stage
-constexpr int CM_AW = CM_TT + CM_KT + 2;         // window length per series and stage (+ one step of prefetch)
-constexpr int CM_ROW = CM_AW / 2 + 1;            // two transposed rows of CM_ROW doubles per series
+using CM = lagt::CrossMsdTiles;
+constexpr int CM_THREADS = CM::THREADS, CM_LPT = CM::LPT, CM_ROW = CM::ROW;
 constexpr int CM_GT = 4;                         // groups per tile
 constexpr int CM_MAX_GROUPS = 16;
 
@@ -112,45 +105,34 @@ __global__ __launch_bounds__(CM_THREADS) void cross_msd_kernel(const double *__r
     constexpr int NP = DIAG ? NA * (NA + 1) / 2 : NA * NB;
     extern __shared__ double s_w[];  // [NS][2][CM_ROW]
     const int tid = threadIdx.x;
-    const int pair_id = blockIdx.x;  // handles lag tiles pair_id and n_tiles-1-pair_id
-    const int slab = blockIdx.y;
+    const int pair_id = blockIdx.x, slab = blockIdx.y;
     const int wave_hi = (__builtin_amdgcn_readfirstlane(tid >> 6) + 1) * 64 * CM_LPT;
     // series s of the workgroup: the 3 NA series of tile A, then (unless DIAG) the 3 NB series of tile B
     const double *const Pa = P + (size_t)(3 * ga0) * (size_t)n, *const Pb = P + (size_t)(3 * gb0) * (size_t)n;
 #define CM_SERIES(s) ((s) < 3 * NA ? Pa + (size_t)(s) * (size_t)n : Pb + (size_t)((s) - 3 * NA) * (size_t)n)
 
     for (int half = 0; half < 2; ++half) {
-        const int tile = half == 0 ? pair_id : n_tiles - 1 - pair_id;
-        if (half == 1 && tile == pair_id) break;
-        const long long Q0 = (long long)tile * CM_KT;  // first lag of the tile, relative to lag0
+        const int tile = CM::tile_of(pair_id, half, n_tiles);
+        if (half == 1 && tile == pair_id) break;  // the middle tile once
+        const long long Q0 = CM::first_lag(tile), K0 = lag0 + Q0;
         if (Q0 >= n_lags) continue;
-        const long long K0 = lag0 + Q0;
-        // time range of this tile: t in [0, n-K0); split evenly into n_slabs slabs (multiples of 2)
-        const long long t_total = n - K0;
-        long long per = (t_total + n_slabs - 1) / n_slabs;
-        per = (per + 1) & ~1LL;
-        const long long t_lo = (long long)slab * per;
-        const long long t_hi = t_lo + per < t_total ? t_lo + per : t_total;
+        long long t_lo, t_hi;
+        CM::slab_range(n - K0, n_slabs, slab, t_lo, t_hi);
         double acc[CM_LPT][NP], acc_abs[CM_LPT][NP];
 #pragma unroll
         for (int j = 0; j < CM_LPT; ++j)
 #pragma unroll
             for (int p = 0; p < NP; ++p) acc[j][p] = acc_abs[j][p] = 0.0;
 
-        for (long long T0 = t_lo; T0 < t_hi; T0 += CM_TT) {
+        for (long long T0 = t_lo; T0 < t_hi; T0 += CM::TT) {
             __syncthreads();
-            // stage P[s][T0+K0 .. T0+K0+AW), zero beyond the series (such entries are never used: see `fast` and `ok`)
+            // (entries beyond the series are never used: see `fast` and `ok`)
 #pragma unroll
-            for (int s = 0; s < NS; ++s)
-                for (int i = tid; i < CM_AW; i += CM_THREADS) {
-                    const long long g = T0 + K0 + i;
-                    s_w[(2 * s + (i & 1)) * CM_ROW + (i >> 1)] = g < n ? CM_SERIES(s)[g] : 0.0;
-                }
+            for (int s = 0; s < NS; ++s) CM::stage(s_w, s, CM_SERIES(s), T0 + K0, n, tid);
             __syncthreads();
-            const long long left = t_hi - T0;
-            const int tt_count = (int)(left < CM_TT ? left : CM_TT);
-            // steps at which every lag of this WAVE (lags K0 .. K0 + wave_hi of the tile at most) still has its partner
-            // inside the series: T0 + tt + K0 + wave_hi - 1 <= n - 1
+            const int tt_count = (int)CM::steps(t_hi, T0);
+            // steps at which every lag of this WAVE (lags K0 .. K0 + wave_hi of the tile at most) still has its partner:
+            // these two lines must equal CM::fast_steps(n, K0, wave_hi, T0, tt_count, 4) (lag_tiles.h has the rule and why)
             const long long room = n - K0 - wave_hi - T0 + 1;
             const int fast = (int)(room <= 0 ? 0 : (room < tt_count ? room : tt_count)) & ~3;
             const double *base = s_w + tid;
@@ -201,7 +183,7 @@ __global__ __launch_bounds__(CM_THREADS) void cross_msd_kernel(const double *__r
                     const bool ok = T0 + K0 + i < n;
 #pragma unroll
                     for (int s = 0; s < NS; ++s) {
-                        double w = s_w[(2 * s + (i & 1)) * CM_ROW + (i >> 1)];
+                        double w = s_w[CM::slot(i, s)];
                         asm volatile("" : "+v"(w));  // (the read itself is unconditional: one select, no branch per series)
                         d[s] = ok ? w - pt[s] : 0.0;
                     }
@@ -211,7 +193,7 @@ __global__ __launch_bounds__(CM_THREADS) void cross_msd_kernel(const double *__r
         }
 #pragma unroll
         for (int j = 0; j < CM_LPT; ++j) {
-            const long long q = Q0 + (long long)tid * CM_LPT + j;
+            const long long q = CM::lane_lag(Q0, tid, j);
             if (q >= n_lags) continue;
             const size_t row = ((size_t)slab * (size_t)n_lags + (size_t)q) * (size_t)(G * G);
             int p = 0;
@@ -366,49 +348,46 @@ int mdhip_cross_msd(mdhip_ctx *ctx, int64_t n, int n_groups, const double *P, in
             if (!d_abs) return MDHIP_ENOMEM;
         }
     }
-    // Time slabs as in xcorr_direct: about six rounds of the resident workgroups; the lag range goes in chunks of whole
-    // tiles whose slab sums stay below ~1 GiB (each chunk pairs its own tiles)
+    // the lag range goes in chunks of whole tiles, each pairing its own tiles; only a <= b is written
     const int n_gt = (G + CM_GT - 1) / CM_GT;
-    const long long n_tiles_all = (n_lags_all + CM_KT - 1) / CM_KT;
-    const long long blocks_all = (n_tiles_all + 1) / 2;
-    long long n_slabs = (6LL * ctx->cu_count * 2 + blocks_all - 1) / blocks_all;
-    n_slabs = std::max<long long>(1, std::min<long long>({n_slabs, (n + CM_TT - 1) / CM_TT, 65535}));
-    const size_t tile_b = (size_t)CM_KT * GG * 8 * (want_abs ? 2 : 1);  // one slab of one lag tile
-    n_slabs = std::max<long long>(1, std::min<long long>(n_slabs, (long long)(((size_t)1 << 30) / tile_b)));
-    const long long chunk_tiles =
-        std::max<long long>(1, std::min<long long>(n_tiles_all, (long long)(((size_t)1 << 30) / (tile_b * n_slabs))));
-    const long long chunk_lags = std::min<long long>(chunk_tiles * CM_KT, n_lags_all);
+    const lagt::Plan pl = lagt::cross_msd_plan(n, n_lags_all, G, want_abs, ctx->cu_count, lagt::PARTIAL_BUDGET);
+    const int n_slabs = pl.n_slabs;
+    const long long chunk_lags = std::min<long long>(pl.chunk * CM::KT, n_lags_all);
     const size_t part_b = (size_t)n_slabs * (size_t)chunk_lags * GG * 8;
     MD_WS(d_part, double, WS_PART, part_b * (want_abs ? 2 : 1));
     double *d_part_abs = want_abs ? d_part + part_b / 8 : nullptr;
     KernelTimer timer(ctx, 0);
     int launches = 0;
-    for (long long lag0 = 0; lag0 < n_lags_all; lag0 += chunk_lags) {
-        const long long n_lags = std::min(chunk_lags, n_lags_all - lag0);
-        const int n_tiles = (int)((n_lags + CM_KT - 1) / CM_KT);
-        const dim3 grid((unsigned)((n_tiles + 1) / 2), (unsigned)n_slabs);
-        // a slab can be empty for short tiles, and only a <= b is written: start from zeros
-        MD_HIP(hipMemsetAsync(d_part, 0, part_b * (want_abs ? 2 : 1), ctx->stream));
-        for (int ta = 0; ta < n_gt; ++ta)
-            for (int tb = ta; tb < n_gt; ++tb, ++launches) {
-                const int ga0 = ta * CM_GT, gb0 = tb * CM_GT;
-                const int na = std::min(CM_GT, G - ga0), nb = std::min(CM_GT, G - gb0);
-                rc = want_abs ? cm_launch_tiles<true>(ctx, grid, d_P, n, G, ga0, na, gb0, nb, lag0, n_lags, n_tiles,
-                                                      (int)n_slabs, d_part, d_part_abs)
-                              : cm_launch_tiles<false>(ctx, grid, d_P, n, G, ga0, na, gb0, nb, lag0, n_lags, n_tiles,
-                                                       (int)n_slabs, d_part, d_part_abs);
-                if (rc) return rc;
+    rc = lagt::run_chunks(
+        ctx, n_lags_all, chunk_lags,
+        [&](long long lag0, long long n_lags) {
+            MD_HIP(hipMemsetAsync(d_part, 0, part_b * (want_abs ? 2 : 1), ctx->stream));  // (and only a <= b is written)
+            const int n_tiles = (int)CM::n_tiles(n_lags);
+            const dim3 grid((unsigned)((n_tiles + 1) / 2), (unsigned)n_slabs);
+            for (int ta = 0; ta < n_gt; ++ta)
+                for (int tb = ta; tb < n_gt; ++tb, ++launches) {
+                    const int ga0 = ta * CM_GT, gb0 = tb * CM_GT;
+                    const int na = std::min(CM_GT, G - ga0), nb = std::min(CM_GT, G - gb0);
+                    const int err = want_abs ? cm_launch_tiles<true>(ctx, grid, d_P, n, G, ga0, na, gb0, nb, lag0, n_lags,
+                                                                    n_tiles, n_slabs, d_part, d_part_abs)
+                                            : cm_launch_tiles<false>(ctx, grid, d_P, n, G, ga0, na, gb0, nb, lag0, n_lags,
+                                                                     n_tiles, n_slabs, d_part, d_part_abs);
+                    if (err) return err;
+                }
+            return MDHIP_OK;
+        },
+        [&](long long lag0, long long n_lags) {
+            const unsigned fin = (unsigned)((n_lags * GG + 255) / 256);
+            hipLaunchKernelGGL(cross_msd_finish_kernel, dim3(fin), dim3(256), 0, ctx->stream, d_part, d_out, (long long)n,
+                               G, lag0, n_lags, n_slabs);
+            if (want_abs) {
+                MD_HIP(hipGetLastError());
+                hipLaunchKernelGGL(cross_msd_finish_kernel, dim3(fin), dim3(256), 0, ctx->stream, d_part_abs, d_abs,
+                                   (long long)n, G, lag0, n_lags, n_slabs);
             }
-        const unsigned fin = (unsigned)((n_lags * GG + 255) / 256);
-        hipLaunchKernelGGL(cross_msd_finish_kernel, dim3(fin), dim3(256), 0, ctx->stream, d_part, d_out, (long long)n, G,
-                           lag0, n_lags, (int)n_slabs);
-        MD_HIP(hipGetLastError());
-        if (want_abs) {
-            hipLaunchKernelGGL(cross_msd_finish_kernel, dim3(fin), dim3(256), 0, ctx->stream, d_part_abs, d_abs,
-                               (long long)n, G, lag0, n_lags, (int)n_slabs);
-            MD_HIP(hipGetLastError());
-        }
-    }
+            return MDHIP_OK;
+        });
+    if (rc) return rc;
     ctx->last_kernel = "cross_msd_kernel";
     ctx->last_launches = launches;
     timer.stop();

@@ -7,24 +7,22 @@
 //   (molecule, frame).
 //
 // mdhip_orient_corr: sums[k][g] = sum over the series m of group g and the origins t of c and of c * c,
-//   c = u_m(t) . u_m(t + k). Organised as cross_msd_kernel (collective.hip): a workgroup owns a tile of OC_KT = 1024
-//   consecutive lags, OC_LPT = 4 per lane, and streams time in stages of OC_TT = 128 steps. A stage holds the window
-//   u[T0 + K0 ..] of the three components of ONE molecule in LDS, transposed ([i mod 4][i div 4]) so that the 64 lanes of
-//   a wave read consecutive doubles; a lane keeps a sliding window of 2 * 4 - 1 entries per component in registers, so
-//   that ONE LDS read per component and step feeds all four of its lags, and u(t) (the same for every lane) arrives
-//   through uniform loads. Unlike cross_msd_kernel the workgroup then goes on to the next molecule of its slab (OC_MS =
-//   8 molecules of one group) with the accumulators carried along: the eight sums of a lane stay in registers over
-//   slab x stage x step. Lag tiles are paired (j, nT - 1 - j) so that every workgroup has the same amount of work;
-//   time is split into slabs as well (about twelve rounds of the resident workgroups); the partial sums per (molecule
-//   slab, time slab) are added by a second kernel in a fixed order (no float atomics). A WAVE (256 lags) runs the steps
-//   up to the last origin of ITS smallest lag; those at which some of its lags have their partner sample beyond the
-//   series — the last 255 at most — run the same blocks of four steps with c selected to zero for such lags. Five FP64
-//   operations per lag and step against three LDS reads per four lags: FP64-VALU bound.
+//   c = u_m(t) . u_m(t + k), with the geometry helpers of lag_tiles.h (tiles of 1024 lags, 4 per lane; time slabs; stages
+//   of 128 steps with the window of the three components of ONE molecule in LDS). The inner loop: a lane keeps a sliding
+//   window of 2 * 4 - 1 entries per component in registers, so that ONE LDS read per component and step feeds all four
+//   of its lags, and u(t) (the same for every lane) arrives through uniform loads. The workgroup goes on to the next
+//   molecule of its slab (OC_MS = 8 molecules of one group) with the accumulators carried along: the eight sums of a
+//   lane stay in registers over slab x stage x step; the partial sums are per (molecule slab, time slab). A WAVE (256
+//   lags) runs the steps up to the last origin of ITS smallest lag; those at which some of its lags have their partner
+//   sample beyond the series — the last 255 at most — run the same blocks of four steps with c selected to zero for
+//   such lags. Five FP64 operations per lag and step against three LDS reads per four lags: FP64-VALU bound (DESIGN
+//   4.13b).
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "ctx.h"
+#include "lag_tiles.h"
 #include "mol_tile.h"
 
 namespace {
@@ -88,18 +86,13 @@ __global__ __launch_bounds__(MT_THREADS) void axis_vectors_kernel(
 // orientational correlation sums
 // ---------------------------------------------------------------------------------------------
 
-constexpr int OC_THREADS = 256;
-constexpr int OC_LPT = 4;                       // consecutive lags per lane
-constexpr int OC_KT = OC_THREADS * OC_LPT;      // lags per tile (1024)
-constexpr int OC_TT = 128;                      // time steps per LDS stage
-constexpr int OC_AW = OC_TT + OC_KT;            // window length per component and stage
-constexpr int OC_ROW = OC_AW / OC_LPT;          // OC_LPT transposed rows of OC_ROW doubles per component
+using OC = lagt::OrientTiles;
+constexpr int OC_THREADS = OC::THREADS, OC_LPT = OC::LPT, OC_TT = OC::TT, OC_ROW = OC::ROW;
 constexpr int OC_MS = 8;                        // molecules per slab
 constexpr int OC_MAX_GROUPS = 16;
 constexpr long long OC_MAX_MSLABS = 32768;      // beyond that the slabs grow (OC_MS, 2 OC_MS, ...)
 constexpr int OC_RESIDENT = 4;                  // workgroups per CU: at most 128 registers per lane (five would spill)
-constexpr int OC_ROUNDS = 12;                   // rounds of the resident workgroups the grid is cut into
-static_assert(OC_AW % OC_LPT == 0 && OC_TT % OC_LPT == 0, "stages are whole blocks of OC_LPT steps");
+static_assert(OC_TT % OC_LPT == 0, "stages are whole blocks of OC_LPT steps");
 static_assert((size_t)3 * OC_LPT * OC_ROW * 8 <= 160 * 1024, "the staged windows must fit LDS");
 
 struct OcGroups {
@@ -118,8 +111,7 @@ __global__ __launch_bounds__(OC_THREADS, OC_RESIDENT) void orient_corr_kernel(co
 {
     __shared__ double s_w[3 * OC_LPT * OC_ROW];  // [3][OC_LPT][OC_ROW]
     const int tid = threadIdx.x;
-    const int pair_id = blockIdx.x;  // handles lag tiles pair_id and n_tiles-1-pair_id
-    const int tslab = blockIdx.y;
+    const int pair_id = blockIdx.x, tslab = blockIdx.y;
     const long long mslab = blockIdx.z;
     const int wave_lo = __builtin_amdgcn_readfirstlane(tid >> 6) * 64 * OC_LPT, wave_hi = wave_lo + 64 * OC_LPT;
     int g = 0;  // the last group whose first slab is not beyond this one (empty groups have none)
@@ -128,16 +120,12 @@ __global__ __launch_bounds__(OC_THREADS, OC_RESIDENT) void orient_corr_kernel(co
     const long long m_hi = m_lo + ms < groups.off[g + 1] ? m_lo + ms : groups.off[g + 1];
 
     for (int half = 0; half < 2; ++half) {
-        const int tile = half == 0 ? pair_id : n_tiles - 1 - pair_id;
-        if (half == 1 && tile == pair_id) break;
-        const long long Q0 = (long long)tile * OC_KT;  // first lag of the tile, relative to lag0
+        const int tile = OC::tile_of(pair_id, half, n_tiles);
+        if (half == 1 && tile == pair_id) break;  // the middle tile once
+        const long long Q0 = OC::first_lag(tile), K0 = lag0 + Q0;
         if (Q0 >= n_lags) continue;
-        const long long K0 = lag0 + Q0;
-        // time range of this tile: t in [0, n-K0); split evenly into n_tslabs slabs
-        const long long t_total = n - K0;
-        const long long per = (t_total + n_tslabs - 1) / n_tslabs;
-        const long long t_lo = (long long)tslab * per;
-        const long long t_hi = t_lo + per < t_total ? t_lo + per : t_total;
+        long long t_lo, t_hi;
+        OC::slab_range(n - K0, n_tslabs, tslab, t_lo, t_hi);
         double acc1[OC_LPT], acc2[OC_LPT];
 #pragma unroll
         for (int j = 0; j < OC_LPT; ++j) acc1[j] = acc2[j] = 0.0;
@@ -146,8 +134,9 @@ __global__ __launch_bounds__(OC_THREADS, OC_RESIDENT) void orient_corr_kernel(co
             const double *const Ux = U + (size_t)m * 3 * (size_t)n, *const Uy = Ux + n, *const Uz = Uy + n;
             for (long long T0 = t_lo; T0 < t_hi; T0 += OC_TT) {
                 __syncthreads();
-                // stage u[x][T0+K0 .. T0+K0+AW), zero beyond the series (such entries are never used: see `fast` and `ok`)
-                for (int i = tid; i < OC_AW; i += OC_THREADS) {
+                // stage u[x][T0+K0 .. T0+K0+AW), zero beyond the series (such entries are never used: see `fast` and `ok`);
+                // one bound test and one slot for the three components, not three lagt stages
+                for (int i = tid; i < OC::AW; i += OC_THREADS) {
                     const long long at = T0 + K0 + i;
                     const int slot = (i % OC_LPT) * OC_ROW + i / OC_LPT;
                     const bool in = at < n;
@@ -156,15 +145,15 @@ __global__ __launch_bounds__(OC_THREADS, OC_RESIDENT) void orient_corr_kernel(co
                     s_w[2 * OC_LPT * OC_ROW + slot] = in ? Uz[at] : 0.0;
                 }
                 __syncthreads();
-                const long long left = t_hi - T0;
+                const long long in_stage = OC::steps(t_hi, T0);
                 // The steps of this WAVE (lags K0 + wave_lo .. K0 + wave_hi of the tile): those at which its smallest lag
-                // still has its partner inside the series, T0 + tt + K0 + wave_lo <= n - 1 — the tile's time range is
-                // that of ITS smallest lag — and none when all its lags lie beyond the requested ones (it only helps
-                // to stage then)
+                // still has its partner inside the series — the tile's time range is that of ITS smallest lag — and
+                // none when all its lags lie beyond the requested ones (it only helps to stage then)
                 const long long some = Q0 + wave_lo >= n_lags ? 0 : n - K0 - wave_lo - T0;
-                const long long in_stage = left < OC_TT ? left : OC_TT;
                 const int tt_count = (int)(some <= 0 ? 0 : (some < in_stage ? some : in_stage));
-                // ... and those at which EVERY lag of the wave has: T0 + tt + K0 + wave_hi - 1 <= n - 1
+                // ... and those at which EVERY lag of the wave has: T0 + tt + K0 + wave_hi - 1 <= n - 1. Both counts must
+                // equal OC::fast_steps (lag_tiles.h has the rule and why): (n, K0, wave_lo + 1, T0, in_stage, 1) and
+                // (n, K0, wave_hi, T0, tt_count, OC_LPT)
                 const long long room = n - K0 - wave_hi - T0 + 1;
                 const int fast = (int)(room <= 0 ? 0 : (room < tt_count ? room : tt_count)) & ~(OC_LPT - 1);
                 const int blocks_end = tt_count & ~(OC_LPT - 1);
@@ -234,7 +223,7 @@ __global__ __launch_bounds__(OC_THREADS, OC_RESIDENT) void orient_corr_kernel(co
         }
 #pragma unroll
         for (int j = 0; j < OC_LPT; ++j) {
-            const long long q = Q0 + (long long)tid * OC_LPT + j;
+            const long long q = OC::lane_lag(Q0, tid, j);
             if (q >= n_lags) continue;
             const size_t at = (((size_t)mslab * (size_t)n_tslabs + (size_t)tslab) * (size_t)n_lags + (size_t)q) * 2;
             partial[at] = acc1[j];
@@ -355,38 +344,34 @@ int mdhip_orient_corr(mdhip_ctx *ctx, int64_t n, int64_t n_series, const double 
         }
         if (n_mslabs <= OC_MAX_MSLABS) break;
     }
-    // Time slabs as in cross_msd, when the molecule slabs alone do not give about twelve rounds of the resident
-    // workgroups (OC_ROUNDS; a workgroup of a paired short tile is done long before one of a full tile, and the last
-    // round runs at the pace of the slowest); the lag range goes in chunks of whole tiles whose slab sums stay below
-    // ~1 GiB (each chunk pairs its own tiles)
-    const long long n_tiles_all = (n_lags_all + OC_KT - 1) / OC_KT;
-    const long long blocks_all = (n_tiles_all + 1) / 2 * std::max<long long>(n_mslabs, 1);
-    long long n_tslabs = ((long long)OC_ROUNDS * OC_RESIDENT * ctx->cu_count + blocks_all - 1) / blocks_all;
-    n_tslabs = std::max<long long>(
-        1, std::min<long long>({n_tslabs, (n + OC_TT - 1) / OC_TT, 65535, 65536 / std::max<long long>(n_mslabs, 1)}));
-    const size_t tile_b = (size_t)OC_KT * 2 * 8 * (size_t)(std::max<long long>(n_mslabs, 1) * n_tslabs);  // all slabs of one lag tile
-    const long long chunk_tiles =
-        std::max<long long>(1, std::min<long long>(n_tiles_all, (long long)(((size_t)1 << 30) / tile_b)));
-    const long long chunk_lags = std::min<long long>(chunk_tiles * OC_KT, n_lags_all);
-    const size_t part_b = (size_t)(std::max<long long>(n_mslabs, 1) * n_tslabs) * (size_t)chunk_lags * 2 * 8;
-    MD_WS(d_part, double, WS_PART, part_b);
+    // time slabs when the molecule slabs alone do not fill the rounds (a workgroup of a paired short tile is done long
+    // before one of a full tile, and the last round runs at the pace of the slowest); the lag range goes in chunks of
+    // whole tiles, each pairing its own tiles. Every (slab, lag) of a chunk is written: nothing to clear.
+    const long long M = std::max<long long>(n_mslabs, 1);
+    const lagt::Plan pl = lagt::orient_plan(n, n_lags_all, n_mslabs, ctx->cu_count, lagt::PARTIAL_BUDGET);
+    const int n_tslabs = pl.n_slabs;
+    const long long chunk_lags = std::min<long long>(pl.chunk * OC::KT, n_lags_all);
+    MD_WS(d_part, double, WS_PART, (size_t)(M * n_tslabs) * (size_t)chunk_lags * 2 * 8);
     KernelTimer timer(ctx, 0);
     int launches = 0;
-    for (long long lag0 = 0; lag0 < n_lags_all; lag0 += chunk_lags) {
-        const long long n_lags = std::min(chunk_lags, n_lags_all - lag0);
-        const int n_tiles = (int)((n_lags + OC_KT - 1) / OC_KT);
-        if (n_mslabs > 0) {
+    rc = lagt::run_chunks(
+        ctx, n_lags_all, chunk_lags,
+        [&](long long lag0, long long n_lags) {
+            if (n_mslabs == 0) return MDHIP_OK;
+            const int n_tiles = (int)OC::n_tiles(n_lags);
             const dim3 grid((unsigned)((n_tiles + 1) / 2), (unsigned)n_tslabs, (unsigned)n_mslabs);
             hipLaunchKernelGGL(orient_corr_kernel, grid, dim3(OC_THREADS), 0, ctx->stream, d_U, (long long)n, groups, G, ms,
-                               lag0, n_lags, n_tiles, (int)n_tslabs, d_part);
-            MD_HIP(hipGetLastError());
+                               lag0, n_lags, n_tiles, n_tslabs, d_part);
             ++launches;
-        }
-        const unsigned fin = (unsigned)((n_lags * 2 * G + 255) / 256);
-        hipLaunchKernelGGL(orient_corr_finish_kernel, dim3(fin), dim3(256), 0, ctx->stream, d_part, d_out, groups, G,
-                           (int)n_tslabs, lag0, n_lags);
-        MD_HIP(hipGetLastError());
-    }
+            return MDHIP_OK;
+        },
+        [&](long long lag0, long long n_lags) {
+            const unsigned fin = (unsigned)((n_lags * 2 * G + 255) / 256);
+            hipLaunchKernelGGL(orient_corr_finish_kernel, dim3(fin), dim3(256), 0, ctx->stream, d_part, d_out, groups, G,
+                               n_tslabs, lag0, n_lags);
+            return MDHIP_OK;
+        });
+    if (rc) return rc;
     ctx->last_kernel = "orient_corr_kernel";
     ctx->last_launches = launches;
     timer.stop();

@@ -9,17 +9,15 @@
 // first call of a process costs what every call costs), with the padding, the spectrum product and the 1/(n-k)
 // scaling fused into their first / pointwise / last kernels (mdhip_fft_xcorr). HBM-bound.
 //
-// MDHIP_XCORR_DIRECT: register-blocked direct lag sums, FP64-FMA bound (n^2/2 fused multiply-adds
-// per pair). A block owns a tile of 2048 consecutive lags (8 per lane) and streams time in chunks
-// staged through LDS; a lane keeps three groups of 8 window entries in registers so that 8 LDS reads feed 64 FMAs, every
-// read issued a whole group before its first use, while b[t] (the same for every lane) arrives through scalar loads,
-// also a group ahead, as the SGPR operand of the FMA. The a-window is stored transposed in LDS ([i mod 8][i div 8]) so that the 64 lanes
-// of a wave read consecutive doubles (no bank conflicts). Lag tiles are paired (j, nT-1-j) so every
-// block has the same amount of work; time is split into slabs whose partial sums are added in a
-// fixed order by a second kernel (no float atomics).
+// MDHIP_XCORR_DIRECT: register-blocked direct lag sums, FP64-FMA bound (n^2/2 fused multiply-adds per pair), with the
+// geometry helpers of lag_tiles.h (tiles of 2048 lags, 8 per lane; time slabs; stages through LDS). The inner loop: a lane
+// keeps three groups of 8 window entries in registers so that 8 LDS reads feed 64 FMAs, every read issued a whole group
+// before its first use, while b[t] (the same for every lane) arrives through scalar loads, also a group ahead, as the
+// SGPR operand of the FMA.
 #include <algorithm>
 
 #include "ctx.h"
+#include "lag_tiles.h"
 
 namespace {
 
@@ -63,13 +61,8 @@ int xcorr_fft(mdhip_ctx *ctx, long long n, int n_pairs, const double *d_a, const
 // direct path
 // ---------------------------------------------------------------------------------------------
 
-constexpr int DX_THREADS = 256;
-constexpr int DX_LPT = 8;                        // consecutive lags per lane
-constexpr int DX_KT = DX_THREADS * DX_LPT;       // lags per tile (2048)
-constexpr int DX_TT = 2016;                      // time steps per LDS stage (42 trips of 48 steps)
-constexpr int DX_AW = DX_TT + DX_KT + 8 + 16;    // a-window length per stage (+ two groups of prefetch)
-constexpr int DX_ROW = DX_AW / 8 + 3;            // transposed rows: 8 rows of DX_ROW doubles (514: rows 4112 B apart,
-                                                 // the 8 rows a staging store walks fall into different banks)
+using DX = lagt::XcorrTiles;  // 42 trips of 48 steps per stage
+constexpr int DX_THREADS = DX::THREADS, DX_LPT = DX::LPT, DX_ROW = DX::ROW;
 
 // partial[slab][q] = sum over the slab's time range of a[t+lag]*b[t], lag = lag0 + q, q < n_lags
 // (lag0 > 0: a lag range of the whole function, the unit of the multi-GPU split by lags)
@@ -77,40 +70,29 @@ __global__ __launch_bounds__(DX_THREADS) void xcorr_direct_kernel(
     const double *__restrict__ a, const double *__restrict__ b, long long n, long long lag0, long long n_lags,
     int n_tiles, int n_slabs, double *__restrict__ partial)
 {
-    __shared__ double s_a[8 * DX_ROW];
+    __shared__ double s_a[DX_LPT * DX_ROW];
     const int tid = threadIdx.x;
-    const int pair_id = blockIdx.x;  // handles lag tiles pair_id and n_tiles-1-pair_id
-    const int slab = blockIdx.y;
+    const int pair_id = blockIdx.x, slab = blockIdx.y;
     a += (size_t)blockIdx.z * n;  // series pair of this block
     b += (size_t)blockIdx.z * n;
     partial += (size_t)blockIdx.z * n_slabs * n_lags;
 
     for (int half = 0; half < 2; ++half) {
-        const int tile = half == 0 ? pair_id : n_tiles - 1 - pair_id;
-        if (half == 1 && tile == pair_id) break;
-        const long long Q0 = (long long)tile * DX_KT;  // first lag of the tile, relative to lag0
+        const int tile = DX::tile_of(pair_id, half, n_tiles);
+        if (half == 1 && tile == pair_id) break;  // the middle tile once
+        const long long Q0 = DX::first_lag(tile), K0 = lag0 + Q0;
         if (Q0 >= n_lags) continue;
-        const long long K0 = lag0 + Q0;
-        // time range of this tile: t in [0, n-K0); split evenly into n_slabs slabs (multiples of 8)
-        const long long t_total = n - K0;
-        long long per = (t_total + n_slabs - 1) / n_slabs;
-        per = (per + 7) & ~7LL;
-        const long long t_lo = (long long)slab * per;
-        const long long t_hi = t_lo + per < t_total ? t_lo + per : t_total;
+        long long t_lo, t_hi;
+        DX::slab_range(n - K0, n_slabs, slab, t_lo, t_hi);
         double acc[DX_LPT];
 #pragma unroll
         for (int m = 0; m < DX_LPT; ++m) acc[m] = 0.0;
 
-        for (long long T0 = t_lo; T0 < t_hi; T0 += DX_TT) {
+        for (long long T0 = t_lo; T0 < t_hi; T0 += DX::TT) {
             __syncthreads();
-            // stage a[T0+K0 .. T0+K0+AW), zero beyond the series (a pair whose a sample does not exist adds 0)
-            for (int i = tid; i < DX_AW; i += DX_THREADS) {
-                const long long g = T0 + K0 + i;
-                s_a[(i & 7) * DX_ROW + (i >> 3)] = g < n ? a[g] : 0.0;
-            }
+            DX::stage(s_a, 0, a, T0 + K0, n, tid);  // (a pair whose a sample does not exist adds 0)
             __syncthreads();
-            const long long left = t_hi - T0;  // time steps of this slab from T0 on
-            const int tt_count = (int)(left < DX_TT ? left : DX_TT);
+            const int tt_count = (int)DX::steps(t_hi, T0);
             // Lane window a_stage[8*tid + t + m], m = 0..7, held as groups of 8 consecutive entries: group g of a
             // trip needs the entries of groups g and g+1 (X, Y) and b[8g..8g+7]. Everything a group needs is requested
             // one whole group (64 FMAs, ~280 cycles) earlier: at the top of group g the 8 LDS reads of group g+2's
@@ -172,7 +154,7 @@ __global__ __launch_bounds__(DX_THREADS) void xcorr_direct_kernel(
         }
 #pragma unroll
         for (int m = 0; m < DX_LPT; ++m) {
-            const long long q = Q0 + (long long)tid * DX_LPT + m;
+            const long long q = DX::lane_lag(Q0, tid, m);
             if (q < n_lags) partial[(size_t)slab * n_lags + q] = acc[m];
         }
     }
@@ -218,43 +200,33 @@ __global__ __launch_bounds__(256) void xcorr_redo_rows_kernel(const double *__re
 int xcorr_direct(mdhip_ctx *ctx, long long n, int n_pairs, const double *d_a, const double *d_b,
                  long long lag0, long long n_lags, double *d_out)
 {
-    const int n_tiles = (int)((n_lags + DX_KT - 1) / DX_KT);
-    const int n_blocks = (n_tiles + 1) / 2;
-    // Time slabs: every block of a launch has the same amount of work (tiles are paired), so the launch ends with a
-    // partly filled last round of blocks: ~6 rounds of the 4 resident blocks per CU keep that below a few percent
-    // (C5, one series: 5 slabs = 1.2 rounds 46.5 TFLOP/s, 25 slabs = 6 rounds 54.3; tools/ab_xcorr_direct.py). All
-    // series pairs of a call share one launch (grid.z) while the slab sums fit ~1 GiB.
-    const long long max_slabs = (n - lag0 + DX_TT - 1) / DX_TT;
+    const int n_tiles = (int)DX::n_tiles(n_lags);
     const size_t slab_b = (size_t)n_lags * 8;
-    int group = (int)std::max<long long>(1, std::min<long long>(std::min(n_pairs, 65535), (1LL << 30) / (slab_b * 8)));
-    int n_slabs = ctx->opt_xcorr_tile > 0
-                      ? ctx->opt_xcorr_tile
-                      : (int)((6LL * ctx->cu_count * 4 + (long long)n_blocks * group - 1) / ((long long)n_blocks * group));
-    if (n_slabs > max_slabs) n_slabs = (int)max_slabs;
-    if (n_slabs > 65535) n_slabs = 65535;
-    if (n_slabs < 1) n_slabs = 1;
-    group = (int)std::max<long long>(1, std::min<long long>(group, (1LL << 30) / (slab_b * n_slabs)));
-    MD_WS(d_partial, double, WS_PART, (size_t)group * n_slabs * slab_b);
-    MD_WS(d_redo, int, WS_MISC, (size_t)group * 4);
-    for (int p0 = 0; p0 < n_pairs; p0 += group) {
-        const int np = std::min(group, n_pairs - p0);
-        // a slab can be empty for short tiles: start from zeros
-        MD_HIP(hipMemsetAsync(d_partial, 0, (size_t)np * n_slabs * slab_b, ctx->stream));
-        MD_HIP(hipMemsetAsync(d_redo, 0, (size_t)np * 4, ctx->stream));
-        hipLaunchKernelGGL(xcorr_direct_kernel, dim3((unsigned)n_blocks, (unsigned)n_slabs, (unsigned)np),
-                           dim3(DX_THREADS), 0, ctx->stream, d_a + (size_t)p0 * n, d_b + (size_t)p0 * n, n,
-                           lag0, n_lags, n_tiles, n_slabs, d_partial);
-        MD_HIP(hipGetLastError());
-        hipLaunchKernelGGL(xcorr_finish_kernel, dim3((unsigned)((n_lags + 255) / 256), (unsigned)np), dim3(256), 0,
-                           ctx->stream, d_partial, d_out + (size_t)p0 * n_lags, n, lag0, n_lags, n_slabs, d_redo);
-        MD_HIP(hipGetLastError());
-        hipLaunchKernelGGL(xcorr_redo_rows_kernel, dim3((unsigned)std::min<long long>((long long)np * ((n_lags + 255) / 256), 8LL * ctx->cu_count)), dim3(256), 0,
-                           ctx->stream,
-                           d_a + (size_t)p0 * n, d_b + (size_t)p0 * n, n, lag0, n_lags, np, d_redo,
-                           d_out + (size_t)p0 * n_lags);
-        MD_HIP(hipGetLastError());
-    }
-    return MDHIP_OK;
+    // all series pairs of a chunk share one launch (grid.z)
+    const lagt::Plan pl = lagt::xcorr_plan(n, lag0, n_lags, n_pairs, ctx->cu_count, ctx->opt_xcorr_tile, lagt::PARTIAL_BUDGET);
+    const int n_slabs = pl.n_slabs;
+    MD_WS(d_partial, double, WS_PART, (size_t)pl.chunk * n_slabs * slab_b);
+    MD_WS(d_redo, int, WS_MISC, (size_t)pl.chunk * 4);
+    return lagt::run_chunks(
+        ctx, n_pairs, pl.chunk,
+        [&](long long p0, long long np) {
+            MD_HIP(hipMemsetAsync(d_partial, 0, (size_t)np * n_slabs * slab_b, ctx->stream));
+            MD_HIP(hipMemsetAsync(d_redo, 0, (size_t)np * 4, ctx->stream));
+            hipLaunchKernelGGL(xcorr_direct_kernel, dim3((unsigned)((n_tiles + 1) / 2), (unsigned)n_slabs, (unsigned)np),
+                               dim3(DX_THREADS), 0, ctx->stream, d_a + (size_t)p0 * n, d_b + (size_t)p0 * n, n, lag0,
+                               n_lags, n_tiles, n_slabs, d_partial);
+            return MDHIP_OK;
+        },
+        [&](long long p0, long long np) {
+            hipLaunchKernelGGL(xcorr_finish_kernel, dim3((unsigned)((n_lags + 255) / 256), (unsigned)np), dim3(256), 0,
+                               ctx->stream, d_partial, d_out + (size_t)p0 * n_lags, n, lag0, n_lags, n_slabs, d_redo);
+            MD_HIP(hipGetLastError());
+            hipLaunchKernelGGL(xcorr_redo_rows_kernel,
+                               dim3((unsigned)std::min<long long>(np * ((n_lags + 255) / 256), 8LL * ctx->cu_count)),
+                               dim3(256), 0, ctx->stream, d_a + (size_t)p0 * n, d_b + (size_t)p0 * n, n, lag0, n_lags,
+                               (int)np, d_redo, d_out + (size_t)p0 * n_lags);
+            return MDHIP_OK;
+        });
 }
 
 // out[p][k] *= scale (direct estimator; the FFT path scales in its last pass)

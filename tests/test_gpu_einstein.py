@@ -5,7 +5,8 @@ and partial sum is an exact double in any order); floating-point ones within bou
 and their absolute sum, never measured: |out - want| <= (3 (n - k) + 4) 2^-52 abs (each side within
 (terms + 2) 2^-53 abs of the true sum, plus the division), |P - want| <= (n_g + 3) 2^-52 sum |c_e d_e|. Shapes are the
 smallest at which the kernels can go wrong: 2 and 3 frames, series either side of the time stage (128) and the lag tile
-(512) and of twice the tile, every lag of a 5000-frame series (ten lag tiles, several time slabs), 70 001 frames, an
+(512) and of twice the tile, every lag of a 5000-frame series (ten lag tiles, several time slabs), 70 001 frames, three
+lag chunks (16 groups with the |term| sums at 70 001 frames and 1101 lags: the slab sums reach the 1 GiB budget), an
 empty group, group counts that take every instance of the kernel (1-4 on the diagonal, 4 x 1-4 off it, 16).
 The independent check is the full-lag MSD kernel.
 """
@@ -61,6 +62,29 @@ def test_exact_integers_5000_frames_every_lag_empty_middle_group(B):
 
 def test_exact_integers_70001_frames(B):
     _walk_case(B, 70001, 3, np.array([0, 3], dtype=np.int64), 64)
+
+
+def test_exact_integers_several_lag_chunks(B):
+    """The chunk loop of csrc/lag_tiles.h (run_chunks), which no other shape reaches: 16 groups with the |term| sums,
+    70 001 samples, 1101 lags are 3 lag tiles and, on 256 CUs, 547 time slabs that the 1 GiB budget of the slab sums
+    cuts to 512 and to one tile per chunk — three chunks of ten 4 x 4 group-tile launches each, every chunk pairing its
+    own tiles from its own first lag. Lags either side of every chunk boundary against int64 sums of those lags alone
+    (the magnitudes stay below 2^43). mdhip_orient_corr runs the same loop, but reaches a second chunk only at about
+    13 GB of input; its plan is walked natively (tests/test_lag_tiles_native_cpu.py)."""
+    P = R.int_series(16, 16, 70001)
+    n, max_lag = P.shape[2], 1100
+    out, ab = B.cross_msd(P, max_lag, with_abs=True)
+    launches = B.default_context().last_kernel_ms()[1]
+    assert out.shape == ab.shape == (max_lag + 1, 16, 16)
+    Pi = P.astype(np.int64)
+    for k in (0, 1, 511, 512, 513, 1023, 1024, 1100):
+        d = Pi[:, :, k:] - Pi[:, :, :n - k]
+        want = np.tensordot(d, d, axes=([1, 2], [1, 2]))
+        want_abs = np.tensordot(np.abs(d), np.abs(d), axes=([1, 2], [1, 2]))
+        assert want_abs.max() < 2 ** 53
+        assert np.array_equal(out[k], want / float(n - k)), k
+        assert np.array_equal(ab[k], want_abs / float(n - k)), k
+    assert launches == 30, launches
 
 
 def test_max_lag_zero(B):
