@@ -22,6 +22,12 @@ def molecule_layout(num_mols, num_atoms_per_mol):
     return seg_off, mol_type, mol_id
 
 
+def atom_molecules(num_mols, num_atoms_per_mol):
+    """(n_atoms, mol_of int32 [n_atoms]: the 0-based molecule of every atom in id order) of the layout."""
+    seg_off = molecule_layout(num_mols, num_atoms_per_mol)[0]
+    return int(seg_off[-1]), np.repeat(np.arange(len(seg_off) - 1), np.diff(seg_off)).astype(np.int32)
+
+
 def calc_atom_type(ids, num_mols, num_atoms):
     """
     Atom id -> 1-based index of the atom inside its molecule type, offset by the atom counts of

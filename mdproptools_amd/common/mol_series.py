@@ -26,6 +26,15 @@ def type_jobs(types, num_mols, num_atoms_per_mol):
             np.asarray([num_atoms_per_mol[t] for t in types], dtype=np.int32))
 
 
+def same_rows(col, start, m, n, what, label):
+    """Row [n] that the m molecules of n atoms from atom `start` on share in the per-atom column `col` (charges,
+    types), or a ValueError."""
+    rows = np.asarray(col[start:start + m * n], dtype=np.float64).reshape(m, n)
+    if m and np.any(rows != rows[0]):
+        raise ValueError("species %s: the molecules of the type do not all carry the same %s" % (label, what))
+    return rows[0] if m else np.zeros(n)
+
+
 def load_series(filename, coords, n_atoms, compute, job_mols, job_rows, n_rows, dt=None, lead="id", **how):
     """Reduces the frames of `filename` batch by batch (trajectory.attribute_batches; `how`: its stream, batch_bytes,
     missing): compute(xyz, box, out, ctx, first) — box None unless coords is "wrapped", first the batch's `lead` column

@@ -1,9 +1,11 @@
 """
 Trajectory ingest shared by the drop-in modules: which route can serve a request, which columns to read, and the
-frames themselves — as host batches (`frame_batches`, the native reader), as page-locked batches from the frame
-stream (`stream_reduced`, mdproptools_amd/stream.py), as two per-atom attributes and three planes from whichever of the
-two can serve (`attribute_batches`: the dynamical drop-ins), or as whole id-sorted frames batched for the pair loops
-(`load_frames`, `batches`, `all_frames`). A new drop-in gets its frames from here.
+frames themselves — as host batches (`frame_batches`, the native reader), as host batches of x y z under one set of
+atom types (`typed_batches`: the structural analyses), as page-locked batches from the frame stream (`stream_reduced`,
+mdproptools_amd/stream.py), as two per-atom attributes and three planes from whichever of the two can serve
+(`attribute_batches`: the dynamical drop-ins), or as whole id-sorted frames batched for the pair loops (`load_frames`,
+`batches`, `all_frames`). `refuse_triclinic` is the box rule of every analysis that takes orthogonal boxes only. A new
+drop-in gets its frames from here.
 """
 
 import numpy as np
@@ -12,6 +14,8 @@ from .. import io as mio
 
 UNWRAPPED = ("xu", "yu", "zu")
 WRAPPED = ("x", "y", "z", "ix", "iy", "iz")
+TYPED_BATCH_BYTES = 1 << 28  # planes of the frames that typed_batches hands over for one library call
+SAME_TYPES = "every frame must hold the same atom types in id order"
 
 
 def streamable_files(pattern, needed, files=None):
@@ -27,6 +31,20 @@ def streamable_files(pattern, needed, files=None):
     finally:
         nd.close()
     return mine if set(needed) <= set(names) else None
+
+
+def refuse_triclinic(pattern):
+    """ValueError when the first frame of a plain-text file of `pattern` has a triclinic box (.gz files are not looked
+    into)."""
+    for fname in mio._sorted_matches(pattern):
+        if str(fname).endswith(".gz"):
+            continue
+        nd = mio.NativeDumpFile(fname)
+        try:
+            if nd.n_frames and nd.header(0)[3] is not None:
+                raise ValueError("triclinic boxes are not supported")
+        finally:
+            nd.close()
 
 
 def frame_refs(pattern):
@@ -112,6 +130,29 @@ def frame_batches(pattern, columns, max_bytes, n_atoms=None, files=None):
         planes.append(pl)
     if planes:
         yield steps, np.stack(boxes), np.stack(planes)
+
+
+def typed_batches(pattern, num_mols, num_atoms_per_mol, altered, max_bytes=None, mismatch=SAME_TYPES):
+    """`frame_batches` of id type x y z for the analyses that run under ONE set of atom types: (timesteps, box lengths
+    [B,3], xyz [B,3,N] C-contiguous float64, types int32 [N]). `types` are the labels of the first frame — with
+    `altered` calc_atom_type of its ids, else its `type` column — and the same array in every batch; a later frame
+    whose labels differ in length or value raises ValueError(`mismatch`). With both layout arguments every frame is
+    checked against the layout's atom count. `max_bytes` None: TYPED_BATCH_BYTES, read when the loop starts."""
+    from .com_mols import calc_atom_type, molecule_layout
+
+    n_atoms = None
+    if num_mols is not None and num_atoms_per_mol is not None:
+        n_atoms = int(molecule_layout(num_mols, num_atoms_per_mol)[0][-1])
+    cap = TYPED_BATCH_BYTES if max_bytes is None else max_bytes
+    types = None
+    for steps, boxes, planes in frame_batches(pattern, ["id", "type", "x", "y", "z"], cap, n_atoms):
+        for pl in planes:
+            lab = calc_atom_type(pl[0], num_mols, num_atoms_per_mol) if altered else pl[1]
+            if types is None:
+                types = lab.astype(np.int32)
+            elif len(lab) != len(types) or not np.array_equal(lab, types):
+                raise ValueError(mismatch)
+        yield steps, boxes, np.ascontiguousarray(planes[:, 2:5]), types
 
 
 def stream_reduced(pattern, files, columns, n_atoms_expected, batch_bytes=None):

@@ -25,6 +25,7 @@ import pandas as pd
 
 from .. import backend
 from ..common import mol_series
+from ..common.trajectory import refuse_triclinic
 from ..dist import is_writer
 
 # True: the dumps are parsed into page-locked staging batches and each is reduced on the GPU while the next one is
@@ -133,9 +134,7 @@ class Reorientation:
         """(U [S,3,F] float64 CUDA tensor, frames in time order; times [F] in ps; group_off [V+1]): read once."""
         if self._traj is not None:
             return self._traj
-        from ..structural.angular_distribution import _refuse_triclinic
-
-        _refuse_triclinic(self.filename)
+        refuse_triclinic(self.filename)
         dipole = any(v[1] == "dipole" for v in self.vectors)
         a0, mols, length = self._jobs()
 

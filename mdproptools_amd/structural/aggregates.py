@@ -22,14 +22,10 @@ import numpy as np
 import pandas as pd
 
 from .. import backend
-from ..common.com_mols import calc_atom_type, molecule_layout
-from ..common.trajectory import frame_batches
+from ..common.com_mols import atom_molecules, molecule_layout
+from ..common.tables import write_csv
+from ..common.trajectory import refuse_triclinic, typed_batches
 from ..dist import is_writer
-from .angular_distribution import _refuse_triclinic
-from .rdf_cn import _write_csv
-
-MAX_BATCH_BYTES = 1 << 28  # planes of the frames handed to the GPU in one call
-_COLS = ["id", "type", "x", "y", "z"]  # the planes of a batch
 
 
 def _contact_table(contacts):
@@ -56,14 +52,15 @@ def _contact_table(contacts):
 
 
 class _Nodes:
-    """The participating nodes of a call and the two atom lists, from the atom types of the first frame."""
+    """The participating nodes of a call and the two atom lists, from the atom types of the first frame; `mol_of` [n]:
+    the molecule of every atom where molecules are the nodes, None where atoms are."""
 
-    def __init__(self, con, ta, tb, types, num_mols, num_atoms_per_mol, mol_types):
+    def __init__(self, con, ta, tb, types, mol_of, num_mols, num_atoms_per_mol, mol_types):
         n = len(types)
         named = sorted(set(ta) | set(tb))
         keep = None if mol_types is None else {int(k) for k in mol_types}
-        if num_mols is not None:
-            seg_off, mol_type, _ = molecule_layout(num_mols, num_atoms_per_mol)
+        if mol_of is not None:
+            mol_type = molecule_layout(num_mols, num_atoms_per_mol)[1]
             # (molecule type k holds the altered atom types upper[k - 2] + 1 .. upper[k - 1])
             upper = np.cumsum(np.asarray(num_atoms_per_mol, dtype=np.int64))
             holder = {t: int(np.searchsorted(upper, t, side="left")) + 1 for t in named if 1 <= t <= upper[-1]}
@@ -72,7 +69,6 @@ class _Nodes:
             in_node = np.isin(mol_type, sorted(part))  # [M]
             node_type = mol_type[in_node]
             node_of_mol = np.cumsum(in_node) - 1
-            mol_of = np.repeat(np.arange(len(mol_type)), np.diff(seg_off))
             listed = in_node[mol_of]  # [n]
             node_of = np.where(listed, node_of_mol[mol_of], 0)
             held = {t for t, k in holder.items() if k in part}
@@ -90,7 +86,7 @@ class _Nodes:
         self.n_atoms = n
         self.n_nodes = int(len(node_type))
         self.node_type = np.asarray(node_type, dtype=np.int64)
-        self.type_ids = sorted(part if num_mols is not None else held)
+        self.type_ids = sorted(part if mol_of is not None else held)
         self.node_of = node_of.astype(np.int32)
         self.atoms_a = np.flatnonzero(listed & np.isin(types, ta)).astype(np.int32)
         self.atoms_b = np.flatnonzero(listed & np.isin(types, tb)).astype(np.int32)
@@ -189,26 +185,17 @@ def calc_aggregates(contacts, filename, num_mols=None, num_atoms_per_mol=None, m
     """
     con, ta, tb, cut = _contact_table(contacts)
     layout = num_mols is not None and num_atoms_per_mol is not None
-    n_layout = None
-    if layout:
-        seg_off, _, _ = molecule_layout(num_mols, num_atoms_per_mol)
-        n_layout = int(seg_off[-1])
-    _refuse_triclinic(filename)
+    mol_of = atom_molecules(num_mols, num_atoms_per_mol)[1] if layout else None  # (a bad layout raises here)
+    refuse_triclinic(filename)
 
-    types = nodes = acc = None
+    nodes = acc = None
     all_labels = []
-    for steps, boxes, planes in frame_batches(filename, _COLS, MAX_BATCH_BYTES, n_layout):
-        for pl in planes:
-            lab = calc_atom_type(pl[0], num_mols, num_atoms_per_mol) if layout else pl[1]
-            if types is None:
-                types = lab.astype(np.int32)
-                nodes = _Nodes(con, ta, tb, types, num_mols if layout else None, num_atoms_per_mol, mol_types)
-                acc = _Census(len(nodes.type_ids))
-            elif len(lab) != len(types) or not np.array_equal(lab, types):
-                raise ValueError("every frame must hold the same atom types in id order")
-        label, _, n_con = backend.contact_components(np.ascontiguousarray(planes[:, 2:5]), boxes, nodes.atoms_a,
-                                                     nodes.class_a, nodes.atoms_b, nodes.class_b, cut, nodes.node_of,
-                                                     nodes.n_nodes)
+    for steps, boxes, xyz, types in typed_batches(filename, num_mols, num_atoms_per_mol, layout):
+        if nodes is None:
+            nodes = _Nodes(con, ta, tb, types, mol_of, num_mols, num_atoms_per_mol, mol_types)
+            acc = _Census(len(nodes.type_ids))
+        label, _, n_con = backend.contact_components(xyz, boxes, nodes.atoms_a, nodes.class_a, nodes.atoms_b,
+                                                     nodes.class_b, cut, nodes.node_of, nodes.n_nodes)
         acc.add(label, nodes.node_type, nodes.type_ids, steps, n_con)
         if return_labels:
             all_labels.append(np.array(label, dtype=np.int32))
@@ -221,7 +208,7 @@ def calc_aggregates(contacts, filename, num_mols=None, num_atoms_per_mol=None, m
         names = [("mol_%d" if layout else "type_%d") % k for k in nodes.type_ids]
     census, sizes, per_frame = acc.tables(names, nodes.n_nodes)
     if save_mode and is_writer():
-        _write_csv(census, path_or_buff)
+        write_csv(census, path_or_buff)
     if return_labels:
         return census, sizes, per_frame, np.concatenate(all_labels)
     return census, sizes, per_frame

@@ -22,14 +22,10 @@ import numpy as np
 import pandas as pd
 
 from .. import backend
-from .. import io as mio
-from ..common.com_mols import calc_atom_type, molecule_layout
-from ..common.trajectory import frame_batches
+from ..common.com_mols import atom_molecules
+from ..common.tables import density, write_csv
+from ..common.trajectory import refuse_triclinic, typed_batches
 from ..dist import is_writer
-from .rdf_cn import _write_csv
-
-MAX_BATCH_BYTES = 1 << 28  # planes of the frames handed to the GPU in one call
-_COLS = ["id", "type", "x", "y", "z"]  # the planes of a batch
 
 
 def _cutoffs(r_cut, n_triplets):
@@ -43,18 +39,6 @@ def _cutoffs(r_cut, n_triplets):
     for t, rc in enumerate(r_cut):
         out[t] = (rc, rc) if np.ndim(rc) == 0 else tuple(rc)
     return out
-
-
-def _refuse_triclinic(filename):
-    for fname in mio._sorted_matches(filename):
-        if str(fname).endswith(".gz"):
-            continue
-        nd = mio.NativeDumpFile(fname)
-        try:
-            if nd.n_frames and nd.header(0)[3] is not None:
-                raise ValueError("triclinic boxes are not supported")
-        finally:
-            nd.close()
 
 
 def calc_angular_distribution(r_cut, bin_size, triplets, filename, num_mols=None, num_atoms_per_mol=None,
@@ -87,26 +71,15 @@ def calc_angular_distribution(r_cut, bin_size, triplets, filename, num_mols=None
     if T * n_bins > backend.ANGLE_MAX_CELLS:
         raise ValueError("%d triplets x %d bins: at most %d histogram cells per call (larger bin_size, or fewer "
                          "triplets)" % (T, n_bins, backend.ANGLE_MAX_CELLS))
-    mol_of = n_layout = None
-    if layout:
-        seg_off, _, _ = molecule_layout(num_mols, num_atoms_per_mol)
-        n_layout = int(seg_off[-1])
-        if exclude_same_molecule:
-            mol_of = np.repeat(np.arange(len(seg_off) - 1), np.diff(seg_off)).astype(np.int32)
-    _refuse_triclinic(filename)
+    mol_of = atom_molecules(num_mols, num_atoms_per_mol)[1] if layout else None  # (a bad layout raises here)
+    refuse_triclinic(filename)
 
     hist = np.zeros((T, n_bins), dtype=np.uint64)
     degen = np.zeros(T, dtype=np.uint64)
     types, n_frames = None, 0
-    for steps, boxes, planes in frame_batches(filename, _COLS, MAX_BATCH_BYTES, n_layout):
-        for pl in planes:
-            lab = calc_atom_type(pl[0], num_mols, num_atoms_per_mol) if altered else pl[1]
-            if types is None:
-                types = lab.astype(np.int32)
-            elif len(lab) != len(types) or not np.array_equal(lab, types):
-                raise ValueError("every frame must hold the same atom types in id order")
-        h, d, _, _ = backend.angle_hist(np.ascontiguousarray(planes[:, 2:5]), boxes, types, trip, rc ** 2, edges,
-                                        mol_of=mol_of)
+    for steps, boxes, xyz, types in typed_batches(filename, num_mols, num_atoms_per_mol, altered):
+        h, d, _, _ = backend.angle_hist(xyz, boxes, types, trip, rc ** 2, edges,
+                                        mol_of=mol_of if exclude_same_molecule else None)
         hist += h
         degen += d
         n_frames += len(steps)
@@ -118,7 +91,7 @@ def calc_angular_distribution(r_cut, bin_size, triplets, filename, num_mols=None
         name = "%d-%d-%d" % (a, c, b)
         cnt = hist[t].astype(np.int64)
         total = int(cnt.sum())
-        adf["adf_" + name] = cnt / (total * float(bin_size)) if total else np.full(n_bins, np.nan)
+        adf["adf_" + name] = density(cnt, float(bin_size))
         adf["count_" + name] = cnt
         n_cen = int((types == c).sum()) if types is not None else 0
         rows.append((name, total, int(degen[t]), float((cnt * centres).sum() / total) if total else np.nan,
@@ -126,5 +99,5 @@ def calc_angular_distribution(r_cut, bin_size, triplets, filename, num_mols=None
     summary = pd.DataFrame(rows, columns=["triplet", "n_angles", "n_degenerate", "mean_angle",
                                           "angles_per_centre_frame"])
     if save_mode and is_writer():
-        _write_csv(adf, path_or_buff)
+        write_csv(adf, path_or_buff)
     return adf, summary

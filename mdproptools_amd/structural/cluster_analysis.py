@@ -35,7 +35,7 @@ import pandas as pd
 
 from .. import backend
 from .. import io as mio
-from ..common.com_mols import calc_atom_type, check_atom_count, molecule_layout
+from ..common.com_mols import atom_molecules, calc_atom_type, check_atom_count, molecule_layout
 from ..common.trajectory import frame_refs, read_frame
 
 FORCE_CONSTANT = 0.043363 / 16.0  # cluster_analysis.py:29
@@ -55,8 +55,7 @@ def cluster_file_name(frame_index, n_frames, centre_index, n_centres):
 
 def _layout(num_mols, num_atoms_per_mol):
     seg_off, mol_type, _ = molecule_layout(num_mols, num_atoms_per_mol)
-    mol_of = np.repeat(np.arange(len(mol_type), dtype=np.int32), np.diff(seg_off))
-    return mol_of, seg_off, mol_type
+    return atom_molecules(num_mols, num_atoms_per_mol)[1], seg_off, mol_type
 
 
 def _element_column(fname, k):

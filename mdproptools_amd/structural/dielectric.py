@@ -101,9 +101,8 @@ def calc_dielectric_constant(filename, num_mols, num_atoms_per_mol, temperature,
     if not asked or len(set(asked)) != len(asked) or not all(1 <= t <= len(per) for t in asked):
         raise ValueError("mol_types must be different types in [1, %d]" % len(per))
     from ..dynamical.conductivity import Conductivity
-    from .angular_distribution import _refuse_triclinic
 
-    _refuse_triclinic(filename)
+    T.refuse_triclinic(filename)
     wrapped = coords == "wrapped"
 
     def missing(lacking, _names):
@@ -117,11 +116,9 @@ def calc_dielectric_constant(filename, num_mols, num_atoms_per_mol, temperature,
     totals, squares, lengths, volumes, steps = [], [], [], [], []
     for ts, q, _types, xyz, box in batches:
         if plan is None:
-            from .orientational_correlation import same_rows
-
             first = np.concatenate(([0], np.cumsum(np.multiply(num_mols, per))))
-            rows = {t: same_rows(q[0], int(first[t - 1]), num_mols[t - 1], per[t - 1], "charges", "%d:dipole" % t)
-                    for t in asked}
+            rows = {t: mol_series.same_rows(q[0], int(first[t - 1]), num_mols[t - 1], per[t - 1], "charges",
+                                            "%d:dipole" % t) for t in asked}
             skipped = [t for t in asked if abs(float(np.sum(rows[t]))) > NEUTRAL]
             kept = [t for t in asked if t not in skipped]
             if not kept:

@@ -26,8 +26,9 @@ import pandas as pd
 
 from .. import backend
 from ..common import mol_series
+from ..common.tables import density
+from ..common.trajectory import refuse_triclinic
 from ..dist import is_writer
-from .angular_distribution import _refuse_triclinic
 
 # True: the dumps are parsed into page-locked staging batches and each is reduced on the GPU while the next one is
 # being parsed (mdproptools_amd/stream.py). False: every frame is parsed first and reduced in one call.
@@ -157,7 +158,7 @@ def calc_dihedral_distribution(dihedrals, filename, num_mols, num_atoms_per_mol,
     n_bins = _n_bins(bin_size)
     D = 360.0 / n_bins
     windows = _state_bins(DEFAULT_STATES if states is None else states, n_bins)
-    _refuse_triclinic(filename)
+    refuse_triclinic(filename)
     a0, mols, length, quads, rows = _jobs(entries, num_mols, per)
     E = len(entries)
     hist = np.zeros((E, n_bins), dtype=np.uint64)
@@ -175,7 +176,7 @@ def calc_dihedral_distribution(dihedrals, filename, num_mols, num_atoms_per_mol,
     for e, (_, _, label) in enumerate(entries):
         cnt = hist[e].astype(np.int64)
         total = int(cnt.sum())
-        dist["p_" + label] = cnt / (total * D) if total else np.full(n_bins, np.nan)
+        dist["p_" + label] = density(cnt, D)
         row = {"dihedral": label}
         for name, (b0, b1, wraps) in windows.items():
             inside = int(cnt[b0:].sum() + cnt[:b1].sum()) if wraps else int(cnt[b0:b1].sum())
@@ -221,7 +222,7 @@ def calc_dihedral_correlation(dihedrals, filename, num_mols, num_atoms_per_mol, 
     the table is written to dihedral_correlation.csv in working_dir (default: the current directory).
     """
     entries, num_mols, per = _prepare(dihedrals, filename, num_mols, num_atoms_per_mol, coords)
-    _refuse_triclinic(filename)
+    refuse_triclinic(filename)
     U, times, group_off, degenerate = _load_series(entries, filename, num_mols, per, dt, coords)
     _refuse_degenerate(entries, degenerate)
     max_lag, sums = mol_series.orient_corr(U, group_off, max_lag)

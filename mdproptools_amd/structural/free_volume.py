@@ -31,7 +31,6 @@ import pandas as pd
 from .. import backend
 from ..common import trajectory as T
 from ..dist import is_writer
-from .angular_distribution import _refuse_triclinic
 from .spatial_distribution import write_cube
 
 MAX_BINS = backend.FREE_VOLUME_MAX_BINS
@@ -171,7 +170,7 @@ def calc_free_volume(filename, radii, num_mols=None, num_atoms_per_mol=None, gri
     MAX_FIELD_FRAMES frames): also "s" float64 and "nearest" int32 (atom index in id order, -1: none), [F,gx,gy,gz] in
     time order.
     """
-    _refuse_triclinic(filename)
+    T.refuse_triclinic(filename)
     n_atoms = None
     if num_mols is not None and num_atoms_per_mol is not None:
         n_atoms = int(np.dot(np.asarray(num_mols, dtype=np.int64), np.asarray(num_atoms_per_mol, dtype=np.int64)))

@@ -25,14 +25,12 @@ import pandas as pd
 
 from .. import backend
 from .. import io as mio
-from ..common.com_mols import calc_atom_type, molecule_layout
-from ..common.trajectory import frame_batches
+from ..common.com_mols import atom_molecules, calc_atom_type
+from ..common.tables import density, write_csv
+from ..common.trajectory import refuse_triclinic, typed_batches
 from ..dist import is_writer
-from .angular_distribution import _refuse_triclinic
-from .rdf_cn import _write_csv
 
-MAX_BATCH_BYTES = 1 << 28  # planes of the frames handed to the GPU in one call
-_COLS = ["id", "type", "x", "y", "z"]  # the planes of a batch
+_SAME_ATOMS = "every frame must hold the same atoms in id order"
 
 
 def _layout(num_mols, num_atoms_per_mol):
@@ -41,8 +39,7 @@ def _layout(num_mols, num_atoms_per_mol):
         raise ValueError("hydrogen bonds need num_mols and num_atoms_per_mol (the molecule layout in id order)")
     if len(num_mols) != len(num_atoms_per_mol):
         raise ValueError("num_mols and num_atoms_per_mol must have the same length")
-    seg_off, _, _ = molecule_layout(num_mols, num_atoms_per_mol)
-    return int(seg_off[-1]), np.repeat(np.arange(len(seg_off) - 1), np.diff(seg_off)).astype(np.int32)
+    return atom_molecules(num_mols, num_atoms_per_mol)
 
 
 def _topology(types, mol_of, donors, acceptors):
@@ -122,37 +119,32 @@ def calc_hydrogen_bonds(donors, acceptors, filename, num_mols, num_atoms_per_mol
         `count_d-a` (int64): the angle D-H...A of every (hydrogen, acceptor) within the distance cutoffs, bonded or
         not: the distribution to choose angle_cut from.
     """
-    n_layout, mol_of = _layout(num_mols, num_atoms_per_mol)
+    _, mol_of = _layout(num_mols, num_atoms_per_mol)
     r_da_sq, r_ha_sq, cos_cut = _geometry(r_da, angle_cut, r_ha)
     if donors is None or acceptors is None or len(donors) == 0 or len(acceptors) == 0:
         raise ValueError("donors and acceptors must be non-empty lists")
     edges = backend.angle_cos_edges(bin_size)
     n_bins = len(edges)
-    _refuse_triclinic(filename)
+    refuse_triclinic(filename)
 
-    top = types = None
+    top = None
     steps_all, per = [], []
     hist = n_don = n_acc = None
     degen = 0
-    for steps, boxes, planes in frame_batches(filename, _COLS, MAX_BATCH_BYTES, n_layout):
-        for pl in planes:
-            lab = _altered_types(pl[0], num_mols, num_atoms_per_mol)
-            if types is None:
-                types = lab
-                top = _topology(types, mol_of, donors, acceptors)
-                n_dc, n_ac = len(top["d_types"]), len(top["a_types"])
-                if n_dc * n_ac > backend.HBOND_MAX_CLASSES or n_dc * n_ac * n_bins > backend.HBOND_MAX_CELLS:
-                    raise ValueError("%d donor x %d acceptor classes x %d bins: at most %d class pairs and %d "
-                                     "histogram cells per call" % (n_dc, n_ac, n_bins, backend.HBOND_MAX_CLASSES,
-                                                                   backend.HBOND_MAX_CELLS))
-                hist = np.zeros((n_dc, n_ac, n_bins), dtype=np.uint64)
-                n_don = np.zeros(len(top["donors"]), dtype=np.uint64)
-                n_acc = np.zeros(len(top["acceptors"]), dtype=np.uint64)
-            elif len(lab) != len(types) or not np.array_equal(lab, types):
-                raise ValueError("every frame must hold the same atoms in id order")
+    for steps, boxes, xyz, types in typed_batches(filename, num_mols, num_atoms_per_mol, True, mismatch=_SAME_ATOMS):
+        if top is None:
+            top = _topology(types, mol_of, donors, acceptors)
+            n_dc, n_ac = len(top["d_types"]), len(top["a_types"])
+            if n_dc * n_ac > backend.HBOND_MAX_CLASSES or n_dc * n_ac * n_bins > backend.HBOND_MAX_CELLS:
+                raise ValueError("%d donor x %d acceptor classes x %d bins: at most %d class pairs and %d "
+                                 "histogram cells per call" % (n_dc, n_ac, n_bins, backend.HBOND_MAX_CLASSES,
+                                                               backend.HBOND_MAX_CELLS))
+            hist = np.zeros((n_dc, n_ac, n_bins), dtype=np.uint64)
+            n_don = np.zeros(len(top["donors"]), dtype=np.uint64)
+            n_acc = np.zeros(len(top["acceptors"]), dtype=np.uint64)
         nb, nd, na, h, dg = backend.hbond_counts(
-            np.ascontiguousarray(planes[:, 2:5]), boxes, top["donors"], top["don_class"], top["h_off"],
-            top["h_atoms"], top["acceptors"], top["acc_class"], r_da_sq, cos_cut, r_ha_sq=r_ha_sq, cos_edges=edges,
+            xyz, boxes, top["donors"], top["don_class"], top["h_off"], top["h_atoms"], top["acceptors"],
+            top["acc_class"], r_da_sq, cos_cut, r_ha_sq=r_ha_sq, cos_edges=edges,
             mol_of=mol_of if exclude_same_molecule else None, n_dc=n_dc, n_ac=n_ac)
         per.append(nb)
         n_don += nd
@@ -175,7 +167,7 @@ def calc_hydrogen_bonds(donors, acceptors, filename, num_mols, num_atoms_per_mol
             per_frame["hb_" + name] = counts[:, dc, ac]
             cnt = hist[dc, ac].astype(np.int64)
             total_angles = int(cnt.sum())
-            angles["adf_" + name] = cnt / (total_angles * float(bin_size)) if total_angles else np.full(n_bins, np.nan)
+            angles["adf_" + name] = density(cnt, float(bin_size))
             angles["count_" + name] = cnt
             total = int(counts[:, dc, ac].sum())
             n_d, n_a = int((top["don_class"] == dc).sum()), int((top["acc_class"] == ac).sum())
@@ -186,7 +178,7 @@ def calc_hydrogen_bonds(donors, acceptors, filename, num_mols, num_atoms_per_mol
     summary["n_degenerate"] = [int(degen)] + [0] * (len(rows) - 1)
     summary.attrs["n_donated"], summary.attrs["n_accepted"] = n_don, n_acc
     if save_mode and is_writer():
-        _write_csv(per_frame, path_or_buff)
+        write_csv(per_frame, path_or_buff)
     return per_frame, summary, angles
 
 
@@ -196,7 +188,7 @@ def _load_compact(filename, num_mols, num_atoms_per_mol, donors, acceptors, dt):
     n_layout, mol_of = _layout(num_mols, num_atoms_per_mol)
     steps, boxes, planes = [], [], []
     types = top = keep = None
-    for ts, bounds, lengths, _, pl in mio.iter_native_frames(filename, _COLS, sort_by="id"):
+    for ts, bounds, lengths, _, pl in mio.iter_native_frames(filename, ["id", "type", "x", "y", "z"], sort_by="id"):
         b = np.asarray(bounds, dtype=np.float64)
         ext = b[:, 1] - b[:, 0]
         if np.any(np.abs(np.asarray(lengths, dtype=np.float64) - ext) > 1e-12 * np.abs(ext)):
@@ -209,7 +201,7 @@ def _load_compact(filename, num_mols, num_atoms_per_mol, donors, acceptors, dt):
             top = _topology(types, mol_of, donors, acceptors)
             keep = np.unique(np.concatenate([top["donors"], top["h_atoms"], top["acceptors"]]))
         elif not np.array_equal(lab, types):
-            raise ValueError("every frame must hold the same atoms in id order")
+            raise ValueError(_SAME_ATOMS)
         steps.append(int(ts))
         boxes.append(ext)
         planes.append(pl[2:5][:, keep])
@@ -275,5 +267,5 @@ def calc_hbond_lifetime(donors, acceptors, filename, num_mols, num_atoms_per_mol
     info = {"tau_int": tau_int, "tau_cont": tau_cont, "n_pairs": n_pairs, "bonds_per_frame": n_rec / n_frames,
             "n_frames": n_frames}
     if save_mode and is_writer():
-        _write_csv(table, path_or_buff)
+        write_csv(table, path_or_buff)
     return table, info

@@ -28,9 +28,8 @@ import pandas as pd
 from .. import backend
 from ..common import mol_series
 from ..common import trajectory as T
+from ..common.tables import density
 from ..dist import is_writer
-from .angular_distribution import _refuse_triclinic
-from .orientational_correlation import same_rows
 
 MAX_BINS = backend.SHAPE_MAX_BINS
 MAX_KAPPA_BINS = backend.SHAPE_MAX_KBINS
@@ -94,13 +93,6 @@ def _n_bins(r_max, bin_size):
     return n
 
 
-def density(counts, width):
-    """counts / (total * width): integrates to 1; all NaN without counts."""
-    counts = np.asarray(counts).astype(np.int64)
-    total = int(counts.sum())
-    return counts / (total * width) if total else np.full(len(counts), np.nan)
-
-
 def summary_row(totals, n_mols):
     """The means of one molecule type from its totals [9,F] (rows backend.SHAPE_TOTALS): every mean the sum over the
     frames divided once by molecules * frames; all NaN for a type without molecules."""
@@ -149,7 +141,7 @@ def weight_rows(types_row, mass, a0, mols, length, names):
         raise ValueError("mass must hold the mass of every atom type")
     rows = []
     for start, m, n, name in zip(a0, mols, length, names):
-        row = same_rows(types_row, int(start), int(m), int(n), "atom types", name)
+        row = mol_series.same_rows(types_row, int(start), int(m), int(n), "atom types", name)
         if m and not (np.all(row >= 1) and np.all(row <= len(mass))):
             raise ValueError("molecule %s: an atom type is outside the %d entries of mass" % (name, len(mass)))
         w = T.masses(row, mass) if m else np.ones(int(n))
@@ -198,7 +190,7 @@ def calc_molecular_shape(filename, num_mols, num_atoms_per_mol, mass, mol_types=
     n_kbins = int(kappa_bins)
     if not 1 <= n_kbins <= MAX_KAPPA_BINS:
         raise ValueError("kappa_bins must be in [1, %d]" % MAX_KAPPA_BINS)
-    _refuse_triclinic(filename)
+    T.refuse_triclinic(filename)
     wrapped = coords == "wrapped"
     J = len(types)
     _, batches = T.attribute_batches(filename, ("id", "type"), ["x", "y", "z"] if wrapped else T.UNWRAPPED,

@@ -26,14 +26,10 @@ import numpy as np
 import pandas as pd
 
 from .. import backend
-from ..common.com_mols import calc_atom_type, molecule_layout
-from ..common.trajectory import frame_batches
+from ..common.com_mols import atom_molecules
+from ..common.tables import density, write_csv
+from ..common.trajectory import refuse_triclinic, typed_batches
 from ..dist import is_writer
-from .angular_distribution import _refuse_triclinic
-from .rdf_cn import _write_csv
-
-MAX_BATCH_BYTES = 1 << 28  # planes of the frames handed to the GPU in one call
-_COLS = ["id", "type", "x", "y", "z"]  # the planes of a batch
 
 
 def _bin_counts(v, lo, bin_size, n_bins):
@@ -84,13 +80,8 @@ def calc_order_parameters(r_cut, centre_type, neighbour_types, filename, degrees
     altered = bool(num_mols and num_atoms_per_mol)
     if exclude_same_molecule and not layout:
         raise ValueError("exclude_same_molecule needs num_mols and num_atoms_per_mol (the molecule layout in id order)")
-    mol_of = n_layout = None
-    if layout:
-        seg_off, _, _ = molecule_layout(num_mols, num_atoms_per_mol)
-        n_layout = int(seg_off[-1])
-        if exclude_same_molecule:
-            mol_of = np.repeat(np.arange(len(seg_off) - 1), np.diff(seg_off)).astype(np.int32)
-    _refuse_triclinic(filename)
+    mol_of = atom_molecules(num_mols, num_atoms_per_mol)[1] if layout else None  # (a bad layout raises here)
+    refuse_triclinic(filename)
 
     B = backend
     names = ["q%d" % l for l in deg] + (["qbar%d" % l for l in deg] if averaged else []) \
@@ -104,16 +95,10 @@ def calc_order_parameters(r_cut, centre_type, neighbour_types, filename, degrees
     chunks = {name: [] for name in names}
     n_short, n_degen = np.zeros(len(names), dtype=np.int64), np.zeros(len(names), dtype=np.int64)
     types, centres = None, np.zeros(0, dtype=np.int32)
-    for steps, boxes, planes in frame_batches(filename, _COLS, MAX_BATCH_BYTES, n_layout):
-        for pl in planes:
-            lab = calc_atom_type(pl[0], num_mols, num_atoms_per_mol) if altered else pl[1]
-            if types is None:
-                types = lab.astype(np.int32)
-            elif len(lab) != len(types) or not np.array_equal(lab, types):
-                raise ValueError("every frame must hold the same atom types in id order")
-        out = B.bond_order(np.ascontiguousarray(planes[:, 2:5]), boxes, types, int(centre_type), nb_types,
-                           backend.cutoff_sq(r_cut), degrees=deg, n_nearest=n_nearest, averaged=averaged,
-                           tetrahedral=tetrahedral, mol_of=mol_of)
+    for steps, boxes, xyz, types in typed_batches(filename, num_mols, num_atoms_per_mol, altered):
+        out = B.bond_order(xyz, boxes, types, int(centre_type), nb_types, backend.cutoff_sq(r_cut), degrees=deg,
+                           n_nearest=n_nearest, averaged=averaged, tetrahedral=tetrahedral,
+                           mol_of=mol_of if exclude_same_molecule else None)
         centres = out["centres"]
         for k, (name, (key, d, short, degen)) in enumerate(zip(names, where)):
             chunks[name].append(np.asarray(out[key][:, :, d], dtype=np.float64))
@@ -129,14 +114,14 @@ def calc_order_parameters(r_cut, centre_type, neighbour_types, filename, degrees
         values[name] = v
         cnt = _bin_counts(v.ravel(), lo, bin_size, n_bins)
         total = int(cnt.sum())
-        dist["p_" + name] = cnt / (total * bin_size) if total else np.full(n_bins, np.nan)
+        dist["p_" + name] = density(cnt, bin_size)
         dist["count_" + name] = cnt
         good = v[~np.isnan(v)]
         rows.append((name, total, int(n_short[k]), int(n_degen[k]), float(good.mean()) if total else np.nan,
                      float(good.std()) if total else np.nan))
     summary = pd.DataFrame(rows, columns=["name", "n_values", "n_short", "n_degenerate", "mean", "std"])
     if save_mode and is_writer():
-        _write_csv(dist, path_or_buff)
+        write_csv(dist, path_or_buff)
     if per_centre:
         values["centres"] = np.asarray(centres)
         return dist, summary, values

@@ -94,15 +94,6 @@ def checked_pairs(pairs, atoms_per_mol, mass=None):
     return species, jobs
 
 
-def same_rows(col, start, m, n, what, label):
-    """Row [n] that the m molecules of n atoms from atom `start` on share in the per-atom column `col` (charges,
-    types), or a ValueError."""
-    rows = np.asarray(col[start:start + m * n], dtype=np.float64).reshape(m, n)
-    if m and np.any(rows != rows[0]):
-        raise ValueError("species %s: the molecules of the type do not all carry the same %s" % (label, what))
-    return rows[0] if m else np.zeros(n)
-
-
 def species_terms(species, num_mols, atoms_per_mol, q=None, types=None, mass=None):
     """(site_terms, vec_terms) of the species, as backend.mol_moments takes them; q, types: per-atom columns [N] of a
     frame (charges for a dipole, atom types for a centre of mass)."""
@@ -113,7 +104,7 @@ def species_terms(species, num_mols, atoms_per_mol, q=None, types=None, mass=Non
         if vector is None:
             vec_terms.append([])
         elif vector == "dipole":
-            row = same_rows(q, start, m, n, "charges", species_label(sp))
+            row = mol_series.same_rows(q, start, m, n, "charges", species_label(sp))
             vec_terms.append([(k, float(row[k])) for k in range(1, n)])
         else:
             pair = [(vector[0] - 1, -1.0), (vector[1] - 1, 1.0)]
@@ -121,7 +112,7 @@ def species_terms(species, num_mols, atoms_per_mol, q=None, types=None, mass=Non
         if site == "first" or site == 1:
             site_terms.append([])
         elif site == "com":
-            row = T.masses(same_rows(types, start, m, n, "atom types", species_label(sp)), mass)
+            row = T.masses(mol_series.same_rows(types, start, m, n, "atom types", species_label(sp)), mass)
             total = float(np.sum(row))
             site_terms.append([(k, float(row[k]) / total) for k in range(1, n)])
         else:
@@ -214,9 +205,7 @@ def calc_orientational_correlation(r_cut, bin_size, pairs, filename, num_mols, n
     n_bins = int(r_cut / bin_size)
     if not 1 <= n_bins <= backend.VECTOR_PAIR_MAX_BINS:
         raise ValueError("int(r_cut / bin_size) must be in [1, %d] (%d)" % (backend.VECTOR_PAIR_MAX_BINS, n_bins))
-    from .angular_distribution import _refuse_triclinic
-
-    _refuse_triclinic(filename)
+    T.refuse_triclinic(filename)
     wrapped = coords == "wrapped"
     dipole = any(sp[1] == "dipole" for sp in species)
     labels = [species_label(sp) for sp in species]

@@ -31,6 +31,7 @@ import pandas as pd
 from .. import backend
 from ..common import sayer
 from ..common.com_mols import calc_atom_type, check_atom_count, molecule_layout
+from ..common.tables import write_csv as _write_csv
 from ..common.trajectory import all_frames, batches, lengths_block, load_frames, same_labels, xyz_block
 from ..dist import is_writer
 
@@ -210,23 +211,6 @@ def _labels_and_props(cache, batch, altered, num_mols, num_atoms_per_mol, num_ty
     props = [cache.props(f.lengths, lab, lab, num_types, mass, partial_relations, altered, num_atoms_per_mol)
              for f, lab in zip(batch, labels)]
     return same_labels(labels).astype(np.int32), props
-
-
-def _write_csv(df, path_or_buf):
-    """`df.to_csv(path_or_buf, index=False)` — byte for byte — for the all-float64 frames these functions write,
-    without pandas' per-cell formatting machinery (20 ms for 400 x 12 values, a quarter of a C2-size call): pandas
-    writes the shortest round-trip decimal of every double, which is Python's repr, and an empty field for NaN."""
-    simple = (isinstance(path_or_buf, (str, bytes)) or hasattr(path_or_buf, "__fspath__")) and \
-        all(str(t) == "float64" for t in df.dtypes) and \
-        not any(ch in str(c) for c in df.columns for ch in ',"\n\r')
-    if not simple:
-        df.to_csv(path_or_buf, index=False)
-        return
-    lines = [",".join(str(c) for c in df.columns)]
-    for row in df.to_numpy().tolist():
-        lines.append(",".join("" if v != v else repr(v) for v in row))
-    with open(path_or_buf, "w", newline="") as fh:
-        fh.write("\n".join(lines) + "\n")
 
 
 def _save_rdf(radii, relation_matrix, path_or_buf, save_mode, rdf_part_sum, rdf_full_sum=None):

@@ -23,14 +23,11 @@ import numpy as np
 import pandas as pd
 
 from .. import backend
-from ..common.com_mols import calc_atom_type, molecule_layout
+from ..common.com_mols import atom_molecules, molecule_layout
 from ..common.constants import BOHR_RADIUS
-from ..common.trajectory import frame_batches
+from ..common.trajectory import refuse_triclinic, typed_batches
 from ..dist import is_writer
-from .angular_distribution import _refuse_triclinic
 
-MAX_BATCH_BYTES = 1 << 28  # planes of the frames handed to the GPU in one call
-_COLS = ["id", "type", "x", "y", "z"]  # the planes of a batch
 _ANGSTROM_PER_BOHR = BOHR_RADIUS * 1e10
 
 
@@ -112,30 +109,20 @@ def calc_spatial_distribution(r_cut, bin_size, reference, observed, filename, nu
     if G > backend.SDF_MAX_GRID or S * G ** 3 > backend.SDF_MAX_CELLS:
         raise ValueError("%d species x %d**3 cells: at most %d cells per axis and %d cells per call (larger bin_size, "
                          "or fewer species)" % (S, G, backend.SDF_MAX_GRID, backend.SDF_MAX_CELLS))
-    seg_off, _, _ = molecule_layout(num_mols, num_atoms_per_mol)
-    n_layout = int(seg_off[-1])
-    mol_of = None
-    if exclude_same_molecule:
-        mol_of = np.repeat(np.arange(len(seg_off) - 1), np.diff(seg_off)).astype(np.int32)
-    _refuse_triclinic(filename)
+    mol_of = atom_molecules(num_mols, num_atoms_per_mol)[1] if exclude_same_molecule else None
+    refuse_triclinic(filename)
     compute = compute or backend.sdf_hist
 
     hist = np.zeros((S, G, G, G), dtype=np.uint64)
     degen = np.zeros(S, dtype=np.uint64)
-    types = cand = cand_class = None
+    cand = cand_class = None
     n_frames, bad_rows, inv_vol = 0, 0, 0.0
-    for steps, boxes, planes in frame_batches(filename, _COLS, MAX_BATCH_BYTES, n_layout):
-        for pl in planes:
-            lab = calc_atom_type(pl[0], num_mols, num_atoms_per_mol)
-            if types is None:
-                types = lab.astype(np.int32)
-                cand = np.flatnonzero(np.isin(types, species)).astype(np.int32)
-                slot = {ty: s for s, ty in enumerate(species)}
-                cand_class = np.array([slot[ty] for ty in types[cand]], dtype=np.int32)
-            elif len(lab) != len(types) or not np.array_equal(lab, types):
-                raise ValueError("every frame must hold the same atom types in id order")
-        h, d, _, bad = compute(np.ascontiguousarray(planes[:, 2:5]), boxes, origin, x_atom, xy_atom, cand, cand_class,
-                               S, r_cut, bin_size, mol_of=mol_of)
+    for steps, boxes, xyz, types in typed_batches(filename, num_mols, num_atoms_per_mol, True):
+        if cand is None:
+            cand = np.flatnonzero(np.isin(types, species)).astype(np.int32)
+            slot = {ty: s for s, ty in enumerate(species)}
+            cand_class = np.array([slot[ty] for ty in types[cand]], dtype=np.int32)
+        h, d, _, bad = compute(xyz, boxes, origin, x_atom, xy_atom, cand, cand_class, S, r_cut, bin_size, mol_of=mol_of)
         hist += np.asarray(h).astype(np.uint64, copy=False)  # (a `compute` may hand back signed counts)
         degen += np.asarray(d).astype(np.uint64, copy=False)
         bad_rows += int(bad)

@@ -206,3 +206,27 @@ def test_changing_types_raise(A, tmp_path):
                    ["id", "type", "x", "y", "z"], tab)
     with pytest.raises(ValueError, match="same atom types"):
         A.calc_angular_distribution(2.5, 7.0, [(1, 1, 1)], str(tmp_path / "t.*.dump"), save_mode=False)
+
+
+def test_where_the_batches_are_cut_shows_in_no_result(A, tmp_path, monkeypatch):
+    """Three different frames in batches of one frame, two frames and everything: equal DataFrames, the same CSV bytes."""
+    from mdproptools_amd import backend
+    from mdproptools_amd.common import trajectory
+
+    fake, calls = backend.angle_hist, []
+    monkeypatch.setattr(backend, "angle_hist", lambda xyz, *a, **kw: calls.append(len(xyz)) or fake(xyz, *a, **kw))
+    n = 30
+    xyz, box = _random_system(11, n, [6.0, 5.0, 4.0], n_frames=3)
+    pattern = R.write_dumps(xyz, box, np.arange(n) % 3 + 1, str(tmp_path))
+    frame_bytes = 5 * n * 8  # the planes id type x y z of one frame
+    results = []
+    for k, cap in enumerate((frame_bytes, 2 * frame_bytes, trajectory.TYPED_BATCH_BYTES)):
+        monkeypatch.setattr(trajectory, "TYPED_BATCH_BYTES", cap)
+        out = tmp_path / ("adf%d.csv" % k)
+        adf, summary = A.calc_angular_distribution([(2.5, 2.5), (2.5, 2.0)], 7.0, [(2, 1, 2), (2, 1, 3)], pattern,
+                                                   path_or_buff=str(out))
+        results.append((adf, summary, out.read_bytes()))
+    assert calls == [1, 1, 1, 2, 1, 3]
+    assert results[0][0]["count_2-1-2"].sum() > 100 and results[0][0]["count_2-1-3"].sum() > 100
+    for adf, summary, text in results[1:]:
+        assert adf.equals(results[0][0]) and summary.equals(results[0][1]) and text == results[0][2]

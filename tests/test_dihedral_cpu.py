@@ -286,7 +286,7 @@ def test_correlation_table_of_a_two_state_series(monkeypatch, tmp_path):
         return np.stack([S1, S2], axis=2)
 
     monkeypatch.setattr(M, "_load_series", load)
-    monkeypatch.setattr(M, "_refuse_triclinic", lambda filename: None)
+    monkeypatch.setattr(M, "refuse_triclinic", lambda filename: None)
     monkeypatch.setattr(backend, "orient_corr", orient_corr)
     entries = [(1, 1, 2, 3, 4), (2, [(1, 2, 3, 4), (3, 4, 5, 6)])]
     df = calc_dihedral_correlation(entries, "none.*", [30, 5], [4, 6], dt=2, working_dir=str(tmp_path))
