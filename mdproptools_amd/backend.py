@@ -1297,10 +1297,7 @@ def axis_vectors(x, box, job_atom0, job_mols, job_len, terms, out=None, ctx=None
     J = len(terms)
     F, A, bx, a0, mols, length, S = _mol_jobs(x, box, job_atom0, job_mols, job_len, J,
                                               "job_atom0, job_mols, job_len and terms must hold one entry per job")
-    t_off = np.zeros(J + 1, dtype=np.int64)
-    t_off[1:] = np.cumsum([len(t) for t in terms])
-    t_atom = _i32([k for t in terms for k, _ in t])
-    t_w = _f64([w for t in terms for _, w in t])
+    t_off, t_atom, t_w = _term_lists(terms, J, "terms")
     xp, x_dev, keep = as_input(x, ctx)
     res, up, u_dev = _dest(out, (S, 3, F), ctx, pinned=True)
     degenerate = np.zeros(max(J, 1), dtype=np.uint64)

@@ -17,6 +17,7 @@
 #include <cmath>
 #include <vector>
 
+#include "call_tables.h"
 #include "ctx.h"
 #include "mol_tile.h"
 
@@ -171,15 +172,16 @@ int mdhip_dihedral_angles(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, con
     const int n_classes = (int)plan.classes.size();
     MolIo io;
     if ((rc = io.open(ctx, n_frames, n_atoms, x, x_on_device, box, U, U_on_device, plan.series))) return rc;
-    // tables: classes | jobs | edges | degenerate counters
-    const size_t cls_b = (size_t)n_classes * sizeof(MolClass), jobs_b = (size_t)n_jobs * sizeof(DhJob);
-    const size_t edge_b = hist ? (size_t)nb2 * 8 : 0, deg_b = (size_t)n_jobs * 8;
-    MD_WS(d_tab, char, WS_TABLES, cls_b + jobs_b + edge_b + deg_b);
-    if ((rc = mdhip_h2d_small(ctx, d_tab, plan.classes.data(), cls_b))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + cls_b, sorted.data(), jobs_b))) return rc;
-    if (hist && (rc = mdhip_h2d_small(ctx, d_tab + cls_b + jobs_b, cos_edges, edge_b))) return rc;
-    unsigned long long *d_deg = (unsigned long long *)(d_tab + cls_b + jobs_b + edge_b);
-    MD_HIP(hipMemsetAsync(d_deg, 0, deg_b, ctx->stream));
+    const MolClass *d_cls;
+    const DhJob *d_jobs;
+    const double *d_edges;
+    unsigned long long *d_deg;
+    CallTables tab;
+    tab.add(plan.classes.data(), (size_t)n_classes, &d_cls);
+    tab.add(sorted.data(), (size_t)n_jobs, &d_jobs);
+    tab.add_optional(hist ? cos_edges : nullptr, (size_t)nb2, &d_edges);
+    tab.add_zeroed((size_t)n_jobs, &d_deg);
+    if ((rc = upload_tables(ctx, tab, WS_TABLES))) return rc;
     const int n_cells = hist ? n_rows * n_bins : 0;
     const size_t hist_b = (size_t)n_cells * 8;
     unsigned long long *d_hist = nullptr;
@@ -194,13 +196,13 @@ int mdhip_dihedral_angles(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, con
     KernelTimer timer(ctx, 0);
     rc = mt_launch(ctx, "dihedral_kernel", timer, plan.tiles, n_frames, [&](dim3 grid, long long t0, long long ft0) {
         hipLaunchKernelGGL(dihedral_kernel, grid, dim3(MT_THREADS), lds, ctx->stream, io.x, io.box, (long long)n_frames,
-                           (long long)n_atoms, (const MolClass *)d_tab, n_classes, (const DhJob *)(d_tab + cls_b),
-                           (const double *)(d_tab + cls_b + jobs_b), n_bins, n_cells, t0, ft0, d_hist, io.U, d_deg);
+                           (long long)n_atoms, d_cls, n_classes, d_jobs, d_edges, n_bins, n_cells, t0, ft0, d_hist, io.U.dev,
+                           d_deg);
     });
     if (rc) return rc;
-    if (U && !U_on_device && (rc = mdhip_result(cs, U, io.U, io.u_bytes, 0))) return rc;
+    if ((rc = io.U.deliver(cs))) return rc;
     if (hist && (rc = mdhip_result(cs, hist, d_hist, hist_b, 0))) return rc;
-    if ((rc = mdhip_result(cs, degenerate, d_deg, deg_b, 0))) return rc;
+    if ((rc = mdhip_result(cs, degenerate, d_deg, (size_t)n_jobs * 8, 0))) return rc;
     return mdhip_end_timed(cs, timer);
 }
 

@@ -25,6 +25,7 @@
 
 #pragma clang fp contract(off)
 
+#include "call_tables.h"
 #include "cell_plan.h"
 #include "shell_search.h"  // (rsq: the single wrap of the shell searches)
 
@@ -365,13 +366,13 @@ int mdhip_free_volume(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const d
     MD_HIP(hipSetDevice(ctx->device));
     int rc;
     const int n_cells = n_classes * nbins + n_classes + 1;
-    // tables: classes | radius | edges | probe
-    const size_t cls_b = (n * 4 + 7) / 8 * 8, rad_b = (size_t)n_classes * 8, edge_b = ((size_t)nbins + 1) * 8, probe_b = (size_t)n_probes * 8;
-    MD_WS(d_tab, char, WS_TABLES, cls_b + rad_b + edge_b + probe_b);
-    if ((rc = mdhip_h2d_small(ctx, d_tab, atom_class, n * 4))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + cls_b, radius, rad_b))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + cls_b + rad_b, edges, edge_b))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + cls_b + rad_b + edge_b, probe, probe_b))) return rc;
+    FvBatch b;
+    CallTables tab;
+    tab.add(atom_class, n, &b.atom_class);
+    tab.add(radius, (size_t)n_classes, &b.radius);
+    tab.add(edges, (size_t)nbins + 1, &b.edges);
+    tab.add(probe, (size_t)n_probes, &b.probe);
+    if ((rc = upload_tables(ctx, tab, WS_TABLES))) return rc;
     MD_WS(d_cnt, unsigned long long, WS_HIST, (size_t)n_cells * 8);
     MD_HIP(hipMemsetAsync(d_cnt, 0, (size_t)n_cells * 8, ctx->stream));
     const size_t free_b = (size_t)n_frames * (size_t)n_probes * 8;
@@ -395,11 +396,6 @@ int mdhip_free_volume(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const d
     if (s_out && !field_on_device && !(d_s = (double *)mdhip_ws(ctx, WS_OUT, (size_t)Fb * (size_t)G * 8))) return MDHIP_ENOMEM;
     if (nearest_out && !field_on_device && !(d_near = (int *)mdhip_ws(ctx, WS_OUT2, (size_t)Fb * (size_t)G * 4))) return MDHIP_ENOMEM;
 
-    FvBatch b;
-    b.atom_class = (const int *)d_tab;
-    b.radius = (const double *)(d_tab + cls_b);
-    b.edges = (const double *)(d_tab + cls_b + rad_b);
-    b.probe = (const double *)(d_tab + cls_b + rad_b + edge_b);
     b.box = d_box, b.fr = d_fr, b.cellid = d_cellid, b.start = d_start, b.cursor = d_cursor, b.planes = d_planes, b.index = d_index;
     b.n = n_atoms, b.units_per_frame = max_units, b.stride = stride;
     b.g[0] = grid[0], b.g[1] = grid[1], b.g[2] = grid[2], b.G = (int)G;

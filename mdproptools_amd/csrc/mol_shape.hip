@@ -20,8 +20,9 @@
 #include <cstring>
 #include <vector>
 
+#include "call_tables.h"
 #include "group_pairs.h"  // (gp_check_edges, gp_edges: the edge table of the siblings)
-#include "mol_tile.h"     // (mt_wrap, MolIo)
+#include "mol_tile.h"     // (mt_wrap, MolIo, MolOut, mt_plan_error, mt_launch_totals)
 #include "shape_plan.h"
 
 #pragma clang fp contract(off)
@@ -263,8 +264,6 @@ __global__ __launch_bounds__(SH_MOLS) void mol_shape_kernel(
 }
 
 constexpr int SHT_THREADS = 256;
-constexpr long long SHT_MAX_X = 1 << 20;  // frames per launch
-constexpr int SHT_MAX_Y = 65535;          // jobs per launch
 
 // Block (x, y): frame f0 + x, job job0 + y. totals[job][.][f] = the sums over the job's molecules of Rg^2, sqrt(Rg^2),
 // Ree^2, lambda1, lambda2, lambda3, kappa^2, I2, Rg^2 * Rg^2 of the values as written: lane i adds the molecules i,
@@ -337,15 +336,14 @@ int mdhip_mol_shape(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const dou
         const int e0 = job_ends[2 * (size_t)j], e1 = job_ends[2 * (size_t)j + 1];
         MD_REQUIRE(e0 >= 0 && e0 < job_len[j] && e1 >= 0 && e1 < job_len[j], "job %d: the end atoms must be in [0, job_len)", j);
     }
-    MD_REQUIRE(plan.error != SH_PLAN_RANGE, "job %d runs past the %lld atoms of a frame", plan.bad_job, (long long)n_atoms);
-    MD_REQUIRE(plan.error != SH_PLAN_RESULT, "result too large");
+    int rc;
+    if ((rc = mt_plan_error(ctx, plan, n_atoms))) return rc;
     MD_REQUIRE(w_off[n_jobs] < (1ll << 31), "weight table too large");
     const std::vector<double> msum = shape_mass_sums(n_jobs, job_len, w_off, w);
     for (int j = 0; j < n_jobs; ++j)
         MD_REQUIRE(msum[(size_t)j] > 0.0 && msum[(size_t)j] < __builtin_inf(), "job %d: the weights must add up to a positive, finite mass", j);
     const int n_cells = 2 * nbins + n_kbins + 3;
     MD_REQUIRE((size_t)n_jobs * (size_t)n_cells < ((size_t)1 << 24), "result too large");
-    int rc;
     if ((rc = gp_check_edges(ctx, edges, nbins, n_jobs))) return rc;
     std::vector<double> own;
     if ((rc = gp_edges(ctx, edges, own, bin_size, nbins))) return rc;
@@ -357,30 +355,24 @@ int mdhip_mol_shape(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const dou
     const long long S = plan.series;
     MolIo io;
     if ((rc = io.open(ctx, n_frames, n_atoms, x, x_on_device, box, nullptr, 0, S))) return rc;
-    // where the kernel writes the values: the caller's buffer when that is on the device, else workspace; the totals read
-    // them back, so they are written somewhere whenever totals are asked for
+    // the totals read the values (and I2, which no caller gets) back, so they are written somewhere whenever totals are
+    // asked for
     const size_t pm_b = (size_t)n_frames * SH_VALS * (size_t)S * 8, i2_b = (size_t)n_frames * (size_t)S * 8;
-    double *d_pm = nullptr, *d_i2 = nullptr;
-    if (per_mol || totals) {
-        d_pm = per_mol && per_mol_on_device ? per_mol : (double *)mdhip_ws(ctx, WS_OUT, std::max<size_t>(pm_b, 8));
-        if (!d_pm) return MDHIP_ENOMEM;
-    }
-    if (totals) {
-        d_i2 = (double *)mdhip_ws(ctx, WS_OUT2, std::max<size_t>(i2_b, 8));
-        if (!d_i2) return MDHIP_ENOMEM;
-    }
-    // tables: jobs | staged runs | walk runs | weights | edges
+    MolOut o_pm, o_i2;
+    if ((rc = o_pm.open(ctx, WS_OUT, per_mol, per_mol_on_device, pm_b, totals != nullptr))) return rc;
+    if ((rc = o_i2.open(ctx, WS_OUT2, nullptr, 0, i2_b, totals != nullptr))) return rc;
+    double *const d_pm = o_pm.dev, *const d_i2 = o_i2.dev;
     const size_t n_st = plan.staged.size(), n_wk = plan.walk.size();
-    const size_t jobs_b = (size_t)n_jobs * sizeof(ShJob), st_b = n_st * sizeof(ShRun), wk_b = n_wk * sizeof(ShRun);
-    const size_t w_b = (size_t)w_off[n_jobs] * 8, edge_b = ((size_t)nbins + 1) * 8;
-    MD_WS(d_tab, char, WS_TABLES, jobs_b + st_b + wk_b + w_b + edge_b);
-    if ((rc = mdhip_h2d_small(ctx, d_tab, jobs.data(), jobs_b))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + jobs_b, plan.staged.data(), st_b))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + jobs_b + st_b, plan.walk.data(), wk_b))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + jobs_b + st_b + wk_b, w, w_b))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + jobs_b + st_b + wk_b + w_b, edges, edge_b))) return rc;
-    const ShJob *d_jobs = (const ShJob *)d_tab;
-    const double *d_w = (const double *)(d_tab + jobs_b + st_b + wk_b), *d_edges = (const double *)(d_tab + jobs_b + st_b + wk_b + w_b);
+    const ShJob *d_jobs;
+    const ShRun *d_staged, *d_walk;
+    const double *d_w, *d_edges;
+    CallTables tab;
+    tab.add(jobs.data(), (size_t)n_jobs, &d_jobs);
+    tab.add(plan.staged.data(), n_st, &d_staged);
+    tab.add(plan.walk.data(), n_wk, &d_walk);
+    tab.add(w, (size_t)w_off[n_jobs], &d_w);
+    tab.add(edges, (size_t)nbins + 1, &d_edges);
+    if ((rc = upload_tables(ctx, tab, WS_TABLES))) return rc;
     const size_t cnt_b = (size_t)n_jobs * (size_t)n_cells * 8;
     MD_WS(d_cnt, unsigned long long, WS_HIST, cnt_b);
     MD_HIP(hipMemsetAsync(d_cnt, 0, cnt_b, ctx->stream));
@@ -399,7 +391,7 @@ int mdhip_mol_shape(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const dou
         MD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mol_shape_kernel<true>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)SH_MAX_LDS));
         hipLaunchKernelGGL(mol_shape_kernel<true>, dim3((unsigned)n_st, gy), dim3(SH_MOLS), lds_staged, ctx->stream, io.x, io.box,
-                           (long long)n_frames, (long long)n_atoms, S, d_jobs, (const ShRun *)(d_tab + jobs_b), d_w, d_edges,
+                           (long long)n_frames, (long long)n_atoms, S, d_jobs, d_staged, d_w, d_edges,
                            gscale, (int)nbins, (int)n_kbins, n_cells, unwrap, d_cnt, d_pm, d_i2);
         MD_HIP(hipGetLastError());
         ++launches;
@@ -407,26 +399,24 @@ int mdhip_mol_shape(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const dou
     if (n_wk) {
         const unsigned gy = shape_frame_slices((long long)n_wk, n_frames, ctx->cu_count);
         hipLaunchKernelGGL(mol_shape_kernel<false>, dim3((unsigned)n_wk, gy), dim3(SH_MOLS), lds, ctx->stream, io.x, io.box,
-                           (long long)n_frames, (long long)n_atoms, S, d_jobs, (const ShRun *)(d_tab + jobs_b + st_b), d_w,
-                           d_edges, gscale, (int)nbins, (int)n_kbins, n_cells, unwrap, d_cnt, d_pm, d_i2);
+                           (long long)n_frames, (long long)n_atoms, S, d_jobs, d_walk, d_w, d_edges, gscale, (int)nbins,
+                           (int)n_kbins, n_cells, unwrap, d_cnt, d_pm, d_i2);
         MD_HIP(hipGetLastError());
         ++launches;
     }
     if (totals) {
-        // (launch dimensions: frames in slices of 2^20 along x, jobs in slices of 65535 along y)
-        for (long long f0 = 0; f0 < n_frames; f0 += SHT_MAX_X)
-            for (int j0 = 0; j0 < n_jobs; j0 += SHT_MAX_Y, ++launches) {
-                const dim3 grid((unsigned)std::min<long long>(SHT_MAX_X, n_frames - f0), (unsigned)std::min(SHT_MAX_Y, n_jobs - j0));
-                hipLaunchKernelGGL(shape_total_kernel, grid, dim3(SHT_THREADS), 0, ctx->stream, (const double *)d_pm,
-                                   (const double *)d_i2, (long long)n_frames, S, d_jobs, f0, j0, d_tot);
-                MD_HIP(hipGetLastError());
-            }
+        rc = mt_launch_totals(ctx, n_frames, n_jobs, [&](dim3 grid, long long f0, int j0) {
+            hipLaunchKernelGGL(shape_total_kernel, grid, dim3(SHT_THREADS), 0, ctx->stream, (const double *)d_pm,
+                               (const double *)d_i2, (long long)n_frames, S, d_jobs, f0, j0, d_tot);
+        });
+        if (rc < 0) return rc;
+        launches += rc;
     }
     ctx->last_kernel = n_st ? "mol_shape_kernel<true>" : "mol_shape_kernel<false>";
     ctx->last_launches = launches;
     timer.stop();
     if (totals && (rc = mdhip_result(cs, totals, d_tot, tot_b, 0))) return rc;
-    if (per_mol && !per_mol_on_device && (rc = mdhip_result(cs, per_mol, d_pm, pm_b, 0))) return rc;
+    if ((rc = o_pm.deliver(cs))) return rc;
     if (hist_rg || hist_ee || hist_k || beyond || degenerate) {
         // the rows come back whole and are dealt to the caller's arrays once the copy has landed
         unsigned long long *h_cnt = (unsigned long long *)mdhip_pin(ctx, cnt_b);

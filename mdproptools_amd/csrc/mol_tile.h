@@ -1,6 +1,14 @@
-// mol_tile.h — the tile, the job plan and the launch plumbing of the per-molecule series kernels: mdhip_axis_vectors
-// (reorient.hip) and mdhip_dihedral_angles (dihedrals.hip). A JOB covers job_mols molecules of job_len atoms from atom
-// job_atom0 on and yields one series U[s][.][t] per molecule; the trajectory is frame-major [F][3][A], U time-major [S][3][F].
+// mol_tile.h — what the four calls over JOBS OF MOLECULES share: mdhip_axis_vectors (reorient.hip), mdhip_dihedral_angles
+// (dihedrals.hip), mdhip_mol_moments (moments.hip) and mdhip_mol_shape (mol_shape.hip, through shape_plan.h). A JOB
+// covers job_mols molecules of job_len atoms from atom job_atom0 on and yields one series per molecule; the trajectory
+// is frame-major [F][3][A].
+// All four: the job walk (mol_jobs: the range rule, series0, the 2^40 result rule), its refusal texts (mt_plan_error),
+//   the call's arrays on the device (MolIo), where a result is written and how it reaches the caller (MolOut) and the
+//   single wrap (mt_wrap). Moments and shape besides: the launch loop of their per-(frame, job) totals
+//   (mt_launch_totals). Axis vectors and moments: the ascent rule of a term list (mt_terms_ascend).
+// Axis vectors, dihedrals and moments work the tile below under mt_launch (shape has runs of its own: shape_plan.h);
+// the first two write series U[s][.][t], time-major [S][3][F], through the LDS tile (mt_store). The device tables of
+// all four are packed by call_tables.h.
 // The tile: a workgroup owns MT_TM = 64 molecules x MT_TF = 64 frames. Lane = molecule while reading (consecutive lanes
 //   read atoms one molecule apart, every fetched line is used by the neighbouring terms and lanes), the finished
 //   components go through an LDS tile ([C][64][64 + 1], conflict-free both ways), lane = frame while writing (512
@@ -42,14 +50,41 @@ struct MolClass {
 // RANGE: job `bad_job` does not lie inside the n_atoms atoms of a frame; RESULT: with it the series times n_frames reach 2^40
 enum MolPlanError { MOL_PLAN_OK = 0, MOL_PLAN_RANGE, MOL_PLAN_RESULT };
 
-struct MolPlan {
-    std::vector<MolClass> classes;   // in the order of their first job
-    std::vector<int> order;          // order[p] = the job (call order) at position p: class after class, call order inside
+// The job walk of every plan: where the series of each job start, and the FIRST job that breaks a rule.
+struct MolJobs {
     std::vector<long long> series0;  // first series of every job, in call order
-    long long series = 0, tiles = 0;
+    long long series = 0;
     int error = MOL_PLAN_OK, bad_job = -1;  // the FIRST offending job
     // the jobs whose own checks an entry point makes before it reports `error` (RESULT comes behind every job's checks)
     int checked_jobs() const { return error == MOL_PLAN_RANGE ? bad_job : (int)series0.size(); }
+};
+
+// Walks the jobs in call order into `w` and stops at the first one out of RANGE. fits(j, atom0, mols, len) sees every
+// job in range and says whether the plan's own result rule still holds with it (true where there is none); the first
+// job at which it does not, or with which the series times n_frames reach 2^40, is the RESULT error — the walk goes on
+// behind it, since a later job out of range is reported first.
+template <class Fits>
+inline void mol_jobs(MolJobs &w, int n_jobs, const int64_t *job_atom0, const int64_t *job_mols, const int32_t *job_len,
+                     int64_t n_atoms, int64_t n_frames, Fits fits)
+{
+    w.series0.resize((size_t)n_jobs);
+    for (int j = 0; j < n_jobs; ++j) {
+        const long long len = job_len[j], mols = job_mols[j], a0 = job_atom0[j];
+        if (!(len >= 1 && mols >= 0 && a0 >= 0 && a0 <= n_atoms && mols <= (n_atoms - a0) / len)) {
+            w.error = MOL_PLAN_RANGE, w.bad_job = j;
+            return;
+        }
+        w.series0[(size_t)j] = w.series;
+        w.series += mols;
+        const bool fit = fits(j, a0, mols, len);
+        if (w.error == MOL_PLAN_OK && (w.series >= (1ll << 40) / n_frames || !fit)) w.error = MOL_PLAN_RESULT, w.bad_job = j;
+    }
+}
+
+struct MolPlan : MolJobs {
+    std::vector<MolClass> classes;  // in the order of their first job
+    std::vector<int> order;         // order[p] = the job (call order) at position p: class after class, call order inside
+    long long tiles = 0;
 };
 
 // pool = false: every job is a class of its own. pool = true: jobs with equal (atom0, mols, len) share a class until it
@@ -59,15 +94,9 @@ inline MolPlan mol_plan(int n_jobs, const int64_t *job_atom0, const int64_t *job
                         int64_t n_atoms, int64_t n_frames, bool pool, int max_class_jobs)
 {
     MolPlan pl;
-    pl.series0.resize((size_t)n_jobs);
     std::vector<int> class_of((size_t)n_jobs);
     std::map<std::tuple<long long, long long, long long>, int> open;  // (atom0, mols, len) -> the class still taking jobs
-    for (int j = 0; j < n_jobs; ++j) {
-        const long long len = job_len[j], mols = job_mols[j], a0 = job_atom0[j];
-        if (!(len >= 1 && mols >= 0 && a0 >= 0 && a0 <= n_atoms && mols <= (n_atoms - a0) / len)) {
-            pl.error = MOL_PLAN_RANGE, pl.bad_job = j;
-            return pl;
-        }
+    mol_jobs(pl, n_jobs, job_atom0, job_mols, job_len, n_atoms, n_frames, [&](int j, long long a0, long long mols, long long len) {
         int &c = class_of[(size_t)j] = -1;
         const auto it = pool ? open.find(std::make_tuple(a0, mols, len)) : open.end();
         if (it != open.end() && pl.classes[(size_t)it->second].n_jobs < max_class_jobs) c = it->second;
@@ -77,10 +106,8 @@ inline MolPlan mol_plan(int n_jobs, const int64_t *job_atom0, const int64_t *job
             if (pool) open.insert_or_assign(std::make_tuple(a0, mols, len), c);
         }
         ++pl.classes[(size_t)c].n_jobs;
-        pl.series0[(size_t)j] = pl.series;
-        pl.series += mols;
-        if (pl.error == MOL_PLAN_OK && pl.series >= (1ll << 40) / n_frames) pl.error = MOL_PLAN_RESULT, pl.bad_job = j;
-    }
+        return true;
+    });
     if (pl.error != MOL_PLAN_OK) return pl;
     int first = 0;
     for (MolClass &c : pl.classes) {
@@ -171,21 +198,50 @@ __device__ __forceinline__ void mt_store(const MolTile &t, const double *s_u, lo
 
 // ---- host launch helpers --------------------------------------------------------------------------------------------
 
-// what mol_plan refused, in the words of the entry points
-inline int mt_plan_error(mdhip_ctx *ctx, const MolPlan &pl, int64_t n_atoms)
+// what the job walk refused, in the words of the entry points
+inline int mt_plan_error(mdhip_ctx *ctx, const MolJobs &pl, int64_t n_atoms)
 {
     MD_REQUIRE(pl.error != MOL_PLAN_RANGE, "job %d runs past the %lld atoms of a frame", pl.bad_job, (long long)n_atoms);
     MD_REQUIRE(pl.error != MOL_PLAN_RESULT, "result too large");
     return MDHIP_OK;
 }
 
+// the rule that the term lists of axis vectors and moments share: the atoms [t0, t1) of job j's list
+inline int mt_terms_ascend(mdhip_ctx *ctx, int j, const int32_t *atom, long long t0, long long t1, long long len)
+{
+    for (long long k = t0; k < t1; ++k)
+        MD_REQUIRE(atom[k] >= 1 && atom[k] < len && (k == t0 || atom[k] > atom[k - 1]),
+                   "job %d: the terms' atoms must ascend strictly within [1, job_len)", j);
+    return MDHIP_OK;
+}
+
+// Where a kernel writes a result of `bytes` bytes: the caller's buffer when that is on the device, else workspace
+// `slot`, from where deliver() sends it to the caller's once the kernel has run. Nothing asked for (dst == NULL):
+// nowhere (dev stays null), unless `needed` says that the kernel must write it somewhere anyway — a later kernel of
+// the call reads it back; that workspace copy is delivered to nobody.
+struct MolOut {
+    double *dev = nullptr;
+    int open(mdhip_ctx *ctx, int slot, double *dst, int dst_on_device, size_t bytes_, bool needed = false)
+    {
+        bytes = bytes_;
+        if (dst && dst_on_device) dev = dst;
+        else host = dst;
+        if (dev || !(dst || needed)) return MDHIP_OK;
+        dev = (double *)mdhip_ws(ctx, slot, std::max<size_t>(bytes, 8));
+        return dev ? MDHIP_OK : MDHIP_ENOMEM;
+    }
+    int deliver(CallScope &cs) const { return host ? mdhip_result(cs, host, dev, bytes, 0) : MDHIP_OK; }
+
+private:
+    double *host = nullptr;  // the caller's buffer, when the result has to be copied out to it
+    size_t bytes = 0;
+};
+
 // A call's arrays on the context's device: x [F][3][A] (staged into WS_XYZ_I unless it is there), box [F][3] (host or NULL, into
-// WS_BOX) and where the kernel writes U [series][3][F] — the caller's buffer when that is on the device, else WS_OUT,
-// from where it goes to the caller's (u_bytes) once the kernel has run. U == NULL: no series.
+// WS_BOX) and the series U [series][3][F] in WS_OUT unless the caller's buffer is on the device. U == NULL: no series.
 struct MolIo {
     const double *x = nullptr, *box = nullptr;
-    double *U = nullptr;
-    size_t u_bytes = 0;
+    MolOut U;
     int open(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const double *x_, int x_on_device, const double *box_,
              double *U_, int U_on_device, long long series)
     {
@@ -198,9 +254,7 @@ struct MolIo {
             if ((rc = mdhip_h2d_small(ctx, d_b, box_, (size_t)n_frames * 3 * 8))) return rc;
             box = d_b;
         }
-        u_bytes = U_ ? (size_t)series * 3 * (size_t)n_frames * 8 : 0;
-        U = U_ && !U_on_device ? (double *)mdhip_ws(ctx, WS_OUT, std::max<size_t>(u_bytes, 8)) : U_;
-        return U_ && !U ? MDHIP_ENOMEM : MDHIP_OK;
+        return U.open(ctx, WS_OUT, U_, U_on_device, (size_t)series * 3 * (size_t)n_frames * 8);
     }
 };
 
@@ -220,6 +274,24 @@ inline int mt_launch(mdhip_ctx *ctx, const char *kernel, KernelTimer &timer, lon
     ctx->last_launches = launches;
     timer.stop();
     return MDHIP_OK;
+}
+
+// launch(grid, f0, j0) for every piece of the frames x jobs grid of a totals kernel (block (x, y): frame f0 + x, job
+// j0 + y): frames in slices of 2^20 along x, jobs in slices of 65535 along y. Returns the number of launches, or the
+// (negative) code of the launch that failed.
+constexpr long long MT_TOTALS_MAX_X = 1 << 20;
+constexpr int MT_TOTALS_MAX_Y = 65535;
+template <class Launch>
+inline int mt_launch_totals(mdhip_ctx *ctx, int64_t n_frames, int n_jobs, Launch launch)
+{
+    int launches = 0;
+    for (long long f0 = 0; f0 < n_frames; f0 += MT_TOTALS_MAX_X)
+        for (int j0 = 0; j0 < n_jobs; j0 += MT_TOTALS_MAX_Y, ++launches) {
+            launch(dim3((unsigned)std::min<long long>(MT_TOTALS_MAX_X, n_frames - f0), (unsigned)std::min(MT_TOTALS_MAX_Y, n_jobs - j0)),
+                   f0, j0);
+            MD_HIP(hipGetLastError());
+        }
+    return launches;
 }
 
 }  // namespace

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "call_tables.h"
 #include "ctx.h"
 #include "mol_tile.h"
 
@@ -83,8 +84,6 @@ __global__ __launch_bounds__(MT_THREADS) void mol_moments_kernel(
 }
 
 constexpr int MM_THREADS = 256;
-constexpr long long MM_MAX_X = 1 << 20;  // frames per launch
-constexpr int MM_MAX_Y = 65535;          // jobs per launch
 
 // Block (x, y): frame f0 + x, job job0 + y. The three axis sums and the sum of squares of the job's vectors at that frame.
 __global__ __launch_bounds__(MM_THREADS) void moments_total_kernel(const double *__restrict__ vec, long long F, long long S,
@@ -153,9 +152,7 @@ int mdhip_mol_moments(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const d
             MD_REQUIRE(t1 >= t0 && t1 - t0 < len && t1 <= (1ll << 29), "job %d takes at most job_len - 1 %s terms", j,
                        list ? "vector" : "site");
             MD_REQUIRE(t1 == t0 || (atom && w), "NULL term array");
-            for (long long k = t0; k < t1; ++k)
-                MD_REQUIRE(atom[k] >= 1 && atom[k] < len && (k == t0 || atom[k] > atom[k - 1]),
-                           "job %d: the terms' atoms must ascend strictly within [1, job_len)", j);
+            if (int rc = mt_terms_ascend(ctx, j, atom, t0, t1, len)) return rc;
             (list ? J.vec0 : J.site0) = (int)t_atom.size();
             (list ? J.n_vec : J.n_site) = (int)(t1 - t0);
             if (t1 > t0) {  // (a NULL array may stand for empty lists)
@@ -169,32 +166,24 @@ int mdhip_mol_moments(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const d
     const long long S = plan.series;
     MolIo io;
     if ((rc = io.open(ctx, n_frames, n_atoms, x, x_on_device, box, nullptr, 0, S))) return rc;
-    // where the kernel writes: the caller's buffers when they are on the device, else workspace; the totals read the
-    // vectors back, so they are written somewhere whenever a total is asked for
+    // the totals read the vectors back, so they are written somewhere whenever a total is asked for
     const bool totals = total || sq_total;
     const size_t out_b = (size_t)n_frames * 3 * (size_t)S * 8;
-    double *d_site = site, *d_vec = vec;
-    if (site && !out_on_device) {
-        d_site = (double *)mdhip_ws(ctx, WS_OUT, std::max<size_t>(out_b, 8));
-        if (!d_site) return MDHIP_ENOMEM;
-    }
-    if ((vec && !out_on_device) || (!vec && totals)) {
-        d_vec = (double *)mdhip_ws(ctx, WS_OUT2, std::max<size_t>(out_b, 8));
-        if (!d_vec) return MDHIP_ENOMEM;
-    }
-    // tables: classes | jobs | term weights | term atoms | degenerate counters
-    const size_t n_terms = t_atom.size();
-    const size_t cls_b = (size_t)n_jobs * sizeof(MolClass), jobs_b = (size_t)n_jobs * sizeof(MmJob), w_b = n_terms * 8;
-    const size_t a_b = (n_terms * 4 + 7) & ~(size_t)7, deg_b = (size_t)n_jobs * 8;
-    MD_WS(d_tab, char, WS_TABLES, cls_b + jobs_b + w_b + a_b + deg_b);
-    if ((rc = mdhip_h2d_small(ctx, d_tab, plan.classes.data(), cls_b))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + cls_b, jobs.data(), jobs_b))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + cls_b + jobs_b, t_w.data(), w_b))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + cls_b + jobs_b + w_b, t_atom.data(), n_terms * 4))) return rc;
-    const MolClass *d_cls = (const MolClass *)d_tab;
-    const MmJob *d_jobs = (const MmJob *)(d_tab + cls_b);
-    unsigned long long *d_deg = (unsigned long long *)(d_tab + cls_b + jobs_b + w_b + a_b);
-    MD_HIP(hipMemsetAsync(d_deg, 0, deg_b, ctx->stream));
+    MolOut o_site, o_vec;
+    if ((rc = o_site.open(ctx, WS_OUT, site, out_on_device, out_b))) return rc;
+    if ((rc = o_vec.open(ctx, WS_OUT2, vec, out_on_device, out_b, totals))) return rc;
+    const MolClass *d_cls;
+    const MmJob *d_jobs;
+    const double *d_w;
+    const int *d_atom;
+    unsigned long long *d_deg;
+    CallTables tab;
+    tab.add(plan.classes.data(), (size_t)n_jobs, &d_cls);
+    tab.add(jobs.data(), (size_t)n_jobs, &d_jobs);
+    tab.add(t_w.data(), t_w.size(), &d_w);
+    tab.add(t_atom.data(), t_atom.size(), &d_atom);
+    tab.add_zeroed((size_t)n_jobs, &d_deg);
+    if ((rc = upload_tables(ctx, tab, WS_TABLES))) return rc;
     const size_t tot_b = (size_t)n_jobs * 3 * (size_t)n_frames * 8, sq_b = (size_t)n_jobs * (size_t)n_frames * 8;
     double *d_total = nullptr, *d_sq = nullptr;
     if (totals) {
@@ -205,25 +194,22 @@ int mdhip_mol_moments(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const d
     KernelTimer timer(ctx, 0);
     rc = mt_launch(ctx, "mol_moments_kernel", timer, plan.tiles, n_frames, [&](dim3 grid, long long t0, long long ft0) {
         hipLaunchKernelGGL(mol_moments_kernel, grid, dim3(MT_THREADS), 0, ctx->stream, io.x, io.box, (long long)n_frames,
-                           (long long)n_atoms, S, d_cls, n_jobs, d_jobs, (const int *)(d_tab + cls_b + jobs_b + w_b),
-                           (const double *)(d_tab + cls_b + jobs_b), t0, ft0, d_site, d_vec, d_deg);
+                           (long long)n_atoms, S, d_cls, n_jobs, d_jobs, d_atom, d_w, t0, ft0, o_site.dev, o_vec.dev, d_deg);
     });
     if (rc) return rc;
     if (totals) {
-        // (launch dimensions: frames in slices of 2^20 along x, jobs in slices of 65535 along y)
-        for (long long f0 = 0; f0 < n_frames; f0 += MM_MAX_X)
-            for (int j0 = 0; j0 < n_jobs; j0 += MM_MAX_Y) {
-                const dim3 grid((unsigned)std::min<long long>(MM_MAX_X, n_frames - f0), (unsigned)std::min(MM_MAX_Y, n_jobs - j0));
-                hipLaunchKernelGGL(moments_total_kernel, grid, dim3(MM_THREADS), 0, ctx->stream, (const double *)d_vec,
-                                   (long long)n_frames, S, d_jobs, d_cls, f0, j0, d_total, d_sq);
-                MD_HIP(hipGetLastError());
-            }
+        // (they are not counted in last_launches)
+        rc = mt_launch_totals(ctx, n_frames, n_jobs, [&](dim3 grid, long long f0, int j0) {
+            hipLaunchKernelGGL(moments_total_kernel, grid, dim3(MM_THREADS), 0, ctx->stream, (const double *)o_vec.dev,
+                               (long long)n_frames, S, d_jobs, d_cls, f0, j0, d_total, d_sq);
+        });
+        if (rc < 0) return rc;
         if (total && (rc = mdhip_result(cs, total, d_total, tot_b, 0))) return rc;
         if (sq_total && (rc = mdhip_result(cs, sq_total, d_sq, sq_b, 0))) return rc;
     }
-    if (site && !out_on_device && (rc = mdhip_result(cs, site, d_site, out_b, 0))) return rc;
-    if (vec && !out_on_device && (rc = mdhip_result(cs, vec, d_vec, out_b, 0))) return rc;
-    if ((rc = mdhip_result(cs, degenerate, d_deg, deg_b, 0))) return rc;
+    if ((rc = o_site.deliver(cs))) return rc;
+    if ((rc = o_vec.deliver(cs))) return rc;
+    if ((rc = mdhip_result(cs, degenerate, d_deg, (size_t)n_jobs * 8, 0))) return rc;
     return mdhip_end_timed(cs, timer);
 }
 

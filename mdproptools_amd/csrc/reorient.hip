@@ -21,6 +21,7 @@
 #include <cmath>
 #include <vector>
 
+#include "call_tables.h"
 #include "ctx.h"
 #include "lag_tiles.h"
 #include "mol_tile.h"
@@ -269,38 +270,37 @@ int mdhip_axis_vectors(mdhip_ctx *ctx, int64_t n_frames, int64_t n_atoms, const 
     for (int j = 0; j < plan.checked_jobs(); ++j) {
         const long long len = job_len[j], t0 = term_off[j], t1 = term_off[j + 1];
         MD_REQUIRE(t1 > t0 && t1 - t0 < len && t1 <= (1ll << 30), "job %d needs between 1 and job_len - 1 terms", j);
-        for (long long k = t0; k < t1; ++k)
-            MD_REQUIRE(term_atom[k] >= 1 && term_atom[k] < len && (k == t0 || term_atom[k] > term_atom[k - 1]),
-                       "job %d: the terms' atoms must ascend strictly within [1, job_len)", j);
+        if (int rc = mt_terms_ascend(ctx, j, term_atom, t0, t1, len)) return rc;
         jobs[(size_t)j] = {plan.series0[(size_t)j], (int)t0, (int)(t1 - t0)};
     }
     int rc;
     if ((rc = mt_plan_error(ctx, plan, n_atoms))) return rc;
     MolIo io;
     if ((rc = io.open(ctx, n_frames, n_atoms, x, x_on_device, box, U, U_on_device, plan.series))) return rc;
-    // tables: classes | jobs | term weights | term atoms | degenerate counters
     const size_t n_terms = (size_t)term_off[n_jobs];
-    const size_t cls_b = (size_t)n_jobs * sizeof(MolClass), jobs_b = (size_t)n_jobs * sizeof(AxJob), w_b = n_terms * 8;
-    const size_t a_b = (n_terms * 4 + 7) & ~(size_t)7, deg_b = (size_t)n_jobs * 8;
-    MD_WS(d_tab, char, WS_TABLES, cls_b + jobs_b + w_b + a_b + deg_b);
-    if ((rc = mdhip_h2d_small(ctx, d_tab, plan.classes.data(), cls_b))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + cls_b, jobs.data(), jobs_b))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + cls_b + jobs_b, term_w, w_b))) return rc;
-    if ((rc = mdhip_h2d_small(ctx, d_tab + cls_b + jobs_b + w_b, term_atom, n_terms * 4))) return rc;
-    unsigned long long *d_deg = (unsigned long long *)(d_tab + cls_b + jobs_b + w_b + a_b);
-    MD_HIP(hipMemsetAsync(d_deg, 0, deg_b, ctx->stream));
+    const MolClass *d_cls;
+    const AxJob *d_jobs;
+    const double *d_w;
+    const int *d_atom;
+    unsigned long long *d_deg;
+    CallTables tab;
+    tab.add(plan.classes.data(), (size_t)n_jobs, &d_cls);
+    tab.add(jobs.data(), (size_t)n_jobs, &d_jobs);
+    tab.add(term_w, n_terms, &d_w);
+    tab.add(term_atom, n_terms, &d_atom);
+    tab.add_zeroed((size_t)n_jobs, &d_deg);
+    if ((rc = upload_tables(ctx, tab, WS_TABLES))) return rc;
     MD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(axis_vectors_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)AX_LDS));
     KernelTimer timer(ctx, 0);
     rc = mt_launch(ctx, "axis_vectors_kernel", timer, plan.tiles, n_frames, [&](dim3 grid, long long t0, long long ft0) {
         hipLaunchKernelGGL(axis_vectors_kernel, grid, dim3(MT_THREADS), AX_LDS, ctx->stream, io.x, io.box,
-                           (long long)n_frames, (long long)n_atoms, (const MolClass *)d_tab, n_jobs,
-                           (const AxJob *)(d_tab + cls_b), (const int *)(d_tab + cls_b + jobs_b + w_b),
-                           (const double *)(d_tab + cls_b + jobs_b), t0, ft0, io.U, d_deg);
+                           (long long)n_frames, (long long)n_atoms, d_cls, n_jobs, d_jobs, d_atom, d_w, t0, ft0, io.U.dev,
+                           d_deg);
     });
     if (rc) return rc;
-    if (U && !U_on_device && (rc = mdhip_result(cs, U, io.U, io.u_bytes, 0))) return rc;
-    if ((rc = mdhip_result(cs, degenerate, d_deg, deg_b, 0))) return rc;
+    if ((rc = io.U.deliver(cs))) return rc;
+    if ((rc = mdhip_result(cs, degenerate, d_deg, (size_t)n_jobs * 8, 0))) return rc;
     return mdhip_end_timed(cs, timer);
 }
 

@@ -16,6 +16,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "mol_tile.h"  // (mol_jobs: the job walk and its errors)
+
 namespace {
 
 constexpr int SH_CAP = 1024;   // atoms per LDS stage
@@ -27,16 +29,10 @@ struct ShRun {
     int job, nm;   // the job (call order) and the molecules of the run
 };
 
-// RANGE: job `bad_job` does not lie inside the n_atoms atoms of a frame; RESULT: with it the series times n_frames reach
-// 2^40, or the runs 2^22 — a run table of 64 MiB — (the rules and the order of mol_tile.h: mol_plan)
-enum ShPlanError { SH_PLAN_OK = 0, SH_PLAN_RANGE, SH_PLAN_RESULT };
-
-struct ShPlan {
+// The job walk of mol_tile.h (mol_jobs: range, series0, 2^40) with one more RESULT rule: the runs reach 2^22 — a run
+// table of 64 MiB. A refused plan holds no run.
+struct ShPlan : MolJobs {
     std::vector<ShRun> staged, walk;  // job after job, molecules ascending
-    std::vector<long long> series0;   // first series of every job, in call order
-    long long series = 0;
-    int error = SH_PLAN_OK, bad_job = -1;  // the FIRST offending job
-    int checked_jobs() const { return error == SH_PLAN_RANGE ? bad_job : (int)series0.size(); }
 };
 
 // molecules per run of a job of `len` atoms, and whether the run is staged
@@ -46,26 +42,19 @@ inline ShPlan shape_plan(int n_jobs, const int64_t *job_atom0, const int64_t *jo
                          int64_t n_atoms, int64_t n_frames)
 {
     ShPlan pl;
-    pl.series0.resize((size_t)n_jobs);
     long long runs = 0;
-    for (int j = 0; j < n_jobs; ++j) {
-        const long long len = job_len[j], mols = job_mols[j], a0 = job_atom0[j];
-        if (!(len >= 1 && mols >= 0 && a0 >= 0 && a0 <= n_atoms && mols <= (n_atoms - a0) / len)) {
-            pl.error = SH_PLAN_RANGE, pl.bad_job = j;
-            pl.staged.clear(), pl.walk.clear();
-            return pl;
-        }
-        pl.series0[(size_t)j] = pl.series;
-        pl.series += mols;
+    mol_jobs(pl, n_jobs, job_atom0, job_mols, job_len, n_atoms, n_frames, [&](int, long long, long long mols, long long len) {
         const int per = sh_run_mols(len);
         runs += (mols + per - 1) / per;
-        if (pl.error == SH_PLAN_OK && (pl.series >= (1ll << 40) / n_frames || runs >= SH_MAX_RUNS))
-            pl.error = SH_PLAN_RESULT, pl.bad_job = j;
-        if (pl.error != SH_PLAN_OK) continue;
+        return runs < SH_MAX_RUNS;
+    });
+    if (pl.error != MOL_PLAN_OK) return pl;
+    for (int j = 0; j < n_jobs; ++j) {
+        const long long len = job_len[j], mols = job_mols[j];
+        const int per = sh_run_mols(len);
         std::vector<ShRun> &to = len > SH_CAP ? pl.walk : pl.staged;
         for (long long m0 = 0; m0 < mols; m0 += per) to.push_back({m0, j, (int)(mols - m0 < per ? mols - m0 : per)});
     }
-    if (pl.error != SH_PLAN_OK) pl.staged.clear(), pl.walk.clear();
     return pl;
 }
 

@@ -59,13 +59,13 @@ static void check(const Table &t, const char *name)
     }
     if (bad_range >= 0 || bad_result >= 0) {
         ++n_rejected;
-        if (bad_range >= 0) CHECK(pl.error == SH_PLAN_RANGE && pl.bad_job == bad_range && pl.checked_jobs() == bad_range);
-        else CHECK(pl.error == SH_PLAN_RESULT && pl.bad_job == bad_result && pl.checked_jobs() == J);
+        if (bad_range >= 0) CHECK(pl.error == MOL_PLAN_RANGE && pl.bad_job == bad_range && pl.checked_jobs() == bad_range);
+        else CHECK(pl.error == MOL_PLAN_RESULT && pl.bad_job == bad_result && pl.checked_jobs() == J);
         CHECK(pl.staged.empty() && pl.walk.empty());
         return;
     }
-    CHECK(pl.error == SH_PLAN_OK && pl.bad_job == -1 && pl.checked_jobs() == J && (int)pl.series0.size() == J);
-    if (pl.error != SH_PLAN_OK || (int)pl.series0.size() != J) return;
+    CHECK(pl.error == MOL_PLAN_OK && pl.bad_job == -1 && pl.checked_jobs() == J && (int)pl.series0.size() == J);
+    if (pl.error != MOL_PLAN_OK || (int)pl.series0.size() != J) return;
     long long series = 0;
     for (int j = 0; j < J; ++j) {
         CHECK(pl.series0[(size_t)j] == series);
