@@ -1053,6 +1053,58 @@ int mdhip_van_hove_distinct(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, con
                             const int32_t *jobs, double bin_size, int32_t nbins, const double *edges, uint64_t *hist,
                             uint64_t *beyond, uint64_t *pairs);
 
+/* ---- structural relaxation (dynamical/relaxation.py, class StructuralRelaxation; no counterpart in the reference) ---- */
+/*
+ * The self-intermediate scattering function F_s(q, t) = < sin(q |dr|) / (q |dr|) > (isotropic, exact) and the overlap
+ * counts behind Q(t) = < theta(a - |dr|) > and chi4(t) = N [<Q^2> - <Q>^2], at EVERY lag 0 .. max_lag and per time
+ * origin: the count n(t0, k) of a group's entities that moved less than a is complete before it is squared.
+ *   r          host|dev (r_on_device) [n_frames][3][n_ent]: the layout mdhip_displacement_hist reads
+ *   box        host [n_frames][3] edge lengths: r is WRAPPED and the image counts are rebuilt by exactly the rule stated
+ *              for mdhip_displacement_hist (strict +-L/2, a NaN shifts nothing, xu = x + (double)n * L unfused);
+ *              NULL: r is unwrapped, xu = x
+ *   group_off  host int64 [n_groups+1] contiguous entity groups, 1 <= n_groups <= 16; empty groups are allowed
+ *   max_lag    0 .. n_frames-1: the lags k = 0 .. max_lag
+ *   origin_stride  s >= 1: the origins of lag k are t0 = 0, s, 2s, ... with t0 + k <= n_frames-1
+ *              (any int64 s >= 1: a stride beyond n_frames-1 leaves the one origin t0 = 0 and is treated as n_frames)
+ *   a_sq       host [n_groups]: the squared overlap length a * a per group, formed once by the caller; NULL: no overlap
+ *              part
+ *   q          host [n_groups][n_q], 0 <= n_q <= 4: wave numbers >= 0 in 1 / length (ignored when n_q == 0)
+ * Per (group g, lag k, origin t0, entity e of g), in float64, unfused:
+ *   d = xu(t0+k) - xu(t0) per axis, rsq = (dx*dx + dy*dy) + dz*dz
+ *   rsq not finite (NaN or Inf): +1 in nonfinite[k][g], and nothing else
+ *   else: n(t0, k) += 1 when rsq < a_sq[g] (strict), and for every j < n_q:
+ *     x = q[g][j] * sqrt(rsq) (sqrt correctly rounded, one multiplication), v = sinc(x), addend = (int64) rint(v * 2^32)
+ *     (half to even). sinc(x) is within 2^-34 absolute of sin(x) / x of the double x (1 at x = 0), for every x >= 0:
+ *       x >= 2^36 (an overflow to +inf included): v = 0; |sin(x) / x| <= 2^-36 there
+ *       x <  2^-8:  the series v = 1 + x2 * (-1/6 + x2 * (1/120)), x2 = x * x; what it leaves out is below
+ *                   x^6 / 5040 <= 2^-48 / 5040 < 2^-60, its roundings below 2^-51
+ *       else:       sin(x) from the argument reduced by multiples of pi/2 (pi/2 as two doubles, fused multiply-adds)
+ *                   and the Taylor polynomials of sine (degree 13) and cosine (degree 14), within 2^-44; one division
+ *                   by x >= 2^-8, where every error is relative while x < pi/4: within 2^-43 (csrc/relaxation_plan.h
+ *                   has the derivation, tests/native/relaxation_plan_main.cpp measures it)
+ * Results, host memory:
+ *   origins    uint64 [max_lag+1]: the number of origins of lag k
+ *   count1     uint64 [max_lag+1][n_groups] = sum over t0 of n(t0, k); count2 the same sum of n(t0, k)^2. With
+ *              a_sq == NULL both are left UNTOUCHED (and may be NULL)
+ *   fs         int64 [max_lag+1][n_groups][n_q] = sum over t0 and e of the addends; untouched (may be NULL) when n_q == 0
+ *   nonfinite  uint64 [max_lag+1][n_groups]
+ * F_s = fs / 2^32 / W and Q = count1 / W with W = origins * group size; chi4 = (O count2 - count1^2) / (O^2 N).
+ * Every result is an integer: exact, independent of the launch geometry and of the order of the entities inside a
+ * group, bit-identical from call to call. No floating-point atomics, no floating-point accumulators.
+ * MDHIP_EINVAL before anything is written: n_groups outside 1..16, n_q outside 0..4, n_frames outside 1..2^29-1,
+ * n_ent outside 0..2^40-1 or n_frames * n_ent >= 2^40 ("trajectory too large"), max_lag outside 0..n_frames-1,
+ * origin_stride < 1, a group_off that does not ascend within [0, n_ent], a negative or
+ * non-finite q, a negative or NaN a_sq, a_sq == NULL together with n_q == 0, a NULL required array, and any group
+ * with origins[0] * size >= 2^30 (fs stays within int64 with the 2^32 unit and count2 within uint64; a larger
+ * origin_stride is the remedy, and the error text says so). Launch dimensions over 65535 are split inside the call.
+ */
+int mdhip_self_relaxation(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, const double *r, int r_on_device,
+                          const double *box, int n_groups, const int64_t *group_off,
+                          int64_t max_lag, int64_t origin_stride,
+                          const double *a_sq, int n_q, const double *q,
+                          uint64_t *origins, uint64_t *count1, uint64_t *count2,
+                          int64_t *fs, uint64_t *nonfinite);
+
 /* ---- Einstein-Helfand conductivity (Conductivity.einstein / nernst; `pass` in the reference,
  *      dynamical/conductivity.py:399-403) ---- */
 /*

@@ -164,6 +164,8 @@ PROTOTYPES = {
                                           C.c_double, C.c_int32, c_dp, c_up, c_up, c_up, c_dp, c_up]),
     "mdhip_van_hove_distinct": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int, c_lp, C.c_int, c_ip,
                                           C.c_double, C.c_int32, c_dp, c_up, c_up, c_up]),
+    "mdhip_self_relaxation": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_int, c_lp, C.c_int64, C.c_int64,
+                                        c_dp, C.c_int, c_dp, c_up, c_up, c_up, c_lp, c_up]),
     "mdhip_collective_displacement": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int, c_dp, C.c_double, C.c_int, c_lp,
                                                 vp, C.c_int, vp]),
     "mdhip_cross_msd": (C.c_int, [vp, C.c_int64, C.c_int, vp, C.c_int, C.c_int64, vp, vp, C.c_int]),

@@ -1206,6 +1206,88 @@ def van_hove_distinct(r, box, group_off, jobs, bin_size, n_bins, ctx=None):
     return hist, beyond, pairs
 
 
+RELAX_MAX_GROUPS = 16
+RELAX_MAX_Q = 4
+RELAX_MAX_FRAMES = (1 << 29) - 1
+RELAX_GUARD = 1 << 30
+
+
+def self_relaxation(r, box, group_off, max_lag, origin_stride=1, a=None, q=None, ctx=None):
+    """
+    Overlap counts and self-intermediate scattering sums at every lag 0 .. max_lag, per time origin (include/mdhip.h:
+    mdhip_self_relaxation): r [F,3,E] (host array or contiguous float64 device tensor), box [F,3] edge lengths when r is
+    wrapped (the kernel rebuilds the image counts) or None when it is unwrapped, group_off int64 [G+1] contiguous entity
+    groups (G <= 16), origins 0, origin_stride, 2 origin_stride, ...; a: the overlap length, a float or one per group [G],
+    or None for no overlap part; q: wave numbers [n_q] shared by the groups or [G,n_q], n_q <= 4, or None ->
+    (origins uint64 [L], count1 uint64 [L,G] = sum over origins of n(t0, k), count2 uint64 [L,G] = the sum of n^2,
+    fs int64 [L,G,n_q] = sum of rint(sinc(q |dr|) 2^32), nonfinite uint64 [L,G]), L = max_lag + 1. Without `a` the
+    counts are zeros; without `q` fs is empty.
+    """
+    F, _, E = _shape3(r, "r")
+    bx = None
+    if box is not None:
+        bx = _f64(box)
+        if bx.shape != (F, 3):
+            raise ValueError("box must have shape [n_frames, 3]")
+    off = _i64(group_off)
+    if off.ndim != 1 or off.size < 2 or off[0] < 0 or off[-1] > E or np.any(np.diff(off) < 0):
+        raise ValueError("group_off must be ascending offsets [n_groups + 1] within [0, n_ent]")
+    G = off.size - 1
+    if G > RELAX_MAX_GROUPS:
+        raise ValueError("at most %d groups per call (%d given)" % (RELAX_MAX_GROUPS, G))
+    if not 1 <= F <= RELAX_MAX_FRAMES:
+        raise ValueError("n_frames must be in [1, 2^29 - 1]")
+    max_lag, stride = int(max_lag), int(origin_stride)
+    if not 0 <= max_lag <= F - 1:
+        raise ValueError("max_lag must be in [0, n_frames - 1 = %d]" % (F - 1))
+    if stride < 1:
+        raise ValueError("origin_stride must be at least 1")
+    stride = min(stride, F)  # (beyond F - 1 every stride leaves the one origin 0; a Python int may not fit int64)
+    if a is None and q is None:
+        raise ValueError("at least one of a and q must be given")
+    a_sq = None
+    if a is not None:
+        av = _f64(np.broadcast_to(_f64(a), (G,)) if np.ndim(a) == 0 else a)
+        if av.shape != (G,):
+            raise ValueError("a must be a number or hold one overlap length per group")
+        if not np.all(av >= 0.0):
+            raise ValueError("a must not be negative or NaN")
+        a_sq = _f64(av * av)
+    qv = np.zeros((G, 0))
+    if q is not None:
+        qv = _f64(q)
+        if qv.ndim <= 1:
+            qv = _f64(np.broadcast_to(qv.reshape(-1), (G, qv.size)))
+        if qv.ndim != 2 or qv.shape[0] != G:
+            raise ValueError("q must be wave numbers [n_q] or [n_groups, n_q]")
+        if qv.shape[1] > RELAX_MAX_Q:
+            raise ValueError("at most %d wave numbers per group (%d given)" % (RELAX_MAX_Q, qv.shape[1]))
+        if not (np.all(qv >= 0.0) and np.all(np.isfinite(qv))):
+            raise ValueError("q must be finite and not negative")
+    n_q = qv.shape[1]
+    if a_sq is None and n_q == 0:
+        raise ValueError("at least one of a and q must be given")
+    n_orig = (F - 1) // stride + 1
+    sizes = np.diff(off)
+    if G and n_orig * int(sizes.max()) >= RELAX_GUARD:
+        raise ValueError("origins * group size = %d * %d reaches 2^30, beyond which the integer sums could overflow: "
+                         "raise origin_stride" % (n_orig, int(sizes.max())))
+    ctx = ctx or default_context()
+    rp, r_dev, keep = as_input(r, ctx)
+    L = max_lag + 1
+    origins = np.empty(L, dtype=np.uint64)
+    count1 = np.zeros((L, G), dtype=np.uint64)
+    count2 = np.zeros((L, G), dtype=np.uint64)
+    fs = np.zeros((L, G, n_q), dtype=np.int64)
+    nonfinite = np.empty((L, G), dtype=np.uint64)
+    ctx.check(ctx.lib.mdhip_self_relaxation(
+        ctx.h, F, E, rp, r_dev, None if bx is None else ptr(bx), G, ptr(off, C.c_int64), max_lag, stride,
+        None if a_sq is None else ptr(a_sq), n_q, ptr(qv) if n_q else None, ptr(origins, C.c_uint64),
+        ptr(count1, C.c_uint64), ptr(count2, C.c_uint64), ptr(fs, C.c_int64) if n_q else None,
+        ptr(nonfinite, C.c_uint64)))
+    return origins, count1, count2, fs, nonfinite
+
+
 def collective_displacement(r, weight, group_off, scale=1.0, out=None, weighted=None, ctx=None):
     """
     Charge-weighted collective displacement of every group per frame (include/mdhip.h: mdhip_collective_displacement):

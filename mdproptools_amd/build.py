@@ -21,8 +21,8 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libmdhip.so")
 SOURCES = ["mdhip_ctx.hip", "pair_hist.hip", "pair_dense.hip", "pair_cull.hip", "pair_sj.hip", "segment_com.hip", "msd.hip", "msd_fft.hip", "xcorr.hip", "fft_pow2.hip", "scan.hip", "residence.hip", "clusters.hip",
-           "configurations.hip", "hydration.hip", "angles.hip", "bond_order.hip", "sdf.hip", "aggregates.hip", "hbonds.hip", "density.hip", "displacement.hip", "vanhove.hip", "collective.hip", "reorient.hip", "dihedrals.hip", "moments.hip", "vector_pairs.hip", "mol_shape.hip", "velocity_spectrum.hip", "free_volume.hip", "dump_reader.cpp"]
-HEADERS = [os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "pair_common.h"), os.path.join(CSRC, "pair_plan.h"), os.path.join(CSRC, "lag_plan.h"), os.path.join(CSRC, "lag_tiles.h"), os.path.join(CSRC, "seg_plan.h"), os.path.join(CSRC, "mol_tile.h"), os.path.join(CSRC, "shape_plan.h"), os.path.join(CSRC, "call_tables.h"), os.path.join(CSRC, "cell_plan.h"), os.path.join(CSRC, "spectrum_plan.h"), os.path.join(CSRC, "group_pairs.h"), os.path.join(CSRC, "msd_fft_w12.h"), os.path.join(CSRC, "msd_fft_w12r.h"), os.path.join(CSRC, "shell_search.h"), os.path.join(CSRC, "shell_gather.h"), os.path.join(CSRC, "presence_table.h"), os.path.join(CSRC, "copy_pool.h"), os.path.join(os.path.dirname(HERE), "include", "mdhip.h")]
+           "configurations.hip", "hydration.hip", "angles.hip", "bond_order.hip", "sdf.hip", "aggregates.hip", "hbonds.hip", "density.hip", "displacement.hip", "vanhove.hip", "collective.hip", "reorient.hip", "dihedrals.hip", "moments.hip", "vector_pairs.hip", "mol_shape.hip", "velocity_spectrum.hip", "free_volume.hip", "relaxation.hip", "dump_reader.cpp"]
+HEADERS = [os.path.join(CSRC, "ctx.h"), os.path.join(CSRC, "pair_common.h"), os.path.join(CSRC, "pair_plan.h"), os.path.join(CSRC, "lag_plan.h"), os.path.join(CSRC, "lag_tiles.h"), os.path.join(CSRC, "seg_plan.h"), os.path.join(CSRC, "mol_tile.h"), os.path.join(CSRC, "shape_plan.h"), os.path.join(CSRC, "call_tables.h"), os.path.join(CSRC, "cell_plan.h"), os.path.join(CSRC, "spectrum_plan.h"), os.path.join(CSRC, "group_pairs.h"), os.path.join(CSRC, "msd_fft_w12.h"), os.path.join(CSRC, "msd_fft_w12r.h"), os.path.join(CSRC, "shell_search.h"), os.path.join(CSRC, "shell_gather.h"), os.path.join(CSRC, "presence_table.h"), os.path.join(CSRC, "copy_pool.h"), os.path.join(CSRC, "fixed_point.h"), os.path.join(CSRC, "image_counts.h"), os.path.join(CSRC, "relaxation_plan.h"), os.path.join(os.path.dirname(HERE), "include", "mdhip.h")]
 ARCH = "gfx950"
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=" + ARCH,
           "-Wall", "-Wno-unused-function"]

@@ -316,6 +316,38 @@ def load_frames(filename, shard=False, stream=False, on_frame=None):
     return frames
 
 
+def load_typed_positions(filename, atom_types, coords, dt_ps, what="a displacement"):
+    """What Displacement and StructuralRelaxation hand the library: (r [F,3,E] the atoms of the requested types, grouped
+    by type in the order of atom_types, ids ascending inside a type; box [F,3]; group_off [T+1]; frame spacing in ps).
+    coords "wrapped" reads x y z, "unwrapped" xu yu zu; dt_ps: the timestep in ps. Triclinic boxes, frames that do not
+    hold the same atoms, fewer than two frames (`what` needs them) and uneven frame spacing raise ValueError."""
+    xyz_cols = ["x", "y", "z"] if coords == "wrapped" else ["xu", "yu", "zu"]
+    steps, boxes, planes = [], [], []
+    ids = types = sel = None
+    for ts, bounds, lengths, _, pl in mio.iter_native_frames(filename, ["id", "type"] + xyz_cols, sort_by="id"):
+        b = np.asarray(bounds, dtype=np.float64)
+        ext = b[:, 1] - b[:, 0]
+        if np.any(np.abs(np.asarray(lengths, dtype=np.float64) - ext) > 1e-12 * np.abs(ext)):
+            raise ValueError("triclinic boxes are not supported")
+        if ids is None:
+            ids, types = pl[0].copy(), pl[1].copy()
+            groups = [np.flatnonzero(types == t) for t in atom_types]
+            group_off = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int64)
+            sel = np.concatenate(groups).astype(np.int64) if groups else np.zeros(0, dtype=np.int64)
+        elif pl.shape[1] != len(ids) or not np.array_equal(pl[0], ids) or not np.array_equal(pl[1], types):
+            raise ValueError("every frame must hold the same atom ids with the same types")
+        steps.append(int(ts))
+        boxes.append(ext)
+        planes.append(pl[2:5][:, sel])
+    if len(steps) < 2:
+        raise ValueError("%s needs at least two frames" % what)
+    d_step = np.diff(np.asarray(steps, dtype=np.int64))
+    if d_step[0] <= 0 or np.any(d_step != d_step[0]):
+        raise ValueError("the frames must be uniformly spaced in time")
+    r = np.ascontiguousarray(np.stack(planes), dtype=np.float64)
+    return r, np.ascontiguousarray(np.stack(boxes)), group_off, float(d_step[0]) * dt_ps
+
+
 def all_frames(per_frame_rows):
     """Per-frame result rows of every rank in frame order (identity without torch.distributed). Ranks hold
     contiguous blocks of the trajectory, so the concatenation in rank order is the frame order, and summing

@@ -12,12 +12,8 @@
 //     edge table (mdhip_bin_edges), counted in hist[job][bin] when bin < nbins, else (NaN included) in overflow[job];
 //   moments[job] = sum sqrt(rsq), sum rsq, sum rsq rsq over all windows of the job.
 //
-// Image counts never wait across workgroups. They take three launches over columns c = (axis, entity) of the
-// F x 3E matrix, threads along c so that every load of [f][.] coalesces:
-//   dp_image_kernel<false>  per (chunk of DP_CHUNK frames, column): the sum of the chunk's shifts, and the crossings
-//   dp_chunk_scan_kernel    per column: exclusive scan of those sums over the chunks (a short serial loop)
-//   dp_image_kernel<true>   per (chunk, column): the shifts again from the chunk's start value -> int32 n [F][3E]
-// The n(f) are integers: the same whatever the chunking.
+// The image counts are image_counts.h (three launches, shared with relaxation.hip): integers, the same whatever the
+// chunking.
 //
 // Binning is one launch for all jobs (blockIdx.y = job, blockIdx.x = a run of `wpb` consecutive windows of the job,
 // window w = origin * group size + entity, so that lanes run along the entities and small groups still fill a wave):
@@ -28,17 +24,15 @@
 // the launch geometry, moments are reproducible for a given geometry. Measured: DESIGN.md 4.12.
 
 #include "group_pairs.h"  // (its three argument checks; the kernels and the plan here are this file's own)
+#include "image_counts.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int DP_THREADS = 256;
-constexpr int DP_CHUNK = 64;           // frames per chunk of the image-count passes
 constexpr int DP_LDS_WORDS = 16128;    // uint32 bins of a job's row in LDS (63 KiB; 64 KiB per workgroup is the limit)
 constexpr long long DP_MIN_WPB = 2048;  // windows per workgroup: at least 8 per lane ...
 constexpr long long DP_BLOCKS = 4096;   // ... and at most this many workgroups per job
-constexpr int DP_MAX_Y = 65535;
 
 struct DpJob {
     long long e0, ng;     // the group's entities [e0, e0 + ng)
@@ -48,76 +42,6 @@ struct DpJob {
     int lag, stride;
     int q, r;             // DP_THREADS = q * ng + r
 };
-
-// Sum of the chunk's shifts per column (WRITE = false: tot[chunk][c], and the number of shifts into *crossings), or the
-// image counts themselves from the scanned sums (WRITE = true: img[f][c]). Block (x, y): columns x * 256 .. (grid
-// stride), chunk ch0 + y.
-template <bool WRITE>
-__global__ __launch_bounds__(DP_THREADS) void dp_image_kernel(const double *__restrict__ r,
-                                                              const double *__restrict__ box, long long F,
-                                                              long long E, long long ch0, int *__restrict__ tot,
-                                                              int *__restrict__ img,
-                                                              unsigned long long *__restrict__ crossings)
-{
-    __shared__ unsigned s_cross;
-    const long long ncol = 3 * E;
-    const long long ch = ch0 + blockIdx.y;
-    const long long f0 = ch * DP_CHUNK, f1 = f0 + DP_CHUNK < F ? f0 + DP_CHUNK : F;
-    unsigned n_cross = 0;
-    if (!WRITE) {
-        if (threadIdx.x == 0) s_cross = 0u;
-        __syncthreads();
-    }
-    for (long long c = (long long)blockIdx.x * DP_THREADS + threadIdx.x; c < ncol;
-         c += (long long)gridDim.x * DP_THREADS) {
-        const int axis = (int)(c / E);
-        int n = WRITE ? tot[ch * ncol + c] : 0;
-        long long f = f0;
-        double prev;
-        if (f0 == 0) {
-            prev = r[c];
-            if (WRITE) img[c] = 0;
-            f = 1;
-        } else {
-            prev = r[(f0 - 1) * ncol + c];
-        }
-#pragma unroll 8
-        for (; f < f1; ++f) {
-            const double x = r[f * ncol + c];
-            const double half = 0.5 * box[f * 3 + axis];
-            const double d = x - prev;
-            const int s = d > half ? -1 : (d < -half ? 1 : 0);  // (a NaN compares false twice)
-            n += s;
-            if (WRITE)
-                img[f * ncol + c] = n;
-            else
-                n_cross += s != 0;
-            prev = x;
-        }
-        if (!WRITE) tot[ch * ncol + c] = n;
-    }
-    if (!WRITE) {
-        for (int o = 32; o; o >>= 1) n_cross += __shfl_xor(n_cross, o);
-        if ((threadIdx.x & 63) == 0 && n_cross) atomicAdd(&s_cross, n_cross);
-        __syncthreads();
-        if (threadIdx.x == 0 && s_cross) atomicAdd(crossings, (unsigned long long)s_cross);
-    }
-}
-
-// tot[ch][c] <- sum of tot[0 .. ch - 1][c]: one lane per column.
-__global__ __launch_bounds__(DP_THREADS) void dp_chunk_scan_kernel(int *__restrict__ tot, long long n_chunks,
-                                                                   long long ncol)
-{
-    for (long long c = (long long)blockIdx.x * DP_THREADS + threadIdx.x; c < ncol;
-         c += (long long)gridDim.x * DP_THREADS) {
-        int run = 0;
-        for (long long ch = 0; ch < n_chunks; ++ch) {
-            const int t = tot[ch * ncol + c];
-            tot[ch * ncol + c] = run;
-            run += t;
-        }
-    }
-}
 
 // Block (x, y): windows [x * wpb, (x + 1) * wpb) of job job0 + y. Dynamic LDS: the job's row when LDS.
 template <bool WRAP, bool LDS>
@@ -306,32 +230,7 @@ int mdhip_displacement_hist(mdhip_ctx *ctx, int64_t n_frames, int64_t n_ent, con
     int launches = 0;
     MD_HIP(hipMemsetAsync(d_misc, 0, ((size_t)n_jobs + 1) * 8, ctx->stream));
     if (wrap) {
-        const long long ncol = 3 * (long long)n_ent, n_chunks = (n_frames + DP_CHUNK - 1) / DP_CHUNK;
-        MD_WS(d_b, double, WS_BOX, (size_t)n_frames * 24);
-        if ((rc = mdhip_h2d_small(ctx, d_b, box, (size_t)n_frames * 24))) return rc;
-        MD_WS(d_tot, int, WS_AUX1, (size_t)n_chunks * (size_t)ncol * 4);
-        MD_WS(d_n, int, WS_AUX0, (size_t)n_frames * (size_t)ncol * 4);
-        const unsigned gx = (unsigned)std::min<long long>((ncol + DP_THREADS - 1) / DP_THREADS, 65535);
-        // grid.y holds at most 65535 chunks: longer trajectories go in slices
-        for (long long c0 = 0; c0 < n_chunks; c0 += DP_MAX_Y, ++launches) {
-            const unsigned gy = (unsigned)std::min<long long>(DP_MAX_Y, n_chunks - c0);
-            hipLaunchKernelGGL(dp_image_kernel<false>, dim3(gx, gy), dim3(DP_THREADS), 0, ctx->stream, d_r, d_b,
-                               (long long)n_frames, (long long)n_ent, c0, d_tot, (int *)nullptr, d_cross);
-            MD_HIP(hipGetLastError());
-        }
-        hipLaunchKernelGGL(dp_chunk_scan_kernel, dim3(gx), dim3(DP_THREADS), 0, ctx->stream, d_tot, n_chunks, ncol);
-        MD_HIP(hipGetLastError());
-        ++launches;
-        for (long long c0 = 0; c0 < n_chunks; c0 += DP_MAX_Y, ++launches) {
-            const unsigned gy = (unsigned)std::min<long long>(DP_MAX_Y, n_chunks - c0);
-            hipLaunchKernelGGL(dp_image_kernel<true>, dim3(gx, gy), dim3(DP_THREADS), 0, ctx->stream, d_r, d_b,
-                               (long long)n_frames, (long long)n_ent, c0, d_tot, d_n,
-                               (unsigned long long *)nullptr);
-            MD_HIP(hipGetLastError());
-        }
-        d_box = d_b;
-        d_img = d_n;
-        ctx->last_kernel = "dp_image_kernel";
+        if ((rc = dp_image_counts(ctx, d_r, box, n_frames, n_ent, d_cross, d_box, d_img, launches))) return rc;
     }
     unsigned long long *d_hist = nullptr;
     double *d_mom = nullptr;

@@ -16,6 +16,7 @@
 // in any order: the low words wrap as often as their exact sum passes 2^64. Integers only: no float atomics, the
 // results do not depend on the launch geometry. Measured: DESIGN.md 4.13d.
 
+#include "fixed_point.h"
 #include "group_pairs.h"
 
 #pragma clang fp contract(off)
@@ -30,18 +31,7 @@ constexpr long long VP_JCHUNK = 1ll << 20;    // uniform entities per unit: 64 *
 constexpr long long VP_BLOCKS = 4096;         // about this many workgroups per job at most
 // Pairs a workgroup bins between zeroing and flushing its row. An addend is rint(v * 2^32) with |v| < 2, so |addend| <
 // 2^33 and an int64 word of the row holds |sum| <= 2^29 * 2^33 = 2^62 < 2^63; the uint32 count holds 2^29 as well.
-constexpr long long VP_MAX_PAIRS = 1ll << 29;
-constexpr double VP_ONE = 4294967296.0;       // 2^32: the fixed-point unit
-
-// (int64) rint(v * 2^32) of |v| < 2 as a two's-complement word. The product is exact (a power of two) and below 2^33 in
-// magnitude; adding 1.5 * 2^52 moves it to where a double's ulp is 1, which rounds it to an integer, half to even, as
-// rint does, and leaves that integer in the low bits of the sum: the difference of the two bit patterns is the value.
-// One addition and one 64-bit subtraction instead of a rounding and a double-to-int64 conversion sequence.
-__device__ __forceinline__ unsigned long long vp_fixed(double v)
-{
-    constexpr double magic = 6755399441055744.0;  // 1.5 * 2^52
-    return (unsigned long long)(__double_as_longlong(v * VP_ONE + magic) - __double_as_longlong(magic));
-}
+constexpr long long VP_MAX_PAIRS = 1ll << 29;  // (the addend itself: vp_fixed, fixed_point.h)
 
 // Dynamic LDS: int64 [3][nbins] | uint32 [nbins].
 __global__ __launch_bounds__(VP_THREADS) void vp_pair_kernel(

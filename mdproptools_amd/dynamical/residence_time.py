@@ -39,11 +39,10 @@ from scipy.optimize import curve_fit
 from scipy.special import gamma
 
 from .. import backend
-from .. import io as mio
 from ..common import sayer
 from ..dist import is_writer
 from ..common.com_mols import calc_atom_type
-from ..common.trajectory import load_frames
+from ..common.trajectory import load_frames, load_typed_positions
 
 VERBOSE = False
 
@@ -192,34 +191,8 @@ class Displacement:
     def _load(self):
         """(r [F,3,E] the atoms of the requested types, grouped by type in the order of atom_types, ids ascending
         inside a type; box [F,3]; group_off [T+1]; frame spacing in ps)."""
-        if self._traj is not None:
-            return self._traj
-        xyz_cols = ["x", "y", "z"] if self.coords == "wrapped" else ["xu", "yu", "zu"]
-        steps, boxes, planes = [], [], []
-        ids = types = sel = None
-        for ts, bounds, lengths, _, pl in mio.iter_native_frames(self.filename, ["id", "type"] + xyz_cols,
-                                                                 sort_by="id"):
-            b = np.asarray(bounds, dtype=np.float64)
-            ext = b[:, 1] - b[:, 0]
-            if np.any(np.abs(np.asarray(lengths, dtype=np.float64) - ext) > 1e-12 * np.abs(ext)):
-                raise ValueError("triclinic boxes are not supported")
-            if ids is None:
-                ids, types = pl[0].copy(), pl[1].copy()
-                groups = [np.flatnonzero(types == t) for t in self.atom_types]
-                group_off = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int64)
-                sel = np.concatenate(groups).astype(np.int64) if groups else np.zeros(0, dtype=np.int64)
-            elif pl.shape[1] != len(ids) or not np.array_equal(pl[0], ids) or not np.array_equal(pl[1], types):
-                raise ValueError("every frame must hold the same atom ids with the same types")
-            steps.append(int(ts))
-            boxes.append(ext)
-            planes.append(pl[2:5][:, sel])
-        if len(steps) < 2:
-            raise ValueError("a displacement needs at least two frames")
-        d_step = np.diff(np.asarray(steps, dtype=np.int64))
-        if d_step[0] <= 0 or np.any(d_step != d_step[0]):
-            raise ValueError("the frames must be uniformly spaced in time")
-        r = np.ascontiguousarray(np.stack(planes), dtype=np.float64)
-        self._traj = (r, np.ascontiguousarray(np.stack(boxes)), group_off, float(d_step[0]) * self.dt)
+        if self._traj is None:
+            self._traj = load_typed_positions(self.filename, self.atom_types, self.coords, self.dt)
         return self._traj
 
     @staticmethod
